@@ -1,20 +1,20 @@
 """TEST INFRASTRUCTURE: the reference's five example programs, compiled UNMODIFIED (read where they lie under
-/root/reference/examples, never copied) in two flavours into the git-ignored tests/cpp/bin/:
+/root/reference/examples, never copied) in two flavours into the git-ignored oracle/_ref/examples/:
 
     <name>.gpu   against include/ (the drop-in headers) + liblbfgsx.so      -- runs on the MI355X
     <name>.ref   against /root/reference/include (the reference's own headers) -- runs on the host
 
 Both see oracle/eigen_shim as <Eigen/Core> (double-double accumulators, the parity build of DESIGN.md section 2), the same
 -ffp-contract=off, and tests/cpp/precise_cout.h force-included so that their printed numbers carry 17 digits.
-__graft_entry__.build() calls build_all() where /root/reference exists (the build container); the binaries travel to the
-GPU box with the snapshot, where tests/test_reference_examples_gpu.py runs each pair and compares what they print.
+__graft_entry__.build() calls build_all() where /root/reference exists (the build container); like the rest of oracle/_ref the
+binaries travel to the GPU box, where tests/test_reference_examples_gpu.py runs each pair and compares what they print.
 """
 import os
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
-BIN = os.path.join(ROOT, "tests", "cpp", "bin")
+BIN = os.path.join(ROOT, "oracle", "_ref", "examples")
 EXAMPLES = ["example-quadratic", "example-rosenbrock", "example-rosenbrock-box", "example-rosenbrock-bracketing",
             "example-rosenbrock-comparison"]
 COMMON = ["g++", "-std=c++17", "-O2", "-march=x86-64-v3", "-ffp-contract=off", "-DSHIM_ACC=1",
@@ -48,7 +48,7 @@ def build_all(force=False):
         src = os.path.join(REF, "examples", name + ".cpp")
         gpu, ref = paths(name)
         if force or _stale(gpu, deps + [src]):
-            # rpath relative to the binary: tests/cpp/bin -> lbfgspp_amd
+            # rpath relative to the binary: oracle/_ref/examples -> lbfgspp_amd
             jobs.append(COMMON + ["-I", inc, src, "-o", gpu, "-L" + lib, "-llbfgsx", "-L/opt/rocm/lib", "-lamdhip64",
                                   "-Wl,-rpath,$ORIGIN/../../../lbfgspp_amd", "-Wl,-rpath,/opt/rocm/lib"])
         if force or _stale(ref, deps + [src]):

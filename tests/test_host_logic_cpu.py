@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import golden_util as GU
 import oracle_lib as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -144,9 +145,7 @@ def test_more_thuente_exhausted_budget_returns_best_point(hl):
     assert (f, d) == _mt2(t) and f <= _mt2(0.0)[0]
 
 
-BAD = [dict(m=0), dict(epsilon=-1.0), dict(epsilon_rel=-1.0), dict(past=-1), dict(delta=-1.0), dict(max_iterations=-1),
-       dict(max_linesearch=0), dict(min_step=-1.0), dict(max_step=1e-30), dict(ftol=0.0), dict(ftol=0.6),
-       dict(wolfe=1e-5), dict(wolfe=1.0)]
+BAD = GU.PARAM_BAD
 
 
 def _check(hl, which, **kw):
@@ -164,15 +163,16 @@ def _check(hl, which, **kw):
 
 @pytest.mark.parametrize("bad", BAD, ids=[list(b)[0] + "=" + str(list(b.values())[0]) for b in BAD])
 def test_param_validation_messages_match_the_reference(hl, bad):
+    """the reference's exception text for each bad parameter: tests/golden/param_messages.json (what oracle/_ref answered,
+    tests/golden/make_host_logic_golden.py), and oracle/_ref itself where it is built"""
     rc, msg = _check(hl, 0, **bad)
     assert rc == 1 and msg
-    try:
-        ref = O.Oracle("ref", "dd")
-    except OSError:
-        pytest.skip("oracle/_ref not built here; message text is pinned where the reference build exists")
-    p = O.lbfgs_params(**bad)
-    _, r = ref.lbfgs(O.F64, O.LS_NW, O.OBJ_ROSEN, np.zeros(4), p)
-    assert r.status == 1 and r.msg.decode() == msg
+    gold = GU.load("param_messages.json")[GU.PARAM_BAD.index(bad)]
+    assert gold["param"] == bad and gold["status"] == 1 and gold["msg"] == msg
+    if O.available("ref", "dd"):
+        p = O.lbfgs_params(**bad)
+        _, r = O.Oracle("ref", "dd").lbfgs(O.F64, O.LS_NW, O.OBJ_ROSEN, np.zeros(4), p)
+        assert r.status == 1 and r.msg.decode() == msg
 
 
 def test_param_validation_accepts_defaults_and_checks_lbfgsb_fields(hl):
@@ -272,59 +272,30 @@ def test_sums_over_L_u_U_are_used_by_the_solve_that_follows_their_pass_only(tmp_
     assert "solve_sweep_rhs" in second and "wtv_prologue" not in second, second
 
 
-REF_INC = "/root/reference/include"
-
-
 @pytest.fixture(scope="module")
-def policy_libs(tmp_path_factory):
-    """tests/cpp/policy10_capi.cpp compiled against the reference's headers and against include/ (the checker needs
-    /root/reference: build container only)"""
-    if not os.path.isdir(REF_INC):
-        pytest.skip("/root/reference is not present on this machine")
-    d = tmp_path_factory.mktemp("p10")
-    libs = []
-    for tag, inc in (("ref", REF_INC), ("ours", os.path.join(ROOT, "include"))):
-        out = str(d / ("libpolicy10_%s.so" % tag))
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off"] + SAN +
-                              ["-I", inc, "-I", os.path.join(ROOT, "oracle", "eigen_shim"),
-                               os.path.join(HERE, "cpp", "policy10_capi.cpp"), "-o", out])
-        lib = C.CDLL(out)
-        lib.policy10.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_double] * 6 + [C.c_int] + [C.c_void_p] * 3
-        libs.append(lib)
-    return libs
+def policy10_ours(tmp_path_factory):
+    """tests/cpp/policy10_capi.cpp compiled against include/; the same source compiled against the reference's headers was
+    run once on the same inputs, its results are tests/golden/policy10_golden.npz (tests/golden/make_host_logic_golden.py)"""
+    out = str(tmp_path_factory.mktemp("p10") / "libpolicy10_ours.so")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=off"] + SAN +
+                          ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "oracle", "eigen_shim"),
+                           os.path.join(HERE, "cpp", "policy10_capi.cpp"), "-o", out])
+    return GU.policy10_lib(out)
 
 
-@pytest.mark.parametrize("policy,conditions", [(0, (1, 2, 3)), (1, (1, 2, 3)), (2, (3,)), (3, (3,))],
+@pytest.mark.parametrize("policy,conditions", GU.POLICY10_CASES,
                          ids=["backtracking", "bracketing", "more-thuente", "nocedal-wright"])
-def test_built_in_policies_offer_the_reference_signature_with_the_reference_results(policy_libs, policy, conditions):
+def test_built_in_policies_offer_the_reference_signature_with_the_reference_results(policy10_ours, policy, conditions):
     """VERDICT r5, missing 2: a program that calls a built-in policy directly through the reference's ten-argument static form
     now compiles -- and gets the reference's result: step, fx, dg, the evaluation count, x, grad and the exception class, on
     random descent (and a few ascent / degenerate) directions of the extended Rosenbrock function"""
-    ref, ours = policy_libs
-    rng = np.random.default_rng(1234 + policy)
+    gold = np.load(os.path.join(HERE, "golden", "policy10_golden.npz"))
     seen = set()
-    for trial in range(300):
-        n = int(rng.choice([2, 6, 20]))
-        xp = np.where(np.arange(n) % 2 == 1, 1.0, -1.2) + 0.4 * rng.random(n)
-        g = np.zeros(n)
-        for i in range(0, n, 2):
-            t1, t2 = 1.0 - xp[i], 10.0 * (xp[i + 1] - xp[i] ** 2)
-            g[i + 1] = 20.0 * t2
-            g[i] = -2.0 * (xp[i] * g[i + 1] + t1)
-        kind = trial % 10
-        drt = -g * (10.0 ** rng.uniform(-4, 1)) + (0.3 * rng.standard_normal(n) * np.abs(g).mean() if kind >= 3 else 0.0)
-        if kind == 9:
-            drt = g.copy()  # ascent: the policies throw
-        step0 = float(10.0 ** rng.uniform(-3, 1)) if kind != 8 else -1.0
-        cond = int(conditions[trial % len(conditions)])
-        args = (policy, cond, n, xp.ctypes.data_as(C.c_void_p), drt.ctypes.data_as(C.c_void_p), step0, 1e20,
-                1e-4, 0.9, 1e-20 if kind != 7 else 1e-3, 1e20 if kind != 6 else 2.0, int(rng.choice([3, 8, 20])))
-        res = []
-        for lib in (ref, ours):
-            out, x, gr = np.zeros(4), np.zeros(n), np.zeros(n)
-            rc = lib.policy10(*args, out.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p), gr.ctypes.data_as(C.c_void_p))
-            res.append((rc, out, x, gr))
-        (rc_r, o_r, x_r, g_r), (rc_o, o_o, x_o, g_o) = res
+    for trial, (_xp, _drt, args) in enumerate(GU.policy10_trials(policy, conditions)):
+        n = args[2]
+        rc_r, o_r = int(gold["p%d_rc" % policy][trial]), gold["p%d_out" % policy][trial]
+        x_r, g_r = gold["p%d_x" % policy][trial, :n], gold["p%d_g" % policy][trial, :n]
+        rc_o, o_o, x_o, g_o = GU.policy10_run(policy10_ours, args)
         assert rc_r == rc_o and o_r[3] == o_o[3], (trial, rc_r, rc_o, o_r, o_o)
         seen.add(rc_r)
         # The interpolation formulas of the More-Thuente / Nocedal-Wright machines are algebraically the reference's, not

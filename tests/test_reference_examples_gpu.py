@@ -1,15 +1,17 @@
-"""-m gpu: the reference's own example programs, compiled UNMODIFIED against the drop-in headers (tests/ref_examples.py,
+"""-m gpu: the reference's own example programs, compiled UNMODIFIED against the drop-in headers (oracle/ref_examples.py,
 built by __graft_entry__.build() in the container that holds /root/reference), run on the MI355X next to the same
 sources compiled against the reference's headers: same iteration counts, same x and f(x) to 1e-10 (double) / 1e-4
 (float), the self-checking loops pass."""
 import os
 import re
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
-import ref_examples as RX
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+import ref_examples as RX  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 NUM = r"[-+]?(?:\d+\.?\d*(?:[eE][-+]?\d+)?|nan|inf)"
@@ -56,7 +58,7 @@ def _fields(text):
 @pytest.mark.parametrize("name,tol", [("example-quadratic", 1e-10), ("example-rosenbrock", 1e-4), ("example-rosenbrock-box", 1e-10)])
 def test_single_solve_examples_print_what_the_reference_prints(name, tol):
     if not _have(name):
-        pytest.skip("tests/cpp/bin/%s.* not built (needs /root/reference at build time)" % name)
+        pytest.skip("oracle/_ref/examples/%s.* not built (needs /root/reference at build time)" % name)
     gpu, ref = RX.paths(name)
     rc_g, out_g, _ = _run(gpu)
     rc_r, out_r, _ = _run(ref)
@@ -139,7 +141,7 @@ def test_comparison_loop_solve_by_solve(policy):
     points from the Eigen stand-in's own generator: std::rand() is shared with the GPU runtime's threads.)"""
     gpu, ref = RX.paths("cmp_probe")
     if not (os.path.exists(gpu) and os.path.exists(ref)):
-        pytest.skip("tests/cpp/bin/cmp_probe.* not built")
+        pytest.skip("oracle/_ref/examples/cmp_probe.* not built")
     rc_g, out_g, _ = _run(gpu, timeout=300, args=(2, policy, 1024))
     rc_r, out_r, _ = _run(ref, args=(2, policy, 1024))
     assert rc_g == 0 and rc_r == 0, out_g[-2000:]
