@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""bench.py -- L-BFGS iterations/s on MI355X (BASELINE.json metric) + roofline + CPU baseline.
+"""bench.py -- L-BFGS iterations/s on MI355X (BASELINE.json metric) + roofline; with --full every other leg + CPU baseline.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one full L-BFGS iteration (line search with the fused trial kernel, the post-line-search
 pass, history commit and the 2m+1-launch two-loop recursion) on the north-star workload: extended
@@ -11,8 +11,11 @@ its own GPU (the path shards by independent minimisations; no data-path collecti
 iterations/s is reported ("scaling": "weak"); RCCL is used only for the barriers / final gather.  Launched under
 torchrun the ranks come from the environment; launched plainly with --gpus N > 1 the script starts its N ranks itself
 (one process per GPU) and fails if the box has fewer than N devices -- it never reports fewer GPUs than it was asked for.
-The timed window always starts with the history full (c = m), whatever --warmup says.  The default workload's line also
-carries the batched mode of BASELINE.json's cfg5 (the mode that shards problem ids over the GPUs) as "cfg5_batched".
+The timed window always starts with the history full (c = m), whatever --warmup says.  A plain run does only what the
+headline needs: set-up, warm-up, the K timed steps, --dump-outputs, the line (its roofline from the timed window's own
+events).  --full adds, after the timed window, the box's copy / triad probe, the other BASELINE.json configurations as legs
+of the same line (cfg2, cfg3, cfg4 at m = 10 and 20, and the batched mode of cfg5 -- the mode that shards problem ids over
+the GPUs -- as "cfg5_batched"), the CPU baselines and the parity objects against the reference.
 Rank 0 prints ONE JSON line.  --dump-outputs DIR also writes what the timed path computed as .npy files (the inputs are the
 same on every run, so that two builds can be compared output for output).
 """
@@ -391,13 +394,16 @@ def run_batched(args, rank, world, local, comm_dev, dist, steps):
     barrier()
     elapsed = local_elapsed = time.perf_counter() - t0
     st = dict(batch.stats)
-    # the same solve once more with a pair of events around every launch (untimed): the kernels' share of a lock-step iteration
-    batch.set_timing(True)
-    recs2 = batch.minimize(first=first, seed_base=1000)
-    kst = dict(batch.stats)
+    kst = None
+    if args.full:
+        # the same solve once more with a pair of events around every launch (untimed): the kernels' share of a lock-step
+        # iteration
+        batch.set_timing(True)
+        recs2 = batch.minimize(first=first, seed_base=1000)
+        kst = dict(batch.stats)
+        if not (np.array_equal(recs["niter"], recs2["niter"]) and np.array_equal(recs["fx"], recs2["fx"])):
+            raise SystemExit("bench.py: two minimisations of one resident batch disagree")
     batch.close()
-    if not (np.array_equal(recs["niter"], recs2["niter"]) and np.array_equal(recs["fx"], recs2["fx"])):
-        raise SystemExit("bench.py: two minimisations of one resident batch disagree")
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=comm_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -439,10 +445,10 @@ def run_batched(args, rank, world, local, comm_dev, dist, steps):
                             "timed window; the timed window is one minimisation of all problems from their start points "
                             "(start points generated in HBM inside it)" % max(1, min(args.warmup, 2)),
                    # host share of a lock-step iteration: wall (timed run) against the kernels' own durations (events around
-                   # every launch of an identical, untimed run)
+                   # every launch of an identical, untimed run; --full only)
                    "wall_ms_per_step": local_elapsed / max(steps, 1) * 1e3,
-                   "kernel_ms_per_step": kst["kernel_ms"] / max(steps, 1),
-                   "launches_per_step": kst["launches"] / float(max(steps, 1)),
+                   "kernel_ms_per_step": kst["kernel_ms"] / max(steps, 1) if kst else None,
+                   "launches_per_step": (kst or st)["launches"] / float(max(steps, 1)),
                    "host_waits_per_step": st["waits"] / float(max(steps, 1)), "wait_timeouts": st["wait_timeouts"],
                    "per_rank": per_rank if world > 1 else None},
         "roofline": dict({"bound": "hbm", "achieved": model_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -775,8 +781,12 @@ def run_north_star(args, rank, world, local, comm_dev, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    copy_gbs, triad_gbs = C.c_double(), C.c_double()
-    L.check(core.lbfgsx_stream_probe(ctx, 10, C.byref(copy_gbs), C.byref(triad_gbs)))
+    # the box's own copy / triad rates (a run of their own, after the window): --full only
+    copy_gbs = triad_gbs = None
+    if args.full:
+        cg, tg = C.c_double(), C.c_double()
+        L.check(core.lbfgsx_stream_probe(ctx, 10, C.byref(cg), C.byref(tg)))
+        copy_gbs, triad_gbs = cg.value, tg.value
     core.lbfgsx_persistent_launches.restype = C.c_int64
     core.lbfgsx_persistent_launches.argtypes = [C.c_void_p]
     persist_launches = core.lbfgsx_persistent_launches(ctx)
@@ -810,7 +820,7 @@ def run_north_star(args, rank, world, local, comm_dev, dist):
         dist.all_reduce(one)
         ranks_counted = int(round(float(one.item())))
     per_rank = gather_objects({"rank": rank, "device": local, "value": K / local_elapsed, "ms_per_step": local_elapsed / K * 1e3,
-                               "stream_copy_GBs": copy_gbs.value, "rows": n}, rank, world, dist)
+                               "stream_copy_GBs": copy_gbs, "rows": n}, rank, world, dist)
     if rank != 0:
         return None
 
@@ -888,8 +898,8 @@ def run_north_star(args, rank, world, local, comm_dev, dist):
                      "apply_Hv_ms": hv_ms / max(hv_n, 1),
                      # bytes of the steps that actually ran in the window / their time
                      "apply_Hv_GBs": (per_launch_bytes * tl_n / (hv_ms * 1e-3) / 1e9) if hv_ms > 0 else None,
-                     "stream_copy_GBs": copy_gbs.value, "stream_triad_GBs": triad_gbs.value,
-                     "frac_of_stream_copy": achieved / copy_gbs.value if copy_gbs.value else None},
+                     "stream_copy_GBs": copy_gbs, "stream_triad_GBs": triad_gbs,
+                     "frac_of_stream_copy": achieved / copy_gbs if copy_gbs else None},
     }
     if world > 1:
         out["per_rank"] = per_rank
@@ -911,7 +921,7 @@ def run_north_star(args, rank, world, local, comm_dev, dist):
                            "combine": {"kernel": "k_gs_combine_mx" if f32h else "k_gs_combine", "algorithmic_bytes_per_launch": comb_bytes,
                                        "avg_launch_ms": comb_s * 1e3,
                                        "achieved": comb_bytes / comb_s / 1e9 if comb_s > 0 else 0.0},
-                           "stream_copy_GBs": copy_gbs.value, "stream_triad_GBs": triad_gbs.value}
+                           "stream_copy_GBs": copy_gbs, "stream_triad_GBs": triad_gbs}
     return out
 
 
@@ -996,7 +1006,7 @@ def run_single_process(args, ndev_asked):
     out["config"]["process_model"] = "one process, one host thread + one solver context per GPU (devices %r)" % devices
     out["collective"] = {"backend": "threads for the barriers; RCCL (dlopen, ncclCommInitAll) for the batch's record gather",
                          "world_size": world, "data_path_collectives": 0}
-    if args.workload == "north-star" and args.recursion == "vector" and not args.no_batched:
+    if args.full and args.workload == "north-star" and args.recursion == "vector" and not args.no_batched:
         n, m, P, steps = 100000, 10, args.problems_per_gpu, args.batched_steps
         total = P * world
         par = A.LBFGSParam(m=m, epsilon=0.0, epsilon_rel=0.0, max_iterations=steps)
@@ -1068,11 +1078,14 @@ def run_single_process(args, ndev_asked):
 
 
 def run_all(args, rank, world, local, comm_dev, dist, batched=True):
-    """Everything one rank does for the chosen workload; the result object on rank 0 (None elsewhere)."""
+    """Everything one rank does for the chosen workload; the result object on rank 0 (None elsewhere).  Without --full that
+    is the timed workload alone; --full adds the other legs, the CPU baselines and the parity objects."""
     if args.workload == "cfg5-batched":
         out = run_batched(args, rank, world, local, comm_dev, dist, args.steps)
     else:
         out = run_north_star(args, rank, world, local, comm_dev, dist)
+        if not args.full:
+            return out
         if args.workload == "north-star" and args.recursion == "vector" and not args.no_batched and batched:
             # the mode that shards naturally (SURVEY 8(e)): same ranks, same barriers, reported inside the one line
             b = run_batched(args, rank, world, local, comm_dev, dist, args.batched_steps)
@@ -1230,34 +1243,39 @@ def main():
     ap.add_argument("--n", type=float, default=1e8)
     ap.add_argument("--m", type=int, default=10)
     ap.add_argument("--objective", default="rosenbrock", choices=["rosenbrock", "quadratic"])
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the timed workload: the box's copy / triad probe, the cfg2 / cfg3 / cfg4 / cfg5 legs, "
+                         "the CPU baselines and the parity objects, the cfg5 batch's instrumented repeat; a plain run only "
+                         "sets up, warms up, times --steps, writes --dump-outputs and prints the line")
     ap.add_argument("--cpu-n", type=float, default=2e7)
     ap.add_argument("--cpu-steps", type=int, default=6)
     ap.add_argument("--cpu-n-all", type=float, default=2e7, help="problem size of the all-cores CPU baseline")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-full", default="auto", choices=["auto", "on", "off"],
-                    help="1-core reference at the metric's own n (m+2 warm-up + --cpu-full-steps timed iterations of one run, "
-                         "un-extrapolated); auto: when the host has >= 48 GB available")
+                    help="with --full: 1-core reference at the metric's own n (m+2 warm-up + --cpu-full-steps timed iterations "
+                         "of one run, un-extrapolated); auto: when the host has >= 48 GB available")
     ap.add_argument("--cpu-full-steps", type=int, default=3)
     ap.add_argument("--cpu-full-dd", action="store_true",
-                    help="with the --cpu-full run: repeat it with the reference built on double-double sums and report the GPU "
-                         "iterate against that one too (`parity_dd`; the expectation is max_abs_dx = 0)")
+                    help="with the --full --cpu-full run: repeat it with the reference built on double-double sums and report "
+                         "the GPU iterate against that one too (`parity_dd`; the expectation is max_abs_dx = 0)")
     ap.add_argument("--workload", default="north-star", choices=["north-star", "cfg5-batched", "sharded"],
-                    help="north-star (default, the BASELINE.json metric: one problem per GPU; its line also carries the "
-                         "cfg5 batch as `cfg5_batched`), the batched cfg5 shard per GPU alone, or sharded: ONE problem of "
+                    help="north-star (default, the BASELINE.json metric: one problem per GPU; with --full its line also "
+                         "carries the cfg5 batch as `cfg5_batched`), the batched cfg5 shard per GPU alone, or sharded: ONE problem of "
                          "--n rows row-sharded over the ranks (strong scaling; opt-in Gram-space recursion, all-reduces "
                          "of <= 6m+7 doubles over RCCL)")
     ap.add_argument("--problems-per-gpu", type=int, default=1024)
     ap.add_argument("--batched-n", type=float, default=1e5, help="dimension of the batched leg's problems (cfg5: 1e5)")
     ap.add_argument("--batched-dtype", default="f32", choices=["f32", "f64"], help="scalar type of the batched leg (cfg5: f32)")
-    ap.add_argument("--batched-steps", type=int, default=50, help="iterations per problem of the cfg5 leg of the default line")
-    ap.add_argument("--no-batched", action="store_true", help="skip the cfg5 leg of the default line")
+    ap.add_argument("--batched-steps", type=int, default=50, help="iterations per problem of the cfg5 leg of the --full line")
+    ap.add_argument("--no-batched", action="store_true", help="skip the cfg5 leg of the --full line")
     ap.add_argument("--single-process", action="store_true",
                     help="--gpus N from ONE process: one host thread + one context per GPU, the batch through "
                          "one resident lock-step batch per device and the record gather natively over RCCL")
     ap.add_argument("--verbose", action="store_true",
-                    help="the full line (~15 KB: explanatory notes, per-iteration times); the default line drops them (< 7 KB)")
+                    help="the uncompacted line (explanatory notes, per-iteration times: ~15 KB with --full); the default line "
+                         "drops them (< 7 KB)")
     ap.add_argument("--full-json", default=None, help="also write the full (verbose) object to this file")
-    ap.add_argument("--no-legs", action="store_true", help="skip the cfg2 / cfg3 / cfg4 legs of the default line")
+    ap.add_argument("--no-legs", action="store_true", help="skip the cfg2 / cfg3 / cfg4 legs of the --full line")
     ap.add_argument("--cfg4-n", type=float, default=1e7, help="problem size of the L-BFGS-B leg (cfg4)")
     ap.add_argument("--cfg4-iters", type=int, default=40, help="iterations from x0 of the L-BFGS-B leg (cfg4)")
     ap.add_argument("--no-cfg4-m20", action="store_true", help="skip the m = 20 repetition of the L-BFGS-B leg")
@@ -1272,6 +1290,8 @@ def main():
                          "the vector form only up to rounding; gram-f32h: the same with S, Y stored as float (SURVEY "
                          "8(f)-4) -- both reported under their own metric names")
     args = ap.parse_args()
+    if not args.full and (args.cpu_full == "on" or args.cpu_full_dd):
+        raise SystemExit("bench.py: --cpu-full on / --cpu-full-dd belong to the --full run")
     launched = "WORLD_SIZE" in os.environ
     if args.gpus is None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))

@@ -23,7 +23,7 @@ for k in sorted(g):
 P
   for e in example-quadratic example-rosenbrock example-rosenbrock-box; do echo "== $e (GPU build)"; ./$e.gpu | head -4; done
 ) > $O/reference_examples.txt 2>&1
-LBFGSX_BENCH_DEVICES=0,0 python bench.py --single-process --gpus 2 --no-cpu --no-legs --n 4e7 --problems-per-gpu 512 > $O/bench_single_process_2x.json 2> /dev/null
+LBFGSX_BENCH_DEVICES=0,0 python bench.py --full --single-process --gpus 2 --no-cpu --no-legs --n 4e7 --problems-per-gpu 512 > $O/bench_single_process_2x.json 2> /dev/null
 if [ -z "$SKIP_DRIFT" ]; then python scripts/drift_curves.py cfg4 --n 1e7 --iters 40 --devmin default > $O/drift_cfg4_1e7_40it.json 2> $O/drift.err; python -c "
 import json; d=json.load(open('$O/drift_cfg4_1e7_40it.json')); print(str(d)[:600])"; fi
 head -14 $O/reference_examples.txt

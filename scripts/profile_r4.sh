@@ -24,11 +24,11 @@ prof3 cfg4_m20 b python scripts/bench_lbfgsb.py --n 1e7 --m 20 --iters 60
 TL_ITERS=60 python scripts/trace_cfg4.py $O/cfg4_m20 > $O/cfg4_m20_timeline.txt 2>&1
 python scripts/bench_lbfgsb.py --n 1e7 --iters 40 --cpu-n 2e5 > $O/bench_cfg4_lbfgsb.json 2> /dev/null
 # cfg5 batch
-prof3 batched bench python bench.py --workload cfg5-batched --steps 50 --no-cpu
+prof3 batched bench python bench.py --full --workload cfg5-batched --steps 50 --no-cpu
 mv $O/batched $O/batched_trace
 # row-sharded mode: one rank through RCCL; two ranks of one process on the one device (host-memory sums)
-python bench.py --workload sharded --no-cpu > $O/bench_sharded_n1.json 2> /dev/null
-LBFGSX_BENCH_DEVICES=0,0 python bench.py --workload sharded --single-process --gpus 2 --no-cpu --n 4e7 > $O/bench_sharded_one_process_2x.json 2> /dev/null
+python bench.py --full --workload sharded --no-cpu > $O/bench_sharded_n1.json 2> /dev/null
+LBFGSX_BENCH_DEVICES=0,0 python bench.py --full --workload sharded --single-process --gpus 2 --no-cpu --n 4e7 > $O/bench_sharded_one_process_2x.json 2> /dev/null
 # keep only what the summaries need (the raw traces are large)
 find $O -name "*.csv" ! -name "*kernel_stats.csv" ! -name "*counter_collection.csv" ! -name "*kernel_trace.csv" -delete
 find $O -path "*pmc*" -name "*kernel_trace.csv" -delete

@@ -93,7 +93,7 @@ def cfg5(prefix, n, m, problems, iters):
     return {"leg": "cfg5", "n": n, "m": m, "hbm_bytes": tot / float(problems * iters * solves),
             "per": "problem-iteration, mean over the %d lock-step iterations from x0 of %d problems (history filling during the first %d), "
                    "%d identical minimisations in the profiled command; all kb_* launches counted" % (iters, problems, m, solves),
-            "how": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of bench.py --workload cfg5-batched --steps %d --no-cpu, taken separately" % iters,
+            "how": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of bench.py --full --workload cfg5-batched --steps %d --no-cpu, taken separately" % iters,
             "one_launch_iteration_full_history_hbm_bytes_per_problem": (max(full) / problems) if full else None}
 
 

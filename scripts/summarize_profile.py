@@ -46,7 +46,7 @@ with open(os.path.join(src, "trace", "bench_kernel_stats.csv")) as f:
 
 out = {"round": rnd, "n": 100000000, "m": 10,  # bench.py's defaults: the profiled command passes no --n / --m
        "command": "rocprofv3 {--kernel-trace --stats | --pmc FETCH_SIZE | --pmc WRITE_SIZE} "
-                                "--output-format csv -- python bench.py --no-cpu --steps 10 --warmup 11",
+                                "--output-format csv -- python bench.py --full --no-cpu --steps 10 --warmup 11",
        "units": "FETCH_SIZE/WRITE_SIZE in KiB; hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 (gfx950 correction)",
        "kernels": {}}
 for k, c in sorted(agg.items()):
@@ -140,7 +140,7 @@ def gram_summary(prefix, tag, flag, kprefix="k_gs_", note=None):
 
 gram_summary("gram", "gram", "--recursion gram")
 gram_summary("f32h", "gram_f32h", "--recursion gram-f32h")
-# cfg5: 1024 lock-step f32 problems of n = 1e5 (bench.py --workload cfg5-batched --steps 50)
+# cfg5: 1024 lock-step f32 problems of n = 1e5 (bench.py --full --workload cfg5-batched --steps 50)
 gram_summary("batched", "batched", "--workload cfg5-batched --steps 50 --no-cpu", kprefix="kb_",
              note="one launch covers the 1024 problems of the batch; launches start from an empty history (m = 10), "
                   "max_* are the full-history launches: kb_twoloop_full reads 4m columns-worth of f32 per problem "

@@ -3,6 +3,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -25,10 +26,10 @@ def _run(*extra, gpus=1, warmup=12, env=None, verbose=True):
 
 def test_default_line_has_the_contract_keys(tmp_path):
     full = str(tmp_path / "full.json")
-    line = _run("--cpu-n", "2000000", "--cpu-steps", "4", "--cpu-n-all", "2000000", "--cpu-full", "off", "--full-json", full,
-                verbose=False)
-    # The default line is the compact one: under 7 KB (the driver keeps the last 8 KB of it), the contract keys and the two
-    # required objects at the top, every leg reduced to its figures, and `legs_digest` as the LAST key so that whatever tail
+    line = _run("--full", "--cpu-n", "2000000", "--cpu-steps", "4", "--cpu-n-all", "2000000", "--cpu-full", "off", "--full-json",
+                full, verbose=False)
+    # The default line is the compact one, and with --full it carries every leg: under 7 KB (the driver keeps the last 8 KB of
+    # it), the contract keys and the two required objects at the top, every leg reduced to its figures, and `legs_digest` as the LAST key so that whatever tail
     # survives holds every leg's value and fractions.  The full object (--verbose prints it, --full-json writes it) is what
     # the rest of this test reads.
     raw = json.dumps(line)
@@ -138,10 +139,37 @@ def test_default_line_has_the_contract_keys(tmp_path):
         assert (rr["traffic"] is None) == (rr.get("traffic_source") is None)
 
 
+def test_plain_line_is_the_headline_alone(tmp_path):
+    """Without --full a run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs and the line.
+    Its headline keys are those of the --full line; no other leg, CPU baseline, parity object or copy probe runs, and the
+    run spends little time outside its steps."""
+    t0 = time.perf_counter()
+    line = _run("--dump-outputs", str(tmp_path / "out"), verbose=False)
+    wall = time.perf_counter() - t0
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "roofline"):
+        assert k in line, k
+    assert line["metric"] == "L-BFGS iterations/sec at n=10^8, m=10; achieved HBM GB/s vs peak"   # BASELINE.json's metric
+    assert line["unit"] == "iterations/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["steps"] == 3 and line["warmup"] == 12 and abs(line["ms_per_step"] * line["value"] - 1e3) < 1e-6 * 1e3
+    for k in ("cfg2", "cfg3", "cfg4_lbfgsb", "cfg4_m20", "cfg5_batched", "cpu_baseline", "cpu_baseline_sample",
+              "cpu_baseline_all_cores", "cpu_baseline_full", "parity", "parity_dd"):
+        assert k not in line, k
+    assert list(line)[-1] == "legs_digest" and list(line["legs_digest"]) == ["north_star"]
+    # the roofline comes from the timed window's own events; the copy probe is a run of its own (--full)
+    r = line["roofline"]
+    assert 0.3 < r["frac"] < 1.0 and r["launches_timed"] == 3 * 21 and r["stream_copy_GBs"] is None
+    assert line["config"]["history_full"] is True
+    assert sorted(os.listdir(tmp_path / "out")) == ["direction.npy", "grad.npy", "index.npy", "result.npy", "x.npy"]
+    # the whole run, interpreter start-up included, less the warm-up and timed iterations
+    outside = wall - (12 + 3) * line["ms_per_step"] * 1e-3
+    assert outside < 30.0, "a plain run spent %.1f s outside its steps" % outside
+
+
 def test_cpu_baseline_at_the_metric_size_is_measured_not_scaled():
     """--cpu-full on (at a size this test can afford): `cpu_baseline` is the un-extrapolated figure of ONE run whose
     iteration boundaries come from the functor-call clock; the scaled small-n sample rides along."""
-    d = _run("--n", "4000000", "--cpu-full", "on", "--cpu-n", "1000000", "--cpu-steps", "3", "--cpu-n-all", "1000000",
+    d = _run("--full", "--n", "4000000", "--cpu-full", "on", "--cpu-n", "1000000", "--cpu-steps", "3", "--cpu-n-all", "1000000",
              "--no-batched", "--no-legs")
     c = d["cpu_baseline"]
     assert c["extrapolated"] is False and c["measured_n"] == 4000000 and c["cores"] == 1 and c["timed_iterations"] == 3
@@ -206,7 +234,7 @@ def test_gpus_2_starts_two_ranks_or_refuses():
     import lbfgspp_amd as A
     ndev = A.load()[0].lbfgsx_device_count()
     env = {} if ndev >= 2 else {"LBFGSX_BENCH_FORCE_DEVICE": "0"}
-    d = _run("--no-cpu", "--n", "20000000", "--problems-per-gpu", "256", gpus=2, env=env)
+    d = _run("--full", "--no-cpu", "--n", "20000000", "--problems-per-gpu", "256", gpus=2, env=env)
     assert d["n_gpus"] == 2 and d["cfg5_batched"]["n_gpus"] == 2 and d["cfg5_batched"]["config"]["problems_total"] == 512
     assert d["config"]["history_full"] is True
     # the N > 1 line explains itself: what every rank saw, which collective library carried the (non data-path) exchanges
@@ -232,7 +260,7 @@ def test_single_process_drives_every_listed_device():
     import lbfgspp_amd as A
     ndev = A.load()[0].lbfgsx_device_count()
     env = {} if ndev >= 2 else {"LBFGSX_BENCH_DEVICES": "0,0"}
-    d = _run("--single-process", "--no-cpu", "--n", "20000000", "--problems-per-gpu", "128", gpus=2, env=env)
+    d = _run("--full", "--single-process", "--no-cpu", "--n", "20000000", "--problems-per-gpu", "128", gpus=2, env=env)
     assert d["n_gpus"] == 2 and len(d["per_rank"]) == 2 and [p["rank"] for p in d["per_rank"]] == [0, 1]
     assert all(p["value"] > 0 and p["stream_copy_GBs"] > 0 for p in d["per_rank"])
     assert abs(d["value"] - 2 * d["steps"] / (d["ms_per_step"] * d["steps"] * 1e-3)) < 1e-6 * d["value"]
@@ -251,8 +279,8 @@ def test_north_star_parity_object_at_a_size_this_test_can_afford():
     """`parity` of the default line: the reference's own run (native accumulators, the same instance, --cpu-full) against the
     GPU solver, all n coordinates.  Here at n = 1e7 (the default line does it at n = 1e8); --cpu-full-dd adds the comparison
     with the reference built on the parity contract's extended sums, where nothing may differ."""
-    d = _run("--n", "10000000", "--cpu-full", "on", "--cpu-full-dd", "--cpu-n", "1000000", "--cpu-steps", "3", "--cpu-n-all", "1000000",
-             "--no-batched", "--no-legs")
+    d = _run("--full", "--n", "10000000", "--cpu-full", "on", "--cpu-full-dd", "--cpu-n", "1000000", "--cpu-steps", "3",
+             "--cpu-n-all", "1000000", "--no-batched", "--no-legs")
     p = d["parity"]
     assert p["n"] == 10000000 and p["m"] == 10 and p["iterations"] == 15 and p["iterations_equal"] and p["nfev_equal"]
     assert p["max_abs_dx"] <= 1e-10 and p["within_tolerance"] is True and p["fx_rel_diff"] <= 1e-11

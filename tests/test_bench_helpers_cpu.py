@@ -37,6 +37,15 @@ def test_every_leg_of_the_default_line_finds_its_pmc_summary():
     assert b.traffic_fields(None) == {"traffic": None, "traffic_static": None, "traffic_source": None}
 
 
+def test_cpu_full_options_belong_to_the_full_run():
+    """--cpu-full on and --cpu-full-dd configure a run that only --full starts: without it bench.py refuses before it touches
+    a GPU, instead of ignoring them."""
+    for extra in (["--cpu-full", "on"], ["--cpu-full-dd"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1"] + extra, capture_output=True,
+                           text=True, timeout=120)
+        assert r.returncode != 0 and "--full" in r.stderr and not r.stdout.strip(), (extra, r.stderr[-500:])
+
+
 def test_pmc_legs_matches_the_two_counter_passes_dispatch_by_dispatch(tmp_path):
     """scripts/r4/pmc_legs.py on a hand-made pair of passes: 12 warm-up + 4 iterations of a two-kernel 'solver'; FETCH_SIZE is
     doubled (gfx950), counters are KiB, the window is the second half of the iterations, delimited by the post kernel."""
