@@ -5,7 +5,8 @@
 // LineSearchNocedalWright -- one machine per problem, advanced one trial per launch; problems that converge, fail or
 // finish a line search early simply sit out of the following launches.  The objective is a built-in one evaluated
 // inside the fused kernels (extended Rosenbrock, diagonal quadratic; BatchObjective) or a device functor evaluated by
-// the caller over the whole batch between two library launches (BatchFunctor).  Per problem the arithmetic is identical
+// the caller over the whole batch between two library launches (BatchFunctor; BatchPackedFunctor for a caller that wants
+// the evaluating problems as one [nact][n] array).  Per problem the arithmetic is identical
 // to the single-problem path, so results are bit-identical to LBFGSSolver<Scalar, LineSearch> on the same problem.
 #ifndef LBFGSX_DROPIN_LBFGS_BATCHED_H
 #define LBFGSX_DROPIN_LBFGS_BATCHED_H
@@ -50,6 +51,23 @@ struct BatchFunctor
 {
     std::function<void(lbfgsx_batch*)> start;
     std::function<void(lbfgsx_batch*, const int*, Scalar*)> eval;
+};
+
+// The same for a caller that wants the batch as ONE array (the C ABI's lbfgsx_lockstep_minimize_fn, a torch callable):
+//   x0                                  count x n start points, row-major, host or device memory
+//   eval(nact, ids, X, G, ld, fx)       row k (ld elements apart) of the packed device arrays X, G belongs to problem ids[k],
+//                                       k < nact; writes grad f(X row k) to G row k and f to fx[k] (host); returns 0, or
+//                                       non-zero to end the minimisation (UserAbort).  The library has drained its stream and
+//                                       made the batch's device current; the callback's work is complete when it returns.
+// Problems that have converged, failed or do not evaluate in this lock-step turn are not in the list.  The library's launches
+// around the call are lbfgsx_bat_pack (x = xp + step * drt into the problem's point slot AND its packed row) and
+// lbfgsx_bat_unpack (packed gradient row -> gradient slot, grad . drt in that pass); the first evaluation finds every problem
+// at point 0, whose rows are already contiguous, and is handed that slot itself.
+template <typename Scalar>
+struct BatchPackedFunctor
+{
+    const void* x0 = nullptr;
+    std::function<int(int, const std::int64_t*, const Scalar*, Scalar*, std::int64_t, double*)> eval;
 };
 
 template <typename Scalar, template <class> class LineSearch = LineSearchMoreThuente>
@@ -127,6 +145,7 @@ public:
         bool fused = false;
         double kernel_ms = 0.0;
         std::int64_t launches = 0, waits = 0, wait_timeouts = 0;
+        std::int64_t user_calls = 0;  // calls of a BatchPackedFunctor's eval
     };
     Stats stats;
 
@@ -167,10 +186,86 @@ public:
             throw std::invalid_argument("LBFGSBatchedSolver::minimize: the functor needs both start and eval");
         run(n, 0, 0, count, device, out, x_out, BatchObjective(), &f);
     }
+    // ... and for one that sees the evaluating problems as one packed array (BatchPackedFunctor)
+    void minimize(const BatchPackedFunctor<Scalar>& f, std::int64_t n, int count, int device, std::vector<Item>& out,
+                  Scalar* x_out = nullptr)
+    {
+        if (!f.x0 || !f.eval)
+            throw std::invalid_argument("LBFGSBatchedSolver::minimize: the functor needs both x0 and eval");
+        run(n, 0, 0, count, device, out, x_out, BatchObjective(), nullptr, &f);
+    }
+
+private:
+    // ---- a BatchPackedFunctor around the library's launches; res as the built-in launches fill it
+    void packed_call(lbfgsx_batch* c, const BatchPackedFunctor<Scalar>& f, int nact, const std::vector<std::int64_t>& ids,
+                     const void* X, void* G, std::vector<double>& fx)
+    {
+        detail::check(lbfgsx_bat_sync(c));  // the points are written: the callback may use any stream
+        struct Current
+        {
+            int prev = -1;
+            explicit Current(lbfgsx_batch* b) { detail::check(lbfgsx_bat_device_push(b, &prev)); }
+            ~Current() { (void) lbfgsx_device_pop(prev); }
+        } current(c);
+        stats.user_calls++;
+        const int rc = f.eval(nact, ids.data(), static_cast<const Scalar*>(X), static_cast<Scalar*>(G), lbfgsx_bat_ld(c), fx.data());
+        if (rc != 0)
+            throw UserAbort("the objective callback returned " + std::to_string(rc) + " at its call " +
+                            std::to_string(stats.user_calls) + " of this minimisation");
+    }
+    // {f, grad.grad, x.x} at point 0 of every problem: the slot's rows are contiguous, it is the packed array
+    void packed_first(lbfgsx_batch* c, const BatchPackedFunctor<Scalar>& f, const std::vector<lbfgsx_bat_desc>& desc,
+                      std::vector<double>& res)
+    {
+        const int P = int(desc.size());
+        std::vector<std::int64_t> ids(static_cast<size_t>(P));
+        std::vector<double> fx(static_cast<size_t>(P)), nrm(static_cast<size_t>(P) * 2);
+        for (int p = 0; p < P; p++)
+            ids[size_t(p)] = p;
+        packed_call(c, f, P, ids, lbfgsx_bat_vec(c, 0, 0, 0), lbfgsx_bat_vec(c, 1, 0, 0), fx);
+        detail::check(lbfgsx_bat_launch(c, LBFGSX_BAT_NORMS, LBFGSX_OBJ_NONE, desc.data(), 2, nrm.data()));
+        for (int p = 0; p < P; p++)
+        {
+            res[size_t(p) * 3 + 0] = fx[size_t(p)];
+            res[size_t(p) * 3 + 1] = nrm[size_t(p) * 2 + 0];
+            res[size_t(p) * 3 + 2] = nrm[size_t(p) * 2 + 1];
+        }
+    }
+    // x_out = x_in + step * drt; {f, grad.drt} there, for every active problem
+    void packed_trial(lbfgsx_batch* c, const BatchPackedFunctor<Scalar>& f, std::vector<lbfgsx_bat_desc>& desc,
+                      std::vector<double>& res)
+    {
+        const int P = int(desc.size());
+        std::vector<std::int64_t> ids;
+        for (int p = 0; p < P; p++)
+            if (desc[size_t(p)].active)
+            {
+                desc[size_t(p)].col_u = int(ids.size());  // its packed row
+                ids.push_back(p);
+            }
+        const int nact = int(ids.size());
+        if (nact == 0)
+            return;
+        std::vector<double> fx(static_cast<size_t>(nact)), dg(static_cast<size_t>(P));
+        void* X = lbfgsx_bat_packed(c, 0);
+        void* G = lbfgsx_bat_packed(c, 1);
+        if (!X || !G)
+            throw std::runtime_error(lbfgsx_last_error());
+        detail::check(lbfgsx_bat_pack(c, desc.data()));
+        packed_call(c, f, nact, ids, X, G, fx);
+        detail::check(lbfgsx_bat_unpack(c, desc.data(), dg.data()));
+        for (int k = 0; k < nact; k++)
+        {
+            const size_t p = size_t(ids[size_t(k)]);
+            res[p * 2 + 0] = fx[size_t(k)];
+            res[p * 2 + 1] = dg[p];
+        }
+    }
 
 private:
     void run(std::int64_t n, std::uint64_t seed_base, std::int64_t first, int count, int device, std::vector<Item>& out,
-             Scalar* x_out, const BatchObjective& bobj, const BatchFunctor<Scalar>* fun)
+             Scalar* x_out, const BatchObjective& bobj, const BatchFunctor<Scalar>* fun,
+             const BatchPackedFunctor<Scalar>* pk = nullptr)
     {
         using std::abs;
         using std::sqrt;
@@ -199,7 +294,7 @@ private:
         if (lbfgsx_bat_iterate_ok(c))
         {
             stats.fused = true;
-            run_fused(c, n, seed_base, first, count, out, x_out, bobj, fun);
+            run_fused(c, n, seed_base, first, count, out, x_out, bobj, fun, pk);
             return;
         }
         auto YS = [&](int col) { return lbfgsx_bat_scalar_index(c, 0, col); };
@@ -346,6 +441,11 @@ private:
         };
         // {f, grad.grad, x.x} at x_in of every active problem
         auto launch_eval = [&]() {
+            if (pk)
+            {
+                packed_first(c, *pk, desc, res);
+                return;
+            }
             if (!fun)
             {
                 detail::check(lbfgsx_bat_launch(c, LBFGSX_BAT_EVAL, bobj.id, desc.data(), 3, res.data()));
@@ -362,6 +462,11 @@ private:
         };
         // x_out = x_in + step * drt; {f, grad.drt} there
         auto launch_trial = [&]() {
+            if (pk)
+            {
+                packed_trial(c, *pk, desc, res);
+                return;
+            }
             if (!fun)
             {
                 detail::check(lbfgsx_bat_launch(c, LBFGSX_BAT_TRIAL, bobj.id, desc.data(), 2, res.data()));
@@ -378,7 +483,9 @@ private:
         };
 
         // fx = f(x, grad); gnorm                                                   (LBFGS.h:91-103)
-        if (fun)
+        if (pk)
+            detail::check(lbfgsx_bat_set_x0(c, pk->x0));
+        else if (fun)
             fun->start(c);
         else if (bobj.id == LBFGSX_OBJ_DIAG_QUAD)
             detail::check(lbfgsx_bat_gen_diag_quad(c, bobj.kappa, seed_base + std::uint64_t(first)));
@@ -579,7 +686,8 @@ private:
     // host applies the reference's tests to the sums in the reference's order; a problem that stops has had its direction
     // and first trial computed in vain, nothing else.
     void run_fused(lbfgsx_batch* c, std::int64_t n, std::uint64_t seed_base, std::int64_t first, int count, std::vector<Item>& out,
-                   Scalar* x_out, const BatchObjective& bobj, const BatchFunctor<Scalar>* fun)
+                   Scalar* x_out, const BatchObjective& bobj, const BatchFunctor<Scalar>* fun,
+                   const BatchPackedFunctor<Scalar>* pk)
     {
         using std::abs;
         using std::sqrt;
@@ -587,7 +695,7 @@ private:
         const int OUT0 = lbfgsx_bat_scalar_index(c, 3, 0);
         const int fpast = m_param.past;
         constexpr Scalar eps = std::numeric_limits<Scalar>::epsilon();
-        const bool fuse_trial = (fun == nullptr);
+        const bool fuse_trial = (fun == nullptr && pk == nullptr);  // the in-kernel first trial cannot host a callback
 
         std::vector<Prob> pr(static_cast<size_t>(P));
         for (int p = 0; p < P; p++)
@@ -620,6 +728,11 @@ private:
             fun->eval(c, fpoint.data(), ffx.data());
         };
         auto launch_eval = [&]() {  // {f, grad.grad, x.x} at x_in of every active problem
+            if (pk)
+            {
+                packed_first(c, *pk, desc, res);
+                return;
+            }
             if (!fun)
             {
                 detail::check(lbfgsx_bat_launch(c, LBFGSX_BAT_EVAL, bobj.id, desc.data(), 3, res.data()));
@@ -635,6 +748,11 @@ private:
             }
         };
         auto launch_trial = [&]() {  // x_out = x_in + step * drt; {f, grad.drt} there
+            if (pk)
+            {
+                packed_trial(c, *pk, desc, res);
+                return;
+            }
             if (!fun)
             {
                 detail::check(lbfgsx_bat_launch(c, LBFGSX_BAT_TRIAL, bobj.id, desc.data(), 2, res.data()));
@@ -651,7 +769,9 @@ private:
         };
 
         // fx = f(x, grad); gnorm                                                   (LBFGS.h:91-103)
-        if (fun)
+        if (pk)
+            detail::check(lbfgsx_bat_set_x0(c, pk->x0));
+        else if (fun)
             fun->start(c);
         else if (bobj.id == LBFGSX_OBJ_DIAG_QUAD)
             detail::check(lbfgsx_bat_gen_diag_quad(c, bobj.kappa, seed_base + std::uint64_t(first)));

@@ -45,6 +45,13 @@ template <> struct dtype_of<double> { static constexpr int value = LBFGSX_F64; }
 template <> struct dtype_of<float> { static constexpr int value = LBFGSX_F32; };
 }  // namespace detail
 
+// What a caller-supplied objective throws to end the minimisation (the C ABI's callbacks return non-zero: LBFGSX_E_USER).
+// It leaves minimize() like any exception of a device functor: x as Evaluator::trial_written decides.
+struct UserAbort : std::runtime_error
+{
+    using std::runtime_error::runtime_error;
+};
+
 // A non-owning handle on a device-resident vector, handed to device functors.
 template <typename Scalar>
 class DeviceVector

@@ -34,7 +34,8 @@ enum
     LBFGSX_E_LOGIC = -2,   /* -> std::logic_error */
     LBFGSX_E_RUNTIME = -3, /* -> std::runtime_error */
     LBFGSX_E_HIP = -4,     /* HIP runtime failure (message holds hipGetErrorString) */
-    LBFGSX_E_NOGPU = -5    /* no usable device: the product never falls back to a CPU path */
+    LBFGSX_E_NOGPU = -5,   /* no usable device: the product never falls back to a CPU path */
+    LBFGSX_E_USER = -6     /* a caller-supplied objective callback returned non-zero (include/lbfgsx_solver.h) */
 };
 /* flags for lbfgsx_create */
 enum { LBFGSX_FLAG_BOUNDED = 1 /* allocate the L-BFGS-B work set (lb, ub, xcp, masks, sort buffers) */ };
@@ -571,6 +572,26 @@ int lbfgsx_bat_timing_read(lbfgsx_batch* c, double out[4]);
 int lbfgsx_bat_fetch(lbfgsx_batch* c, const int* idx, double* out);
 int lbfgsx_bat_download_x(lbfgsx_batch* c, int p, int point, void* host);
 int lbfgsx_bat_sync(lbfgsx_batch* c);
+/* ---- a user objective that sees the batch as ONE packed array (lbfgsx_lockstep_minimize_fn, include/lbfgsx_solver.h) ----
+ * The trial of problem p lives in its own point slot (desc[p].x_out), a different one per problem, so the rows of the
+ * evaluating problems are neither adjacent nor in one slot.  These two launches replace LBFGSX_BAT_POINT and LBFGSX_BAT_GDOT
+ * around the caller's evaluation and keep a packed copy: row k (lbfgsx_bat_ld() elements apart) of lbfgsx_bat_packed(c, 0)
+ * holds the trial point of the k-th evaluating problem, row k of lbfgsx_bat_packed(c, 1) receives its gradient.
+ *   lbfgsx_bat_pack    for every active p: x(x_out) = x(x_in) + step * drt, written to the point slot AND to packed row
+ *                      desc[p].col_u in the same pass (one read of xp and of drt, two writes): 4 n elements per problem
+ *   lbfgsx_bat_unpack  for every active p: packed gradient row desc[p].col_u -> gradient slot of x_out, and grad . drt
+ *                      formed in that pass (one read of the row and of drt, one write: 3 n elements); out[p] = that sum,
+ *                      the bits LBFGSX_BAT_GDOT returns for the same gradient (same accumulators, csrc/reduce.cuh)
+ * Both refuse a descriptor table whose active entries name a point outside 0..2, x_in == x_out, a row outside 0..P-1, one
+ * row twice or a scalar index outside the table (LBFGSX_E_INVALID, nothing launched).  lbfgsx_bat_packed allocates the two
+ * arrays on first use (2 P ld elements) and returns NULL when it cannot.  lbfgsx_bat_set_x0 places P start points (src:
+ * P x n elements, row-major, host or device memory) in point 0.  lbfgsx_bat_device_push makes the batch's device current
+ * for the calling thread as lbfgsx_device_push does for a context (undo with lbfgsx_device_pop). */
+void* lbfgsx_bat_packed(lbfgsx_batch* c, int kind);
+int lbfgsx_bat_pack(lbfgsx_batch* c, const lbfgsx_bat_desc* desc);
+int lbfgsx_bat_unpack(lbfgsx_batch* c, const lbfgsx_bat_desc* desc, double* out);
+int lbfgsx_bat_set_x0(lbfgsx_batch* c, const void* src);
+int lbfgsx_bat_device_push(const lbfgsx_batch* c, int* prev);
 
 /* ---- the exchange step of the batched mode over RCCL --------------------------------------
  * After a batch has been sharded over the GPUs of a node (lbfgsx_batch_minimize_lockstep_multi in lbfgsx_solver.h, or one

@@ -1,5 +1,6 @@
 /* include/lbfgsx_solver.h -- C ABI of liblbfgsx_solver.so: the drop-in C++ solvers (include/LBFGS.h,
- * include/LBFGSB.h) instantiated for the built-in device objectives, for callers without a C++ compiler
+ * include/LBFGSB.h) instantiated for the built-in device objectives and for a caller-supplied objective on device
+ * memory (lbfgsx_solver_minimize_fn, lbfgsx_lockstep_minimize_fn), for callers without a C++ compiler
  * (ctypes / cgo / JNI ...).  Mirrors LBFGSSolver<T, LineSearch>::minimize (reference LBFGS.h:78-173) and
  * LBFGSBSolver<T>::minimize (reference LBFGSB.h:116-262): same parameters (LBFGSParam / LBFGSBParam fields),
  * same return value (iteration count), exceptions mapped to status codes + message.
@@ -102,6 +103,23 @@ int lbfgsx_solver_stats3(lbfgsx_solver* s, long long out[8]);
  * start point in LBFGSX_VEC_X, result left there); lb/ub host arrays or NULL (resident), L-BFGS-B only */
 int lbfgsx_solver_minimize(lbfgsx_solver* s, int objective, int64_t n, const void* a, const void* b, void* x,
                            const void* lb, const void* ub, lbfgsx_trace* trace, lbfgsx_result* out);
+/* A caller-supplied objective on device memory.  fn(user, x_dev, grad_dev, n, fx): x_dev and grad_dev are the context's
+ * own device vectors of n elements of the solver's dtype (no staging copy; which named vector they are changes from call to
+ * call); the callback writes grad f(x) to grad_dev and f(x) to *fx and returns 0, or non-zero to end the minimisation.
+ * It is what a C++ device functor gets (LBFGSpp/Device.h, Evaluator::call_user): the library has drained its stream and made
+ * the context's device current for the calling thread before the call, so the callback may use any stream; its work must be
+ * complete when it returns (the solver's next kernel reads grad_dev).  It runs on the thread that called minimize.
+ * lbfgsx_solver_minimize_fn: x, lb, ub, trace and out as lbfgsx_solver_minimize; every algorithm, line search and dtype the
+ * solver was created with -- the same templates with one more functor.  A non-zero return ends the call with status
+ * LBFGSX_E_USER, out->nfev = the number of calls made (the failing one included), the message naming it, and x left as an
+ * exception of a C++ device functor leaves it: the trial point if the running line search had written one, else the current
+ * iterate.  A non-finite *fx is not an abort: the line searches' own checks meet it, with the reference's messages.
+ * Extensions: lbfgsx_solver_set_recursion applies to a callback as to a built-in objective; after lbfgsx_solver_set_devices
+ * (row shards: each evaluates its own rows of a built-in objective) the call is refused with LBFGSX_E_INVALID.
+ * Without a GPU: LBFGSX_E_NOGPU, the callback is never called. */
+typedef int (*lbfgsx_objective_fn)(void* user, const void* x_dev, void* grad_dev, int64_t n, double* fx);
+int lbfgsx_solver_minimize_fn(lbfgsx_solver* s, int64_t n, lbfgsx_objective_fn fn, void* user, void* x, const void* lb,
+                              const void* ub, lbfgsx_trace* trace, lbfgsx_result* out);
 
 /* ---- batched mode (BASELINE.json cfg5): many independent minimisations on one GPU ------------------------
  * Problem `id` is the extended Rosenbrock (or diag quadratic) instance generated on the device from seed
@@ -135,8 +153,8 @@ int lbfgsx_batch_minimize_lockstep_multi(int dtype, const lbfgsx_params* p, int6
  * policies that exist as state machines, LBFGSX_LS_MORE_THUENTE and LBFGSX_LS_NOCEDAL_WRIGHT -- and the built-in
  * objective: LBFGSX_OBJ_EXT_ROSENBROCK (start points of seed seed_base + id) or LBFGSX_OBJ_DIAG_QUAD (a, b of
  * lbfgsx_gen_diag_quad(kappa, seed_base + id), x0 = 0).  Every problem follows the trajectory of the single-problem solver
- * with that policy, bit for bit.  (A user objective on device memory: LBFGSBatchedSolver::minimize(BatchFunctor, ...) in
- * include/LBFGSBatched.h, over lbfgsx_bat_launch(LBFGSX_BAT_POINT / _GDOT / _NORMS).) */
+ * with that policy, bit for bit.  (A user objective on device memory: lbfgsx_lockstep_minimize_fn below, or from C++
+ * LBFGSBatchedSolver::minimize(BatchFunctor / BatchPackedFunctor, ...) in include/LBFGSBatched.h.) */
 int lbfgsx_batch_minimize_lockstep_ex(int dtype, int linesearch, int objective, double kappa, const lbfgsx_params* p, int64_t n,
                                       int64_t first, int count, uint64_t seed_base, const int* devices, int ndev,
                                       lbfgsx_batch_item* out, void* x_out, char* errbuf, int errlen);
@@ -152,6 +170,21 @@ int lbfgsx_lockstep_create(lbfgsx_lockstep** out, int dtype, int linesearch, con
                            int device, int timing, char* errbuf, int errlen);
 int lbfgsx_lockstep_minimize(lbfgsx_lockstep* h, int objective, double kappa, uint64_t seed_base, int64_t first,
                              lbfgsx_batch_item* out, void* x_out, double stats[8], char* errbuf, int errlen);
+/* The batch for a caller-supplied objective that sees the evaluating problems as ONE array.  x0: count x n start points of
+ * the handle's dtype, row-major, host or device memory (read before the call returns).
+ * eval(user, nact, ids, X, G, ld, fx): X and G are packed device arrays, row k (ld elements apart, k < nact) belonging to problem
+ * ids[k] (ascending); the callback writes grad f(X row k) to G row k and f to fx[k] (host) and returns 0, or non-zero to fail
+ * the call.  Problems that have converged, failed or do not evaluate in this lock-step turn are not in the list.  The stream
+ * and device contract is lbfgsx_objective_fn's.  The first call carries all count problems.  Around every further call the
+ * library runs lbfgsx_bat_pack and lbfgsx_bat_unpack (include/lbfgsx.h); the statements after a line search and the recursion
+ * stay in the one launch per lock-step iteration where that form applies, its in-kernel first trial does not (it cannot host a
+ * callback).  Every member follows the trajectory of lbfgsx_solver_minimize_fn on its own problem with the same per-row
+ * arithmetic.  stats as lbfgsx_lockstep_minimize, plus stats[6] = calls of eval.  A non-zero return: LBFGSX_E_USER, out
+ * undefined, the handle stays usable.  Without a GPU (no handle can exist): LBFGSX_E_NOGPU. */
+typedef int (*lbfgsx_batch_objective_fn)(void* user, int nact, const int64_t* ids, const void* X, void* G, int64_t ld,
+                                         double* fx);
+int lbfgsx_lockstep_minimize_fn(lbfgsx_lockstep* h, const void* x0, lbfgsx_batch_objective_fn eval, void* user,
+                                lbfgsx_batch_item* out, void* x_out, double stats[8], char* errbuf, int errlen);
 int lbfgsx_lockstep_set_timing(lbfgsx_lockstep* h, int on);  /* for the minimisations that follow */
 void lbfgsx_lockstep_destroy(lbfgsx_lockstep* h);
 

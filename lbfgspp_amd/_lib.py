@@ -11,7 +11,7 @@ ALGO_LBFGS, ALGO_LBFGSB = 0, 1
 RECURSION_VECTOR, RECURSION_GRAM_SPACE, RECURSION_GRAM_SPACE_F32H = 0, 1, 2
 FLAG_BOUNDED = 1
 (VEC_X, VEC_G, VEC_XP, VEC_GP, VEC_D, VEC_XT, VEC_GT, VEC_A, VEC_B, VEC_LB, VEC_UB, VEC_XCP) = range(12)
-E_INVALID, E_LOGIC, E_RUNTIME, E_HIP, E_NOGPU = -1, -2, -3, -4, -5
+E_INVALID, E_LOGIC, E_RUNTIME, E_HIP, E_NOGPU, E_USER = -1, -2, -3, -4, -5, -6
 
 
 class Params(C.Structure):
@@ -37,6 +37,10 @@ class Trace(C.Structure):
 
 ITER_HOOK = C.CFUNCTYPE(None, C.c_int, C.c_void_p)
 ALLREDUCE = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.c_int, C.c_void_p)
+# lbfgsx_objective_fn / lbfgsx_batch_objective_fn (include/lbfgsx_solver.h)
+OBJECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double))
+BATCH_OBJECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.POINTER(C.c_double))
 
 _core = None
 _solver = None
@@ -176,6 +180,9 @@ def load():
     sig(sol, "lbfgsx_solver_stats2", i32, vp, C.POINTER(C.c_longlong * 8))
     sig(sol, "lbfgsx_solver_stats3", i32, vp, C.POINTER(C.c_longlong * 8))
     sig(sol, "lbfgsx_solver_minimize", i32, vp, i32, i64, vp, vp, vp, vp, vp, C.POINTER(Trace), C.POINTER(Result))
+    sig(sol, "lbfgsx_solver_minimize_fn", i32, vp, i64, OBJECTIVE_FN, vp, vp, vp, vp, C.POINTER(Trace), C.POINTER(Result))
+    sig(sol, "lbfgsx_lockstep_minimize_fn", i32, vp, vp, BATCH_OBJECTIVE_FN, vp, C.POINTER(BatchItem), vp, C.POINTER(dbl * 8),
+        C.c_char_p, i32)
     _core, _solver = core, sol
     return core, sol
 
@@ -186,9 +193,38 @@ def last_error():
 
 
 _EXC = {E_INVALID: ValueError, E_LOGIC: ArithmeticError, E_RUNTIME: RuntimeError, E_HIP: RuntimeError,
-        E_NOGPU: RuntimeError}
+        E_NOGPU: RuntimeError, E_USER: RuntimeError}
 
 
 def check(rc, msg=None):
     if rc != 0:
         raise _EXC.get(rc, RuntimeError)(msg if msg is not None else last_error())
+
+
+def require_torch(who):
+    """torch, for the entry points that hand device memory to a Python callable as tensors."""
+    try:
+        import torch
+    except ImportError as e:
+        raise ImportError("%s needs PyTorch (ROCm build): its callable receives torch tensors that alias the library's "
+                          "device vectors" % who) from e
+    return torch
+
+
+class _DeviceMemory:
+    """Device memory the library owns, described through __cuda_array_interface__ (torch on ROCm reads it)."""
+
+    def __init__(self, ptr, shape, np_dtype, strides):
+        import numpy as np
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": np.dtype(np_dtype).str, "data": (int(ptr), False),
+                                         "version": 2, "strides": strides}
+
+
+def device_tensor(ptr, shape, np_dtype, device, row_stride=None):
+    """A torch tensor that ALIASES `ptr` (no copy): shape (n,) or (rows, n) with rows `row_stride` elements apart.  The
+    memory stays the library's; the tensor must not outlive the call it was made for."""
+    import numpy as np
+    torch = require_torch("device_tensor")
+    esz = np.dtype(np_dtype).itemsize
+    strides = None if row_stride is None else (int(row_stride) * esz, esz)
+    return torch.as_tensor(_DeviceMemory(ptr, shape, np_dtype, strides), device=torch.device("cuda", int(device)))

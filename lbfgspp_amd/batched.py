@@ -76,6 +76,7 @@ class LockstepBatch:
     def __init__(self, param, n, count, dtype=np.float32, device=0, linesearch=L.LS_MORE_THUENTE, timing=False):
         _, self._sol = L.load()
         self.n, self.count, self.dtype = int(n), int(count), np.dtype(dtype)
+        self.device = int(device)
         self._h = C.c_void_p()
         self._items = (L.BatchItem * max(self.count, 1))()
         self.stats = None
@@ -95,11 +96,67 @@ class LockstepBatch:
         L.check(rc, err.value.decode())
         self.stats = {"lockstep_iterations": int(st[0]), "fused": bool(st[1]), "kernel_ms": float(st[2]),
                       "launches": int(st[3]), "waits": int(st[4]), "wait_timeouts": int(st[5])}
+        return self._records(xs, return_x)
+
+    def _records(self, xs, return_x):
         out = np.zeros(self.count, dtype=RECORD)
         for k in range(self.count):
             it = self._items[k]
             out[k] = (it.niter, it.nfev, it.status, it.fx, it.gnorm)
         return (out, xs) if return_x else out
+
+    def minimize_fn(self, fn, x0, return_x=False):
+        """The caller's objective over the batch: fn(ids, X, G) -> fx.  X and G are torch views [nact, n] (row stride ld) of
+        the library's packed device arrays, row k belonging to problem ids[k] (a numpy int64 array); fn fills G in place and
+        returns the nact values of f (tensor or array).  Problems that have converged, failed or do not evaluate in this turn
+        are not in the list.  x0: the `count` start points, numpy or torch [count, n].  An exception raised by fn fails the
+        call, reaches the caller as itself and leaves the batch usable."""
+        if not callable(fn):
+            raise TypeError("LockstepBatch.minimize_fn: fn must be callable as fn(ids, X, G) -> fx")
+        if tuple(getattr(x0, "shape", ())) != (self.count, self.n):
+            raise ValueError("LockstepBatch.minimize_fn: x0 must have shape (count, n) = (%d, %d)" % (self.count, self.n))
+        torch = L.require_torch("LockstepBatch.minimize_fn")
+        if isinstance(x0, torch.Tensor):
+            x0 = x0.detach().to(dtype=torch.float64 if self.dtype == np.float64 else torch.float32).contiguous()
+            if x0.is_cuda:
+                torch.cuda.synchronize(x0.device)
+            x0_ptr = C.c_void_p(x0.data_ptr())
+        else:
+            x0 = np.ascontiguousarray(x0, self.dtype)
+            x0_ptr = x0.ctypes.data_as(C.c_void_p)
+        raised = []
+
+        def cb(_user, nact, ids_p, Xp, Gp, ld, fxp):
+            try:
+                ids = np.ctypeslib.as_array(ids_p, shape=(nact,)).copy()
+                with torch.cuda.device(self.device):
+                    X = L.device_tensor(Xp, (nact, self.n), self.dtype, self.device, row_stride=ld)
+                    G = L.device_tensor(Gp, (nact, self.n), self.dtype, self.device, row_stride=ld)
+                    fx = fn(ids, X, G)
+                    if isinstance(fx, torch.Tensor):
+                        fx = fx.detach().cpu().numpy()
+                    torch.cuda.current_stream().synchronize()  # G is complete when the library reads it
+                fx = np.asarray(fx, np.float64).reshape(-1)
+                if fx.size != nact:
+                    raise ValueError("fn must return one value per row: %d for %d rows" % (fx.size, nact))
+                np.ctypeslib.as_array(fxp, shape=(nact,))[:] = fx
+                return 0
+            except BaseException as e:  # re-raised below, after the C call has unwound
+                raised.append(e)
+                return 1
+
+        xs = np.empty((self.count, self.n), dtype=self.dtype) if return_x else None
+        st = (C.c_double * 8)()
+        err = C.create_string_buffer(256)
+        rc = self._sol.lbfgsx_lockstep_minimize_fn(self._h, x0_ptr, L.BATCH_OBJECTIVE_FN(cb), None, self._items,
+                                                   xs.ctypes.data_as(C.c_void_p) if return_x else None, C.byref(st), err, 256)
+        self.status = rc
+        if raised:
+            raise raised[0]
+        L.check(rc, err.value.decode())
+        self.stats = {"lockstep_iterations": int(st[0]), "fused": bool(st[1]), "kernel_ms": float(st[2]),
+                      "launches": int(st[3]), "waits": int(st[4]), "wait_timeouts": int(st[5]), "user_calls": int(st[6])}
+        return self._records(xs, return_x)
 
     def set_timing(self, on):
         L.check(self._sol.lbfgsx_lockstep_set_timing(self._h, 1 if on else 0))

@@ -637,7 +637,7 @@ void lbfgsx_bat_destroy(lbfgsx_batch* c)
     if (c->stream)
         (void) lbfgsx::stream_sync(c->stream);
     live_add(c->device, -1);
-    void* ptrs[] = {c->X, c->G, c->D, c->S, c->Y, c->sc, c->QA, c->QB, c->ws.partials, c->ws.ticket, c->ws.done_cnt, c->xch};
+    void* ptrs[] = {c->X, c->G, c->D, c->S, c->Y, c->sc, c->QA, c->QB, c->UX, c->UG, c->ws.partials, c->ws.ticket, c->ws.done_cnt, c->xch};
     for (void* p : ptrs)
         if (p)
             (void) hipFree(p);

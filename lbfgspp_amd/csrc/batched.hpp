@@ -208,6 +208,7 @@ struct lbfgsx_batch
     hipStream_t stream = nullptr;
     void *X = nullptr, *G = nullptr, *D = nullptr, *S = nullptr, *Y = nullptr, *sc = nullptr;
     void *QA = nullptr, *QB = nullptr;  // a, b of the diagonal quadratics, [P][ld] each (lbfgsx_bat_gen_diag_quad)
+    void *UX = nullptr, *UG = nullptr;  // packed trial points / gradients of a user objective, [P][ld] each (batched_user.hip)
     lbfgsx::BatWs ws;
     void* hout = nullptr;  // pinned staging for lbfgsx_bat_fetch (the step-wise recursion's last dot)
     size_t hout_cap = 0;

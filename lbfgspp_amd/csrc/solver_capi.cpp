@@ -1,5 +1,6 @@
 // lbfgspp_amd/csrc/solver_capi.cpp -- liblbfgsx_solver.so: the drop-in C++ solver templates instantiated
-// for the built-in objectives behind include/lbfgsx_solver.h.  Plain host C++ (g++), links liblbfgsx.so.
+// for the built-in objectives and for a C callback on device memory behind include/lbfgsx_solver.h.  Plain host C++ (g++),
+// links liblbfgsx.so.
 #include <cstdio>
 #include <cstring>
 #include <atomic>
@@ -29,6 +30,8 @@ struct lbfgsx_solver
     long long stats3[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     virtual void minimize(int objective, int64_t n, const void* a, const void* b, void* x, const void* lb,
                           const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) = 0;
+    virtual void minimize_fn(int64_t n, lbfgsx_objective_fn fn, void* user, void* x, const void* lb, const void* ub,
+                             lbfgsx_trace* tr, lbfgsx_result* out) = 0;
 };
 
 namespace {
@@ -82,6 +85,24 @@ void install_trace(lbfgsx_trace* tr, std::function<void(int, Scalar, DeviceState
         tr->count = k + 1;
     };
 }
+
+// lbfgsx_objective_fn as the device functor the solver templates take (LBFGSpp/Device.h: it names DeviceVector)
+template <class Scalar>
+struct CallbackObjective
+{
+    lbfgsx_objective_fn fn;
+    void* user;
+    int calls = 0;
+    Scalar operator()(const DeviceVector<Scalar>& x, DeviceVector<Scalar>& grad)
+    {
+        double fx = 0.0;
+        calls++;
+        const int rc = fn(user, x.data(), grad.data(), x.size(), &fx);
+        if (rc != 0)
+            throw UserAbort("the objective callback returned " + std::to_string(rc) + " at evaluation " + std::to_string(calls));
+        return Scalar(fx);
+    }
+};
 
 template <class Scalar, template <class> class LS>
 struct LbfgsImpl : lbfgsx_solver
@@ -142,6 +163,25 @@ struct LbfgsImpl : lbfgsx_solver
                   lbfgsx_trace* tr, lbfgsx_result* out) override
     {
         BuiltinObjective<Scalar> f(objective, static_cast<const Scalar*>(a), static_cast<const Scalar*>(b));
+        run(f, n, x, tr, out);
+    }
+    void minimize_fn(int64_t n, lbfgsx_objective_fn fn, void* user, void* x, const void*, const void*, lbfgsx_trace* tr,
+                     lbfgsx_result* out) override
+    {
+        CallbackObjective<Scalar> f = {fn, user};
+        try
+        {
+            run(f, n, x, tr, out);
+        }
+        catch (const UserAbort&)
+        {
+            out->nfev = f.calls;  // the failing call included
+            throw;
+        }
+    }
+    template <class Foo>
+    void run(Foo& f, int64_t n, void* x, lbfgsx_trace* tr, lbfgsx_result* out)
+    {
         std::function<void(int, Scalar, DeviceState<Scalar>&)> cb;
         install_trace<Scalar>(tr, cb);
         solver->set_trace(cb);
@@ -223,6 +263,25 @@ struct LbfgsbImpl : lbfgsx_solver
                   lbfgsx_trace* tr, lbfgsx_result* out) override
     {
         BuiltinObjective<Scalar> f(objective, static_cast<const Scalar*>(a), static_cast<const Scalar*>(b));
+        run(f, n, x, lb, ub, tr, out);
+    }
+    void minimize_fn(int64_t n, lbfgsx_objective_fn fn, void* user, void* x, const void* lb, const void* ub, lbfgsx_trace* tr,
+                     lbfgsx_result* out) override
+    {
+        CallbackObjective<Scalar> f = {fn, user};
+        try
+        {
+            run(f, n, x, lb, ub, tr, out);
+        }
+        catch (const UserAbort&)
+        {
+            out->nfev = f.calls;  // the failing call included
+            throw;
+        }
+    }
+    template <class Foo>
+    void run(Foo& f, int64_t n, void* x, const void* lb, const void* ub, lbfgsx_trace* tr, lbfgsx_result* out)
+    {
         std::function<void(int, Scalar, DeviceState<Scalar>&)> cb;
         install_trace<Scalar>(tr, cb);
         solver->set_trace(cb);
@@ -274,6 +333,11 @@ int guarded(lbfgsx_result* out, F&& body)
     try
     {
         body();
+    }
+    catch (const UserAbort& e)
+    {
+        status = LBFGSX_E_USER;
+        keep = e.what();
     }
     catch (const std::invalid_argument& e)
     {
@@ -531,6 +595,7 @@ struct lbfgsx_lockstep
     void (*destroy)(void*) = nullptr;
     void (*timing)(void*, int) = nullptr;
     void (*run)(lbfgsx_lockstep*, int, double, uint64_t, int64_t, lbfgsx_batch_item*, void*, double*) = nullptr;
+    void (*run_fn)(lbfgsx_lockstep*, const void*, lbfgsx_batch_objective_fn, void*, lbfgsx_batch_item*, void*, double*) = nullptr;
 };
 
 template <class T, template <class> class LS>
@@ -545,21 +610,14 @@ static void lockstep_bind(lbfgsx_lockstep* h, LBFGSParam<T>& param, int timing)
     h->timing = [](void* p, int on) { static_cast<S*>(p)->set_timing(on != 0); };
     s->set_timing(timing != 0);
     s->prepare(h->n, h->count, h->device);
-    h->run = [](lbfgsx_lockstep* hh, int objective, double kappa, uint64_t seed_base, int64_t first, lbfgsx_batch_item* out,
-                void* x_out, double* st) {
-        S* sv = static_cast<S*>(hh->solver);
-        std::vector<typename S::Item> items;
-        BatchObjective obj;
-        obj.id = objective;
-        obj.kappa = kappa;
-        sv->minimize(obj, hh->n, seed_base, first, hh->count, hh->device, items, static_cast<T*>(x_out));
-        for (int k = 0; k < hh->count; k++)
+    static const auto report = [](S* sv, const std::vector<typename S::Item>& items, lbfgsx_batch_item* out, double* st) {
+        for (size_t k = 0; k < items.size(); k++)
         {
-            out[k].niter = items[size_t(k)].niter;
-            out[k].nfev = items[size_t(k)].nfev;
-            out[k].status = items[size_t(k)].status;
-            out[k].fx = double(items[size_t(k)].fx);
-            out[k].gnorm = double(items[size_t(k)].gnorm);
+            out[k].niter = items[k].niter;
+            out[k].nfev = items[k].nfev;
+            out[k].status = items[k].status;
+            out[k].fx = double(items[k].fx);
+            out[k].gnorm = double(items[k].gnorm);
         }
         if (st)
         {
@@ -569,8 +627,31 @@ static void lockstep_bind(lbfgsx_lockstep* h, LBFGSParam<T>& param, int timing)
             st[3] = double(sv->stats.launches);
             st[4] = double(sv->stats.waits);
             st[5] = double(sv->stats.wait_timeouts);
-            st[6] = st[7] = 0.0;
+            st[6] = double(sv->stats.user_calls);
+            st[7] = 0.0;
         }
+    };
+    h->run = [](lbfgsx_lockstep* hh, int objective, double kappa, uint64_t seed_base, int64_t first, lbfgsx_batch_item* out,
+                void* x_out, double* st) {
+        S* sv = static_cast<S*>(hh->solver);
+        std::vector<typename S::Item> items;
+        BatchObjective obj;
+        obj.id = objective;
+        obj.kappa = kappa;
+        sv->minimize(obj, hh->n, seed_base, first, hh->count, hh->device, items, static_cast<T*>(x_out));
+        report(sv, items, out, st);
+    };
+    h->run_fn = [](lbfgsx_lockstep* hh, const void* x0, lbfgsx_batch_objective_fn eval, void* user, lbfgsx_batch_item* out,
+                   void* x_out, double* st) {
+        S* sv = static_cast<S*>(hh->solver);
+        std::vector<typename S::Item> items;
+        BatchPackedFunctor<T> f;
+        f.x0 = x0;
+        f.eval = [eval, user](int nact, const std::int64_t* ids, const T* X, T* G, std::int64_t ld, double* fx) {
+            return eval(user, nact, ids, X, G, ld, fx);
+        };
+        sv->minimize(f, hh->n, hh->count, hh->device, items, static_cast<T*>(x_out));
+        report(sv, items, out, st);
     };
 }
 
@@ -635,6 +716,27 @@ int lbfgsx_lockstep_minimize(lbfgsx_lockstep* h, int objective, double kappa, ui
             throw std::invalid_argument("lbfgsx_lockstep_minimize: unknown built-in objective");
         h->run(h, objective, kappa, seed_base, first, out, x_out, stats);
     });
+    if (errbuf && errlen > 0)
+        std::snprintf(errbuf, size_t(errlen), "%s", r.msg);
+    return rc;
+}
+
+int lbfgsx_lockstep_minimize_fn(lbfgsx_lockstep* h, const void* x0, lbfgsx_batch_objective_fn eval, void* user,
+                                lbfgsx_batch_item* out, void* x_out, double stats[8], char* errbuf, int errlen)
+{
+    lbfgsx_result r;
+    int rc = LBFGSX_OK;
+    if (lbfgsx_device_count() <= 0)  // (no handle can exist: lbfgsx_lockstep_create allocates on the device)
+    {
+        rc = LBFGSX_E_NOGPU;
+        std::snprintf(r.msg, sizeof(r.msg), "lbfgsx_lockstep_minimize_fn: no HIP device available (this library has no CPU fallback)");
+    }
+    else
+        rc = guarded(&r, [&]() {
+            if (!h || !x0 || !eval || !out)
+                throw std::invalid_argument("lbfgsx_lockstep_minimize_fn: invalid argument");
+            h->run_fn(h, x0, eval, user, out, x_out, stats);
+        });
     if (errbuf && errlen > 0)
         std::snprintf(errbuf, size_t(errlen), "%s", r.msg);
     return rc;
@@ -720,5 +822,22 @@ int lbfgsx_solver_minimize(lbfgsx_solver* s, int objective, int64_t n, const voi
 {
     std::memset(out, 0, sizeof(*out));
     return guarded(out, [&]() { s->minimize(objective, n, a, b, x, lb, ub, trace, out); });
+}
+
+int lbfgsx_solver_minimize_fn(lbfgsx_solver* s, int64_t n, lbfgsx_objective_fn fn, void* user, void* x, const void* lb,
+                              const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_fn: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    return guarded(out, [&]() {
+        if (!s || !fn || n <= 0)
+            throw std::invalid_argument("lbfgsx_solver_minimize_fn: invalid argument");
+        s->minimize_fn(n, fn, user, x, lb, ub, trace, out);
+    });
 }
 }

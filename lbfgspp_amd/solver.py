@@ -6,7 +6,8 @@ Names, argument meaning and error behaviour follow yixuan/LBFGSpp:
   LBFGSBSolver(param).minimize(f, x, lb, ub)     -> (niter, fx)      reference include/LBFGSB.h:116-262
 Exceptions: std::invalid_argument -> ValueError, std::logic_error -> ArithmeticError,
 std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device objective
-(`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`); all O(n) work runs in the HIP library, Python only passes
+(`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`) or the caller's own, `DeviceObjective(fn)`: fn(x, grad) -> float on torch
+tensors that alias the library's device vectors.  All O(n) work of the solver runs in the HIP library, Python only passes
 pointers.  There is no CPU fallback: without the built extension or a GPU these calls raise.
 """
 import ctypes as C
@@ -68,6 +69,40 @@ class ExtendedRosenbrock:
     a = b = None
 
 
+class DeviceObjective:
+    """The caller's objective on device memory: fn(x, grad) -> float.  x and grad are 1-D torch tensors that ALIAS the
+    solver's own device vectors (no copy; on the solver's device, of its dtype): fn fills grad in place and returns f(x).
+    They are valid during the call only.  An exception raised by fn ends the minimisation and reaches the caller of
+    minimize() as itself (solver.last.status == LBFGSX_E_USER); a non-finite value is left to the line search, as in the
+    reference.  Usable wherever DiagQuadratic / ExtendedRosenbrock are."""
+
+    def __init__(self, fn):
+        if not callable(fn):
+            raise TypeError("DeviceObjective: fn must be callable as fn(x, grad) -> float")
+        L.require_torch("DeviceObjective")
+        self.fn = fn
+
+    @classmethod
+    def from_autograd(cls, loss):
+        """fn built from a scalar-valued torch function of x: the gradient comes from torch.autograd.grad."""
+        if not callable(loss):
+            raise TypeError("DeviceObjective.from_autograd: loss must be callable as loss(x) -> scalar tensor")
+        torch = L.require_torch("DeviceObjective.from_autograd")
+
+        def fn(x, grad):
+            with torch.enable_grad():
+                xv = x.detach().requires_grad_(True)
+                f = loss(xv)
+                (g,) = torch.autograd.grad(f, xv)
+            grad.copy_(g)
+            return float(f.detach())
+        return cls(fn)
+
+
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
 class TraceBuffer:
     """Per-evaluation record (fx and x[::stride]) for the parity tests."""
 
@@ -96,6 +131,7 @@ class _SolverBase:
     def __init__(self, param, linesearch=L.LS_NOCEDAL_WRIGHT, dtype=np.float64, device=0):
         self._core, self._sol = L.load()
         self.dtype = L.F64 if np.dtype(dtype) == np.float64 else L.F32
+        self.device = int(device)
         self.param = param
         self._h = C.c_void_p()
         cp = param._c()
@@ -166,7 +202,62 @@ class _SolverBase:
         assert arr.dtype == _NP[self.dtype] and arr.flags["C_CONTIGUOUS"]
         return arr.ctypes.data_as(C.c_void_p)
 
+    def _vec(self, which, n):
+        """torch view of a named device vector of the prepared state (valid until the next call into the solver)"""
+        return L.device_tensor(self._core.lbfgsx_vec(self.ctx, which), (n,), _NP[self.dtype], self.device)
+
+    def _minimize_device(self, f, x, bounds, trace):
+        """x (and bounds) as torch tensors on the solver's device: placed in the resident state, solved there, x updated in
+        place.  When minimize raises, x keeps its start point."""
+        torch = L.require_torch("minimize with a torch x")
+        n = x.numel()
+        want = torch.float64 if self.dtype == L.F64 else torch.float32
+        if x.dim() != 1 or x.dtype != want or not x.is_cuda or x.device.index != self.device:
+            raise ValueError("x must be a 1-D %s tensor on cuda:%d" % (want, self.device))
+        self.prepare(n)
+        with torch.cuda.device(self.device):
+            self._vec(L.VEC_X, n).copy_(x)
+            for which, v in bounds:
+                v = torch.as_tensor(v, dtype=want)
+                if v.numel() != n:
+                    raise ValueError("'lb' and 'ub' must have the same size as 'x'")
+                self._vec(which, n).copy_(v.reshape(n))
+            torch.cuda.current_stream().synchronize()
+            r = self._minimize(f, n, None, None, None, trace)
+            x.copy_(self._vec(L.VEC_X, n))
+            torch.cuda.current_stream().synchronize()
+        return r.niter, r.fx
+
+    def _minimize_fn(self, f, n, x, lb, ub, trace):
+        torch = L.require_torch("DeviceObjective")
+        raised = []
+
+        def cb(_user, xp, gp, nn, fxp):
+            try:
+                with torch.cuda.device(self.device):
+                    xt = L.device_tensor(xp, (nn,), _NP[self.dtype], self.device)
+                    gt = L.device_tensor(gp, (nn,), _NP[self.dtype], self.device)
+                    fxp[0] = float(f.fn(xt, gt))
+                    torch.cuda.current_stream().synchronize()  # grad is complete when the library reads it
+                return 0
+            except BaseException as e:  # re-raised below, after the C call has unwound
+                raised.append(e)
+                return 1
+
+        res = L.Result()
+        rc = self._sol.lbfgsx_solver_minimize_fn(self._h, n, L.OBJECTIVE_FN(cb), None, self._ptr(x), self._ptr(lb),
+                                                 self._ptr(ub), C.byref(trace.c) if trace else None, C.byref(res))
+        self.last = Result(res)
+        if raised:
+            raise raised[0]
+        L.check(rc, self.last.msg)
+        return self.last
+
     def _minimize(self, f, n, x, lb, ub, trace):
+        if isinstance(f, DeviceObjective):
+            return self._minimize_fn(f, n, x, lb, ub, trace)
+        if not hasattr(f, "objective"):
+            raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock or DeviceObjective(fn)")
         res = L.Result()
         a = None if f.a is None else np.ascontiguousarray(f.a, _NP[self.dtype])
         b = None if f.b is None else np.ascontiguousarray(f.b, _NP[self.dtype])
@@ -183,7 +274,10 @@ class LBFGSSolver(_SolverBase):
     _algo = L.ALGO_LBFGS
 
     def minimize(self, f, x, trace=None):
-        """x: numpy vector, updated in place.  Returns (niter, fx) like minimize(f, x, fx)."""
+        """x: numpy vector, or a torch tensor on the solver's device, updated in place.  Returns (niter, fx) like
+        minimize(f, x, fx)."""
+        if _is_torch(x):
+            return self._minimize_device(f, x, (), trace)
         xx = np.ascontiguousarray(x, _NP[self.dtype])
         r = self._minimize(f, xx.size, xx, None, None, trace)
         if xx is not x:
@@ -216,6 +310,8 @@ class LBFGSBSolver(_SolverBase):
     def minimize(self, f, x, lb, ub, trace=None):
         """minimize(f, x, fx, lb, ub): x updated in place; raises ValueError when lb/ub sizes differ from x."""
         dt = _NP[self.dtype]
+        if _is_torch(x):
+            return self._minimize_device(f, x, ((L.VEC_LB, lb), (L.VEC_UB, ub)), trace)
         xx = np.ascontiguousarray(x, dt)
         lbv, ubv = np.ascontiguousarray(lb, dt), np.ascontiguousarray(ub, dt)
         if lbv.size != xx.size or ubv.size != xx.size:
