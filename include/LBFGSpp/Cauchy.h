@@ -370,9 +370,10 @@ public:
         detail::check(lbfgsx_b_cauchy_finish(c, double(t_cross), double(tfinal), crossed_all ? 1 : 0, &out.nact, &out.nfree));
         out.t_fetch = fetch_seconds;
         if (std::getenv("LBFGSX_TRACE_PHASES"))
+        {
             std::fprintf(stderr, "[gcp] ncorr %d nord %lld nfree %lld crossings %lld dev %lld crossed_all %d\n", ncorr, (long long) nord, (long long) nfree, (long long) out.crossings, (long long) out.dev_crossings, int(crossed_all));
-        if (std::getenv("LBFGSX_TRACE_PHASES"))
             std::fprintf(stderr, "[gcp] sorted %lld of %lld, tau_next %g, fallbacks %lld\n", (long long) lim, (long long) nord, out.tau_hint, (long long) out.sort_fallbacks);
+        }
         out.t_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     }
 };

@@ -89,24 +89,23 @@ public:
         bfgs.gram_cache_reset();
         const char* fuse_env = std::getenv("LBFGSX_SUB_FUSE");
         const bool fuse = !(fuse_env && fuse_env[0] == '0');
+        const char* os_env = std::getenv("LBFGSX_LU_ONE_SIDED");
+        const bool one_sided = !(os_env && os_env[0] == '0');
         // The first solve takes its sweep form (one pass: y, the in-bounds test, the partition) whether or not the previous call
         // needed sweeps: until round 6 a call that followed one without sweeps ran the solve, the test and -- when it did need
-        // sweeps after all -- the partition as three passes (m = 20: +1.3 %, m = 10: even; LBFGSX_SUB_EARLY=0: as before).
-        const char* early_env = std::getenv("LBFGSX_SUB_EARLY");
-        const int early_mode = early_env ? std::atoi(early_env) : 1;
-        const bool early = fuse && (early_mode == 1 || bfgs.sweeps_expected());
+        // sweeps after all -- the partition as three passes (m = 20: +1.3 %, m = 10: even).
         std::int64_t s7[7] = {0, 0, 0, 0, 0, 0, 0};
         bool swept = false;
-        if (early)  // sweeps ahead: the first solve's Gram pass leaves a compact copy of the free rows for their passes
+        if (fuse)  // the first solve's Gram pass leaves a compact copy of the free rows for the passes of the sweeps
             detail::check(lbfgsx_b_set_compaction(c, 1));
         bfgs.solve_PtBP(LBFGSX_ST_FREE, nfree, LBFGSX_VS_NEG_CF, LBFGSX_GP_LINEAR,   // ... fused with
                         has_lin ? lcoef.data() : nullptr, nullptr, nullptr, 0,      // vecy = -inv(B[F,F]) c (:159)
-                        /*keep_as_F=*/true, 0, -1, early ? s7 : nullptr, true, &swept);
+                        /*keep_as_F=*/true, 0, -1, fuse ? s7 : nullptr, true, &swept);
         // The element-wise statements between two solves -- yfallback / lambda = mu = 0 (:170-172) before the first
         // sweep, the convergence counts (:271) before the others, then the partition (:194-219) and rhs = c_P (:232) --
         // are one pass (lbfgsx_b_sub_sweep_begin); LBFGSX_SUB_FUSE=0 runs them as the reference's separate statements.
-        // When the previous call needed sweeps, the in_bounds test (:162-166) rides on that pass as well (the pass
-        // moves no y when everything is in bounds, so taking it early is harmless).
+        // The in_bounds test (:162-166) rides on that pass as well (the pass moves no y when everything is in bounds, so
+        // taking it early is harmless).
         // With a sweep expected the pass even rides on the solve before it: the solve's kernel has the row's y in a
         // register (lbfgsx_b_solve_sweep); the rows of L and U, which wait for their multipliers, follow through the index
         // list of the last partition (lbfgsx_b_lu_sweep).
@@ -122,23 +121,16 @@ public:
         int nfused = swept ? 1 : 0;
         if (swept)
             take(s7, nullptr);
-        else if (early)
+        else if (fuse)
             detail::check(lbfgsx_b_sub_sweep_begin(c, 1, &nL, &nU, &nP, cnt));
         else
             detail::check(lbfgsx_b_sub_check(c, cnt));
         if (cnt[0] == 0)                                                // in_bounds (:162-166)
         {
-            bfgs.expect_sweeps(false);
             detail::check(lbfgsx_b_sub_op(c, LBFGSX_SO_ASSIGN_Y));
             return;
         }
-        bfgs.expect_sweeps(true);
-        if (fuse)
-        {
-            if (!early)
-                detail::check(lbfgsx_b_sub_sweep_begin(c, 1, &nL, &nU, &nP, cnt));
-        }
-        else
+        if (!fuse)
             detail::check(lbfgsx_b_sub_op(c, LBFGSX_SO_SAVE_FALLBACK)); // yfallback, lambda = mu = 0 (:170-172)
 
         int k;
@@ -164,8 +156,6 @@ public:
                 // (its sum and its count are zero then, i.e. hasL / hasU false exactly as PtBQv_coef answers for nQ = 0): the
                 // list pass is what leaves the sums the solve below needs to do without a Gram pass over P
                 // (LBFGSX_LU_ONE_SIDED=0: only when both are non-empty, as before round 6 -- the A/B switch)
-                const char* os_env = std::getenv("LBFGSX_LU_ONE_SIDED");
-                const bool one_sided = !(os_env && os_env[0] == '0');
                 if ((one_sided ? (nL > 0 || nU > 0) : (nL > 0 && nU > 0)) && bfgs.Wtv_lu(wl, zl, wu, zu))
                 {
                     hasL = zl >= 1;                                     // test_zero (BFGSMat.h:388-412), as PtBQv_coef

@@ -357,10 +357,10 @@ __global__ void __launch_bounds__(kBlock) kb_twoloop(BatBufs<T> b, const BatDesc
     const int64_t rev_top = rev ? ((nv + tile - 1) / tile - 1) * tile : int64_t(-1);
     switch (mode)  // uniform per problem (per blockIdx.y): no divergence
     {
-    case TL_INIT: twoloop_body<T, TL_INIT, U, true, 0>(q, gcur, a, u, w, n, coef, theta, first, nv, stride, nv, rev_top, tail, acc[0]); break;
-    case TL_SUB: twoloop_body<T, TL_SUB, U, true, 0>(q, gcur, a, u, w, n, coef, theta, first, nv, stride, nv, rev_top, tail, acc[0]); break;
-    case TL_SUBDIV: twoloop_body<T, TL_SUBDIV, U, true, 0>(q, gcur, a, u, w, n, coef, theta, first, nv, stride, nv, rev_top, tail, acc[0]); break;
-    default: twoloop_body<T, TL_ADD, U, true, 0>(q, gcur, a, u, w, n, coef, theta, first, nv, stride, nv, rev_top, tail, acc[0]); break;
+    case TL_INIT: twoloop_body<T, TL_INIT, U>(q, gcur, a, u, w, n, coef, theta, first, nv, stride, nv, rev_top, tail, acc[0]); break;
+    case TL_SUB: twoloop_body<T, TL_SUB, U>(q, gcur, a, u, w, n, coef, theta, first, nv, stride, nv, rev_top, tail, acc[0]); break;
+    case TL_SUBDIV: twoloop_body<T, TL_SUBDIV, U>(q, gcur, a, u, w, n, coef, theta, first, nv, stride, nv, rev_top, tail, acc[0]); break;
+    default: twoloop_body<T, TL_ADD, U>(q, gcur, a, u, w, n, coef, theta, first, nv, stride, nv, rev_top, tail, acc[0]); break;
     }
     if (bat_reduce<1>(acc, ws) && threadIdx.x == 0)
         sc[de.i_out] = T(acc[0].value());
@@ -554,27 +554,12 @@ int lbfgsx_bat_create(lbfgsx_batch** out, int dtype, int64_t n, int m, int nprob
     int64_t gx_n = (n / w + 4 * kBlock - 1) / (4 * kBlock);
     gx_n = std::max<int64_t>(1, std::min<int64_t>((gx_n + 3) / 4, 64));
     int64_t gx = std::max<int64_t>(1, std::min<int64_t>(gx_n, 1024 / std::max(nproblems, 1)));
-    if (const char* e = getenv("LBFGSX_ZIGZAG"))
-        c->zigzag = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_BAT_FUSED_HV"))
         c->fused_hv = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_BAT_FUSED_ITER"))
         c->fused_iter = atoi(e) != 0;
-    if (const char* e = getenv("LBFGSX_BAT_MIN_PARTS"))
-        c->min_parts = std::max(0, std::min(atoi(e), 16));
-    if (const char* e = getenv("LBFGSX_BAT_MAX_PARTS"))
-        c->max_parts = std::max(0, atoi(e));
     if (const char* e = getenv("LBFGSX_BAT_DEBUG_XCH_FAULT"))
         c->dbg_xch_fault = std::max(0, atoi(e));
-    if (const char* e = getenv("LBFGSX_BAT_POLL"))
-        c->poll = atoi(e) != 0;
-    if (const char* e = getenv("LBFGSX_BAT_GX"))
-    {
-        gx = std::max(1, std::min(atoi(e), 256));
-        c->adaptive_gx = false;
-    }
-    if (const char* e = getenv("LBFGSX_BAT_ADAPTIVE_GX"))
-        c->adaptive_gx = atoi(e) != 0;
     c->gx = int(gx);
     live_add(c->device, +1);
     const int rc = bat_alloc(c);
@@ -783,7 +768,7 @@ int lbfgsx_bat_launch(lbfgsx_batch* c, int kind, int objective, const lbfgsx_bat
         const int64_t w = (c->dtype == LBFGSX_F64) ? 2 : 4;
         const int64_t tiles = std::max<int64_t>(1, (c->n / w + 4 * kBlock - 1) / (4 * kBlock));
         const int64_t want = std::max<int64_t>(c->gx, std::min<int64_t>(std::min<int64_t>(1024 / nactive, kBatGxMax), tiles));
-        if (c->adaptive_gx && kind != 3)
+        if (kind != 3)
             grid_x = int(want);
     }
     const dim3 grid(unsigned(grid_x), unsigned(c->P));
@@ -808,7 +793,7 @@ int lbfgsx_bat_launch(lbfgsx_batch* c, int kind, int objective, const lbfgsx_bat
         case 6: BAT_LAUNCH(c, (kb_gdot<T, 1>), grid, dim3(kBlock), 0, c->stream, b, desc_dev, c->n, ws); break;
         case 2: BAT_LAUNCH(c, (kb_post<T>), grid, dim3(kBlock), 0, c->stream, b, desc_dev, c->n, ws); break;
         default: BAT_LAUNCH(c, (kb_twoloop<T>), grid, dim3(kBlock), 0, c->stream, b, desc_dev, c->n, ws,
-                                    (c->zigzag && (c->tl_step++ & 1u)) ? 1 : 0); break;
+                                    (c->tl_step++ & 1u) ? 1 : 0); break;
         }
     });
     LBFGSX_HIP(hipGetLastError());

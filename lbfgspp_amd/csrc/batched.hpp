@@ -213,19 +213,15 @@ struct lbfgsx_batch
     void* hout = nullptr;  // pinned staging for lbfgsx_bat_fetch (the step-wise recursion's last dot)
     size_t hout_cap = 0;
     lbfgsx::ScLayout sl;
-    bool zigzag = true;
     unsigned tl_step = 0;
     bool fused_hv = true;    // LBFGSX_BAT_FUSED_HV=0: always the step-wise two-loop launches
     bool fused_iter = true;  // LBFGSX_BAT_FUSED_ITER=0: never the one-launch lock-step iteration
-    int min_parts = 0;       // LBFGSX_BAT_MIN_PARTS=k: split every problem over at least k blocks (experiments: shorter blocks, several per CU)
-    int max_parts = 0;       // LBFGSX_BAT_MAX_PARTS=k: a problem may be split over at most k blocks (0: as many as it needs, <= 16)
     int dbg_xch_fault = 0;   // test hook, LBFGSX_BAT_DEBUG_XCH_FAULT=k: the k-th split-problem launch of this batch runs with part 1 of
                              // every problem "timed out" from the start (it publishes nothing) and the error word set
     int xch_launches = 0;
     unsigned* xch = nullptr; // exchange area of the parts of a problem (batched_iter.hip), allocated on first use
     unsigned xch_seq = 0;
-    bool adaptive_gx = true; // LBFGSX_BAT_ADAPTIVE_GX=0: every launch with the batch's blocks per problem
-    bool poll = true;        // LBFGSX_BAT_POLL=0: wait for the stream instead of polling the completion word
+    bool poll = true;        // false (after two misses, bat_wait): wait for the stream instead of polling the completion word
     // Descriptor staging: kBatStages host-mapped buffers the kernels read in place (no copy in the stream, nothing to wait
     // for before the host fills the next one); a launch takes the next buffer, and the stream is drained before a buffer
     // that an un-waited launch may still be reading comes round again.

@@ -155,8 +155,6 @@ static int user_desc_check(const lbfgsx_batch* c, const lbfgsx_bat_desc* desc, c
 // blocks per problem of a launch that `nactive` problems take part in (the rule of lbfgsx_bat_launch)
 static int user_grid_x(const lbfgsx_batch* c, int nactive)
 {
-    if (!c->adaptive_gx)
-        return c->gx;
     const int64_t w = (c->dtype == LBFGSX_F64) ? 2 : 4;
     const int64_t tiles = std::max<int64_t>(1, (c->n / w + 4 * kBlock - 1) / (4 * kBlock));
     return int(std::max<int64_t>(c->gx, std::min<int64_t>(std::min<int64_t>(1024 / nactive, kBatGxMax), tiles)));

@@ -148,6 +148,9 @@ struct EventPair
     hipEvent_t a, b;
 };
 
+constexpr int kGridCap = 1024;        // blocks per launch of the streaming kernels (4 per CU; tuned on MI355X, see profiles/)
+constexpr int kGridCapTwoloop = 512;  // of the two-loop step launches (k_twoloop)
+
 }  // namespace lbfgsx
 
 struct lbfgsx_ctx
@@ -198,22 +201,13 @@ struct lbfgsx_ctx
     long long poll_late = 0;    // consecutive time-outs whose stream wait returned at once (store visible only at kernel end)
     bool poll_pending = false;  // poll_arm ran and no wait has consumed it yet
     bool poll_off = false;      // two lost / late waits: this context waits for its stream from now on
-    int grid_cap = 1024;     // blocks per launch of the streaming kernels (4 per CU; tuned on MI355X, see profiles/)
-    int grid_cap_twoloop = 512;
-    int unroll = 4;   // 16-byte loads in flight per stream per thread in the two-loop kernels
-    bool nt = true;   // non-temporal hints on the streaming accesses (+8% on MI355X)
-    bool chunked = false;  // contiguous slab per block instead of grid-stride tiles
-    int q_policy = 0;      // non-temporal hint on q itself (bit 0 loads, bit 1 stores).  q is the vector every two-loop
-                           // step re-reads, so it stays eligible for the memory-side cache by default
-    int trial_policy = 0;  // LBFGSX_TRIAL_POLICY: bit 0 NT loads, bit 1 NT stores, 4: 8 vectors in flight (k_trial A/B)
-    bool zigzag = true;    // alternate the traversal direction of consecutive two-loop steps (MALL reuse of q's tail)
+    // consecutive two-loop steps (and trial / post passes) alternate the traversal direction (MALL reuse of q's tail)
     unsigned tl_step = 0;  // launches issued so far (parity selects the direction)
     // persistent one-launch apply_Hv (k_twoloop_persist)
     bool persist = true;           // LBFGSX_PERSIST=0: always the 2c+1 step launches
     bool meet_all = true;          // how the blocks of the persistent launch learn a step's dot (lbfgs_kernels.cuh, persist_publish):
                                    // one tagged 16-byte word polled after the next step's loads are issued (default), or
                                    // LBFGSX_MEET=last: generation word + scalar table, waited for at the end of the step
-    bool meet_pub_first = true;    // the polled word before the dot's copy for the host (LBFGSX_MEET_PUB=0: after it, as in round 4)
     // A persistent launch whose meeting points timed out (CUs held by another process) is redone with the step launches,
     // which the context then keeps for `persist_cooldown` products before it tries the persistent form again; every
     // further time-out quadruples the pause (8, 32, ... 8192 products), a clean persistent product resets it.
@@ -276,8 +270,8 @@ struct lbfgsx_ctx
         int64_t blocks = (nelem / w + tile - 1) / tile;
         if (blocks < 1)
             blocks = 1;
-        if (blocks > grid_cap)
-            blocks = grid_cap;
+        if (blocks > lbfgsx::kGridCap)
+            blocks = lbfgsx::kGridCap;
         return int(blocks);
     }
 };

@@ -419,8 +419,9 @@ struct GsState  // per-context scratch of this mode, allocated on first use
     unsigned* ticket = nullptr;
     float* S32 = nullptr;        // f32 copy of the history of an f64 context (lbfgsx_gs_set_history_dtype), (m+1) columns
     float* Y32 = nullptr;
-    int grid_post = 512, grid_combine = 1024;  // measured flat (+-2 %) between 256 and 2048 blocks on the north-star size
 };
+// blocks of the post and combine passes: measured flat (+-2 %) between 256 and 2048 blocks on the north-star size
+constexpr int kGsGridPost = 512, kGsGridCombine = 1024;
 
 static int gs_ensure(lbfgsx_ctx* c)
 {
@@ -432,10 +433,6 @@ static int gs_ensure(lbfgsx_ctx* c)
     LBFGSX_HIP(hipHostMalloc(reinterpret_cast<void**>(&g->out_host), sizeof(double) * nout, hipHostMallocDefault));
     LBFGSX_HIP(hipMalloc(reinterpret_cast<void**>(&g->ticket), sizeof(unsigned)));
     LBFGSX_HIP(hipMemsetAsync(g->ticket, 0, sizeof(unsigned), c->stream));
-    if (const char* e = getenv("LBFGSX_GS_GRID_POST"))
-        g->grid_post = std::max(1, std::min(atoi(e), 2048));
-    if (const char* e = getenv("LBFGSX_GS_GRID_COMBINE"))
-        g->grid_combine = std::max(1, std::min(atoi(e), 2048));
     c->gs = g;
     return LBFGSX_OK;
 }
@@ -481,9 +478,9 @@ static int gs_post_t(lbfgsx_ctx* c, double* scal, double* sdots, double* gdots)
     const int cn = c->ncorr, nc = 2 * cn, m = c->m;
     GsCols<T> cols;
     gs_fill_cols<T>(c, cols);
-    const int grid = gs_grid(c, g->grid_post);
+    const int grid = gs_grid(c, kGsGridPost);
     T* sc = static_cast<T*>(c->sc);
-    const int rev = (c->zigzag && (c->tl_step++ & 1u)) ? 1 : 0;
+    const int rev = (c->tl_step++ & 1u) ? 1 : 0;
     int NCsel = 0;
     EventPair ev;
     if (c->timing)
@@ -553,8 +550,8 @@ static int gs_direction_t(lbfgsx_ctx* c, const double* coef, double coef_g, doub
         cf.c[j] = T(coef[j]);
         cf.c[cn + j] = T(coef[m + j]);
     }
-    const int grid = gs_grid(c, g->grid_combine);
-    const int rev = (c->zigzag && (c->tl_step++ & 1u)) ? 1 : 0;
+    const int grid = gs_grid(c, kGsGridCombine);
+    const int rev = (c->tl_step++ & 1u) ? 1 : 0;
     EventPair hv;
     if (c->timing)
     {
@@ -613,9 +610,9 @@ static int gs_post_mx(lbfgsx_ctx* c, double* scal, double* sdots, double* gdots,
     GsCols<float> cols;
     gs_fill_cols32(c, cols);
     const int64_t nq = c->n / 4;
-    const int grid = int(std::max<int64_t>(1, std::min<int64_t>((nq + kBlock - 1) / kBlock, g->grid_post)));
+    const int grid = int(std::max<int64_t>(1, std::min<int64_t>((nq + kBlock - 1) / kBlock, kGsGridPost)));
     double* sc = static_cast<double*>(c->sc);
-    const int rev = (c->zigzag && (c->tl_step++ & 1u)) ? 1 : 0;
+    const int rev = (c->tl_step++ & 1u) ? 1 : 0;
     int NCsel = 0;
     EventPair ev;
     if (c->timing)
@@ -688,8 +685,8 @@ static int gs_direction_mx(lbfgsx_ctx* c, const double* coef, double coef_g, dou
         cf.c[cn + j] = coef[m + j];
     }
     const int64_t nq = c->n / 4;
-    const int grid = int(std::max<int64_t>(1, std::min<int64_t>((nq + kBlock - 1) / kBlock, g->grid_combine)));
-    const int rev = (c->zigzag && (c->tl_step++ & 1u)) ? 1 : 0;
+    const int grid = int(std::max<int64_t>(1, std::min<int64_t>((nq + kBlock - 1) / kBlock, kGsGridCombine)));
+    const int rev = (c->tl_step++ & 1u) ? 1 : 0;
     EventPair hv;
     if (c->timing)
     {

@@ -119,14 +119,16 @@ __global__ void __launch_bounds__(kBlock) k_eval(const T* __restrict__ x, T* __r
 
 // ---------------------------------------------------------------- K2: line-search trial
 // x = xp + step*d ; g = grad f(x) ; out[0] = f(x), out[1] = g.d
-// NTL / NTS: non-temporal hint on the loads of xp and d / on the stores of x and g (measured, profiles/r2_trial_policy_ab.txt)
-template <class T, class OBJ, int U = 4, bool NTL = false, bool NTS = false>
+// Plain (cacheable) loads of xp and d and stores of x and g, 4 vectors per stream and thread in flight: non-temporal hints
+// and 8 in flight were measured and lost (profiles/r2_trial_policy_ab.txt)
+template <class T, class OBJ>
 __global__ void __launch_bounds__(kBlock) k_trial(const T* __restrict__ xp, const T* __restrict__ d, T step,
                                                   T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj,
                                                   RedWs ws, T* __restrict__ out, int rev)
 {
     typedef typename AccOf<T>::type A;
     constexpr int W = Vec16<T>::W;
+    constexpr int U = 4;
     A acc[2];
     const int64_t nv = n / W;
     // tiles of U x kBlock vectors; both loads of every vector are issued before the first use.  The tile order
@@ -141,8 +143,8 @@ __global__ void __launch_bounds__(kBlock) k_trial(const T* __restrict__ xp, cons
         for (int u = 0; u < U; u++)
             if (base + u * kBlock < nv)
             {
-                pxp[u] = ldv<T, NTL>(xp, base + u * kBlock);
-                pd[u] = ldv<T, NTL>(d, base + u * kBlock);
+                pxp[u] = ldv(xp, base + u * kBlock);
+                pd[u] = ldv(d, base + u * kBlock);
             }
 #pragma unroll
         for (int u = 0; u < U; u++)
@@ -155,8 +157,8 @@ __global__ void __launch_bounds__(kBlock) k_trial(const T* __restrict__ xp, cons
                 for (int k = 0; k < W; k++)
                     px.e[k] = pxp[u].e[k] + step * pd[u].e[k];
                 obj.pack(vi, px, pg, acc[0]);
-                stv<T, NTS>(x, vi, px);
-                stv<T, NTS>(g, vi, pg);
+                stv(x, vi, px);
+                stv(g, vi, pg);
 #pragma unroll
                 for (int k = 0; k < W; k++)
                     acc[1].add_prod(pg.e[k], pd[u].e[k]);
@@ -327,7 +329,6 @@ enum { TL_INIT = 0, TL_SUB = 1, TL_SUBDIV = 2, TL_ADD = 3 };
 
 struct TwoLoopArgs
 {
-    int chunked;  // 1: each block streams one contiguous slab (DRAM-page friendly); 0: grid-stride tiles
     int i_num;    // sc[i_num] / sc[i_den] = alpha_j            (TL_SUB, TL_SUBDIV, TL_ADD)
     int i_den;    // ys_j
     int i_num2;   // sc[i_num2] / sc[i_den] = beta             (TL_ADD)
@@ -341,9 +342,9 @@ struct TwoLoopArgs
 // The streaming body shared by the single-problem and the lock-step batched kernels: tile bases first, first+stride,
 // ... < last (in 16-byte vectors), each tile U independent 16-byte accesses per stream, then (do_tail) the scalar
 // remainder.  rev_top >= 0 mirrors the tile order (tile base b -> rev_top - b); limit bounds the vector index.
-// NT: non-temporal hint on the history / gradient streams (read once per launch); QPOL: the same hint on q itself,
-// bit 0 = its loads, bit 1 = its stores (q is re-read by the next step).
-template <class T, int MODE, int U, bool NT, int QPOL, class A>
+// The history / gradient streams (read once per launch) carry the non-temporal hint (+8 % on MI355X); q itself, which the
+// next step re-reads, does not: it stays eligible for the memory-side cache.
+template <class T, int MODE, int U, class A>
 __device__ __forceinline__ void twoloop_body(T* __restrict__ q, const T* __restrict__ vin, T a, const T* __restrict__ u,
                                              const T* __restrict__ w, int64_t n, T coef, T theta, int64_t first,
                                              int64_t last, int64_t stride, int64_t limit, int64_t rev_top, bool do_tail,
@@ -362,14 +363,14 @@ __device__ __forceinline__ void twoloop_body(T* __restrict__ q, const T* __restr
             if (vi < limit)
             {
                 if (MODE == TL_INIT)
-                    pq[k] = ldv<T, NT>(vin, vi);
+                    pq[k] = ldv<T, true>(vin, vi);
                 else
                 {
-                    pq[k] = ldv<T, (QPOL & 1) != 0>(q, vi);
-                    pu[k] = ldv<T, NT>(u, vi);
+                    pq[k] = ldv(q, vi);
+                    pu[k] = ldv<T, true>(u, vi);
                 }
                 if (MODE != TL_SUBDIV)  // TL_SUBDIV reduces against the column it just subtracted
-                    pw[k] = ldv<T, NT>(w, vi);
+                    pw[k] = ldv<T, true>(w, vi);
             }
         }
 #pragma unroll
@@ -390,7 +391,7 @@ __device__ __forceinline__ void twoloop_body(T* __restrict__ q, const T* __restr
                     if (MODE == TL_SUBDIV)
                         pq[k].e[e] = pq[k].e[e] / theta;  // res /= theta (:293)
                 }
-                stv<T, (QPOL & 2) != 0>(q, vi, pq[k]);
+                stv(q, vi, pq[k]);
 #pragma unroll
                 for (int e = 0; e < W; e++)
                     acc.add_prod(MODE == TL_SUBDIV ? pu[k].e[e] : pw[k].e[e], pq[k].e[e]);
@@ -418,12 +419,9 @@ __device__ __forceinline__ void twoloop_body(T* __restrict__ q, const T* __restr
         }
 }
 
-__device__ __forceinline__ int64_t slab_of(int64_t nv, int64_t tile, int64_t blocks)
-{
-    return ((nv + blocks - 1) / blocks + tile - 1) / tile * tile;
-}
-
-template <class T, int MODE, int U, bool NT, int QPOL>
+// grid-stride tiles of U = 4 16-byte accesses per stream and thread (8 in flight and a contiguous slab per block were
+// measured and lost, profiles/)
+template <class T, int MODE>
 __global__ void __launch_bounds__(kBlock) k_twoloop(T* __restrict__ q, const T* __restrict__ vin, T a,
                                                     const T* __restrict__ u, const T* __restrict__ w, int64_t n,
                                                     T* __restrict__ sc, TwoLoopArgs args, RedWs ws)
@@ -438,29 +436,13 @@ __global__ void __launch_bounds__(kBlock) k_twoloop(T* __restrict__ q, const T* 
     if (MODE == TL_SUBDIV)
         theta = sc[args.i_theta];
 
+    constexpr int U = 4;
     A acc[1];
     const int64_t nv = n / W;
     const int64_t tile = int64_t(kBlock) * U;
-    int64_t first, last, stride;
-    if (args.chunked)
-    {
-        const int64_t slab = slab_of(nv, tile, gridDim.x);
-        first = int64_t(blockIdx.x) * slab;
-        last = first + slab < nv ? first + slab : nv;
-        stride = tile;
-    }
-    else
-    {
-        first = int64_t(blockIdx.x) * tile;
-        last = nv;
-        stride = int64_t(gridDim.x) * tile;
-    }
-    int64_t rev_top = -1;
-    if (args.rev)
-        rev_top = args.chunked ? (int64_t(gridDim.x) * (slab_of(nv, tile, gridDim.x) / tile) - 1) * tile
-                               : ((nv + tile - 1) / tile - 1) * tile;
-    twoloop_body<T, MODE, U, NT, QPOL>(q, vin, a, u, w, n, coef, theta, first, last, stride, nv, rev_top,
-                                      blockIdx.x == 0 && threadIdx.x == 0, acc[0]);
+    const int64_t rev_top = args.rev ? ((nv + tile - 1) / tile - 1) * tile : -1;
+    twoloop_body<T, MODE, U>(q, vin, a, u, w, n, coef, theta, int64_t(blockIdx.x) * tile, nv, int64_t(gridDim.x) * tile, nv,
+                             rev_top, blockIdx.x == 0 && threadIdx.x == 0, acc[0]);
     if (grid_reduce<1>(acc, ws) && threadIdx.x == 0)
         sc[args.i_out] = T(acc[0].value());
 }
@@ -578,10 +560,11 @@ struct PersistArgs
     int ncorr, m;
     int pcol[kPersistMaxM];  // physical columns newest -> oldest
     unsigned gen_base;     // generation word value before this launch
-    int zigzag;
+    int zigzag;            // always 1 (consecutive steps alternate the traversal direction); kept as an argument: the kernel
+                           // sits at its register cap and its code is left as measured
     unsigned first_rev;    // direction parity of the first step
     int64_t ld;            // column stride of S / Y (elements)
-    int pub_first;         // MEET: a step's {generation, dot} goes out before the dot's copy for the host (LBFGSX_MEET_PUB=0: after it)
+    int pub_first;         // always 1: a step's {generation, dot} goes out before the dot's copy for the host (see zigzag)
 };
 
 constexpr int kSc1 = 16;  // cache-policy bit of the buffer instructions: agent scope (loads bypass L1, stores write through)

@@ -46,7 +46,6 @@ struct lbfgsb_state
     int *vals_in = nullptr, *vals_out = nullptr;
     bool keys_valid = false;   // keys_in holds the sort keys of the break points in brk (a build may leave them out: ensure_keys)
     bool vals_iota = false;    // vals_in holds 0..n-1 (written by the first build, never changed by the sorts, which write vals_out)
-    bool keys_lazy = true;     // LBFGSX_KEYS_LAZY=0: every build writes keys and indices (A/B, tests)
     void* sort_tmp = nullptr;
     size_t sort_tmp_bytes = 0;
     int* phys_dev = nullptr;          // logical slot -> physical column, device copy
@@ -84,10 +83,9 @@ struct lbfgsb_state
     unsigned lu_cap = 0;
     int lu_n = 0;
     int64_t lu_pred = int64_t(1) << 40;  // |L u U| of the previous partition: the list is only kept while the sets are small
-    int64_t lu_max = 262144;             // ... i.e. up to this many rows (LBFGSX_LU_MAX; 16384 until round 3: with 65536 .. 2^20
-                                         // the iterations whose sets hold 10^4..10^5 rows keep the fused sweeps, +2 % from x0)
+    static constexpr int64_t kLuMax = 262144;  // ... i.e. up to this many rows (16384 until round 3: with 65536 .. 2^20
+                                               // the iterations whose sets hold 10^4..10^5 rows keep the fused sweeps, +2 % from x0)
     bool lu_valid = false;
-    bool lu_use = true;                   // LBFGSX_LU_LIST=0: always scan
     bool sweep_fuse = true;               // LBFGSX_SWEEP_SOLVE_FUSE=0: the solve and the sweep's statements stay separate passes
     // compact copy of the free rows of [Y S] (GramRows, lbfgsb_kernels.cuh): written by the full Gram pass of the first
     // BOXCQP solve when the caller expects sweeps (lbfgsx_b_set_compaction), read by the passes of the sweeps
@@ -124,7 +122,8 @@ struct lbfgsb_state
     int64_t psel_last = -1;               // candidates of the previous partial sort: the in-pass list pays while they are few
     bool list12 = true;                   // W_{L u U}'(-c) inside the pass that computes W_L'l and W_U'u (LBFGSX_LIST12=0: a launch of its own)
     bool psel_small = true;               // <= kPselSmallCap listed candidates: ordered by one block (LBFGSX_PSEL_SMALL=0: the three launches)
-    int64_t psel_max = int64_t(1) << 17;  // (appending and ordering 10^6 rows costs more than the separate selection pass)
+    static constexpr int64_t kPselMax = int64_t(1) << 17;  // candidates of the previous search up to which the build lists them
+                                          // (appending and ordering 10^6 rows costs more than the separate selection pass)
     // W'd of the Cauchy search (and the deferred dots of add_correction) from the kept compact copy (k_multidot2_wf)
     bool wtdc_use = true;                 // LBFGSX_WTD_COMPACT=0: always the pass over the full-length columns
     int* wtdc_list = nullptr;             // rows outside the copy with d != 0 or s_new != 0 (k_cauchy_build)
@@ -137,15 +136,12 @@ struct lbfgsb_state
     void* cv_buf = nullptr;               // 8 vectors of cv_cap elements + cv_cap state bytes
     int64_t cv_cap = 0;
     int64_t cv_backs = 0, cv_starts = 0;  // instrumentation: passes that put them back early / minimisations that used them
-    int vonly_groups = 0;                 // LBFGSX_VONLY_GROUPS=1: the v-row Gram walks one row per step (A/B of the lane groups)
-    bool vrows = true;                    // LBFGSX_VROWS=0: the v-row / selected-entries passes through the LDS tile kernel (k_gram_dd<.., VONLY>)
-                                          // instead of the register kernel k_vrows (A/B; same sums)
     bool wf_on = false;                   // the caller's hint for the current subspace minimisation
     bool wf_valid = false;
     int64_t wf_n = 0;                     // rows in the copy
     int64_t nfree_last = 0;               // |F| of the last lbfgsx_b_cauchy_finish
     hipEvent_t chain_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // pieces of a Cauchy chunk
-    int chain_pieces = 8;                 // LBFGSX_GCP_PIECES=1: a chunk's terms arrive in one piece
+    static constexpr int kChainPieces = 8;  // a chunk of 2^17 crossings or more travels in this many pieces
     // rows that entered / left the free set since the last lbfgsx_b_free_delta (the carried Gram of BFGSMatB::solve_PtBP)
     unsigned char* fprev = nullptr;       // [n] free bit at that call
     int* dl_enter = nullptr;              // [dl_cap]
@@ -163,7 +159,6 @@ struct lbfgsb_state
     long long wf_epoch = -2;              // the one that last wrote or patched the copy
     long long wf_patched_epoch = -2;      // sub_epoch at which the W'd pass wrote the replaced pair into the copy ...
     int wf_patched_slot = -1;             // ... and the storage slot it wrote
-    bool wf_prepatch = true;              // LBFGSX_WF_PREPATCH=0: leave the patch to the carried Gram's pass (A/B, tests)
     int* wf_pos = nullptr;                // [n] row -> position, -1: none
     double* g_host = nullptr;             // pinned landing zone of lbfgsx_b_cauchy_chunk
     // the first chunk of the sorted break points, gathered and copied behind the build's sort and ahead of its W'd pass: it
@@ -182,10 +177,10 @@ struct lbfgsb_state
     int* g_idx = nullptr;
     int64_t g_cap = 0;
     int g_ncorr = 0;
-    double* gram_partial = nullptr;   // [gram_blocks][3][256][2]
+    double* gram_partial = nullptr;   // [kGramBlocks][3][256][2]
     double* gram_partial2 = nullptr;  // [32][3][256][2]
     double* gram_out = nullptr;       // [3][256]
-    int gram_blocks = 1024;  // 4 resident blocks per CU (33 KB of LDS each)
+    static constexpr int kGramBlocks = 1024;  // 4 resident blocks per CU (33 KB of LDS each)
     // exact Gram on the matrix cores (gram_i8.cuh): radix-256 digits, v_mfma_i32_32x32x32_i8, integer sums
     bool gram_i8 = false;                    // LBFGSX_GRAM=i8
     int i8_min_tot = 1;                      // fewer columns than this: the double-double kernel (LBFGSX_GRAM_I8_MIN)
@@ -196,9 +191,8 @@ struct lbfgsb_state
     unsigned long long* i8_vsum = nullptr;   // [11][ne_pad]
     int i8_waves = 0, i8_nepad = 0;
     int gram_mode = 0;       // 2 (LBFGSX_GRAM=blocked): force the multi-launch blocked Gram + separate W'v
-    int gram_dd_blocks = 0;          // LBFGSX_GRAM_DD_BLOCKS: 0 = occupancy x CUs
     int num_cus = 256;
-    int dots_grid = 512;            // LBFGSX_DOTS_GRID: blocks of the all-column multi-dot kernels
+    static constexpr int kDotsGrid = 512;  // blocks of the all-column multi-dot kernels
     bool multidot_chunked = false;  // LBFGSX_MULTIDOT=chunked: 8 columns per launch (round-1a kernel)
     // device GCP search (gcp_scan.cuh): per-chunk work set, allocated on first use
     double *s_brk = nullptr, *s_g = nullptr, *s_z = nullptr, *s_W = nullptr, *s_P = nullptr, *s_C = nullptr,
@@ -468,16 +462,10 @@ int bounded_alloc(lbfgsx_ctx* c)
     LBFGSX_HIP(hipMalloc(reinterpret_cast<void**>(&b->lu_list), sizeof(int) * 2 * size_t(b->lu_cap)));
     LBFGSX_HIP(hipMalloc(reinterpret_cast<void**>(&b->lu_cnt), sizeof(unsigned)));
     LBFGSX_HIP(hipMemset(b->lu_cnt, 0, sizeof(unsigned)));
-    if (const char* e = getenv("LBFGSX_LU_LIST"))
-        b->lu_use = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_SWEEP_SOLVE_FUSE"))
         b->sweep_fuse = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_COMPACT_FREE"))
         b->wf_use = atoi(e) != 0;
-    if (const char* e = getenv("LBFGSX_VONLY_GROUPS"))
-        b->vonly_groups = atoi(e);
-    if (const char* e = getenv("LBFGSX_VROWS"))
-        b->vrows = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_SPLIT"))
         b->split = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_FINISH_FUSE"))
@@ -508,8 +496,6 @@ int bounded_alloc(lbfgsx_ctx* c)
         b->gpre_use = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_DELTA_AHEAD"))
         b->fd_use = atoi(e) != 0;
-    if (const char* e = getenv("LBFGSX_SELECT_MAX"))  // candidates of the previous search up to which the build lists them
-        b->psel_max = std::max<int64_t>(0, atoll(e));
     if (const char* e = getenv("LBFGSX_LIST12"))
         b->list12 = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_PSEL_SMALL"))  // 0: a short candidate list is ordered by the three launches of round 4
@@ -520,10 +506,6 @@ int bounded_alloc(lbfgsx_ctx* c)
         b->stash_use = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_WTD_LIST_CAP"))  // test aid: a short list overflows
         b->wtdc_cap = unsigned(std::max(1, std::min(1 << 20, atoi(e))));
-    if (const char* e = getenv("LBFGSX_LU_MAX"))
-        b->lu_max = std::max<int64_t>(0, atoll(e));
-    if (const char* e = getenv("LBFGSX_GCP_PIECES"))
-        b->chain_pieces = std::max(1, std::min(8, atoi(e)));
     LBFGSX_HIP(hipMalloc(reinterpret_cast<void**>(&b->colmax), sizeof(unsigned long long) * 2 * size_t(c->m + 1)));
     LBFGSX_HIP(hipMemset(b->colmax, 0, sizeof(unsigned long long) * 2 * size_t(c->m + 1)));
     b->colmax_ok.assign(size_t(c->m + 1), 0);
@@ -560,27 +542,17 @@ int bounded_alloc(lbfgsx_ctx* c)
             warned = true;
         }
     }
-    if (const char* e = getenv("LBFGSX_KEYS_LAZY"))
-        b->keys_lazy = atoi(e) != 0;
-    if (const char* e = getenv("LBFGSX_WF_PREPATCH"))
-        b->wf_prepatch = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_GCP_CHAIN"))
         b->chain_host = std::strcmp(e, "scan") != 0;
-    if (const char* e = getenv("LBFGSX_DOTS_GRID"))
-        b->dots_grid = std::max(64, std::min(atoi(e), 4096));
     if (const char* e = getenv("LBFGSX_MULTIDOT"))
         b->multidot_chunked = (std::strcmp(e, "chunked") == 0);
-    if (const char* e = getenv("LBFGSX_GRAM_BLOCKS"))
-        b->gram_blocks = std::max(64, std::min(atoi(e), 4096));
-    if (const char* e = getenv("LBFGSX_GRAM_DD_BLOCKS"))
-        b->gram_dd_blocks = std::max(0, atoi(e));
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0)
             b->num_cus = prop.multiProcessorCount;
     }
     const size_t gent = size_t(b->gtile) * 256;  // entries the Gram buffers hold
-    LBFGSX_HIP(hipMalloc(reinterpret_cast<void**>(&b->gram_partial), sizeof(double) * size_t(b->gram_blocks) * gent * 2));
+    LBFGSX_HIP(hipMalloc(reinterpret_cast<void**>(&b->gram_partial), sizeof(double) * size_t(lbfgsb_state::kGramBlocks) * gent * 2));
     LBFGSX_HIP(hipMalloc(reinterpret_cast<void**>(&b->gram_partial2), sizeof(double) * 32 * gent * 2));
     if (c->outmap_dev)
     {
@@ -845,7 +817,7 @@ static int wtv_all(lbfgsx_ctx* c, int total, int vsel_id, const T* vcol, int mas
     Cols<T, 32> cl = col_list<T, 32>(c, which, total);
     // 2c + 1 grid reductions per launch: fewer, fatter blocks keep the reduction tail short (each thread already has
     // 2c 16-byte loads in flight)
-    const int grid = std::min(c->grid_for(c->n), c->bstate->dots_grid);
+    const int grid = std::min(c->grid_for(c->n), lbfgsb_state::kDotsGrid);
     LBFGSX_LAUNCH((k_multidot_all<T, NC>), dim3(grid), dim3(kBlock), 0, c->stream, cl, total, bvecs<T>(c), vsel_id, vcol,
                        mask, c->n, c->ws, c->bstate->dout);
     LBFGSX_HIP(hipGetLastError());
@@ -971,7 +943,7 @@ static int wtd2_all(lbfgsx_ctx* c, int total, const T* snew, const T* dvec, doub
     for (int k = 0; k < total; k++)
         which[k] = k;
     Cols<T, 32> cl = col_list<T, 32>(c, which, total);
-    const int grid = std::min(c->grid_for(c->n), c->bstate->dots_grid);
+    const int grid = std::min(c->grid_for(c->n), lbfgsb_state::kDotsGrid);
     LBFGSX_LAUNCH((k_multidot2_all<T, NC>), dim3(grid), dim3(kBlock), 0, c->stream, cl, total, snew, dvec, c->n, c->ws,
                        c->bstate->dout);
     LBFGSX_HIP(hipGetLastError());
@@ -1063,14 +1035,14 @@ static int wtd2_wf_x(lbfgsx_ctx* c, int total, int newest, double* wtd)
     const T* ynew = static_cast<const T*>(c->col(c->Y, c->phys[size_t(newest)]));
     // the pass also writes the new pair into the copy (lbfgsb_x.cuh: kx_multidot2_wf, dst_a / dst_b): the carried Gram's pass of
     // this iteration's subspace minimisation (lbfgsx_b_gram_pairs_dd) then has nothing to patch.  Remembered by epoch and slot.
-    T* dst_a = b->wf_prepatch ? static_cast<T*>(b->wf) + int64_t(wf_col(c, fresh_a, total)) * b->wf_ld : nullptr;
-    T* dst_b = b->wf_prepatch ? static_cast<T*>(b->wf) + int64_t(wf_col(c, fresh_b, total)) * b->wf_ld : nullptr;
+    T* dst_a = static_cast<T*>(b->wf) + int64_t(wf_col(c, fresh_a, total)) * b->wf_ld;
+    T* dst_b = static_cast<T*>(b->wf) + int64_t(wf_col(c, fresh_b, total)) * b->wf_ld;
     lbfgsx::poll_arm(c);
     rc = xl::multidot2_wf<T>(c->stream, b->num_cus, wfc, total, fresh_a, fresh_b, snew, ynew, static_cast<const T*>(b->dvec), b->wf_idx,
                              b->wf_n, full, b->wtdc_list, int(b->wtdc_n), wsx(c), b->dout, dst_a, dst_b);
     if (rc)
         return rc;
-    b->wf_patched_epoch = dst_a ? b->sub_epoch : -2;
+    b->wf_patched_epoch = b->sub_epoch;
     b->wf_patched_slot = newest;
     double r[2 * kColsX];
     rc = fetch_doubles(c, 2 * total, r);
@@ -1333,7 +1305,7 @@ template <class T, class OBJ>
 static int dg_maxstep_trial_t(lbfgsx_ctx* c, OBJ obj, T step, double* r4)
 {
     const int grid = c->grid_for(c->n);
-    const int rev = (c->zigzag && (c->tl_step & 1u)) ? 1 : 0;  // the order the trial launch it stands for would have taken
+    const int rev = (c->tl_step & 1u) ? 1 : 0;  // the order the trial launch it stands for would have taken
     lbfgsx::poll_arm(c);
     // byte model: xp, g, d, lb, ub read, x and grad written, + the objective's own vectors (a, b of the quadratic)
     lbfgsx::model_add(double(c->n) * sizeof(T) * (7 + (sizeof(OBJ) >= 2 * sizeof(void*) ? 2 : 0)));
@@ -1466,7 +1438,7 @@ int lbfgsx_b_post_linesearch_build(lbfgsx_ctx* c, double tau, double* projgnorm,
     // sort whose selection rides behind the build keeps the two-pass form.  The build half is computed for the state the
     // solver will be in if it goes on and accepts the pair: lbfgsx_b_cauchy_build_partial checks that it is.
     const bool tau_ok = tau > 0.0 && std::isfinite(tau);
-    const bool sel_inline = tau_ok && b->psel_use && b->psel_last >= 0 && b->psel_last <= b->psel_max &&
+    const bool sel_inline = tau_ok && b->psel_use && b->psel_last >= 0 && b->psel_last <= lbfgsb_state::kPselMax &&
                             c->n < (int64_t(1) << 31) && psel_alloc(c);
     const bool sel_ahead = !sel_inline && b->stash_use && b->dout_host && tau_ok;
     if (!(b->pb_use && c->outmap_dev && b->dout_host && !b->gram_i8 && !sel_ahead))
@@ -1479,9 +1451,8 @@ int lbfgsx_b_post_linesearch_build(lbfgsx_ctx* c, double tau, double* projgnorm,
         lbfgsx::poll_arm(c);
         // the sort keys over all n rows are only wanted when the candidates of the partial sort are NOT listed by this pass; the
         // indices once (ensure_keys rebuilds either on demand)
-        const bool lazy_keys = b->keys_lazy && sel_inline;
-        T* keys_arg = lazy_keys ? static_cast<T*>(nullptr) : P<T>(b->keys_in);
-        int* vals_arg = (b->keys_lazy && b->vals_iota) ? static_cast<int*>(nullptr) : b->vals_in;
+        T* keys_arg = sel_inline ? static_cast<T*>(nullptr) : P<T>(b->keys_in);
+        int* vals_arg = b->vals_iota ? static_cast<int*>(nullptr) : b->vals_in;
         // byte model: x, xp, g, gp, lb, ub and the positions read; s, y, brk, d, xcp (and the keys / indices, when wanted) written
         lbfgsx::model_add(double(c->n) * (11 * sizeof(T) + 4 + (keys_arg ? sizeof(T) : 0) + (vals_arg ? 4 : 0)));
         b->keys_valid = keys_arg != nullptr;
@@ -1874,7 +1845,7 @@ int lbfgsx_b_cauchy_build_partial(lbfgsx_ctx* c, double tau, int64_t* nfree, int
     int64_t ns = 0;
     const bool tau_ok = tau > 0.0 && std::isfinite(tau);
     // the candidates of the partial sort: collected by the build itself, else selected by a pass that rides behind it
-    const bool sel_inline = tau_ok && b->psel_use && b->psel_last >= 0 && b->psel_last <= b->psel_max &&
+    const bool sel_inline = tau_ok && b->psel_use && b->psel_last >= 0 && b->psel_last <= lbfgsb_state::kPselMax &&
                             c->n < (int64_t(1) << 31) && psel_alloc(c);
     const bool sel_ahead = !sel_inline && b->stash_use && b->dout_host && tau_ok;
     DISPATCH_T(c, {
@@ -2314,9 +2285,9 @@ int lbfgsx_b_cauchy_scan(lbfgsx_ctx* c, int64_t first, int64_t count, int64_t no
         double* hB = hA + (count + 1);
         // 24 bytes per crossing over PCIe and ~1.4 ns of host arithmetic per crossing are about the same time: the chunk
         // travels in pieces and the host walks a piece while the next ones are still on the way
-        const int nsub = (count >= (int64_t(1) << 17) && b->chain_pieces > 1) ? b->chain_pieces : 1;
+        const int nsub = count >= (int64_t(1) << 17) ? lbfgsb_state::kChainPieces : 1;
         if (nsub > 1 && !b->chain_ev[0])
-            for (int q = 0; q < 8; q++)
+            for (int q = 0; q < lbfgsb_state::kChainPieces; q++)
                 LBFGSX_HIP(hipEventCreateWithFlags(&b->chain_ev[q], hipEventDisableTiming));
         for (int q = 0; q < nsub; q++)
         {
@@ -2821,9 +2792,7 @@ static int launch_gram_dd(lbfgsx_ctx* c, int64_t nbatch, int tot, int vsel_id, i
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_gram_dd<T, KP>, kBlock, lds) != hipSuccess || occ < 1)
         occ = 2;
-    int blocks = std::min(b->gram_blocks, occ * b->num_cus);
-    if (b->gram_dd_blocks > 0)
-        blocks = std::min(b->gram_blocks, b->gram_dd_blocks);
+    int blocks = std::min(lbfgsb_state::kGramBlocks, occ * b->num_cus);
     blocks = int(std::max<int64_t>(1, std::min<int64_t>(blocks, (nbatch + 3) / 4)));
     int which[32];
     for (int k = 0; k < tot; k++)
@@ -2846,7 +2815,7 @@ static int launch_gram_vonly(lbfgsx_ctx* c, int64_t nbatch, int tot, int vsel_id
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_gram_dd<T, 1, CS, true>, kBlock, lds) != hipSuccess || occ < 1)
         occ = 2;
-    int blocks = std::min(b->gram_blocks, occ * b->num_cus);
+    int blocks = std::min(lbfgsb_state::kGramBlocks, occ * b->num_cus);
     blocks = int(std::max<int64_t>(1, std::min<int64_t>(blocks, (nbatch + 3) / 4)));
     int which[32];
     for (int k = 0; k < tot; k++)
@@ -2908,7 +2877,7 @@ static bool gram_stash_launch(lbfgsx_ctx* c, int slot, int mask, const int* list
                 gr.st_alt = bvecs_cv<T>(c).st;
                 gr.st_pos = b->wf_pos;
             }
-            blocks = xl::gram<T>(c->stream, single ? list_blocks(nlist) : b->gram_blocks, colsx_full<T>(c, tot),
+            blocks = xl::gram<T>(c->stream, single ? list_blocks(nlist) : lbfgsb_state::kGramBlocks, colsx_full<T>(c, tot),
                                  tot, bvecs<T>(c), -1, mask, nlist, b->gram_partial, pro, gr, out, out_dd,
                                  (signal && single) ? c->ws.done : static_cast<unsigned long long*>(nullptr),
                                  (signal && single) ? c->ws.seq : 0ull, b->xtickets + 1 + kMaxGridX / kGroupX);
@@ -3101,7 +3070,7 @@ int lbfgsx_b_wtv_prologue(lbfgsx_ctx* c, int mask, int vsel_id, int prologue, co
         return rc;
     lbfgsb_state* b = c->bstate;
     const int tot = 2 * c->ncorr, ntot = tot + 1;
-    const bool xsplit = b->split && b->vrows;  // kx_rows: any 2c <= 80
+    const bool xsplit = b->split;  // kx_rows: any 2c <= 80
     if (tot < 1 || (ntot > kGramDDCS && !xsplit) || tot > kColsX || vsel_id < 0 || !wtv || b->gram_mode == 2 ||
         prologue < LBFGSX_GP_NONE || prologue > LBFGSX_GP_LINEAR)
     {
@@ -3109,7 +3078,7 @@ int lbfgsx_b_wtv_prologue(lbfgsx_ctx* c, int mask, int vsel_id, int prologue, co
         return LBFGSX_E_INVALID;
     }
     // the compact vectors serve the pass between two sweeps: rhs += ..., v = -rhs on the P rows of the compact copy
-    const bool by_pos = b->cv_live && b->vrows && wf_serves(c, mask) && prologue != LBFGSX_GP_LINEAR &&
+    const bool by_pos = b->cv_live && wf_serves(c, mask) && prologue != LBFGSX_GP_LINEAR &&
                         (vsel_id == VS_NEG_RHS || vsel_id == VS_NEG_CF || vsel_id == VS_Y);
     if (b->cv_live && !by_pos)
     {
@@ -3119,11 +3088,9 @@ int lbfgsx_b_wtv_prologue(lbfgsx_ctx* c, int mask, int vsel_id, int prologue, co
     }
     const bool compact = wf_serves(c, mask);
     const int64_t nrows = compact ? b->wf_n : c->n;
-    const int64_t nbatch = (nrows + kGramDDRows - 1) / kGramDDRows;
     rc = upload_phys(c);
     if (rc)
         return rc;
-    int blocks = 1;
     if (xsplit)
     {
         DISPATCH_T(c, {
@@ -3166,47 +3133,16 @@ int lbfgsx_b_wtv_prologue(lbfgsx_ctx* c, int mask, int vsel_id, int prologue, co
         }
         GramRows<T> gr{};
         gr.in_idx = (compact && !by_pos) ? b->wf_idx : nullptr;
-        gr.vgroups = b->vonly_groups;
-        if (b->vrows)
-        {
-            const BVecs<T> cvb = bvecs_cv<T>(c);
-            lbfgsx::poll_arm(c);
-            rc = launch_vrows_v<T>(c, tot, vsel_id, mask, pro, gr, nrows, by_pos ? &cvb : nullptr);
-            blocks = 0;
-        }
-        // the tile row stride must hold ntot columns: the strides of the full kernel's KP classes
-        else if (ntot <= 11) blocks = launch_gram_vonly<T, 11>(c, nbatch, tot, vsel_id, mask, pro, gr, nrows);
-        else if (ntot <= 15) blocks = launch_gram_vonly<T, 15>(c, nbatch, tot, vsel_id, mask, pro, gr, nrows);
-        else if (ntot <= 23) blocks = launch_gram_vonly<T, 23>(c, nbatch, tot, vsel_id, mask, pro, gr, nrows);
-        else if (ntot <= 27) blocks = launch_gram_vonly<T, 27>(c, nbatch, tot, vsel_id, mask, pro, gr, nrows);
-        else blocks = launch_gram_vonly<T, 31>(c, nbatch, tot, vsel_id, mask, pro, gr, nrows);
+        const BVecs<T> cvb = bvecs_cv<T>(c);
+        lbfgsx::poll_arm(c);
+        rc = launch_vrows_v<T>(c, tot, vsel_id, mask, pro, gr, nrows, by_pos ? &cvb : nullptr);
     });
     if (rc)
         return rc;
     double h[64];
-    if (blocks == 0)  // k_vrows: the last block has published the rounded sums
-    {
-        rc = fetch_gram_out(c, 0, tot, h);
-        if (rc)
-            return rc;
-        for (int j = 0; j < tot; j++)
-            wtv[j] = h[j];
-        return LBFGSX_OK;
-    }
-    const int nch = std::min(blocks, 32);
-    LBFGSX_LAUNCH(k_gram_finish, dim3(1, nch), dim3(kBlock), 0, c->stream, b->gram_partial, blocks, b->gram_partial2, 0);
-    LBFGSX_LAUNCH(k_gram_finish, dim3(1, 1), dim3(kBlock), 0, c->stream, b->gram_partial2, nch, b->gram_out, 1);
-    LBFGSX_HIP(hipGetLastError());
-    if (b->gram_out_host)
-    {
-        LBFGSX_HIP(lbfgsx::stream_sync(c->stream));
-        std::memcpy(h, b->gram_out_host, sizeof(h));
-    }
-    else
-    {
-        LBFGSX_HIP(lbfgsx::copy_async(h, b->gram_out, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        LBFGSX_HIP(lbfgsx::stream_sync(c->stream));
-    }
+    rc = fetch_gram_out(c, 0, tot, h);  // k_vrows: the last block has published the rounded sums
+    if (rc)
+        return rc;
     for (int j = 0; j < tot; j++)
         wtv[j] = h[j];
     return LBFGSX_OK;
@@ -3223,8 +3159,6 @@ static int delta_alloc(lbfgsx_ctx* c)
     {
         // room for n / 64 changed rows (what is worth patching instead of recomputing grows with n), 2^14 .. 2^20
         b->dl_cap = unsigned(std::min<int64_t>(c->n, std::max<int64_t>(int64_t(1) << 14, std::min<int64_t>(int64_t(1) << 20, c->n / 64))));
-        if (const char* e = getenv("LBFGSX_DELTA_CAP"))  // tuning aid
-            b->dl_cap = unsigned(std::min<int64_t>(c->n, std::max<int64_t>(64, atoll(e))));
         LBFGSX_HIP(hipMalloc(reinterpret_cast<void**>(&b->fprev), size_t(c->ld)));   // padded like the state bytes
         LBFGSX_HIP(hipMemsetAsync(b->fprev, 0, size_t(c->ld), c->stream));
         LBFGSX_HIP(hipMalloc(reinterpret_cast<void**>(&b->dl_enter), sizeof(int) * size_t(b->dl_cap)));
@@ -3345,7 +3279,7 @@ int lbfgsx_b_gram_pairs_max(lbfgsx_ctx* c)
     const int tot = 2 * c->ncorr;
     if (tot < 1 || tot > kColsX || b->gram_mode == 2)
         return 0;
-    if (b->split && b->vrows)
+    if (b->split)
         return 3 * (tot + 1);
     return tot + 1 <= kGramDDCS ? 64 : 0;
 }
@@ -3359,7 +3293,7 @@ int lbfgsx_b_gram_pairs_dd(lbfgsx_ctx* c, int mask, int vsel_id, int prologue, c
         return rc;
     lbfgsb_state* b = c->bstate;
     const int tot = 2 * c->ncorr, ntot = tot + 1;
-    const bool xsplit = b->split && b->vrows;  // kx_rows: any 2c <= 80, up to 3 (2c + 1) entries
+    const bool xsplit = b->split;  // kx_rows: any 2c <= 80, up to 3 (2c + 1) entries
     if (tot < 1 || tot > kColsX || vsel_id < 0 || !out_dd || b->gram_mode == 2 || npairs < 1 ||
         (xsplit ? npairs > 3 * (kColsX + 1) : (npairs > 64 || ntot > kGramDDCS)) || prologue < LBFGSX_GP_NONE || prologue > LBFGSX_GP_LINEAR)
     {
@@ -3470,7 +3404,7 @@ int lbfgsx_b_gram_pairs_dd(lbfgsx_ctx* c, int mask, int vsel_id, int prologue, c
             return LBFGSX_OK;
         }
     }
-    bool use_vrows = b->vrows && !compact_out && vrows_plan(npairs, pair_i, pair_j, tot, (tot <= 20 ? 20 : 32) + 1, col_a, col_b, slot);
+    bool use_vrows = !compact_out && vrows_plan(npairs, pair_i, pair_j, tot, (tot <= 20 ? 20 : 32) + 1, col_a, col_b, slot);
     if (use_vrows && col_a >= 0 && (tot > 20 || !compact_in))  // the three-row form walks the compact copy's row list
         use_vrows = false;
     if (use_vrows && col_a < 0)  // v row only: the row length of the class launch_vrows_v picks
@@ -3611,7 +3545,7 @@ static int gram_dd_core(lbfgsx_ctx* c, int mask, int vsel_id, int prologue, cons
     b->vrow_dd_valid = false;
     const int tot = 2 * c->ncorr;
     const int ntot = tot + (vsel_id >= 0 ? 1 : 0);
-    const bool lu_walk = !list && b->lu_valid && b->lu_use && vsel_id < 0 && prologue == LBFGSX_GP_NONE && mask != 0 &&
+    const bool lu_walk = !list && b->lu_valid && vsel_id < 0 && prologue == LBFGSX_GP_NONE && mask != 0 &&
                          (mask & ~(ST_L | ST_U)) == 0;
     // launched ahead?  (slot 0: the rows of L u U behind lbfgsx_b_wtv_lu; slots 1, 2: the entered / left rows behind
     // lbfgsx_b_gram_pairs_dd)
@@ -3737,7 +3671,7 @@ static int gram_dd_core(lbfgsx_ctx* c, int mask, int vsel_id, int prologue, cons
                 gr.out_pos = b->wf_pos;
             }
             const ColsX<T> cl = (gr.in_idx && !gr.w_by_row) ? colsx_wf<T>(c, tot) : colsx_full<T>(c, tot);
-            blocks = xl::gram<T>(c->stream, one_block ? list_blocks(nrows) : b->gram_blocks, cl, tot, bvecs<T>(c),
+            blocks = xl::gram<T>(c->stream, one_block ? list_blocks(nrows) : lbfgsb_state::kGramBlocks, cl, tot, bvecs<T>(c),
                                  vsel_id, mask, nrows, b->gram_partial, pro, gr, b->gram_out,
                                  gram_dd ? b->gram_dd : static_cast<double*>(nullptr), nullptr, 0ull,
                                  one_block ? b->xtickets + 1 + kMaxGridX / kGroupX : static_cast<unsigned*>(nullptr));
@@ -3888,7 +3822,7 @@ static int solve_dots_t(lbfgsx_ctx* c, int pmask, int vsel_id, const double* coe
     CoefArg<T> cf;
     for (int k = 0; k < 80; k++)
         cf.c[k] = (coef && k < total) ? T(coef[k]) : T(0);
-    const int grid = std::min(c->grid_for(nrows), c->bstate->dots_grid);
+    const int grid = std::min(c->grid_for(nrows), lbfgsb_state::kDotsGrid);
     LBFGSX_LAUNCH((k_solve_dots<T, NC>), dim3(grid), dim3(kBlock), 0, c->stream, cl, total, bvecs<T>(c), vsel_id, cf,
                        coef ? 1 : 0, pmask, fmask, T(theta), nrows, c->ws, c->bstate->dout,
                        compact ? c->bstate->wf_idx : static_cast<const int*>(nullptr));
@@ -3978,7 +3912,7 @@ int lbfgsx_b_sub_sweep_begin(lbfgsx_ctx* c, int first, int64_t* nL, int64_t* nU,
     double r[7];
     // the list pays while L u U is a few thousand rows (steady state: 10^1..10^3); in the early iterations the sets hold
     // 10^5..10^6 rows and the dense scans are the better form -- decided from the size the previous partition found
-    const unsigned lu_cap_now = (c->bstate->lu_use && c->bstate->lu_pred <= c->bstate->lu_max) ? c->bstate->lu_cap : 0u;
+    const unsigned lu_cap_now = c->bstate->lu_pred <= lbfgsb_state::kLuMax ? c->bstate->lu_cap : 0u;
     DISPATCH_T(c, {
         BVecs<T> bv = bvecs<T>(c);
         lbfgsx::model_add(double(c->n) * (7 * sizeof(T) + 2));  // byte model: y, lam, mu, lb, ub, x0, cF and the state byte; state and rhs written
@@ -4022,7 +3956,7 @@ static int solve_sweep_t(lbfgsx_ctx* c, int first, int vsel_id, const double* co
     CoefArg<T> cf;
     for (int k = 0; k < 80; k++)
         cf.c[k] = (coef && k < total) ? T(coef[k]) : T(0);
-    const int grid = std::min(c->grid_for(nrows), b->dots_grid);
+    const int grid = std::min(c->grid_for(nrows), lbfgsb_state::kDotsGrid);
     // compact vectors: the first solve over the compact copy starts them (when an index list of L u U will let the sweeps
     // that follow stay on the fused path), the later solves use them
     int cv = 0;
@@ -4192,7 +4126,7 @@ int lbfgsx_b_solve_sweep_rhs(lbfgsx_ctx* c, int first, int vsel_id, const double
     int* dst;
     if (first)
     {
-        cap = (b->lu_use && b->lu_pred <= b->lu_max) ? b->lu_cap : 0u;
+        cap = b->lu_pred <= lbfgsb_state::kLuMax ? b->lu_cap : 0u;
         dst = b->lu_ptr();
     }
     else

@@ -74,11 +74,6 @@ struct RowsX
 // 2 no stores, 3 no cross-lane moves -- what each part of a trip costs (kx_rows); kx_solve_sweep: 16 no sweep statements (and
 // their stores), 32 no y / rhs stores, 64 no double-double products, 128 no left-to-right sums, 256 no list appends.
 // 0 in the product.
-// experiment builds only: 3 = kx_solve_sweep with three register sets (two trips of loads in the air): 250-256 VGPRs, no
-// scratch, and no faster (182 -> 187 us) -- the pass is at the floor of its access pattern with two
-#ifndef LBFGSX_X_NBUF
-#define LBFGSX_X_NBUF 2
-#endif
 #ifndef LBFGSX_X_DBG
 #define LBFGSX_X_DBG 0
 #endif
@@ -127,10 +122,6 @@ struct LaneX
 //   v_permlane16_swap a, b : the odd 16-lane rows of a <-> the even rows of b
 // With a = b = x the first result holds the lower half (even rows) in both halves (row pairs), the second the upper half
 // (odd rows): a shift up by one group and the broadcast of the last group come out of one or two of them.
-// (LBFGSX_X_PERMLANE=0 at compile time: the shuffles as before; the tests compare bits either way.)
-#ifndef LBFGSX_X_PERMLANE
-#define LBFGSX_X_PERMLANE 1
-#endif
 template <int WHICH, bool HALF32>
 __device__ __forceinline__ double swap_x(double v)
 {
@@ -161,8 +152,6 @@ __device__ __forceinline__ float swap_x(float v)
 template <class T, int G>
 __device__ __forceinline__ T from_prev_group_x(T x, int round)
 {
-    if (!LBFGSX_X_PERMLANE)
-        return __shfl_up(x, 64 / G, 64);
     if (G == 2)
         return swap_x<0, true>(x);                       // [lower, lower]
     // G == 4, rows r0..r3: round 1 and 3 need row r <- row r - 1 for odd r: [r0, r0, r2, r2]; round 2 needs r2 <- r1
@@ -174,8 +163,6 @@ __device__ __forceinline__ T from_prev_group_x(T x, int round)
 template <class T, int G>
 __device__ __forceinline__ T from_last_group_x(T x, int rr)
 {
-    if (!LBFGSX_X_PERMLANE)
-        return __shfl(x, (G - 1) * (64 / G) + rr, 64);
     if (G == 2)
         return swap_x<1, true>(x);                       // [upper, upper]
     return swap_x<1, true>(swap_x<1, false>(x));         // [r1, r1, r3, r3] -> upper half everywhere: [r3, r3, r3, r3]
@@ -656,33 +643,8 @@ __global__ void __launch_bounds__(kBlock, occ_sweep_x(NCL, G, FIRST))
         int64_t base = (int64_t(blockIdx.x) * kWaves + L.wave) * RPW;
         if (base < n)
         {
-#if LBFGSX_X_NBUF == 3
-            // three register sets: two trips of loads in the air while a third is worked on (the passes are bound by the
-            // bytes a CU keeps in flight, and at 2 waves per SIMD there are registers to spare for it)
-            int64_t i0 = rowof(base), i1 = rowof(base + stride), i2 = rowof(base + 2 * stride);
-            Buf A0, A1, A2;
-            fetch(base, i0, A0);
-            fetch(base + stride, i1, A1);
-            for (; base < n; base += 3 * stride)
-            {
-                const int64_t b1 = base + stride, b2 = b1 + stride, b3 = b2 + stride, b4 = b3 + stride, b5 = b4 + stride;
-                fetch(b2, i2, A2);
-                compute(base, i0, A0);
-                const int64_t i3 = rowof(b3);
-                if (b1 >= n)
-                    break;
-                fetch(b3, i3, A0);
-                compute(b1, i1, A1);
-                const int64_t i4 = rowof(b4);
-                if (b2 >= n)
-                    break;
-                fetch(b4, i4, A1);
-                compute(b2, i2, A2);
-                i0 = i3;
-                i1 = i4;
-                i2 = rowof(b5);
-            }
-#else
+            // two register sets; a third (two trips of loads in the air) fits in 250-256 VGPRs without scratch and is no faster
+            // (182 -> 187 us): the pass is at the floor of its access pattern with two
             int64_t i0 = rowof(base), i1 = rowof(base + stride);
             Buf A0, A1;
             fetch(base, i0, A0);
@@ -698,7 +660,6 @@ __global__ void __launch_bounds__(kBlock, occ_sweep_x(NCL, G, FIRST))
                 i0 = i2;
                 i1 = i3;
             }
-#endif
         }
     }
     if (lu_cap)

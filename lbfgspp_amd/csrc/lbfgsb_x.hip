@@ -63,10 +63,7 @@ namespace xl {
 // many gather streams in the air.  (scripts/experiments/kernels_x.hip, where everything is by position, says two for all.)
 static inline int grid_rows(int64_t n, int rpw, int per_cu, int num_cus)
 {
-    if (const char* e = getenv("LBFGSX_X_PER_CU"))  // A/B
-        per_cu = std::max(1, atoi(e));
-    else
-        per_cu = std::min(per_cu, 2);
+    per_cu = std::min(per_cu, 2);
     const int64_t per_block = int64_t(kWaves) * rpw;
     const int64_t want = (n + per_block - 1) / per_block;
     return int(std::max<int64_t>(1, std::min<int64_t>(want, std::min<int64_t>(int64_t(per_cu) * num_cus, kMaxGridX))));
@@ -195,7 +192,7 @@ int multidot2_wf(hipStream_t s, int num_cus, const ColsX<T>& wfc, int ncols, int
     model_add(double(npos) * (double(ncols) * sizeof(T) + 4 + (dst_a ? 2.0 * sizeof(T) : 0.0)) +
               3.0 * model_gather(npos, npos * 2, int(sizeof(T))) + double(nlist) * 64.0 * (ncols + 2));
     model_compact_pass(npos);
-    static const int dots_per_cu = [] { const char* e = getenv("LBFGSX_X_DOTS_PER_CU"); return e ? std::max(1, atoi(e)) : 1; }();  // see grid_rows
+    constexpr int dots_per_cu = 1;  // this pass gathers by row number: see grid_rows
 #define CALL(NCL, G)                                                                                                          \
     LBFGSX_LAUNCH((kx_multidot2_wf<T, NCL, G>),                                                                               \
                   dim3(grid_rows(std::max<int64_t>(npos, nlist), 64 / G, std::min(dots_per_cu, occ_dots_x(NCL)), num_cus)),   \

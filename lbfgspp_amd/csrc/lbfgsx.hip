@@ -341,22 +341,6 @@ static int create_fill(lbfgsx_ctx* c, int dtype, int64_t n, int m, int device, i
     c->device = device;
     c->flags = flags;
     c->sl.m = m;
-    if (const char* e = getenv("LBFGSX_GRID_CAP"))
-        c->grid_cap = atoi(e) > 0 ? atoi(e) : c->grid_cap;
-    if (c->grid_cap > 8192)
-        c->grid_cap = 8192;
-    if (const char* e = getenv("LBFGSX_GRID_CAP_TWOLOOP"))
-        c->grid_cap_twoloop = atoi(e) > 0 ? std::min(atoi(e), 8192) : c->grid_cap_twoloop;
-    if (const char* e = getenv("LBFGSX_UNROLL"))
-        c->unroll = (atoi(e) == 1 || atoi(e) == 2 || atoi(e) == 8) ? atoi(e) : 4;
-    if (const char* e = getenv("LBFGSX_NT"))
-        c->nt = atoi(e) != 0;
-    if (const char* e = getenv("LBFGSX_CHUNKED"))
-        c->chunked = atoi(e) != 0;
-    if (const char* e = getenv("LBFGSX_Q_POLICY"))
-        c->q_policy = atoi(e) & 3;
-    if (const char* e = getenv("LBFGSX_ZIGZAG"))
-        c->zigzag = atoi(e) != 0;
     LBFGSX_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     c->own_stream = true;
     {
@@ -374,10 +358,6 @@ static int create_fill(lbfgsx_ctx* c, int dtype, int64_t n, int m, int device, i
         c->persist = atoi(e) != 0 && c->persist;
     if (const char* e = getenv("LBFGSX_MEET"))  // "last": the round-1..3 meeting points (the last block reduces and publishes)
         c->meet_all = std::strcmp(e, "last") != 0;
-    if (const char* e = getenv("LBFGSX_MEET_PUB"))  // 0: the dot's copy for the host before the word the blocks poll (rounds 4)
-        c->meet_pub_first = atoi(e) != 0;
-    if (const char* e = getenv("LBFGSX_TRIAL_POLICY"))
-        c->trial_policy = atoi(e);
     if (const char* e = getenv("LBFGSX_PERSIST_POLL"))
         c->fast_persist_out = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_FUSE_POST"))
@@ -769,7 +749,7 @@ template <class T>
 static int apply_Hv_t(lbfgsx_ctx* c, const T* v, T a, double* dg)
 {
     const int cn = c->ncorr, m = c->m;
-    const int grid = std::min(c->grid_for(c->n, c->unroll), c->grid_cap_twoloop);
+    const int grid = std::min(c->grid_for(c->n, 4), kGridCapTwoloop);
     T* q = P<T>(c->d);
     T* sc = P<T>(c->sc);
     const T* gcur = P<T>(c->gb[c->cur]);
@@ -803,9 +783,9 @@ static int apply_Hv_t(lbfgsx_ctx* c, const T* v, T a, double* dg)
         for (int i = 0; i < kPersistMaxM; i++)
             pa.pcol[i] = i < cn ? pcol[i] : 0;
         pa.gen_base = c->gen_count;
-        pa.zigzag = c->zigzag ? 1 : 0;
+        pa.zigzag = 1;
         pa.first_rev = c->tl_step;
-    pa.pub_first = c->meet_pub_first ? 1 : 0;
+        pa.pub_first = 1;
         pa.ld = c->ld;
         // one generation number per meeting point: the word the blocks wait for (LBFGSX_MEET=last) or the tag of the
         // 16-byte words they exchange (the default)
@@ -866,40 +846,22 @@ static int apply_Hv_t(lbfgsx_ctx* c, const T* v, T a, double* dg)
         c->persist_cooldown--;
     auto launch = [&](int mode, const T* u, const T* w, TwoLoopArgs args) -> int {
         EventPair ev;
-        args.rev = (c->zigzag && (c->tl_step++ & 1u)) ? 1 : 0;
+        args.rev = (c->tl_step++ & 1u) ? 1 : 0;
         if (c->timing && c->timing_per_launch)
         {
             LBFGSX_HIP(hipEventCreate(&ev.a));
             LBFGSX_HIP(hipEventCreate(&ev.b));
             LBFGSX_HIP(hipEventRecord(ev.a, c->stream));
         }
-#define TL_LAUNCH(MODE, U, NT, QPOL)                                                                                  \
-    LBFGSX_LAUNCH((k_twoloop<T, MODE, U, NT, QPOL>), dim3(grid), dim3(kBlock), 0, c->stream, q, v, a, u, w, c->n, \
-                       sc, args, c->ws)
-#define TL_POLICY(MODE, U)                                        \
-    do                                                            \
-    {                                                             \
-        if (!c->nt) TL_LAUNCH(MODE, U, false, 0);                 \
-        else if (c->q_policy == 3) TL_LAUNCH(MODE, U, true, 3);   \
-        else if (c->q_policy == 2) TL_LAUNCH(MODE, U, true, 2);   \
-        else if (c->q_policy == 1) TL_LAUNCH(MODE, U, true, 1);   \
-        else TL_LAUNCH(MODE, U, true, 0);                         \
-    } while (0)
-#define TL_VARIANT(MODE)                          \
-    do                                            \
-    {                                             \
-        if (c->unroll == 8) TL_POLICY(MODE, 8);   \
-        else TL_POLICY(MODE, 4);                  \
-    } while (0)
+#define TL_LAUNCH(MODE) \
+    LBFGSX_LAUNCH((k_twoloop<T, MODE>), dim3(grid), dim3(kBlock), 0, c->stream, q, v, a, u, w, c->n, sc, args, c->ws)
         switch (mode)
         {
-        case TL_INIT: TL_VARIANT(TL_INIT); break;
-        case TL_SUB: TL_VARIANT(TL_SUB); break;
-        case TL_SUBDIV: TL_VARIANT(TL_SUBDIV); break;
-        default: TL_VARIANT(TL_ADD); break;
+        case TL_INIT: TL_LAUNCH(TL_INIT); break;
+        case TL_SUB: TL_LAUNCH(TL_SUB); break;
+        case TL_SUBDIV: TL_LAUNCH(TL_SUBDIV); break;
+        default: TL_LAUNCH(TL_ADD); break;
         }
-#undef TL_VARIANT
-#undef TL_POLICY
 #undef TL_LAUNCH
         if (c->timing && c->timing_per_launch)
         {
@@ -911,7 +873,7 @@ static int apply_Hv_t(lbfgsx_ctx* c, const T* v, T a, double* dg)
     auto Scol = [&](int i) { return static_cast<const T*>(c->col(c->S, pcol[i])); };
     auto Ycol = [&](int i) { return static_cast<const T*>(c->col(c->Y, pcol[i])); };
     int rc;
-    TwoLoopArgs args = {c->chunked ? 1 : 0, 0, 0, 0, 0, 0, 0};
+    TwoLoopArgs args = {0, 0, 0, 0, 0, 0};
     if (cn == 0)
     {
         // res = a*v; res /= theta with theta == 1 is the identity (BFGSMat.h:283,293)
@@ -1067,24 +1029,13 @@ template <class T, class OBJ>
 static int trial_t(lbfgsx_ctx* c, OBJ obj, T step, double* out2)
 {
     const int grid = c->grid_for(c->n);
-    const int rev = (c->zigzag && (c->tl_step++ & 1u)) ? 1 : 0;
+    const int rev = (c->tl_step++ & 1u) ? 1 : 0;
     lbfgsx::poll_arm(c);
     // byte model (counters, L-BFGS-B legs): xp and d read, x and grad written, + the objective's own vectors
     lbfgsx::model_add(double(c->n) * sizeof(T) * (4 + (sizeof(OBJ) >= 2 * sizeof(void*) ? 2 : 0)));
     // 4 vectors per stream and thread in flight (measured +1 % on the north-star against 2; profiles/r1_mall_policy_ab.txt)
-#define TRIAL_LAUNCH(UU, NTL, NTS)                                                                                            \
-    LBFGSX_LAUNCH((k_trial<T, OBJ, UU, NTL, NTS>), dim3(grid), dim3(kBlock), 0, c->stream, P<T>(c->xb[c->xp]), P<T>(c->d), \
-                       step, P<T>(c->xb[c->trial]), P<T>(c->gb[c->trial]), c->n, obj, c->ws, c->out_slot<T>(), rev)
-    switch (c->trial_policy)
-    {
-    case 1: TRIAL_LAUNCH(4, true, false); break;
-    case 2: TRIAL_LAUNCH(4, false, true); break;
-    case 3: TRIAL_LAUNCH(4, true, true); break;
-    case 4: TRIAL_LAUNCH(8, false, false); break;
-    case 7: TRIAL_LAUNCH(8, true, true); break;
-    default: TRIAL_LAUNCH(4, false, false); break;
-    }
-#undef TRIAL_LAUNCH
+    LBFGSX_LAUNCH((k_trial<T, OBJ>), dim3(grid), dim3(kBlock), 0, c->stream, P<T>(c->xb[c->xp]), P<T>(c->d), step,
+                       P<T>(c->xb[c->trial]), P<T>(c->gb[c->trial]), c->n, obj, c->ws, c->out_slot<T>(), rev);
     LBFGSX_HIP(hipGetLastError());
     return fetch_scalars<T>(c, c->sl.out(0), 2, out2);
 }
@@ -1182,7 +1133,7 @@ int lbfgsx_post_linesearch(lbfgsx_ctx* c, double* gnorm2, double* xnorm2, double
     const int grid = c->grid_for(c->n);
     double r[4];
     DISPATCH_T(c, {
-        const int rev = (c->zigzag && (c->tl_step++ & 1u)) ? 1 : 0;
+        const int rev = (c->tl_step++ & 1u) ? 1 : 0;
         LBFGSX_LAUNCH((k_post<T, 4>), dim3(grid), dim3(kBlock), 0, c->stream, P<T>(c->xb[c->cur]), P<T>(c->xb[c->xp]),
                            P<T>(c->gb[c->cur]), P<T>(c->gb[c->xp]), P<T>(c->col(c->S, c->spare)),
                            P<T>(c->col(c->Y, c->spare)), c->n, c->ws, c->out_slot<T>(), P<T>(c->sc) + c->sl.ys(c->spare),
@@ -1231,9 +1182,9 @@ static int post_spec_t(lbfgsx_ctx* c, T a, double* r4)
         }
     }
     pa.gen_base = c->gen_count;
-    pa.zigzag = c->zigzag ? 1 : 0;
+    pa.zigzag = 1;
     pa.first_rev = c->tl_step;
-    pa.pub_first = c->meet_pub_first ? 1 : 0;
+    pa.pub_first = 1;
     pa.ld = c->ld;
     c->gen_count += unsigned(2 * cn + 1);
     c->tl_step += unsigned(2 * cn + 1);
