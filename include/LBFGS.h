@@ -75,6 +75,12 @@ class LBFGSSolver
                                             "two-loop reduces its dot products on the device, inside one launch");
             ev.reduce = m_reducer;
         }
+        if constexpr (std::is_same<typename std::decay<Foo>::type, TermObjective<Scalar> >::value)
+        {
+            if (m_recursion != RECURSION_VECTOR || m_reducer)
+                throw std::invalid_argument("a TermObjective runs with the vector recursion on one device: the Gram-space and "
+                                            "row-sharded modes take the built-in objectives or a device functor");
+        }
         lbfgsx_ctx* c = m_dev.ctx();
         detail::check(lbfgsx_bfgs_reset(c));
         if (m_recursion == RECURSION_VECTOR)  // a previous minimize() of this solver may have run with an f32 history

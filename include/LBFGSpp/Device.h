@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdint>
 #include <functional>
+#include <initializer_list>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -86,6 +87,89 @@ inline BuiltinObjective<Scalar> ExtendedRosenbrock()
     return BuiltinObjective<Scalar>(LBFGSX_OBJ_EXT_ROSENBROCK);
 }
 
+// An objective that is a sum of terms over K consecutive coordinates, given as device code for ONE term and compiled at
+// run time into the fused kernels (include/lbfgsx.h, "term objectives"): the solvers take every path they take for a
+// built-in objective.  body sees T, const T x[K], T g[K], int64_t i, const T* p0..p3, T c[8] and returns the term's value.
+//     TermObjective<double> f(2, "const T t1 = T(1) - x[0]; ... return t1 * t1 + t2 * t2;");
+//     f.data(p0_dev, p1_dev).scalars({0.5});      solver.minimize(f, x, fx);
+// data(): device arrays of n elements owned by the caller; host_data(slot, ptr): a host array the solver copies to the device
+// at every minimize().  The constructor throws std::invalid_argument with the compiler's log when the body does not
+// compile.  Not for the Gram-space recursion or row-sharded runs (refused), nor the lock-step batch.
+template <typename Scalar>
+class TermObjective
+{
+    lbfgsx_objective* m_h = nullptr;
+    bool m_own = false;
+    const Scalar* m_p[4] = {nullptr, nullptr, nullptr, nullptr};
+    const Scalar* m_host[4] = {nullptr, nullptr, nullptr, nullptr};
+    double m_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+    TermObjective(const TermObjective&) = delete;
+    TermObjective& operator=(const TermObjective&) = delete;
+
+public:
+    int id = LBFGSX_OBJ_NONE;  // LBFGSX_OBJ_BOUND once bound to a solver's context (Evaluator::prepare)
+
+    TermObjective(int K, const std::string& body)
+    {
+        std::vector<char> log(16384, '\0');
+        const int rc = lbfgsx_objective_compile(&m_h, detail::dtype_of<Scalar>::value, K, body.c_str(), log.data(), log.size());
+        if (rc == LBFGSX_E_INVALID)
+            throw std::invalid_argument(std::string("TermObjective: ") + log.data());
+        if (rc != LBFGSX_OK)
+            throw std::runtime_error(std::string("TermObjective: ") + log.data());
+        m_own = true;
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile); it stays the caller's
+    explicit TermObjective(const lbfgsx_objective* compiled) : m_h(const_cast<lbfgsx_objective*>(compiled)) {}
+    ~TermObjective()
+    {
+        if (m_own)
+            lbfgsx_objective_destroy(m_h);
+    }
+    TermObjective& data(const Scalar* p0, const Scalar* p1 = nullptr, const Scalar* p2 = nullptr, const Scalar* p3 = nullptr)
+    {
+        m_p[0] = p0;
+        m_p[1] = p1;
+        m_p[2] = p2;
+        m_p[3] = p3;
+        return *this;
+    }
+    TermObjective& host_data(int slot, const Scalar* host)
+    {
+        if (slot < 0 || slot >= 4)
+            throw std::invalid_argument("TermObjective: a term objective has at most four data arrays (slots 0..3)");
+        m_host[slot] = host;
+        return *this;
+    }
+    TermObjective& scalars(std::initializer_list<double> c) { return scalars(c.begin(), int(c.size())); }
+    TermObjective& scalars(const double* c, int count)
+    {
+        if (count > 8)
+            throw std::invalid_argument("TermObjective: a term objective has at most eight scalars");
+        for (int k = 0; k < 8; k++)
+            m_c[k] = (k < count) ? c[k] : 0.0;
+        return *this;
+    }
+    const lbfgsx_objective* handle() const { return m_h; }
+    // copy the host arrays, bind to the context: `id` is what the fused entry points take from here on
+    void bind(lbfgsx_ctx* c)
+    {
+        const void* p[4];
+        for (int k = 0; k < 4; k++)
+        {
+            p[k] = m_p[k];
+            if (m_host[k])
+            {
+                void* dev = nullptr;
+                detail::check(lbfgsx_objective_upload(c, k, m_host[k], &dev));
+                p[k] = dev;
+            }
+        }
+        detail::check(lbfgsx_objective_bind(c, m_h, p, m_c, &id));
+    }
+};
+
 template <typename Scalar>
 class DeviceState
 {
@@ -131,8 +215,9 @@ public:
 
 namespace detail {
 
-// Uniform view of the three kinds of objective `Foo` the solvers accept:
+// Uniform view of the four kinds of objective `Foo` the solvers accept:
 //   BuiltinObjective<Scalar>                              -> fused device kernels
+//   TermObjective<Scalar>                                 -> the same kernels, compiled at run time for the caller's term
 //   Scalar f(const DeviceVector<Scalar>& x, DeviceVector<Scalar>& grad)   -> user device functor
 //   Scalar f(const Vec& x, Vec& grad) with host vectors   -> staged through host memory (compatibility)
 template <typename Scalar, typename Foo, typename HostVec>
@@ -143,7 +228,9 @@ class Evaluator
     HostVec m_hx, m_hg;  // staging for host functors only
     int m_nfev = 0;
 
-    static constexpr bool is_builtin = std::is_same<typename std::decay<Foo>::type, BuiltinObjective<Scalar> >::value;
+    static constexpr bool is_term = std::is_same<typename std::decay<Foo>::type, TermObjective<Scalar> >::value;
+    // evaluated inside the fused kernels under an objective id: the two built-in ones and a bound term objective
+    static constexpr bool is_builtin = is_term || std::is_same<typename std::decay<Foo>::type, BuiltinObjective<Scalar> >::value;
     // A functor that accepts the caller's host vectors is a host functor even if it would also accept device vectors
     // (a generic `template <class V> operator()(const V&, V&)` or `[](const auto& x, auto& g)` satisfies both traits;
     // handing it raw HBM pointers to dereference on the host would crash).  Device functors name DeviceVector.
@@ -201,7 +288,7 @@ public:
     bool trial_written = false;
 
     Evaluator(Foo& f, DeviceState<Scalar>& s) : m_f(f), m_s(s) {}
-    // the id of a built-in objective (the fused kernels know it), -1 for a functor
+    // the id of a built-in or bound term objective (the fused kernels know it), -1 for a functor
     int builtin_id() const
     {
         if constexpr (is_builtin)
@@ -213,7 +300,9 @@ public:
 
     void prepare()
     {
-        if constexpr (is_builtin)
+        if constexpr (is_term)
+            m_f.bind(m_s.ctx());
+        else if constexpr (is_builtin)
         {
             if (m_f.a) m_s.upload(LBFGSX_VEC_A, m_f.a);
             if (m_f.b) m_s.upload(LBFGSX_VEC_B, m_f.b);

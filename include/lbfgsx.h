@@ -17,6 +17,7 @@
 #ifndef LBFGSX_H
 #define LBFGSX_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -26,7 +27,8 @@ extern "C" {
 typedef struct lbfgsx_ctx lbfgsx_ctx;
 
 enum { LBFGSX_F64 = 0, LBFGSX_F32 = 1 };
-enum { LBFGSX_OBJ_NONE = -1, LBFGSX_OBJ_DIAG_QUAD = 0, LBFGSX_OBJ_EXT_ROSENBROCK = 1 };
+enum { LBFGSX_OBJ_NONE = -1, LBFGSX_OBJ_DIAG_QUAD = 0, LBFGSX_OBJ_EXT_ROSENBROCK = 1,
+       LBFGSX_OBJ_BOUND = 64 /* the term objective bound to the context (lbfgsx_objective_bind below) */ };
 enum
 {
     LBFGSX_OK = 0,
@@ -137,6 +139,45 @@ int lbfgsx_commit_correction(lbfgsx_ctx* c);
 int lbfgsx_post_linesearch_spec(lbfgsx_ctx* c, double a, double* gnorm2, double* xnorm2, double* sy, double* yy);
 /* instrumentation: {fused launches, directions taken over by lbfgsx_apply_Hv, pairs rejected by the kernel} */
 int lbfgsx_spec_counts(const lbfgsx_ctx* c, int64_t out[3]);
+/* ---- term objectives compiled at run time -------------------------------------------------------------------------
+ * An objective that is a sum of terms over K consecutive coordinates (K = 1 or 2), evaluated INSIDE the fused kernels like
+ * the two built-in ones.  `body` is HIP/C++ text for one term: statements that see
+ *     T (the scalar type), const T x[K], T g[K] (to fill), int64_t i (index of x[0]),
+ *     const T* p0..p3 (per-coordinate data arrays of n elements, device memory of the caller), T c[8] (scalars)
+ * and return the term's value; f is the sum of the returned values (the order-independent sum of the built-in objectives).
+ * No shared memory, no synchronisation, no other coordinates, no inline assembly.  The library wraps the body into the
+ * objective struct the kernel templates take, compiles k_eval, k_trial, k_b_eval and k_b_dg_maxstep_trial for it with
+ * hipRTC for gfx950 (-O3 -ffp-contract=off: the build's own floating-point contract, no device needed), and caches the
+ * result per process by (body, K, dtype).  A body that does not compile: LBFGSX_E_INVALID, the compiler's log in `log`
+ * (line numbers count from the first line of the body, file name "objective_body").
+ * lbfgsx_objective_source: the generated translation unit (returns the length needed, text truncated to len).
+ * lbfgsx_objective_info: out = {VGPRs (largest of the four kernels), scratch bytes (largest), 1 if this handle was served
+ * from the cache, compile time in ms, scratch bytes of k_eval, k_trial, k_b_eval, k_b_dg_maxstep_trial}, read from the
+ * code object.
+ * lbfgsx_objective_bind: loads the code object on the context's device (once per device) and binds the objective with its
+ * data arrays p[0..3] (device pointers; NULL = unused) and scalars c[0..7] to the context; n must be a multiple of K.  *id
+ * receives LBFGSX_OBJ_BOUND, the value that lbfgsx_eval, lbfgsx_trial, lbfgsx_b_eval and lbfgsx_b_dg_maxstep_trial then take
+ * for `objective`; they launch the loaded kernels with the grid, arguments and workspace of the built-in launch.  obj = NULL
+ * unbinds.  The binding holds the cached code, not the handle: the handle may be destroyed while bound.
+ * lbfgsx_objective_upload copies a host array of n elements into a buffer the context owns for `slot` and returns its device
+ * address in *dev, to be passed to lbfgsx_objective_bind like any other device array.
+ * A body that contains the word asm is refused (LBFGSX_E_INVALID): inline assembly is not part of the contract.
+ * Lifetime: a compiled (body, K, dtype) and the modules loaded from it stay until the process ends -- there is no eviction,
+ * so a program that generates bodies without bound grows by a code object (tens of KB) and a module per body.
+ * LBFGSX_KERNEL_DIR (environment): the directory of lbfgs_kernels.cuh / lbfgsb_kernels.cuh / reduce.cuh for a library that
+ * was installed apart from them; by default csrc/ next to the library.
+ * lbfgsx_objective_bound: the four data pointers currently bound.  No reference counterpart (the reference's objectives
+ * are host functors). */
+typedef struct lbfgsx_objective lbfgsx_objective;
+int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len);
+void lbfgsx_objective_destroy(lbfgsx_objective* obj);
+long long lbfgsx_objective_source(int dtype, int K, const char* body, char* out, size_t len);
+int lbfgsx_objective_info(const lbfgsx_objective* obj, long long out[8]);
+int lbfgsx_objective_K(const lbfgsx_objective* obj);
+int lbfgsx_objective_dtype(const lbfgsx_objective* obj);
+int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void* const p[4], const double cs[8], int* id);
+int lbfgsx_objective_upload(lbfgsx_ctx* c, int slot, const void* host, void** dev);
+int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4]);
 /* Every entry point of this ABI makes the context's device current for its own duration and restores the caller's
  * afterwards.  Code that launches its OWN kernels on the context's vectors (a device functor, lbfgsx_vec) must run with
  * that device current too: lbfgsx_device tells which one it is, lbfgsx_device_push makes it current for the calling

@@ -120,6 +120,17 @@ int lbfgsx_solver_minimize(lbfgsx_solver* s, int objective, int64_t n, const voi
 typedef int (*lbfgsx_objective_fn)(void* user, const void* x_dev, void* grad_dev, int64_t n, double* fx);
 int lbfgsx_solver_minimize_fn(lbfgsx_solver* s, int64_t n, lbfgsx_objective_fn fn, void* user, void* x, const void* lb,
                               const void* ub, lbfgsx_trace* trace, lbfgsx_result* out);
+/* A term objective compiled at run time (include/lbfgsx.h, lbfgsx_objective_compile) through the solver: the objective is
+ * bound to the solver's context and the templates run as for a built-in objective -- every fused launch (the trial pass, and
+ * for L-BFGS-B the dg / max-step / first-trial pass), every line search, both dtypes, with the launches a built-in objective
+ * gets.  p[0..3]: the per-coordinate data arrays, n elements of
+ * the solver's dtype each or NULL -- device memory of the caller used in place, or, for the slots whose bit is set in host_mask,
+ * host arrays copied to the device first; c[0..7]: the scalars (NULL = zeros).  x, lb, ub, trace and out as
+ * lbfgsx_solver_minimize.  n must be a multiple of the objective's K (LBFGSX_E_INVALID).  Refused with LBFGSX_E_INVALID after
+ * lbfgsx_solver_set_recursion(1 | 2) or lbfgsx_solver_set_devices / _set_allreduce.  Without a GPU: LBFGSX_E_NOGPU. */
+int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, const void* const p[4], int host_mask,
+                               const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
+                               lbfgsx_result* out);
 
 /* ---- batched mode (BASELINE.json cfg5): many independent minimisations on one GPU ------------------------
  * Problem `id` is the extended Rosenbrock (or diag quadratic) instance generated on the device from seed

@@ -6,6 +6,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 F64, F32 = 0, 1
 OBJ_DIAG_QUAD, OBJ_EXT_ROSENBROCK = 0, 1
+OBJ_BOUND = 64  # the term objective bound to a context (lbfgsx_objective_bind)
 LS_NOCEDAL_WRIGHT, LS_MORE_THUENTE, LS_BACKTRACKING, LS_BRACKETING = 0, 1, 2, 3
 ALGO_LBFGS, ALGO_LBFGSB = 0, 1
 RECURSION_VECTOR, RECURSION_GRAM_SPACE, RECURSION_GRAM_SPACE_F32H = 0, 1, 2
@@ -183,6 +184,18 @@ def load():
     sig(sol, "lbfgsx_solver_minimize_fn", i32, vp, i64, OBJECTIVE_FN, vp, vp, vp, vp, C.POINTER(Trace), C.POINTER(Result))
     sig(sol, "lbfgsx_lockstep_minimize_fn", i32, vp, vp, BATCH_OBJECTIVE_FN, vp, C.POINTER(BatchItem), vp, C.POINTER(dbl * 8),
         C.c_char_p, i32)
+    # term objectives compiled at run time
+    sig(core, "lbfgsx_objective_compile", i32, C.POINTER(vp), i32, i32, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_destroy", None, vp)
+    sig(core, "lbfgsx_objective_source", C.c_longlong, i32, i32, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_info", i32, vp, C.POINTER(C.c_longlong * 8))
+    sig(core, "lbfgsx_objective_K", i32, vp)
+    sig(core, "lbfgsx_objective_dtype", i32, vp)
+    sig(core, "lbfgsx_objective_bind", i32, vp, vp, C.POINTER(vp * 4), C.POINTER(dbl * 8), C.POINTER(i32))
+    sig(core, "lbfgsx_objective_upload", i32, vp, i32, vp, C.POINTER(vp))
+    sig(core, "lbfgsx_objective_bound", i32, vp, C.POINTER(vp * 4))
+    sig(sol, "lbfgsx_solver_minimize_obj", i32, vp, vp, i64, C.POINTER(vp * 4), i32, C.POINTER(dbl * 8), vp, vp, vp,
+        C.POINTER(Trace), C.POINTER(Result))
     _core, _solver = core, sol
     return core, sol
 

@@ -241,6 +241,16 @@ struct lbfgsx_ctx
     double spec_a = 0.0, spec_dg = 0.0;
     int64_t spec_launches = 0, spec_used = 0, spec_rejected = 0;  // instrumentation
 
+    // a term objective compiled at run time and bound to this context (lbfgsx_objective_bind, jit_objective.hip): the id
+    // LBFGSX_OBJ_BOUND then evaluates it inside the fused kernels.  term_p: the caller's device arrays (term_own: the
+    // context's copies of host arrays, lbfgsx_objective_upload, bound only when the caller passes them), term_c: its scalars
+    const struct lbfgsx_objective* term = nullptr;
+    void* term_fn[4] = {nullptr, nullptr, nullptr, nullptr};  // its four kernels on this context's device (hipFunction_t)
+    const void* term_p[4] = {nullptr, nullptr, nullptr, nullptr};
+    double term_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int term_np = 0;  // data arrays bound (byte model)
+    void* term_own[4] = {nullptr, nullptr, nullptr, nullptr};
+
     // L-BFGS-B work set (allocated with LBFGSX_FLAG_BOUNDED) lives in lbfgsb part
     void* lb = nullptr;
     void* ub = nullptr;

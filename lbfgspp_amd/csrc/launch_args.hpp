@@ -1,0 +1,117 @@
+// lbfgspp_amd/csrc/launch_args.hpp -- grid and arguments of the four launches that evaluate an objective (k_eval, k_trial,
+// k_b_eval, k_b_dg_maxstep_trial), worked out once for both forms of the launch: the built-in instantiations
+// (hipLaunchKernelGGL in lbfgsx.hip / lbfgsb.hip) and the instantiations compiled at run time for a term objective
+// (hipModuleLaunchKernel, jit_objective.hip).  The members are the kernels' arguments in order, the objective left out.
+#pragma once
+#include "ctx.hpp"
+
+namespace lbfgsx {
+
+template <class T>
+struct EvalLaunch
+{
+    int grid;
+    const T* x;
+    T* g;
+    int64_t n;
+    RedWs ws;
+    T* out;
+};
+template <class T>
+inline EvalLaunch<T> eval_launch(lbfgsx_ctx* c)
+{
+    return {c->grid_for(c->n), static_cast<const T*>(c->xb[c->cur]), static_cast<T*>(c->gb[c->cur]), c->n, c->ws,
+            c->out_slot<T>()};
+}
+
+template <class T>
+struct TrialLaunch
+{
+    int grid;
+    const T *xp, *d;
+    T step;
+    T *x, *g;
+    int64_t n;
+    RedWs ws;
+    T* out;
+    int rev;
+};
+// obj_vectors: n-vectors of its own the objective reads (byte model of the counters)
+template <class T>
+inline TrialLaunch<T> trial_launch(lbfgsx_ctx* c, T step, int obj_vectors)
+{
+    const int rev = (c->tl_step++ & 1u) ? 1 : 0;
+    poll_arm(c);
+    // byte model (counters, L-BFGS-B legs): xp and d read, x and grad written, + the objective's own vectors
+    model_add(double(c->n) * sizeof(T) * (4 + obj_vectors));
+    return {c->grid_for(c->n), static_cast<const T*>(c->xb[c->xp]), static_cast<const T*>(c->d), step,
+            static_cast<T*>(c->xb[c->trial]), static_cast<T*>(c->gb[c->trial]), c->n, c->ws, c->out_slot<T>(), rev};
+}
+
+template <class T>
+struct BEvalLaunch
+{
+    int grid;
+    const T* x;
+    T* g;
+    const T *lb, *ub;
+    int64_t n;
+    RedWs ws;
+    T* out;
+};
+template <class T>
+inline BEvalLaunch<T> b_eval_launch(lbfgsx_ctx* c)
+{
+    return {c->grid_for(c->n), static_cast<const T*>(c->xb[c->cur]), static_cast<T*>(c->gb[c->cur]),
+            static_cast<const T*>(c->lb), static_cast<const T*>(c->ub), c->n, c->ws, c->out_slot<T>()};
+}
+
+template <class T>
+struct DgTrialLaunch
+{
+    int grid;
+    const T *xp, *g0, *d, *lb, *ub;
+    T step;
+    T *x, *g;
+    int64_t n;
+    RedWs ws;
+    T* out;
+    int rev;
+};
+template <class T>
+inline DgTrialLaunch<T> dg_maxstep_trial_launch(lbfgsx_ctx* c, T step, int obj_vectors)
+{
+    const int rev = (c->tl_step & 1u) ? 1 : 0;  // the order the trial launch it stands for would have taken
+    poll_arm(c);
+    // byte model: xp, g, d, lb, ub read, x and grad written, + the objective's own vectors (a, b of the quadratic)
+    model_add(double(c->n) * sizeof(T) * (7 + obj_vectors));
+    return {c->grid_for(c->n), static_cast<const T*>(c->xb[c->xp]), static_cast<const T*>(c->gb[c->cur]),
+            static_cast<const T*>(c->d), static_cast<const T*>(c->lb), static_cast<const T*>(c->ub), step,
+            static_cast<T*>(c->xb[c->trial]), static_cast<T*>(c->gb[c->trial]), c->n, c->ws, c->out_slot<T>(), rev};
+}
+
+// ---- a term objective bound to the context (lbfgsx_objective_bind, jit_objective.hip)
+enum { JIT_K_EVAL = 0, JIT_K_TRIAL = 1, JIT_K_B_EVAL = 2, JIT_K_B_DG_MAXSTEP_TRIAL = 3, JIT_NKERNELS = 4 };
+// the by-value kernel argument: layout of the generated struct ObjTerm (four data pointers, eight scalars of type T)
+template <class T>
+struct TermArgs
+{
+    const T* p[4];
+    T c[8];
+};
+template <class T>
+inline TermArgs<T> term_args(const lbfgsx_ctx* c)
+{
+    TermArgs<T> a;
+    for (int j = 0; j < 4; j++)
+        a.p[j] = static_cast<const T*>(c->term_p[j]);
+    for (int j = 0; j < 8; j++)
+        a.c[j] = T(c->term_c[j]);
+    return a;
+}
+inline bool term_bound(const lbfgsx_ctx* c, int objective) { return objective == LBFGSX_OBJ_BOUND && c->term != nullptr; }
+// one launch of loaded kernel `which` of the bound objective on the context's stream, block of kBlock threads; params as
+// hipModuleLaunchKernel takes them (one pointer per kernel argument)
+int jit_launch(lbfgsx_ctx* c, int which, int grid, void** params);
+
+}  // namespace lbfgsx

@@ -33,6 +33,7 @@
 #include "ctx.hpp"
 #include "lbfgs_kernels.cuh"
 #include "lbfgsb_kernels.cuh"
+#include "launch_args.hpp"
 #include "gcp_scan.cuh"
 #include "gram_i8.cuh"
 #include "lbfgsb_x.hpp"
@@ -1217,10 +1218,21 @@ namespace lbfgsx {
 template <class T, class OBJ>
 static int b_eval_t(lbfgsx_ctx* c, OBJ obj, double* r3)
 {
-    const int grid = c->grid_for(c->n);
-    LBFGSX_LAUNCH((k_b_eval<T, OBJ>), dim3(grid), dim3(kBlock), 0, c->stream, P<T>(c->xb[c->cur]), P<T>(c->gb[c->cur]),
-                       P<T>(c->lb), P<T>(c->ub), c->n, obj, c->ws, c->out_slot<T>());
+    const BEvalLaunch<T> a = b_eval_launch<T>(c);
+    LBFGSX_LAUNCH((k_b_eval<T, OBJ>), dim3(a.grid), dim3(kBlock), 0, c->stream, a.x, a.g, a.lb, a.ub, a.n, obj, a.ws, a.out);
     LBFGSX_HIP(hipGetLastError());
+    return fetch_T<T>(c, c->sl.out(0), 3, r3);
+}
+// the same launch of the kernel compiled for the context's bound term objective
+template <class T>
+static int b_eval_term_t(lbfgsx_ctx* c, double* r3)
+{
+    BEvalLaunch<T> a = b_eval_launch<T>(c);
+    TermArgs<T> obj = term_args<T>(c);
+    void* params[] = {&a.x, &a.g, &a.lb, &a.ub, &a.n, &obj, &a.ws, &a.out};
+    const int rc = jit_launch(c, JIT_K_B_EVAL, a.grid, params);
+    if (rc)
+        return rc;
     return fetch_T<T>(c, c->sl.out(0), 3, r3);
 }
 }  // namespace lbfgsx
@@ -1244,6 +1256,8 @@ int lbfgsx_b_eval(lbfgsx_ctx* c, int objective, double* fx, double* projgnorm, d
             rc = b_eval_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, r);
         else if (objective == LBFGSX_OBJ_EXT_ROSENBROCK)
             rc = b_eval_t<T>(c, ObjRosen<T>{}, r);
+        else if (lbfgsx::term_bound(c, objective))
+            rc = b_eval_term_t<T>(c, r);
         else
             set_error("lbfgsx_b_eval: unknown objective");
     });
@@ -1304,15 +1318,21 @@ namespace lbfgsx {
 template <class T, class OBJ>
 static int dg_maxstep_trial_t(lbfgsx_ctx* c, OBJ obj, T step, double* r4)
 {
-    const int grid = c->grid_for(c->n);
-    const int rev = (c->tl_step & 1u) ? 1 : 0;  // the order the trial launch it stands for would have taken
-    lbfgsx::poll_arm(c);
-    // byte model: xp, g, d, lb, ub read, x and grad written, + the objective's own vectors (a, b of the quadratic)
-    lbfgsx::model_add(double(c->n) * sizeof(T) * (7 + (sizeof(OBJ) >= 2 * sizeof(void*) ? 2 : 0)));
-    LBFGSX_LAUNCH((k_b_dg_maxstep_trial<T, OBJ>), dim3(grid), dim3(kBlock), 0, c->stream, P<T>(c->xb[c->xp]), P<T>(c->gb[c->cur]),
-                       P<T>(c->d), P<T>(c->lb), P<T>(c->ub), step, P<T>(c->xb[c->trial]), P<T>(c->gb[c->trial]), c->n, obj, c->ws,
-                       c->out_slot<T>(), rev);
+    const DgTrialLaunch<T> a = dg_maxstep_trial_launch<T>(c, step, sizeof(OBJ) >= 2 * sizeof(void*) ? 2 : 0);
+    LBFGSX_LAUNCH((k_b_dg_maxstep_trial<T, OBJ>), dim3(a.grid), dim3(kBlock), 0, c->stream, a.xp, a.g0, a.d, a.lb, a.ub, a.step,
+                       a.x, a.g, a.n, obj, a.ws, a.out, a.rev);
     LBFGSX_HIP(hipGetLastError());
+    return fetch_T<T>(c, c->sl.out(0), 4, r4);
+}
+template <class T>
+static int dg_maxstep_trial_term_t(lbfgsx_ctx* c, T step, double* r4)
+{
+    DgTrialLaunch<T> a = dg_maxstep_trial_launch<T>(c, step, c->term_np);
+    TermArgs<T> obj = term_args<T>(c);
+    void* params[] = {&a.xp, &a.g0, &a.d, &a.lb, &a.ub, &a.step, &a.x, &a.g, &a.n, &obj, &a.ws, &a.out, &a.rev};
+    const int rc = jit_launch(c, JIT_K_B_DG_MAXSTEP_TRIAL, a.grid, params);
+    if (rc)
+        return rc;
     return fetch_T<T>(c, c->sl.out(0), 4, r4);
 }
 }  // namespace lbfgsx
@@ -1322,7 +1342,7 @@ int lbfgsx_b_dg_maxstep_trial(lbfgsx_ctx* c, int objective, double step0, double
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
     const bool use = c->bstate && c->bstate->st_use;
-    const bool builtin = objective == LBFGSX_OBJ_DIAG_QUAD || objective == LBFGSX_OBJ_EXT_ROSENBROCK;
+    const bool builtin = objective == LBFGSX_OBJ_DIAG_QUAD || objective == LBFGSX_OBJ_EXT_ROSENBROCK || lbfgsx::term_bound(c, objective);
     // after a trial that was evaluated ahead and not used (step_max < 1: the early iterations) a few iterations go without
     if (!use || !builtin || !c->outmap_dev || c->xp != c->cur || !(step0 > 0.0) || c->st_cooldown > 0)
     {
@@ -1338,8 +1358,10 @@ int lbfgsx_b_dg_maxstep_trial(lbfgsx_ctx* c, int objective, double step0, double
     DISPATCH_T(c, {
         if (objective == LBFGSX_OBJ_DIAG_QUAD)
             rc = dg_maxstep_trial_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, T(step0), r);
-        else
+        else if (objective == LBFGSX_OBJ_EXT_ROSENBROCK)
             rc = dg_maxstep_trial_t<T>(c, ObjRosen<T>{}, T(step0), r);
+        else
+            rc = dg_maxstep_trial_term_t<T>(c, T(step0), r);
     });
     if (rc)
         return rc;

@@ -17,6 +17,7 @@
 
 #include "ctx.hpp"
 #include "lbfgs_kernels.cuh"
+#include "launch_args.hpp"
 
 namespace lbfgsx {
 
@@ -467,6 +468,8 @@ void lbfgsx_destroy(lbfgsx_ctx* c)
     (void) hipFree(c->d);
     (void) hipFree(c->a);
     (void) hipFree(c->b);
+    for (int k = 0; k < 4; k++)
+        (void) hipFree(c->term_own[k]);
     (void) hipFree(c->S);
     (void) hipFree(c->Y);
     (void) hipFree(c->sc);
@@ -962,10 +965,21 @@ int lbfgsx_apply_Hv(lbfgsx_ctx* c, int v_which, double a, double* dg)
 template <class T, class OBJ>
 static int eval_t(lbfgsx_ctx* c, OBJ obj, double* out3)
 {
-    const int grid = c->grid_for(c->n);
-    LBFGSX_LAUNCH((k_eval<T, OBJ>), dim3(grid), dim3(kBlock), 0, c->stream, P<T>(c->xb[c->cur]),
-                       P<T>(c->gb[c->cur]), c->n, obj, c->ws, c->out_slot<T>());
+    const lbfgsx::EvalLaunch<T> a = lbfgsx::eval_launch<T>(c);
+    LBFGSX_LAUNCH((k_eval<T, OBJ>), dim3(a.grid), dim3(kBlock), 0, c->stream, a.x, a.g, a.n, obj, a.ws, a.out);
     LBFGSX_HIP(hipGetLastError());
+    return fetch_scalars<T>(c, c->sl.out(0), 3, out3);
+}
+// the same launch of the kernel compiled for the context's bound term objective
+template <class T>
+static int eval_term_t(lbfgsx_ctx* c, double* out3)
+{
+    lbfgsx::EvalLaunch<T> a = lbfgsx::eval_launch<T>(c);
+    lbfgsx::TermArgs<T> obj = lbfgsx::term_args<T>(c);
+    void* params[] = {&a.x, &a.g, &a.n, &obj, &a.ws, &a.out};
+    const int rc = lbfgsx::jit_launch(c, lbfgsx::JIT_K_EVAL, a.grid, params);
+    if (rc)
+        return rc;
     return fetch_scalars<T>(c, c->sl.out(0), 3, out3);
 }
 extern "C" {
@@ -986,6 +1000,8 @@ int lbfgsx_eval(lbfgsx_ctx* c, int objective, double* fx, double* gnorm2, double
             rc = eval_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, r);
         else if (objective == LBFGSX_OBJ_EXT_ROSENBROCK)
             rc = eval_t<T>(c, ObjRosen<T>{}, r);
+        else if (lbfgsx::term_bound(c, objective))
+            rc = eval_term_t<T>(c, r);
         else
             set_error("lbfgsx_eval: unknown objective");
     });
@@ -1028,15 +1044,22 @@ int lbfgsx_ls_begin(lbfgsx_ctx* c)
 template <class T, class OBJ>
 static int trial_t(lbfgsx_ctx* c, OBJ obj, T step, double* out2)
 {
-    const int grid = c->grid_for(c->n);
-    const int rev = (c->tl_step++ & 1u) ? 1 : 0;
-    lbfgsx::poll_arm(c);
-    // byte model (counters, L-BFGS-B legs): xp and d read, x and grad written, + the objective's own vectors
-    lbfgsx::model_add(double(c->n) * sizeof(T) * (4 + (sizeof(OBJ) >= 2 * sizeof(void*) ? 2 : 0)));
+    const lbfgsx::TrialLaunch<T> a = lbfgsx::trial_launch<T>(c, step, sizeof(OBJ) >= 2 * sizeof(void*) ? 2 : 0);
     // 4 vectors per stream and thread in flight (measured +1 % on the north-star against 2; profiles/r1_mall_policy_ab.txt)
-    LBFGSX_LAUNCH((k_trial<T, OBJ>), dim3(grid), dim3(kBlock), 0, c->stream, P<T>(c->xb[c->xp]), P<T>(c->d), step,
-                       P<T>(c->xb[c->trial]), P<T>(c->gb[c->trial]), c->n, obj, c->ws, c->out_slot<T>(), rev);
+    LBFGSX_LAUNCH((k_trial<T, OBJ>), dim3(a.grid), dim3(kBlock), 0, c->stream, a.xp, a.d, a.step, a.x, a.g, a.n, obj, a.ws,
+                       a.out, a.rev);
     LBFGSX_HIP(hipGetLastError());
+    return fetch_scalars<T>(c, c->sl.out(0), 2, out2);
+}
+template <class T>
+static int trial_term_t(lbfgsx_ctx* c, T step, double* out2)
+{
+    lbfgsx::TrialLaunch<T> a = lbfgsx::trial_launch<T>(c, step, c->term_np);
+    lbfgsx::TermArgs<T> obj = lbfgsx::term_args<T>(c);
+    void* params[] = {&a.xp, &a.d, &a.step, &a.x, &a.g, &a.n, &obj, &a.ws, &a.out, &a.rev};
+    const int rc = lbfgsx::jit_launch(c, lbfgsx::JIT_K_TRIAL, a.grid, params);
+    if (rc)
+        return rc;
     return fetch_scalars<T>(c, c->sl.out(0), 2, out2);
 }
 extern "C" {
@@ -1067,6 +1090,8 @@ int lbfgsx_trial(lbfgsx_ctx* c, int objective, double step, double* fx, double* 
             rc = trial_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, T(step), r);
         else if (objective == LBFGSX_OBJ_EXT_ROSENBROCK)
             rc = trial_t<T>(c, ObjRosen<T>{}, T(step), r);
+        else if (lbfgsx::term_bound(c, objective))
+            rc = trial_term_t<T>(c, T(step), r);
         else
             set_error("lbfgsx_trial: unknown objective");
     });

@@ -1,5 +1,6 @@
 // lbfgspp_amd/csrc/solver_capi.cpp -- liblbfgsx_solver.so: the drop-in C++ solver templates instantiated
-// for the built-in objectives and for a C callback on device memory behind include/lbfgsx_solver.h.  Plain host C++ (g++),
+// for the built-in objectives, for a term objective compiled at run time and for a C callback on device memory behind
+// include/lbfgsx_solver.h.  Plain host C++ (g++),
 // links liblbfgsx.so.
 #include <cstdio>
 #include <cstring>
@@ -24,6 +25,7 @@ struct lbfgsx_solver
     virtual int set_recursion(int) { return LBFGSX_E_INVALID; }
     virtual int set_allreduce(void (*)(double*, int, void*), void*) { return LBFGSX_E_INVALID; }
     virtual int set_devices(const int*, int) { return LBFGSX_E_INVALID; }
+    int dtype = LBFGSX_F64;
     long long stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long stats_submin_us = 0;
     long long stats2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -32,6 +34,8 @@ struct lbfgsx_solver
                           const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) = 0;
     virtual void minimize_fn(int64_t n, lbfgsx_objective_fn fn, void* user, void* x, const void* lb, const void* ub,
                              lbfgsx_trace* tr, lbfgsx_result* out) = 0;
+    virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, const void* const p[4], int host_mask, const double c[8],
+                              void* x, const void* lb, const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) = 0;
 };
 
 namespace {
@@ -103,6 +107,24 @@ struct CallbackObjective
         return Scalar(fx);
     }
 };
+
+// a compiled term objective with its data (device pointers, or host arrays where host_mask has the slot's bit) and scalars
+template <class Scalar>
+void fill_term(TermObjective<Scalar>& f, const void* const p[4], int host_mask, const double c[8])
+{
+    const Scalar* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; k++)
+    {
+        const Scalar* q = p ? static_cast<const Scalar*>(p[k]) : nullptr;
+        if (q && (host_mask >> k & 1))
+            f.host_data(k, q);
+        else
+            dev[k] = q;
+    }
+    f.data(dev[0], dev[1], dev[2], dev[3]);
+    if (c)
+        f.scalars(c, 8);
+}
 
 template <class Scalar, template <class> class LS>
 struct LbfgsImpl : lbfgsx_solver
@@ -178,6 +200,13 @@ struct LbfgsImpl : lbfgsx_solver
             out->nfev = f.calls;  // the failing call included
             throw;
         }
+    }
+    void minimize_obj(const lbfgsx_objective* obj, int64_t n, const void* const p[4], int host_mask, const double c[8], void* x,
+                      const void*, const void*, lbfgsx_trace* tr, lbfgsx_result* out) override
+    {
+        TermObjective<Scalar> f(obj);
+        fill_term<Scalar>(f, p, host_mask, c);
+        run(f, n, x, tr, out);
     }
     template <class Foo>
     void run(Foo& f, int64_t n, void* x, lbfgsx_trace* tr, lbfgsx_result* out)
@@ -278,6 +307,13 @@ struct LbfgsbImpl : lbfgsx_solver
             out->nfev = f.calls;  // the failing call included
             throw;
         }
+    }
+    void minimize_obj(const lbfgsx_objective* obj, int64_t n, const void* const p[4], int host_mask, const double c[8], void* x,
+                      const void* lb, const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) override
+    {
+        TermObjective<Scalar> f(obj);
+        fill_term<Scalar>(f, p, host_mask, c);
+        run(f, n, x, lb, ub, tr, out);
     }
     template <class Foo>
     void run(Foo& f, int64_t n, void* x, const void* lb, const void* ub, lbfgsx_trace* tr, lbfgsx_result* out)
@@ -385,6 +421,7 @@ int lbfgsx_solver_create(lbfgsx_solver** out, int algo, int dtype, int linesearc
         }
         else
             throw std::invalid_argument("unknown algorithm");
+        (*out)->dtype = dtype;
     });
 }
 
@@ -839,5 +876,31 @@ int lbfgsx_solver_minimize_fn(lbfgsx_solver* s, int64_t n, lbfgsx_objective_fn f
             throw std::invalid_argument("lbfgsx_solver_minimize_fn: invalid argument");
         s->minimize_fn(n, fn, user, x, lb, ub, trace, out);
     });
+}
+
+int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, const void* const p[4], int host_mask,
+                               const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
+                               lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    // what is wrong with the request itself is said first, with or without a device
+    const int bad = guarded(out, [&]() {
+        if (!s || !obj || n <= 0)
+            throw std::invalid_argument("lbfgsx_solver_minimize_obj: invalid argument");
+        if (lbfgsx_objective_dtype(obj) != s->dtype)
+            throw std::invalid_argument("lbfgsx_solver_minimize_obj: the objective was compiled for the other dtype");
+        const int K = lbfgsx_objective_K(obj);
+        if (n % K != 0)
+            throw std::invalid_argument("term objective: n = " + std::to_string(n) + " is not a multiple of K = " + std::to_string(K));
+    });
+    if (bad)
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_obj: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    return guarded(out, [&]() { s->minimize_obj(obj, n, p, host_mask, c, x, lb, ub, trace, out); });
 }
 }

@@ -6,7 +6,8 @@ Names, argument meaning and error behaviour follow yixuan/LBFGSpp:
   LBFGSBSolver(param).minimize(f, x, lb, ub)     -> (niter, fx)      reference include/LBFGSB.h:116-262
 Exceptions: std::invalid_argument -> ValueError, std::logic_error -> ArithmeticError,
 std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device objective
-(`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`) or the caller's own, `DeviceObjective(fn)`: fn(x, grad) -> float on torch
+(`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`), the caller's own term compiled into the same kernels (`TermObjective(body)`)
+or the caller's own callable, `DeviceObjective(fn)`: fn(x, grad) -> float on torch
 tensors that alias the library's device vectors.  All O(n) work of the solver runs in the HIP library, Python only passes
 pointers.  There is no CPU fallback: without the built extension or a GPU these calls raise.
 """
@@ -97,6 +98,82 @@ class DeviceObjective:
             grad.copy_(g)
             return float(f.detach())
         return cls(fn)
+
+
+class TermObjective:
+    """An objective that is a sum of terms over K consecutive coordinates (K = 1 or 2), given as HIP/C++ text for ONE term
+    and compiled at run time into the fused kernels the built-in objectives use (include/lbfgsx.h, "term objectives").
+    The body sees T (scalar type), const T x[K], T g[K] (to fill), int64_t i (index of x[0]), const T* p0..p3 (`data`) and
+    T c[8] (`scalars`) and returns the term's value; f is the sum of the returned values.
+
+        rosen = TermObjective("const T t1 = T(1) - x[0]; const T t2 = T(10) * (x[1] - x[0] * x[0]);"
+                              "g[1] = T(20) * t2; g[0] = T(-2) * (x[0] * g[1] + t1); return t1 * t1 + t2 * t2;", K=2)
+
+    data: up to four per-coordinate arrays of n elements -- numpy arrays (copied to the device at every minimise) or torch
+    tensors on the solver's device (used in place); scalars: up to eight numbers.  Both may be replaced between minimises
+    (set_data / set_scalars): the compiled code is kept.  Usable wherever ExtendedRosenbrock / DeviceObjective are, except
+    with the Gram-space recursion, row shards and the lock-step batch.  A body that does not compile raises ValueError with
+    the compiler's log (line numbers count from the body's first line)."""
+    MAX_DATA, MAX_SCALARS = 4, 8
+
+    def __init__(self, body, K=1, data=(), scalars=()):
+        if K not in (1, 2):
+            raise ValueError("TermObjective: K = %r is not supported: a term reads K = 1 or K = 2 consecutive coordinates" % (K,))
+        self.body, self.K = str(body), int(K)
+        self._h = {}
+        self.set_data(*data)
+        self.set_scalars(*scalars)
+
+    def set_data(self, *data):
+        if len(data) > self.MAX_DATA:
+            raise ValueError("TermObjective: %d data arrays given, at most %d (p0..p3) are supported" % (len(data), self.MAX_DATA))
+        self.data = tuple(data)
+
+    def set_scalars(self, *scalars):
+        if len(scalars) > self.MAX_SCALARS:
+            raise ValueError("TermObjective: %d scalars given, at most %d (c[0..7]) are supported" % (len(scalars), self.MAX_SCALARS))
+        self.scalars = tuple(float(v) for v in scalars)
+
+    def source(self, dtype=np.float64):
+        """The translation unit the library generates around the body."""
+        core, _ = L.load()
+        dt = L.F64 if np.dtype(dtype) == np.float64 else L.F32
+        need = core.lbfgsx_objective_source(dt, self.K, self.body.encode(), None, 0)
+        L.check(min(need, 0))
+        buf = C.create_string_buffer(int(need))
+        core.lbfgsx_objective_source(dt, self.K, self.body.encode(), buf, need)
+        return buf.value.decode()
+
+    def compile(self, dtype=np.float64):
+        """Compile for gfx950 (no device needed) or fetch from the process-wide cache; returns the handle."""
+        core, _ = L.load()
+        dt = L.F64 if np.dtype(dtype) == np.float64 else L.F32
+        if dt not in self._h:
+            h = C.c_void_p()
+            log = C.create_string_buffer(1 << 16)
+            rc = core.lbfgsx_objective_compile(C.byref(h), dt, self.K, self.body.encode(), log, len(log))
+            if rc == L.E_INVALID:
+                raise ValueError("TermObjective: the body does not compile\n" + log.value.decode(errors="replace"))
+            L.check(rc, log.value.decode(errors="replace"))
+            self._h[dt] = h
+        return self._h[dt]
+
+    def info(self, dtype=np.float64):
+        """{vgprs, scratch_bytes, cache_hit, compile_ms, scratch_by_kernel} of the compiled code object."""
+        core, _ = L.load()
+        arr = (C.c_longlong * 8)()
+        L.check(core.lbfgsx_objective_info(self.compile(dtype), C.byref(arr)))
+        return {"vgprs": arr[0], "scratch_bytes": arr[1], "cache_hit": bool(arr[2]), "compile_ms": arr[3],
+                "scratch_by_kernel": dict(zip(("k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial"), list(arr)[4:8]))}
+
+    def __del__(self):
+        try:
+            core, _ = L.load()
+            for h in self._h.values():
+                core.lbfgsx_objective_destroy(h)
+            self._h = {}
+        except Exception:
+            pass
 
 
 def _is_torch(x):
@@ -253,11 +330,56 @@ class _SolverBase:
         L.check(rc, self.last.msg)
         return self.last
 
+    def _minimize_obj(self, f, n, x, lb, ub, trace):
+        np_dt = _NP[self.dtype]
+        if n % f.K:
+            raise ValueError("TermObjective: n = %d is not a multiple of K = %d" % (n, f.K))
+        h = f.compile(np_dt)
+        ptrs = (C.c_void_p * 4)()
+        keep, mask = [], 0
+        for k, d in enumerate(f.data):
+            if d is None:
+                continue
+            if _is_torch(d):
+                torch = L.require_torch("TermObjective with torch data")
+                want = torch.float64 if self.dtype == L.F64 else torch.float32
+                if d.dim() != 1 or d.numel() != n or d.dtype != want or not d.is_cuda or d.device.index != self.device \
+                        or not d.is_contiguous():
+                    raise ValueError("TermObjective: data[%d] must be a contiguous 1-D %s tensor of %d elements on cuda:%d"
+                                     % (k, want, n, self.device))
+                ptrs[k] = d.data_ptr()
+                keep.append(d)
+            else:
+                a = np.ascontiguousarray(d, np_dt)
+                if a.ndim != 1 or a.size != n:
+                    raise ValueError("TermObjective: data[%d] must have %d elements" % (k, n))
+                ptrs[k] = a.ctypes.data
+                mask |= 1 << k
+                keep.append(a)  # the converted copy, not d: its address is what the library reads
+        cs = (C.c_double * 8)(*(f.scalars + (0.0,) * (8 - len(f.scalars))))
+        res = L.Result()
+        if any(_is_torch(d) for d in f.data):
+            torch.cuda.current_stream().synchronize()  # the data arrays are complete when the library reads them
+        rc = self._sol.lbfgsx_solver_minimize_obj(self._h, h, n, C.byref(ptrs), mask, C.byref(cs), self._ptr(x), self._ptr(lb),
+                                                  self._ptr(ub), C.byref(trace.c) if trace else None, C.byref(res))
+        del keep
+        self.last = Result(res)
+        L.check(rc, self.last.msg)
+        return self.last
+
+    def bound_data(self):
+        """The four device pointers of the term objective bound to this solver's context (0 = unused)."""
+        arr = (C.c_void_p * 4)()
+        L.check(self._core.lbfgsx_objective_bound(self.ctx, C.byref(arr)))
+        return [int(v or 0) for v in arr]
+
     def _minimize(self, f, n, x, lb, ub, trace):
         if isinstance(f, DeviceObjective):
             return self._minimize_fn(f, n, x, lb, ub, trace)
+        if isinstance(f, TermObjective):
+            return self._minimize_obj(f, n, x, lb, ub, trace)
         if not hasattr(f, "objective"):
-            raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock or DeviceObjective(fn)")
+            raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body) or DeviceObjective(fn)")
         res = L.Result()
         a = None if f.a is None else np.ascontiguousarray(f.a, _NP[self.dtype])
         b = None if f.b is None else np.ascontiguousarray(f.b, _NP[self.dtype])
