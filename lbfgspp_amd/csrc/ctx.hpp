@@ -137,9 +137,9 @@ struct ScLayout
 void live_add(int device, int delta);   // lbfgsx.hip
 int live_count(int device);
 
-int bounded_alloc(lbfgsx_ctx* c);   // lbfgsb.hip
+int bounded_alloc(lbfgsx_ctx* c);   // lbfgsb.hip (the state itself: lbfgsb_state.hpp)
 void bounded_free(lbfgsx_ctx* c);
-int bounded_note_column(lbfgsx_ctx* c, int col);  // a history column pair was written outside k_b_post: refresh its max |.|
+int bounded_note_column(lbfgsx_ctx* c, int col);  // lbfgsb_gram.hip: a history column pair was written outside k_b_post: refresh its max |.|
 struct GsState;                     // gram_space.hip: scratch of the Gram-space recursion (allocated on first use)
 void gs_free(lbfgsx_ctx* c);
 

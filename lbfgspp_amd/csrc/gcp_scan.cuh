@@ -339,7 +339,7 @@ __global__ void __launch_bounds__(kGcpTile) k_gcp_a3b1(GcpBufs b, int64_t count,
 //     dfp[k] = g^2 + theta g z - g (M w).c_k         (:227, without the dt f'' term of :218)
 //     fpp[k] = theta g^2 + 2 g (M w).p_{k-1} + g^2 w.(M w)      (:228, the amount subtracted from f'')
 //     fp[k]  = dt_k  (fp[count] = distance to the next break point after the chunk, or -1 at the end of the list)
-// and the host runs the two chains in the reference's order (gcp_chain_host in lbfgsb.hip).
+// and the host runs the two chains in the reference's order (gcp_chain_host in lbfgsb_cauchy.hip).
 template <int NC, bool CHAIN = false>
 __global__ void __launch_bounds__(kGcpTile) k_gcp_b3c1(GcpBufs b, int64_t count, int ncorr, double theta, double t_prev,
                                                        const double* __restrict__ Mg, const double* __restrict__ offB,

@@ -1,6 +1,6 @@
 // lbfgspp_amd/csrc/launch_args.hpp -- grid and arguments of the four launches that evaluate an objective (k_eval, k_trial,
 // k_b_eval, k_b_dg_maxstep_trial), worked out once for both forms of the launch: the built-in instantiations
-// (hipLaunchKernelGGL in lbfgsx.hip / lbfgsb.hip) and the instantiations compiled at run time for a term objective
+// (hipLaunchKernelGGL in lbfgsx.hip / lbfgsb_linesearch.hip) and the instantiations compiled at run time for a term objective
 // (hipModuleLaunchKernel, jit_objective.hip).  The members are the kernels' arguments in order, the objective left out.
 #pragma once
 #include "ctx.hpp"

@@ -1,5 +1,5 @@
 // lbfgspp_amd/csrc/lbfgsb_x.hpp -- launchers of the kernels of lbfgsb_x.cuh (defined and instantiated in lbfgsb_x.hip, a
-// translation unit of its own: 8 column classes x 2 element types x 7 kernels compile next to lbfgsb.hip, not inside it).
+// translation unit of its own: 8 column classes x 2 element types x 7 kernels compile next to the lbfgsb_*.hip phase files, not inside them).
 // Every launcher picks the class (NCL columns per lane, G lanes per row) from 2c and the grid from the rows.
 #pragma once
 #include "ctx.hpp"
