@@ -75,7 +75,7 @@ class LBFGSSolver
                                             "two-loop reduces its dot products on the device, inside one launch");
             ev.reduce = m_reducer;
         }
-        if constexpr (std::is_same<typename std::decay<Foo>::type, TermObjective<Scalar> >::value)
+        if constexpr (detail::is_compiled_objective<Scalar, Foo>::value)
         {
             if (m_recursion != RECURSION_VECTOR || m_reducer)
                 throw std::invalid_argument("a TermObjective runs with the vector recursion on one device: the Gram-space and "

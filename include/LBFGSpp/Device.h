@@ -110,18 +110,25 @@ class TermObjective
 public:
     int id = LBFGSX_OBJ_NONE;  // LBFGSX_OBJ_BOUND once bound to a solver's context (Evaluator::prepare)
 
-    TermObjective(int K, const std::string& body)
-    {
-        std::vector<char> log(16384, '\0');
-        const int rc = lbfgsx_objective_compile(&m_h, detail::dtype_of<Scalar>::value, K, body.c_str(), log.data(), log.size());
-        if (rc == LBFGSX_E_INVALID)
-            throw std::invalid_argument(std::string("TermObjective: ") + log.data());
-        if (rc != LBFGSX_OK)
-            throw std::runtime_error(std::string("TermObjective: ") + log.data());
-        m_own = true;
-    }
+    TermObjective(int K, const std::string& body) : TermObjective(LBFGSX_FORM_TERM, K, body, "TermObjective: ") {}
     // a handle compiled elsewhere (lbfgsx_objective_compile); it stays the caller's
     explicit TermObjective(const lbfgsx_objective* compiled) : m_h(const_cast<lbfgsx_objective*>(compiled)) {}
+
+protected:
+    TermObjective(int form, int K, const std::string& body, const char* who)
+    {
+        std::vector<char> log(16384, '\0');
+        const int dt = detail::dtype_of<Scalar>::value;
+        const int rc = (form == LBFGSX_FORM_CHAIN) ? lbfgsx_objective_compile_chain(&m_h, dt, K, body.c_str(), log.data(), log.size())
+                                                   : lbfgsx_objective_compile(&m_h, dt, K, body.c_str(), log.data(), log.size());
+        if (rc == LBFGSX_E_INVALID)
+            throw std::invalid_argument(std::string(who) + log.data());
+        if (rc != LBFGSX_OK)
+            throw std::runtime_error(std::string(who) + log.data());
+        m_own = true;
+    }
+
+public:
     ~TermObjective()
     {
         if (m_own)
@@ -170,6 +177,30 @@ public:
     }
 };
 
+// An objective whose terms OVERLAP: f(x) = sum over t = 0 .. n-K of phi(x[t], .., x[t+K-1]; t), K = 2 or 3, one term starting
+// at every coordinate (include/lbfgsx.h, "chain objectives").  The body is a TermObjective's; data, scalars and binding too.
+//     ChainObjective<double> f(2, "const T u = x[1] - x[0] * x[0]; const T v = T(1) - x[0]; g[1] = T(200) * u;"
+//                                 "g[0] = T(-400) * (u * x[0]) - T(2) * v; return T(100) * (u * u) + v * v;");   // chained Rosenbrock
+// Accepted by LBFGSSolver::minimize and LBFGSBSolver::minimize wherever a TermObjective is, refused where it is.
+template <typename Scalar>
+class ChainObjective : public TermObjective<Scalar>
+{
+public:
+    ChainObjective(int K, const std::string& body) : TermObjective<Scalar>(LBFGSX_FORM_CHAIN, K, body, "ChainObjective: ") {}
+    // a handle compiled elsewhere (lbfgsx_objective_compile_chain); it stays the caller's
+    explicit ChainObjective(const lbfgsx_objective* compiled) : TermObjective<Scalar>(compiled) {}
+};
+
+namespace detail {
+// the objectives compiled at run time into the fused kernels: a TermObjective or a ChainObjective
+template <typename Scalar, typename Foo>
+struct is_compiled_objective
+{
+    typedef typename std::decay<Foo>::type F;
+    static constexpr bool value = std::is_same<F, TermObjective<Scalar> >::value || std::is_same<F, ChainObjective<Scalar> >::value;
+};
+}  // namespace detail
+
 template <typename Scalar>
 class DeviceState
 {
@@ -217,7 +248,7 @@ namespace detail {
 
 // Uniform view of the four kinds of objective `Foo` the solvers accept:
 //   BuiltinObjective<Scalar>                              -> fused device kernels
-//   TermObjective<Scalar>                                 -> the same kernels, compiled at run time for the caller's term
+//   TermObjective<Scalar>, ChainObjective<Scalar>         -> the same kernels, compiled at run time for the caller's term
 //   Scalar f(const DeviceVector<Scalar>& x, DeviceVector<Scalar>& grad)   -> user device functor
 //   Scalar f(const Vec& x, Vec& grad) with host vectors   -> staged through host memory (compatibility)
 template <typename Scalar, typename Foo, typename HostVec>
@@ -228,7 +259,7 @@ class Evaluator
     HostVec m_hx, m_hg;  // staging for host functors only
     int m_nfev = 0;
 
-    static constexpr bool is_term = std::is_same<typename std::decay<Foo>::type, TermObjective<Scalar> >::value;
+    static constexpr bool is_term = is_compiled_objective<Scalar, Foo>::value;
     // evaluated inside the fused kernels under an objective id: the two built-in ones and a bound term objective
     static constexpr bool is_builtin = is_term || std::is_same<typename std::decay<Foo>::type, BuiltinObjective<Scalar> >::value;
     // A functor that accepts the caller's host vectors is a host functor even if it would also accept device vectors

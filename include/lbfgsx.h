@@ -148,7 +148,8 @@ int lbfgsx_spec_counts(const lbfgsx_ctx* c, int64_t out[3]);
  * No shared memory, no synchronisation, no other coordinates, no inline assembly.  The library wraps the body into the
  * objective struct the kernel templates take, compiles k_eval, k_trial, k_b_eval and k_b_dg_maxstep_trial for it with
  * hipRTC for gfx950 (-O3 -ffp-contract=off: the build's own floating-point contract, no device needed), and caches the
- * result per process by (body, K, dtype).  A body that does not compile: LBFGSX_E_INVALID, the compiler's log in `log`
+ * result per process by (form, body, K, dtype); "chain objectives" below are the other form.  A body that does not compile:
+ * LBFGSX_E_INVALID, the compiler's log in `log`
  * (line numbers count from the first line of the body, file name "objective_body").
  * lbfgsx_objective_source: the generated translation unit (returns the length needed, text truncated to len).
  * lbfgsx_objective_info: out = {VGPRs (largest of the four kernels), scratch bytes (largest), 1 if this handle was served
@@ -178,6 +179,30 @@ int lbfgsx_objective_dtype(const lbfgsx_objective* obj);
 int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void* const p[4], const double cs[8], int* id);
 int lbfgsx_objective_upload(lbfgsx_ctx* c, int slot, const void* host, void** dev);
 int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4]);
+/* ---- chain objectives: overlapping terms ------------------------------------------------------------------------------
+ * f(x) = sum over t = 0 .. n-K of phi(x[t], .., x[t+K-1]; t) with K = 2 or 3: ONE TERM STARTS AT EVERY COORDINATE, so
+ * neighbouring terms overlap -- the chained Rosenbrock function, first- and second-difference regularisers, any nearest-
+ * neighbour energy.  `body` is what a term objective's is: it sees T, const T x[K], T g[K] (the term's K partial derivatives,
+ * to fill), int64_t i (the index of x[0]), p0..p3, c[8] and returns the term's value.  It may read p0[i] .. p0[i+K-1]: a term
+ * that does not lie inside [0, n) is never evaluated.
+ * Semantics (a numpy restatement with one operation per source operation is bit-exact):
+ *   grad[j] = the sum of g_t[j-t] over the terms t = max(0, j-K+1) .. min(j, n-K), in ascending t, started from the first
+ *             contribution (no leading 0 +);
+ *   f       = the order-independent (compensated) sum of the terms' values, each added once, by the thread that owns the
+ *             coordinate the term starts at;
+ *   one rounding per source operation, no contraction.
+ * lbfgsx_objective_compile_chain wraps the body for the four kernels of csrc/chain_kernels.cuh -- the counterparts of k_eval,
+ * k_trial, k_b_eval and k_b_dg_maxstep_trial with the same arguments, grids, tiles and reductions, so the byte model is the
+ * built-in's (the halo of a pack comes from the neighbouring lanes) -- and caches by (form, body, K, dtype): the same body as
+ * a term objective and as a chain objective are two entries.  K outside {2, 3}: LBFGSX_E_INVALID.  The handle carries its
+ * form (lbfgsx_objective_form: LBFGSX_FORM_TERM or LBFGSX_FORM_CHAIN); lbfgsx_objective_bind, lbfgsx_objective_info,
+ * lbfgsx_solver_minimize_obj and the four evaluation entry points take it like a term objective's.  Binding to a context
+ * with n < K is refused (any n >= K is accepted: n need not be a multiple of anything).  The compile log, the refusal of
+ * asm and the line numbers are those of lbfgsx_objective_compile. */
+enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1 };
+int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len);
+long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char* out, size_t len);
+int lbfgsx_objective_form(const lbfgsx_objective* obj);
 /* Every entry point of this ABI makes the context's device current for its own duration and restores the caller's
  * afterwards.  Code that launches its OWN kernels on the context's vectors (a device functor, lbfgsx_vec) must run with
  * that device current too: lbfgsx_device tells which one it is, lbfgsx_device_push makes it current for the calling

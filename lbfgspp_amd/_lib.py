@@ -189,6 +189,9 @@ def load():
     sig(core, "lbfgsx_objective_destroy", None, vp)
     sig(core, "lbfgsx_objective_source", C.c_longlong, i32, i32, C.c_char_p, C.c_char_p, C.c_size_t)
     sig(core, "lbfgsx_objective_info", i32, vp, C.POINTER(C.c_longlong * 8))
+    sig(core, "lbfgsx_objective_compile_chain", i32, C.POINTER(vp), i32, i32, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_source_chain", C.c_longlong, i32, i32, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_form", i32, vp)
     sig(core, "lbfgsx_objective_K", i32, vp)
     sig(core, "lbfgsx_objective_dtype", i32, vp)
     sig(core, "lbfgsx_objective_bind", i32, vp, vp, C.POINTER(vp * 4), C.POINTER(dbl * 8), C.POINTER(i32))

@@ -7,6 +7,11 @@
 // (-O3 -ffp-contract=off), which is what makes a re-statement of a built-in objective bit-identical to the built-in: the
 // same kernel text, the same flags, the same sums.  The code object is loaded per device with hipModuleLoadData and the
 // kernels are launched with hipModuleLaunchKernel from the arguments launch_args.hpp works out for both forms.
+//
+// Two forms of objective share all of this (include/lbfgsx.h): a TERM objective (terms that do not overlap: the struct with
+// pack / tail / finish above) and a CHAIN objective (one term starting at every coordinate: a second generated wrapper that
+// includes chain_kernels.cuh and instantiates its four kernels, which take the arguments of the four above).  A handle
+// carries its form; the four slots of the loaded-kernel table and everything that launches them are the same.
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
 
@@ -24,7 +29,11 @@
 
 namespace {
 
-const char* const kKernelNames[lbfgsx::JIT_NKERNELS] = {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial"};
+const char* const kKernelNames[2][lbfgsx::JIT_NKERNELS] = {
+    {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial"},
+    {"k_chain_eval", "k_chain_trial", "k_chain_b_eval", "k_chain_b_dg_maxstep_trial"}};
+const char* const kObjStruct[2] = {"ObjTerm", "ObjChain"};
+const char* const kFormName[2] = {"term objective", "chain objective"};
 
 // ---- hipRTC, loaded on first use (a process that never compiles an objective does not need it)
 struct Rtc
@@ -96,8 +105,12 @@ std::string kernel_dir()
 }
 
 // ---- the generated translation unit
-std::string generate(int dtype, int K, const char* body)
+std::string generate_chain(int dtype, int K, const char* body);
+
+std::string generate(int form, int dtype, int K, const char* body)
 {
+    if (form == LBFGSX_FORM_CHAIN)
+        return generate_chain(dtype, K, body);
     std::string s;
     s += "// generated by lbfgsx_objective_compile: one term objective for the fused kernels\n";
     s += "#include \"lbfgs_kernels.cuh\"\n";
@@ -150,8 +163,52 @@ std::string generate(int dtype, int K, const char* body)
     return s;
 }
 
-bool valid_request(int dtype, int K, const char* body, std::string& why)
+// the wrapper of a chain objective: the struct chain_kernels.cuh asks for (K and term), and its four kernels
+std::string generate_chain(int dtype, int K, const char* body)
 {
+    std::string s;
+    s += "// generated by lbfgsx_objective_compile_chain: one chain objective for the fused kernels\n";
+    s += "#include \"chain_kernels.cuh\"\n";
+    s += "namespace lbfgsx {\n";
+    s += std::string("typedef ") + (dtype == LBFGSX_F64 ? "double" : "float") + " term_scalar_t;\n";
+    s += "struct ObjChain\n{\n";
+    s += "    typedef term_scalar_t T;\n";
+    s += "    static constexpr int K = " + std::to_string(K) + ";\n";
+    s += "    const T* p0;\n    const T* p1;\n    const T* p2;\n    const T* p3;\n    T c[8];\n";
+    s += "    // the term that starts at coordinate i: x[0..K) in, its K partial derivatives g[0..K) out, its value returned\n";
+    s += "    __device__ __forceinline__ T term(const T (&x)[K], T (&g)[K], int64_t i) const\n    {\n";
+    s += "#line 1 \"objective_body\"\n";
+    s += body;
+    s += "\n#line 1 \"objective_wrapper\"\n";
+    s += "    }\n";
+    s += "};\n";
+    s += "typedef term_scalar_t S;\n";
+    s += "template __global__ void k_chain_eval<S, ObjChain>(const S*, S*, int64_t, ObjChain, RedWs, S*);\n";
+    s += "template __global__ void k_chain_trial<S, ObjChain>(const S*, const S*, S, S*, S*, int64_t, ObjChain, RedWs, S*, int);\n";
+    s += "template __global__ void k_chain_b_eval<S, ObjChain>(const S*, S*, const S*, const S*, int64_t, ObjChain, RedWs, S*);\n";
+    s += "template __global__ void k_chain_b_dg_maxstep_trial<S, ObjChain>(const S*, const S*, const S*, const S*, const S*, S, S*, "
+         "S*, int64_t, ObjChain, RedWs, S*, int);\n";
+    s += "}  // namespace lbfgsx\n";
+    return s;
+}
+
+bool valid_request(int form, int dtype, int K, const char* body, std::string& why)
+{
+    if (form == LBFGSX_FORM_CHAIN)
+    {
+        if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
+            why = "chain objective: unknown dtype";
+        else if (K != 2 && K != 3)
+            why = "chain objective: K = " + std::to_string(K) + " is not supported: a chain term reads K = 2 or K = 3 consecutive "
+                  "coordinates (its halo of K - 1 values must lie inside the neighbouring 16-byte pack of two doubles)";
+        else if (!body || !*body)
+            why = "chain objective: empty body";
+        else if (std::strstr(body, "asm"))
+            why = "chain objective: the body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
+        else
+            return true;
+        return false;
+    }
     if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
         why = "term objective: unknown dtype";
     else if (K != 1 && K != 2)
@@ -269,11 +326,11 @@ struct lbfgsx_objective
     bool cache_hit = false;
 };
 
-// one compiled (body, K, dtype): lives until the process ends (the cache)
+// one compiled (form, body, K, dtype): lives until the process ends (the cache)
 struct lbfgsx_objective_code
 {
     lbfgsx_objective self;  // what a context's binding points to: it outlives every handle given to a caller
-    int dtype = LBFGSX_F64, K = 1;
+    int form = LBFGSX_FORM_TERM, dtype = LBFGSX_F64, K = 1;
     std::vector<char> code;
     std::string lowered[lbfgsx::JIT_NKERNELS];
     long long vgprs[lbfgsx::JIT_NKERNELS] = {0, 0, 0, 0}, scratch[lbfgsx::JIT_NKERNELS] = {0, 0, 0, 0};
@@ -296,7 +353,7 @@ std::map<std::string, std::unique_ptr<lbfgsx_objective_code> >& cache()
     return m;
 }
 
-int compile_code(int dtype, int K, const char* body, std::unique_ptr<lbfgsx_objective_code>& out, std::string& log)
+int compile_code(int form, int dtype, int K, const char* body, std::unique_ptr<lbfgsx_objective_code>& out, std::string& log)
 {
     const Rtc& r = rtc();
     if (!r.error.empty())
@@ -304,7 +361,7 @@ int compile_code(int dtype, int K, const char* body, std::unique_ptr<lbfgsx_obje
         log = r.error;
         return LBFGSX_E_RUNTIME;
     }
-    const std::string src = generate(dtype, K, body);
+    const std::string src = generate(form, dtype, K, body);
     // the kernel headers ask for <hip/hip_runtime.h>; hipRTC has the runtime's declarations built in, so the name resolves
     // to an empty header instead of depending on where ROCm's headers are installed
     const char* hsrc[] = {"\n"};
@@ -318,7 +375,7 @@ int compile_code(int dtype, int K, const char* body, std::unique_ptr<lbfgsx_obje
     std::string expr[lbfgsx::JIT_NKERNELS];
     for (int k = 0; k < lbfgsx::JIT_NKERNELS; k++)
     {
-        expr[k] = std::string("lbfgsx::") + kKernelNames[k] + "<lbfgsx::term_scalar_t, lbfgsx::ObjTerm>";
+        expr[k] = std::string("lbfgsx::") + kKernelNames[form][k] + "<lbfgsx::term_scalar_t, lbfgsx::" + kObjStruct[form] + ">";
         (void) r.add_name(prog, expr[k].c_str());
     }
     const std::string inc = "-I" + kernel_dir();
@@ -342,6 +399,7 @@ int compile_code(int dtype, int K, const char* body, std::unique_ptr<lbfgsx_obje
         return LBFGSX_E_INVALID;
     }
     std::unique_ptr<lbfgsx_objective_code> code(new lbfgsx_objective_code());
+    code->form = form;
     code->dtype = dtype;
     code->K = K;
     code->compile_ms = ms;
@@ -365,7 +423,7 @@ int compile_code(int dtype, int K, const char* body, std::unique_ptr<lbfgsx_obje
     (void) r.destroy(&prog);
     if (!ok)
     {
-        log = "term objective: the compiled code object lacks a kernel or its descriptor";
+        log = std::string(kFormName[form]) + ": the compiled code object lacks a kernel or its descriptor";
         return LBFGSX_E_RUNTIME;
     }
     code->self.code = code.get();
@@ -393,30 +451,30 @@ int jit_launch(lbfgsx_ctx* c, int which, int grid, void** params)
     }
     counters().launches.fetch_add(1, std::memory_order_relaxed);
     if (host_trace_on())
-        host_trace(kKernelNames[which]);
+        host_trace(kKernelNames[c->term->code->form][which]);
     LBFGSX_HIP(hipModuleLaunchKernel(fn, unsigned(grid), 1, 1, unsigned(kBlock), 1, 1, 0, c->stream, params, nullptr));
     return LBFGSX_OK;
 }
 
 }  // namespace lbfgsx
 
-extern "C" {
+namespace {
 
-long long lbfgsx_objective_source(int dtype, int K, const char* body, char* out, size_t len)
+long long objective_source(int form, int dtype, int K, const char* body, char* out, size_t len)
 {
     std::string why;
-    if (!valid_request(dtype, K, body, why))
+    if (!valid_request(form, dtype, K, body, why))
     {
         lbfgsx::set_error(why);
         return LBFGSX_E_INVALID;
     }
-    const std::string s = generate(dtype, K, body);
+    const std::string s = generate(form, dtype, K, body);
     if (out && len > 0)
         std::snprintf(out, len, "%s", s.c_str());
     return (long long) s.size() + 1;
 }
 
-int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
+int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
 {
     if (log && log_len > 0)
         log[0] = '\0';
@@ -424,13 +482,13 @@ int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const cha
         return LBFGSX_E_INVALID;
     *out = nullptr;
     std::string why;
-    if (!valid_request(dtype, K, body, why))
+    if (!valid_request(form, dtype, K, body, why))
     {
         lbfgsx::set_error(why);
         put_log(log, log_len, why);
         return LBFGSX_E_INVALID;
     }
-    const std::string key = std::to_string(dtype) + "/" + std::to_string(K) + "/" + body;
+    const std::string key = std::to_string(form) + "/" + std::to_string(dtype) + "/" + std::to_string(K) + "/" + body;
     std::lock_guard<std::mutex> lock(g_cache_mu);
     auto it = cache().find(key);
     const bool hit = it != cache().end();
@@ -438,10 +496,10 @@ int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const cha
     {
         std::unique_ptr<lbfgsx_objective_code> code;
         std::string text;
-        const int rc = compile_code(dtype, K, body, code, text);
+        const int rc = compile_code(form, dtype, K, body, code, text);
         if (rc)
         {
-            lbfgsx::set_error("term objective: compilation failed\n" + text);
+            lbfgsx::set_error(std::string(kFormName[form]) + ": compilation failed\n" + text);
             put_log(log, log_len, text);
             return rc;
         }
@@ -453,6 +511,28 @@ int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const cha
     h->cache_hit = hit;
     *out = h;
     return LBFGSX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+long long lbfgsx_objective_source(int dtype, int K, const char* body, char* out, size_t len)
+{
+    return objective_source(LBFGSX_FORM_TERM, dtype, K, body, out, len);
+}
+long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char* out, size_t len)
+{
+    return objective_source(LBFGSX_FORM_CHAIN, dtype, K, body, out, len);
+}
+
+int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_TERM, out, dtype, K, body, log, log_len);
+}
+int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_CHAIN, out, dtype, K, body, log, log_len);
 }
 
 void lbfgsx_objective_destroy(lbfgsx_objective* obj) { delete obj; }
@@ -476,6 +556,7 @@ int lbfgsx_objective_info(const lbfgsx_objective* obj, long long out[8])
 
 int lbfgsx_objective_K(const lbfgsx_objective* obj) { return obj ? obj->code->K : LBFGSX_E_INVALID; }
 int lbfgsx_objective_dtype(const lbfgsx_objective* obj) { return obj ? obj->code->dtype : LBFGSX_E_INVALID; }
+int lbfgsx_objective_form(const lbfgsx_objective* obj) { return obj ? obj->code->form : LBFGSX_E_INVALID; }
 
 int lbfgsx_objective_upload(lbfgsx_ctx* c, int slot, const void* host, void** dev)
 {
@@ -514,7 +595,16 @@ int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void
         lbfgsx::set_error("lbfgsx_objective_bind: the objective was compiled for the other dtype");
         return LBFGSX_E_INVALID;
     }
-    if (c->n % code->K != 0)
+    if (code->form == LBFGSX_FORM_CHAIN)
+    {
+        if (c->n < code->K)
+        {
+            lbfgsx::set_error("chain objective: n = " + std::to_string(c->n) + " is less than K = " + std::to_string(code->K) +
+                              ": there is no term");
+            return LBFGSX_E_INVALID;
+        }
+    }
+    else if (c->n % code->K != 0)
     {
         lbfgsx::set_error("term objective: n = " + std::to_string(c->n) + " is not a multiple of K = " + std::to_string(code->K));
         return LBFGSX_E_INVALID;

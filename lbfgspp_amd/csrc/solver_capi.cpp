@@ -890,7 +890,13 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
         if (lbfgsx_objective_dtype(obj) != s->dtype)
             throw std::invalid_argument("lbfgsx_solver_minimize_obj: the objective was compiled for the other dtype");
         const int K = lbfgsx_objective_K(obj);
-        if (n % K != 0)
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_CHAIN)
+        {
+            if (n < K)
+                throw std::invalid_argument("chain objective: n = " + std::to_string(n) + " is less than K = " + std::to_string(K) +
+                                            ": there is no term");
+        }
+        else if (n % K != 0)
             throw std::invalid_argument("term objective: n = " + std::to_string(n) + " is not a multiple of K = " + std::to_string(K));
     });
     if (bad)

@@ -6,7 +6,8 @@ Names, argument meaning and error behaviour follow yixuan/LBFGSpp:
   LBFGSBSolver(param).minimize(f, x, lb, ub)     -> (niter, fx)      reference include/LBFGSB.h:116-262
 Exceptions: std::invalid_argument -> ValueError, std::logic_error -> ArithmeticError,
 std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device objective
-(`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`), the caller's own term compiled into the same kernels (`TermObjective(body)`)
+(`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`), the caller's own term compiled into the same kernels (`TermObjective(body)`,
+or `ChainObjective(body)` for terms that overlap)
 or the caller's own callable, `DeviceObjective(fn)`: fn(x, grad) -> float on torch
 tensors that alias the library's device vectors.  All O(n) work of the solver runs in the HIP library, Python only passes
 pointers.  There is no CPU fallback: without the built extension or a GPU these calls raise.
@@ -115,10 +116,13 @@ class TermObjective:
     with the Gram-space recursion, row shards and the lock-step batch.  A body that does not compile raises ValueError with
     the compiler's log (line numbers count from the body's first line)."""
     MAX_DATA, MAX_SCALARS = 4, 8
+    # what ChainObjective replaces: the name in messages, the K accepted, the two entry points of the library
+    _NAME, _KS, _K_RULE = "TermObjective", (1, 2), "a term reads K = 1 or K = 2 consecutive coordinates"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile", "lbfgsx_objective_source"
 
     def __init__(self, body, K=1, data=(), scalars=()):
-        if K not in (1, 2):
-            raise ValueError("TermObjective: K = %r is not supported: a term reads K = 1 or K = 2 consecutive coordinates" % (K,))
+        if K not in self._KS:
+            raise ValueError("%s: K = %r is not supported: %s" % (self._NAME, K, self._K_RULE))
         self.body, self.K = str(body), int(K)
         self._h = {}
         self.set_data(*data)
@@ -126,22 +130,24 @@ class TermObjective:
 
     def set_data(self, *data):
         if len(data) > self.MAX_DATA:
-            raise ValueError("TermObjective: %d data arrays given, at most %d (p0..p3) are supported" % (len(data), self.MAX_DATA))
+            raise ValueError("%s: %d data arrays given, at most %d (p0..p3) are supported" % (self._NAME, len(data), self.MAX_DATA))
         self.data = tuple(data)
 
     def set_scalars(self, *scalars):
         if len(scalars) > self.MAX_SCALARS:
-            raise ValueError("TermObjective: %d scalars given, at most %d (c[0..7]) are supported" % (len(scalars), self.MAX_SCALARS))
+            raise ValueError("%s: %d scalars given, at most %d (c[0..7]) are supported"
+                             % (self._NAME, len(scalars), self.MAX_SCALARS))
         self.scalars = tuple(float(v) for v in scalars)
 
     def source(self, dtype=np.float64):
         """The translation unit the library generates around the body."""
         core, _ = L.load()
         dt = L.F64 if np.dtype(dtype) == np.float64 else L.F32
-        need = core.lbfgsx_objective_source(dt, self.K, self.body.encode(), None, 0)
+        source = getattr(core, self._SOURCE)
+        need = source(dt, self.K, self.body.encode(), None, 0)
         L.check(min(need, 0))
         buf = C.create_string_buffer(int(need))
-        core.lbfgsx_objective_source(dt, self.K, self.body.encode(), buf, need)
+        source(dt, self.K, self.body.encode(), buf, need)
         return buf.value.decode()
 
     def compile(self, dtype=np.float64):
@@ -151,9 +157,9 @@ class TermObjective:
         if dt not in self._h:
             h = C.c_void_p()
             log = C.create_string_buffer(1 << 16)
-            rc = core.lbfgsx_objective_compile(C.byref(h), dt, self.K, self.body.encode(), log, len(log))
+            rc = getattr(core, self._COMPILE)(C.byref(h), dt, self.K, self.body.encode(), log, len(log))
             if rc == L.E_INVALID:
-                raise ValueError("TermObjective: the body does not compile\n" + log.value.decode(errors="replace"))
+                raise ValueError("%s: the body does not compile\n" % self._NAME + log.value.decode(errors="replace"))
             L.check(rc, log.value.decode(errors="replace"))
             self._h[dt] = h
         return self._h[dt]
@@ -166,6 +172,10 @@ class TermObjective:
         return {"vgprs": arr[0], "scratch_bytes": arr[1], "cache_hit": bool(arr[2]), "compile_ms": arr[3],
                 "scratch_by_kernel": dict(zip(("k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial"), list(arr)[4:8]))}
 
+    def _check_n(self, n):
+        if n % self.K:
+            raise ValueError("TermObjective: n = %d is not a multiple of K = %d" % (n, self.K))
+
     def __del__(self):
         try:
             core, _ = L.load()
@@ -174,6 +184,29 @@ class TermObjective:
             self._h = {}
         except Exception:
             pass
+
+
+class ChainObjective(TermObjective):
+    """An objective whose terms OVERLAP: f(x) = sum over t = 0 .. n-K of phi(x[t], .., x[t+K-1]; t) with K = 2 or 3, one term
+    starting at every coordinate -- the chained Rosenbrock function, difference regularisers, nearest-neighbour energies
+    (include/lbfgsx.h, "chain objectives").  The body is a TermObjective's: it sees T, const T x[K], T g[K] (the term's K
+    partial derivatives, to fill), int64_t i (index of x[0]), p0..p3 and c[8], may read p0[i] .. p0[i+K-1], and returns the
+    term's value.  grad[j] is the sum of the g_t[j-t] of the terms that cover j, in ascending t.
+
+        chained = ChainObjective("const T u = x[1] - x[0] * x[0]; const T v = T(1) - x[0]; g[1] = T(200) * u;"
+                                 "g[0] = T(-400) * (u * x[0]) - T(2) * v; return T(100) * (u * u) + v * v;", K=2)
+
+    Any n >= K.  data, scalars, set_data, set_scalars, source, compile and info as for a TermObjective (scratch_by_kernel
+    names the four kernels by their counterparts); usable wherever one is, refused where one is."""
+    _NAME, _KS, _K_RULE = "ChainObjective", (2, 3), "a chain term reads K = 2 or K = 3 consecutive coordinates"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_chain", "lbfgsx_objective_source_chain"
+
+    def __init__(self, body, K=2, data=(), scalars=()):
+        super().__init__(body, K, data, scalars)
+
+    def _check_n(self, n):
+        if n < self.K:
+            raise ValueError("ChainObjective: n = %d is less than K = %d: there is no term" % (n, self.K))
 
 
 def _is_torch(x):
@@ -332,8 +365,7 @@ class _SolverBase:
 
     def _minimize_obj(self, f, n, x, lb, ub, trace):
         np_dt = _NP[self.dtype]
-        if n % f.K:
-            raise ValueError("TermObjective: n = %d is not a multiple of K = %d" % (n, f.K))
+        f._check_n(n)
         h = f.compile(np_dt)
         ptrs = (C.c_void_p * 4)()
         keep, mask = [], 0
@@ -341,18 +373,18 @@ class _SolverBase:
             if d is None:
                 continue
             if _is_torch(d):
-                torch = L.require_torch("TermObjective with torch data")
+                torch = L.require_torch("%s with torch data" % f._NAME)
                 want = torch.float64 if self.dtype == L.F64 else torch.float32
                 if d.dim() != 1 or d.numel() != n or d.dtype != want or not d.is_cuda or d.device.index != self.device \
                         or not d.is_contiguous():
-                    raise ValueError("TermObjective: data[%d] must be a contiguous 1-D %s tensor of %d elements on cuda:%d"
-                                     % (k, want, n, self.device))
+                    raise ValueError("%s: data[%d] must be a contiguous 1-D %s tensor of %d elements on cuda:%d"
+                                     % (f._NAME, k, want, n, self.device))
                 ptrs[k] = d.data_ptr()
                 keep.append(d)
             else:
                 a = np.ascontiguousarray(d, np_dt)
                 if a.ndim != 1 or a.size != n:
-                    raise ValueError("TermObjective: data[%d] must have %d elements" % (k, n))
+                    raise ValueError("%s: data[%d] must have %d elements" % (f._NAME, k, n))
                 ptrs[k] = a.ctypes.data
                 mask |= 1 << k
                 keep.append(a)  # the converted copy, not d: its address is what the library reads
@@ -379,7 +411,8 @@ class _SolverBase:
         if isinstance(f, TermObjective):
             return self._minimize_obj(f, n, x, lb, ub, trace)
         if not hasattr(f, "objective"):
-            raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body) or DeviceObjective(fn)")
+            raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body) or "
+                            "DeviceObjective(fn)")
         res = L.Result()
         a = None if f.a is None else np.ascontiguousarray(f.a, _NP[self.dtype])
         b = None if f.b is None else np.ascontiguousarray(f.b, _NP[self.dtype])
