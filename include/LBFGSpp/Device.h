@@ -103,6 +103,7 @@ class TermObjective
     const Scalar* m_p[4] = {nullptr, nullptr, nullptr, nullptr};
     const Scalar* m_host[4] = {nullptr, nullptr, nullptr, nullptr};
     double m_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::int64_t m_rows = 0, m_cols = 0;  // a GridObjective's shape; 0: the handle is bound without one
 
     TermObjective(const TermObjective&) = delete;
     TermObjective& operator=(const TermObjective&) = delete;
@@ -119,13 +120,19 @@ protected:
     {
         std::vector<char> log(16384, '\0');
         const int dt = detail::dtype_of<Scalar>::value;
-        const int rc = (form == LBFGSX_FORM_CHAIN) ? lbfgsx_objective_compile_chain(&m_h, dt, K, body.c_str(), log.data(), log.size())
-                                                   : lbfgsx_objective_compile(&m_h, dt, K, body.c_str(), log.data(), log.size());
+        const int rc = (form == LBFGSX_FORM_GRID)    ? lbfgsx_objective_compile_grid(&m_h, dt, body.c_str(), log.data(), log.size())
+                       : (form == LBFGSX_FORM_CHAIN) ? lbfgsx_objective_compile_chain(&m_h, dt, K, body.c_str(), log.data(), log.size())
+                                                     : lbfgsx_objective_compile(&m_h, dt, K, body.c_str(), log.data(), log.size());
         if (rc == LBFGSX_E_INVALID)
             throw std::invalid_argument(std::string(who) + log.data());
         if (rc != LBFGSX_OK)
             throw std::runtime_error(std::string(who) + log.data());
         m_own = true;
+    }
+    void set_shape(std::int64_t rows, std::int64_t cols)
+    {
+        m_rows = rows;
+        m_cols = cols;
     }
 
 public:
@@ -173,7 +180,10 @@ public:
                 p[k] = dev;
             }
         }
-        detail::check(lbfgsx_objective_bind(c, m_h, p, m_c, &id));
+        if (m_rows || m_cols)
+            detail::check(lbfgsx_objective_bind_grid(c, m_h, m_rows, m_cols, p, m_c, &id));
+        else
+            detail::check(lbfgsx_objective_bind(c, m_h, p, m_c, &id));
     }
 };
 
@@ -191,13 +201,37 @@ public:
     explicit ChainObjective(const lbfgsx_objective* compiled) : TermObjective<Scalar>(compiled) {}
 };
 
+// An objective on a row-major rows x cols grid, x of rows*cols elements: f(x) = the sum over the (rows-1)(cols-1) cells of
+// phi(x[r,c], x[r,c+1], x[r+1,c], x[r+1,c+1]; r, c) (include/lbfgsx.h, "grid objectives").  The body is the text of one cell:
+// it sees T, const T x[4], T g[4], int64_t i (= row*cols + col), row, col, rows, cols, p0..p3 and c[8].
+//     GridObjective<double> f(rows, cols, "const T a = x[1] - x[0]; const T b = x[2] - x[0]; g[1] = a; g[2] = b; g[3] = T(0);"
+//                                         "g[0] = -a - b; return T(0.5) * (a * a + b * b);");
+// data, scalars and binding are a TermObjective's.  Accepted by LBFGSSolver::minimize and LBFGSBSolver::minimize wherever a
+// ChainObjective is, refused where it is; x.size() != rows*cols throws std::invalid_argument.
+template <typename Scalar>
+class GridObjective : public TermObjective<Scalar>
+{
+public:
+    GridObjective(std::int64_t rows, std::int64_t cols, const std::string& body)
+        : TermObjective<Scalar>(LBFGSX_FORM_GRID, 4, body, "GridObjective: ")
+    {
+        this->set_shape(rows, cols);
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile_grid); it stays the caller's
+    GridObjective(const lbfgsx_objective* compiled, std::int64_t rows, std::int64_t cols) : TermObjective<Scalar>(compiled)
+    {
+        this->set_shape(rows, cols);
+    }
+};
+
 namespace detail {
-// the objectives compiled at run time into the fused kernels: a TermObjective or a ChainObjective
+// the objectives compiled at run time into the fused kernels: a TermObjective, a ChainObjective or a GridObjective
 template <typename Scalar, typename Foo>
 struct is_compiled_objective
 {
     typedef typename std::decay<Foo>::type F;
-    static constexpr bool value = std::is_same<F, TermObjective<Scalar> >::value || std::is_same<F, ChainObjective<Scalar> >::value;
+    static constexpr bool value = std::is_same<F, TermObjective<Scalar> >::value || std::is_same<F, ChainObjective<Scalar> >::value ||
+                                  std::is_same<F, GridObjective<Scalar> >::value;
 };
 }  // namespace detail
 
@@ -248,7 +282,7 @@ namespace detail {
 
 // Uniform view of the four kinds of objective `Foo` the solvers accept:
 //   BuiltinObjective<Scalar>                              -> fused device kernels
-//   TermObjective<Scalar>, ChainObjective<Scalar>         -> the same kernels, compiled at run time for the caller's term
+//   TermObjective<Scalar>, ChainObjective<Scalar>, GridObjective<Scalar> -> the same kernels, compiled at run time
 //   Scalar f(const DeviceVector<Scalar>& x, DeviceVector<Scalar>& grad)   -> user device functor
 //   Scalar f(const Vec& x, Vec& grad) with host vectors   -> staged through host memory (compatibility)
 template <typename Scalar, typename Foo, typename HostVec>

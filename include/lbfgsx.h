@@ -199,10 +199,41 @@ int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4]);
  * lbfgsx_solver_minimize_obj and the four evaluation entry points take it like a term objective's.  Binding to a context
  * with n < K is refused (any n >= K is accepted: n need not be a multiple of anything).  The compile log, the refusal of
  * asm and the line numbers are those of lbfgsx_objective_compile. */
-enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1 };
+enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2 };
 int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len);
 long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char* out, size_t len);
 int lbfgsx_objective_form(const lbfgsx_objective* obj);
+/* ---- grid objectives: 2x2-cell terms on a row-major grid ----------------------------------------------------------------
+ * x is a row-major rows x cols array, n = rows*cols, rows >= 2, cols >= 2, and
+ *     f(x) = sum over cells (r, c), 0 <= r < rows-1, 0 <= c < cols-1, of phi(x[r,c], x[r,c+1], x[r+1,c], x[r+1,c+1]; r, c)
+ * -- the MINPACK-2 energies (a cell covers both triangles of their discretisation), smoothness terms of image problems,
+ * membrane and Allen-Cahn energies.  `body` is the text of ONE CELL: it sees T, const T x[4] in the order above, T g[4] (the
+ * cell's four partial derivatives, to fill), int64_t i (the flat index of x[0], row*cols + col), int64_t row, col, rows, cols,
+ * p0..p3 and c[8], and returns the cell's value.  It may read p0[i], p0[i+1], p0[i+cols] and p0[i+cols+1]: a cell that does
+ * not exist is never evaluated.  A per-node term (a data-fidelity term, say) is written inside the body: node (row, col)
+ * goes to the cell that starts there, and the cells of the last row and column of cells pick up the nodes nobody starts at,
+ *     T v = ...cell...;  v += node(x[0], i);                      if (col + 2 == cols) v += node(x[1], i + 1);
+ *     if (row + 2 == rows) { v += node(x[2], i + cols);           if (col + 2 == cols) v += node(x[3], i + cols + 1); }
+ * with the matching additions to g[0..3].
+ * Semantics (a numpy restatement with one operation per source operation is bit-exact):
+ *   grad[r,c] = g[3] of cell (r-1, c-1) + g[2] of cell (r-1, c) + g[1] of cell (r, c-1) + g[0] of cell (r, c): the cells that
+ *               exist, in this order (ascending flat index of the cell's origin), started from the first (no leading 0 +);
+ *   f         = the order-independent (compensated) sum of the cells' values, each added once, by the thread that owns the
+ *               cell's origin;
+ *   one rounding per source operation, no contraction.
+ * lbfgsx_objective_compile_grid wraps the body for the four kernels of csrc/grid_kernels.cuh -- the counterparts of k_eval,
+ * k_trial, k_b_eval and k_b_dg_maxstep_trial with the same arguments, grids and reductions; the rows above and below a
+ * thread's pack are re-read through the caches -- and caches by (form, body, K, dtype) with K = 4 (lbfgsx_objective_K).  The
+ * handle's form is LBFGSX_FORM_GRID.  lbfgsx_objective_bind_grid binds it with the grid's shape; it refuses (LBFGSX_E_INVALID,
+ * the values named) a handle of another form, rows < 2, cols < 2 and rows*cols != n.  lbfgsx_objective_bind refuses a grid
+ * handle.  lbfgsx_objective_shape reads the bound shape back.  lbfgsx_objective_info, lbfgsx_objective_upload and the four
+ * evaluation entry points take it like a term objective's; the compile log, the refusal of asm and the line numbers are
+ * those of lbfgsx_objective_compile. */
+int lbfgsx_objective_compile_grid(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len);
+long long lbfgsx_objective_source_grid(int dtype, const char* body, char* out, size_t len);
+int lbfgsx_objective_bind_grid(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
+                               const double cs[8], int* id);
+int lbfgsx_objective_shape(const lbfgsx_ctx* c, int64_t* rows, int64_t* cols);
 /* Every entry point of this ABI makes the context's device current for its own duration and restores the caller's
  * afterwards.  Code that launches its OWN kernels on the context's vectors (a device functor, lbfgsx_vec) must run with
  * that device current too: lbfgsx_device tells which one it is, lbfgsx_device_push makes it current for the calling

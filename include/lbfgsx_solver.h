@@ -131,6 +131,12 @@ int lbfgsx_solver_minimize_fn(lbfgsx_solver* s, int64_t n, lbfgsx_objective_fn f
 int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, const void* const p[4], int host_mask,
                                const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
                                lbfgsx_result* out);
+/* lbfgsx_solver_minimize_obj for a grid objective (include/lbfgsx.h, lbfgsx_objective_compile_grid): x is a row-major
+ * rows x cols array, n = rows*cols.  rows < 2, cols < 2 and a handle of another form are refused with LBFGSX_E_INVALID;
+ * lbfgsx_solver_minimize_obj refuses a grid handle (it carries no shape). */
+int lbfgsx_solver_minimize_grid(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
+                                int host_mask, const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
+                                lbfgsx_result* out);
 
 /* ---- batched mode (BASELINE.json cfg5): many independent minimisations on one GPU ------------------------
  * Problem `id` is the extended Rosenbrock (or diag quadratic) instance generated on the device from seed

@@ -199,6 +199,13 @@ def load():
     sig(core, "lbfgsx_objective_bound", i32, vp, C.POINTER(vp * 4))
     sig(sol, "lbfgsx_solver_minimize_obj", i32, vp, vp, i64, C.POINTER(vp * 4), i32, C.POINTER(dbl * 8), vp, vp, vp,
         C.POINTER(Trace), C.POINTER(Result))
+    # grid objectives: the shape travels with the binding
+    sig(core, "lbfgsx_objective_compile_grid", i32, C.POINTER(vp), i32, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_source_grid", C.c_longlong, i32, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_bind_grid", i32, vp, vp, i64, i64, C.POINTER(vp * 4), C.POINTER(dbl * 8), C.POINTER(i32))
+    sig(core, "lbfgsx_objective_shape", i32, vp, C.POINTER(i64), C.POINTER(i64))
+    sig(sol, "lbfgsx_solver_minimize_grid", i32, vp, vp, i64, i64, C.POINTER(vp * 4), i32, C.POINTER(dbl * 8), vp, vp, vp,
+        C.POINTER(Trace), C.POINTER(Result))
     _core, _solver = core, sol
     return core, sol
 

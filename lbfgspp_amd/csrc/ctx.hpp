@@ -249,6 +249,8 @@ struct lbfgsx_ctx
     const void* term_p[4] = {nullptr, nullptr, nullptr, nullptr};
     double term_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int term_np = 0;  // data arrays bound (byte model)
+    int term_form = 0;  // the bound handle's form (LBFGSX_FORM_*): which argument struct its kernels take (launch_args.hpp)
+    int64_t term_rows = 0, term_cols = 0;  // a grid objective's shape (lbfgsx_objective_bind_grid)
     void* term_own[4] = {nullptr, nullptr, nullptr, nullptr};
 
     // L-BFGS-B work set (allocated with LBFGSX_FLAG_BOUNDED) lives in lbfgsb part

@@ -8,10 +8,12 @@
 // same kernel text, the same flags, the same sums.  The code object is loaded per device with hipModuleLoadData and the
 // kernels are launched with hipModuleLaunchKernel from the arguments launch_args.hpp works out for both forms.
 //
-// Two forms of objective share all of this (include/lbfgsx.h): a TERM objective (terms that do not overlap: the struct with
-// pack / tail / finish above) and a CHAIN objective (one term starting at every coordinate: a second generated wrapper that
-// includes chain_kernels.cuh and instantiates its four kernels, which take the arguments of the four above).  A handle
-// carries its form; the four slots of the loaded-kernel table and everything that launches them are the same.
+// Three forms of objective share all of this (include/lbfgsx.h): a TERM objective (terms that do not overlap: the struct with
+// pack / tail / finish above), a CHAIN objective (one term starting at every coordinate: a second generated wrapper that
+// includes chain_kernels.cuh and instantiates its four kernels, which take the arguments of the four above) and a GRID
+// objective (one term per 2x2 cell of a row-major grid: a third wrapper around grid_kernels.cuh, whose struct also carries
+// the grid's shape).  A handle carries its form; the four slots of the loaded-kernel table and everything that launches
+// them are the same.
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
 
@@ -29,11 +31,12 @@
 
 namespace {
 
-const char* const kKernelNames[2][lbfgsx::JIT_NKERNELS] = {
+const char* const kKernelNames[3][lbfgsx::JIT_NKERNELS] = {
     {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial"},
-    {"k_chain_eval", "k_chain_trial", "k_chain_b_eval", "k_chain_b_dg_maxstep_trial"}};
-const char* const kObjStruct[2] = {"ObjTerm", "ObjChain"};
-const char* const kFormName[2] = {"term objective", "chain objective"};
+    {"k_chain_eval", "k_chain_trial", "k_chain_b_eval", "k_chain_b_dg_maxstep_trial"},
+    {"k_grid_eval", "k_grid_trial", "k_grid_b_eval", "k_grid_b_dg_maxstep_trial"}};
+const char* const kObjStruct[3] = {"ObjTerm", "ObjChain", "ObjGrid"};
+const char* const kFormName[3] = {"term objective", "chain objective", "grid objective"};
 
 // ---- hipRTC, loaded on first use (a process that never compiles an objective does not need it)
 struct Rtc
@@ -106,11 +109,14 @@ std::string kernel_dir()
 
 // ---- the generated translation unit
 std::string generate_chain(int dtype, int K, const char* body);
+std::string generate_grid(int dtype, const char* body);
 
 std::string generate(int form, int dtype, int K, const char* body)
 {
     if (form == LBFGSX_FORM_CHAIN)
         return generate_chain(dtype, K, body);
+    if (form == LBFGSX_FORM_GRID)
+        return generate_grid(dtype, body);
     std::string s;
     s += "// generated by lbfgsx_objective_compile: one term objective for the fused kernels\n";
     s += "#include \"lbfgs_kernels.cuh\"\n";
@@ -192,8 +198,54 @@ std::string generate_chain(int dtype, int K, const char* body)
     return s;
 }
 
+// the wrapper of a grid objective: the struct grid_kernels.cuh asks for (the shape and term), and its four kernels.  The
+// leading members are TermArgs' (launch_args.hpp: GridArgs)
+std::string generate_grid(int dtype, const char* body)
+{
+    std::string s;
+    s += "// generated by lbfgsx_objective_compile_grid: one grid objective for the fused kernels\n";
+    s += "#include \"grid_kernels.cuh\"\n";
+    s += "namespace lbfgsx {\n";
+    s += std::string("typedef ") + (dtype == LBFGSX_F64 ? "double" : "float") + " term_scalar_t;\n";
+    s += "struct ObjGrid\n{\n";
+    s += "    typedef term_scalar_t T;\n";
+    s += "    static constexpr int K = 4;\n";
+    s += "    const T* p0;\n    const T* p1;\n    const T* p2;\n    const T* p3;\n    T c[8];\n";
+    s += "    int64_t rows, cols;\n";
+    s += "    // the cell whose origin is node (row, col), flat index i = row*cols + col: x = {x[row,col], x[row,col+1], x[row+1,col],\n";
+    s += "    // x[row+1,col+1]} in, its four partial derivatives g out, its value returned\n";
+    s += "    __device__ __forceinline__ T term(const T (&x)[4], T (&g)[4], int64_t i, int64_t row, int64_t col) const\n    {\n";
+    s += "#line 1 \"objective_body\"\n";
+    s += body;
+    s += "\n#line 1 \"objective_wrapper\"\n";
+    s += "    }\n";
+    s += "};\n";
+    s += "typedef term_scalar_t S;\n";
+    s += "template __global__ void k_grid_eval<S, ObjGrid>(const S*, S*, int64_t, ObjGrid, RedWs, S*);\n";
+    s += "template __global__ void k_grid_trial<S, ObjGrid>(const S*, const S*, S, S*, S*, int64_t, ObjGrid, RedWs, S*, int);\n";
+    s += "template __global__ void k_grid_b_eval<S, ObjGrid>(const S*, S*, const S*, const S*, int64_t, ObjGrid, RedWs, S*);\n";
+    s += "template __global__ void k_grid_b_dg_maxstep_trial<S, ObjGrid>(const S*, const S*, const S*, const S*, const S*, S, S*, "
+         "S*, int64_t, ObjGrid, RedWs, S*, int);\n";
+    s += "}  // namespace lbfgsx\n";
+    return s;
+}
+
 bool valid_request(int form, int dtype, int K, const char* body, std::string& why)
 {
+    if (form == LBFGSX_FORM_GRID)
+    {
+        if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
+            why = "grid objective: unknown dtype";
+        else if (K != 4)
+            why = "grid objective: a cell reads K = 4 coordinates";
+        else if (!body || !*body)
+            why = "grid objective: empty body";
+        else if (std::strstr(body, "asm"))
+            why = "grid objective: the body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
+        else
+            return true;
+        return false;
+    }
     if (form == LBFGSX_FORM_CHAIN)
     {
         if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
@@ -525,6 +577,10 @@ long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char
 {
     return objective_source(LBFGSX_FORM_CHAIN, dtype, K, body, out, len);
 }
+long long lbfgsx_objective_source_grid(int dtype, const char* body, char* out, size_t len)
+{
+    return objective_source(LBFGSX_FORM_GRID, dtype, 4, body, out, len);
+}
 
 int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
 {
@@ -533,6 +589,10 @@ int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const cha
 int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
 {
     return objective_compile(LBFGSX_FORM_CHAIN, out, dtype, K, body, log, log_len);
+}
+int lbfgsx_objective_compile_grid(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_GRID, out, dtype, 4, body, log, log_len);
 }
 
 void lbfgsx_objective_destroy(lbfgsx_objective* obj) { delete obj; }
@@ -575,16 +635,22 @@ int lbfgsx_objective_upload(lbfgsx_ctx* c, int slot, const void* host, void** de
     return LBFGSX_OK;
 }
 
-int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void* const p[4], const double cs[8], int* id)
+}  // extern "C"
+
+namespace {
+
+// lbfgsx_objective_bind and lbfgsx_objective_bind_grid: rows = cols = 0 for a handle without a shape
+int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
+                   const double cs[8], int* id)
 {
-    if (!c)
-        return LBFGSX_E_INVALID;
     c->st_valid = false;
     c->spec_valid = false;
     if (!obj)
     {
         c->term = nullptr;
         c->term_np = 0;
+        c->term_form = LBFGSX_FORM_TERM;
+        c->term_rows = c->term_cols = 0;
         if (id)
             *id = LBFGSX_OBJ_NONE;
         return LBFGSX_OK;
@@ -604,7 +670,7 @@ int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void
             return LBFGSX_E_INVALID;
         }
     }
-    else if (c->n % code->K != 0)
+    else if (code->form == LBFGSX_FORM_TERM && c->n % code->K != 0)
     {
         lbfgsx::set_error("term objective: n = " + std::to_string(c->n) + " is not a multiple of K = " + std::to_string(code->K));
         return LBFGSX_E_INVALID;
@@ -625,6 +691,9 @@ int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void
             c->term_fn[k] = it->second.fn[k];
     }
     c->term = &code->self;
+    c->term_form = code->form;
+    c->term_rows = rows;
+    c->term_cols = cols;
     c->term_np = 0;
     for (int j = 0; j < 4; j++)
     {
@@ -635,6 +704,62 @@ int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void
         c->term_c[j] = cs ? cs[j] : 0.0;
     if (id)
         *id = LBFGSX_OBJ_BOUND;
+    return LBFGSX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void* const p[4], const double cs[8], int* id)
+{
+    if (!c)
+        return LBFGSX_E_INVALID;
+    if (obj && obj->code->form == LBFGSX_FORM_GRID)
+    {
+        lbfgsx::set_error("a grid objective is bound with its shape: lbfgsx_objective_bind_grid");
+        return LBFGSX_E_INVALID;
+    }
+    return objective_bind(c, obj, 0, 0, p, cs, id);
+}
+
+int lbfgsx_objective_bind_grid(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
+                               const double cs[8], int* id)
+{
+    if (!c || !obj)
+        return LBFGSX_E_INVALID;
+    if (obj->code->form != LBFGSX_FORM_GRID)
+    {
+        lbfgsx::set_error(std::string("lbfgsx_objective_bind_grid: the handle is a ") + kFormName[obj->code->form] +
+                          ", not a grid objective (lbfgsx_objective_compile_grid)");
+        return LBFGSX_E_INVALID;
+    }
+    const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
+    long long prod = 0;
+    if (rows < 2 || cols < 2)
+    {
+        lbfgsx::set_error("grid objective: " + shape + ": a grid has at least 2 rows and 2 columns (rows >= 2, cols >= 2)");
+        return LBFGSX_E_INVALID;
+    }
+    if (__builtin_mul_overflow((long long) rows, (long long) cols, &prod) || prod != (long long) c->n)
+    {
+        lbfgsx::set_error("grid objective: " + shape + " does not multiply to n = " + std::to_string(c->n));
+        return LBFGSX_E_INVALID;
+    }
+    return objective_bind(c, obj, rows, cols, p, cs, id);
+}
+
+int lbfgsx_objective_shape(const lbfgsx_ctx* c, int64_t* rows, int64_t* cols)
+{
+    if (!c || !c->term || c->term_form != LBFGSX_FORM_GRID)
+    {
+        lbfgsx::set_error("lbfgsx_objective_shape: no grid objective is bound to this context");
+        return LBFGSX_E_INVALID;
+    }
+    if (rows)
+        *rows = c->term_rows;
+    if (cols)
+        *cols = c->term_cols;
     return LBFGSX_OK;
 }
 

@@ -109,6 +109,26 @@ inline TermArgs<T> term_args(const lbfgsx_ctx* c)
         a.c[j] = T(c->term_c[j]);
     return a;
 }
+// the by-value argument of a grid objective's kernels: layout of the generated struct ObjGrid (TermArgs, then the shape)
+template <class T>
+struct GridArgs
+{
+    TermArgs<T> t;
+    int64_t rows, cols;
+};
+// the objective argument of the bound handle's kernels, by its form: &term for a term or chain objective, &grid for a grid one
+template <class T>
+struct BoundArgs
+{
+    TermArgs<T> term;
+    GridArgs<T> grid;
+    void* ptr;
+    explicit BoundArgs(const lbfgsx_ctx* c) : term(term_args<T>(c)), grid{term, c->term_rows, c->term_cols}
+    {
+        ptr = (c->term_form == LBFGSX_FORM_GRID) ? static_cast<void*>(&grid) : static_cast<void*>(&term);
+    }
+    BoundArgs(const BoundArgs&) = delete;
+};
 inline bool term_bound(const lbfgsx_ctx* c, int objective) { return objective == LBFGSX_OBJ_BOUND && c->term != nullptr; }
 // one launch of loaded kernel `which` of the bound objective on the context's stream, block of kBlock threads; params as
 // hipModuleLaunchKernel takes them (one pointer per kernel argument)

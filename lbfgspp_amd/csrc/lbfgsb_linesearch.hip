@@ -28,8 +28,8 @@ template <class T>
 static int b_eval_term_t(lbfgsx_ctx* c, double* r3)
 {
     BEvalLaunch<T> a = b_eval_launch<T>(c);
-    TermArgs<T> obj = term_args<T>(c);
-    void* params[] = {&a.x, &a.g, &a.lb, &a.ub, &a.n, &obj, &a.ws, &a.out};
+    BoundArgs<T> obj(c);
+    void* params[] = {&a.x, &a.g, &a.lb, &a.ub, &a.n, obj.ptr, &a.ws, &a.out};
     const int rc = jit_launch(c, JIT_K_B_EVAL, a.grid, params);
     if (rc)
         return rc;
@@ -48,8 +48,8 @@ template <class T>
 static int dg_maxstep_trial_term_t(lbfgsx_ctx* c, T step, double* r4)
 {
     DgTrialLaunch<T> a = dg_maxstep_trial_launch<T>(c, step, c->term_np);
-    TermArgs<T> obj = term_args<T>(c);
-    void* params[] = {&a.xp, &a.g0, &a.d, &a.lb, &a.ub, &a.step, &a.x, &a.g, &a.n, &obj, &a.ws, &a.out, &a.rev};
+    BoundArgs<T> obj(c);
+    void* params[] = {&a.xp, &a.g0, &a.d, &a.lb, &a.ub, &a.step, &a.x, &a.g, &a.n, obj.ptr, &a.ws, &a.out, &a.rev};
     const int rc = jit_launch(c, JIT_K_B_DG_MAXSTEP_TRIAL, a.grid, params);
     if (rc)
         return rc;

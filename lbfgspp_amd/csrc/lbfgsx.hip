@@ -975,8 +975,8 @@ template <class T>
 static int eval_term_t(lbfgsx_ctx* c, double* out3)
 {
     lbfgsx::EvalLaunch<T> a = lbfgsx::eval_launch<T>(c);
-    lbfgsx::TermArgs<T> obj = lbfgsx::term_args<T>(c);
-    void* params[] = {&a.x, &a.g, &a.n, &obj, &a.ws, &a.out};
+    lbfgsx::BoundArgs<T> obj(c);
+    void* params[] = {&a.x, &a.g, &a.n, obj.ptr, &a.ws, &a.out};
     const int rc = lbfgsx::jit_launch(c, lbfgsx::JIT_K_EVAL, a.grid, params);
     if (rc)
         return rc;
@@ -1055,8 +1055,8 @@ template <class T>
 static int trial_term_t(lbfgsx_ctx* c, T step, double* out2)
 {
     lbfgsx::TrialLaunch<T> a = lbfgsx::trial_launch<T>(c, step, c->term_np);
-    lbfgsx::TermArgs<T> obj = lbfgsx::term_args<T>(c);
-    void* params[] = {&a.xp, &a.d, &a.step, &a.x, &a.g, &a.n, &obj, &a.ws, &a.out, &a.rev};
+    lbfgsx::BoundArgs<T> obj(c);
+    void* params[] = {&a.xp, &a.d, &a.step, &a.x, &a.g, &a.n, obj.ptr, &a.ws, &a.out, &a.rev};
     const int rc = lbfgsx::jit_launch(c, lbfgsx::JIT_K_TRIAL, a.grid, params);
     if (rc)
         return rc;

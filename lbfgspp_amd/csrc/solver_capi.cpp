@@ -34,8 +34,10 @@ struct lbfgsx_solver
                           const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) = 0;
     virtual void minimize_fn(int64_t n, lbfgsx_objective_fn fn, void* user, void* x, const void* lb, const void* ub,
                              lbfgsx_trace* tr, lbfgsx_result* out) = 0;
-    virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, const void* const p[4], int host_mask, const double c[8],
-                              void* x, const void* lb, const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) = 0;
+    // rows, cols: the shape of a grid objective, 0 for the other forms
+    virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const void* const p[4],
+                              int host_mask, const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* tr,
+                              lbfgsx_result* out) = 0;
 };
 
 namespace {
@@ -201,10 +203,11 @@ struct LbfgsImpl : lbfgsx_solver
             throw;
         }
     }
-    void minimize_obj(const lbfgsx_objective* obj, int64_t n, const void* const p[4], int host_mask, const double c[8], void* x,
-                      const void*, const void*, lbfgsx_trace* tr, lbfgsx_result* out) override
+    void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const void* const p[4], int host_mask,
+                      const double c[8], void* x, const void*, const void*, lbfgsx_trace* tr, lbfgsx_result* out) override
     {
-        TermObjective<Scalar> f(obj);
+        GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
+        TermObjective<Scalar>& f = shaped;
         fill_term<Scalar>(f, p, host_mask, c);
         run(f, n, x, tr, out);
     }
@@ -308,10 +311,11 @@ struct LbfgsbImpl : lbfgsx_solver
             throw;
         }
     }
-    void minimize_obj(const lbfgsx_objective* obj, int64_t n, const void* const p[4], int host_mask, const double c[8], void* x,
-                      const void* lb, const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) override
+    void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const void* const p[4], int host_mask,
+                      const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) override
     {
-        TermObjective<Scalar> f(obj);
+        GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
+        TermObjective<Scalar>& f = shaped;
         fill_term<Scalar>(f, p, host_mask, c);
         run(f, n, x, lb, ub, tr, out);
     }
@@ -890,6 +894,8 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
         if (lbfgsx_objective_dtype(obj) != s->dtype)
             throw std::invalid_argument("lbfgsx_solver_minimize_obj: the objective was compiled for the other dtype");
         const int K = lbfgsx_objective_K(obj);
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID)
+            throw std::invalid_argument("a grid objective is minimised with its shape: lbfgsx_solver_minimize_grid");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_CHAIN)
         {
             if (n < K)
@@ -907,6 +913,36 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
         std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_obj: no HIP device available (this library has no CPU fallback)");
         return out->status;
     }
-    return guarded(out, [&]() { s->minimize_obj(obj, n, p, host_mask, c, x, lb, ub, trace, out); });
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, p, host_mask, c, x, lb, ub, trace, out); });
+}
+
+int lbfgsx_solver_minimize_grid(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
+                                int host_mask, const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
+                                lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    long long n = 0;
+    const int bad = guarded(out, [&]() {
+        if (!s || !obj)
+            throw std::invalid_argument("lbfgsx_solver_minimize_grid: invalid argument");
+        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_GRID)
+            throw std::invalid_argument("lbfgsx_solver_minimize_grid: the handle is not a grid objective (lbfgsx_objective_compile_grid)");
+        if (lbfgsx_objective_dtype(obj) != s->dtype)
+            throw std::invalid_argument("lbfgsx_solver_minimize_grid: the objective was compiled for the other dtype");
+        const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
+        if (rows < 2 || cols < 2)
+            throw std::invalid_argument("grid objective: " + shape + ": a grid has at least 2 rows and 2 columns (rows >= 2, cols >= 2)");
+        if (__builtin_mul_overflow((long long) rows, (long long) cols, &n))
+            throw std::invalid_argument("grid objective: " + shape + ": rows*cols overflows");
+    });
+    if (bad)
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_grid: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    return guarded(out, [&]() { s->minimize_obj(obj, int64_t(n), rows, cols, p, host_mask, c, x, lb, ub, trace, out); });
 }
 }

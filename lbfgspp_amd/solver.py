@@ -7,7 +7,7 @@ Names, argument meaning and error behaviour follow yixuan/LBFGSpp:
 Exceptions: std::invalid_argument -> ValueError, std::logic_error -> ArithmeticError,
 std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device objective
 (`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`), the caller's own term compiled into the same kernels (`TermObjective(body)`,
-or `ChainObjective(body)` for terms that overlap)
+`ChainObjective(body)` for terms that overlap, or `GridObjective(body, shape)` for 2x2-cell terms on a grid)
 or the caller's own callable, `DeviceObjective(fn)`: fn(x, grad) -> float on torch
 tensors that alias the library's device vectors.  All O(n) work of the solver runs in the HIP library, Python only passes
 pointers.  There is no CPU fallback: without the built extension or a GPU these calls raise.
@@ -144,10 +144,10 @@ class TermObjective:
         core, _ = L.load()
         dt = L.F64 if np.dtype(dtype) == np.float64 else L.F32
         source = getattr(core, self._SOURCE)
-        need = source(dt, self.K, self.body.encode(), None, 0)
+        need = source(dt, *self._form_args(), self.body.encode(), None, 0)
         L.check(min(need, 0))
         buf = C.create_string_buffer(int(need))
-        source(dt, self.K, self.body.encode(), buf, need)
+        source(dt, *self._form_args(), self.body.encode(), buf, need)
         return buf.value.decode()
 
     def compile(self, dtype=np.float64):
@@ -157,7 +157,7 @@ class TermObjective:
         if dt not in self._h:
             h = C.c_void_p()
             log = C.create_string_buffer(1 << 16)
-            rc = getattr(core, self._COMPILE)(C.byref(h), dt, self.K, self.body.encode(), log, len(log))
+            rc = getattr(core, self._COMPILE)(C.byref(h), dt, *self._form_args(), self.body.encode(), log, len(log))
             if rc == L.E_INVALID:
                 raise ValueError("%s: the body does not compile\n" % self._NAME + log.value.decode(errors="replace"))
             L.check(rc, log.value.decode(errors="replace"))
@@ -171,6 +171,10 @@ class TermObjective:
         L.check(core.lbfgsx_objective_info(self.compile(dtype), C.byref(arr)))
         return {"vgprs": arr[0], "scratch_bytes": arr[1], "cache_hit": bool(arr[2]), "compile_ms": arr[3],
                 "scratch_by_kernel": dict(zip(("k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial"), list(arr)[4:8]))}
+
+    def _form_args(self):
+        """what the form's compile and source entry points take between dtype and body"""
+        return (self.K,)
 
     def _check_n(self, n):
         if n % self.K:
@@ -207,6 +211,57 @@ class ChainObjective(TermObjective):
     def _check_n(self, n):
         if n < self.K:
             raise ValueError("ChainObjective: n = %d is less than K = %d: there is no term" % (n, self.K))
+
+
+class GridObjective(TermObjective):
+    """An objective on a 2-D grid: x is a row-major rows x cols array (flattened, n = rows*cols, rows >= 2, cols >= 2) and
+    f(x) = sum over the (rows-1)(cols-1) cells of phi(x[r,c], x[r,c+1], x[r+1,c], x[r+1,c+1]; r, c) -- the MINPACK-2 energies
+    (a cell covers both triangles of their discretisation), smoothness terms of image problems, membrane and Allen-Cahn
+    energies (include/lbfgsx.h, "grid objectives").  The body is the text of ONE CELL: it sees T, const T x[4] in the order
+    above, T g[4] (the cell's four partial derivatives, to fill), int64_t i (the flat index of x[0], row*cols + col),
+    int64_t row, col, rows, cols, p0..p3 and c[8], may read p0[i], p0[i+1], p0[i+cols] and p0[i+cols+1], and returns the
+    cell's value.  grad[r,c] is g[3] of cell (r-1,c-1) + g[2] of cell (r-1,c) + g[1] of cell (r,c-1) + g[0] of cell (r,c),
+    those that exist, in this order.
+
+        membrane = GridObjective("const T a = x[1] - x[0]; const T b = x[2] - x[0];"
+                                 "g[0] = T(0) - a - b; g[1] = a; g[2] = b; g[3] = T(0);"
+                                 "return T(0.5) * (a * a + b * b);", shape=(rows, cols))
+
+    A per-node term is written inside the body: node (row, col) goes to the cell that starts there, and the cells of the last
+    row and column of cells pick up the nodes no cell starts at (row + 2 == rows, col + 2 == cols).  A denoiser with data p0
+    and fidelity weight c[0] appends this to the membrane body in place of its return:
+
+        T v = T(0.5) * (a * a + b * b);
+        const bool lastc = col + 2 == cols, lastr = row + 2 == rows;
+        const T r0 = x[0] - p0[i];
+        g[0] = g[0] + c[0] * r0;  v = v + T(0.5) * (c[0] * (r0 * r0));
+        if (lastc) { const T r1 = x[1] - p0[i + 1];  g[1] = g[1] + c[0] * r1;  v = v + T(0.5) * (c[0] * (r1 * r1)); }
+        if (lastr) { const T r2 = x[2] - p0[i + cols];  g[2] = g[2] + c[0] * r2;  v = v + T(0.5) * (c[0] * (r2 * r2)); }
+        if (lastr && lastc) { const T r3 = x[3] - p0[i + cols + 1];  g[3] = g[3] + c[0] * r3;  v = v + T(0.5) * (c[0] * (r3 * r3)); }
+        return v;
+
+    data, scalars, set_data, set_scalars, source, compile and info as for a TermObjective (scratch_by_kernel names the four
+    kernels by their counterparts); usable wherever a ChainObjective is, refused where one is.  minimize raises ValueError
+    when rows*cols != len(x)."""
+    _NAME = "GridObjective"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_grid", "lbfgsx_objective_source_grid"
+
+    def __init__(self, body, shape, data=(), scalars=()):
+        rows, cols = (int(v) for v in shape)
+        if rows < 2 or cols < 2:
+            raise ValueError("GridObjective: shape = (%d, %d): a grid has at least 2 rows and 2 columns" % (rows, cols))
+        self.shape = (rows, cols)
+        self.body, self.K = str(body), 4
+        self._h = {}
+        self.set_data(*data)
+        self.set_scalars(*scalars)
+
+    def _form_args(self):
+        return ()
+
+    def _check_n(self, n):
+        if self.shape[0] * self.shape[1] != n:
+            raise ValueError("GridObjective: shape = (%d, %d) does not multiply to n = %d" % (self.shape + (n,)))
 
 
 def _is_torch(x):
@@ -392,8 +447,12 @@ class _SolverBase:
         res = L.Result()
         if any(_is_torch(d) for d in f.data):
             torch.cuda.current_stream().synchronize()  # the data arrays are complete when the library reads them
-        rc = self._sol.lbfgsx_solver_minimize_obj(self._h, h, n, C.byref(ptrs), mask, C.byref(cs), self._ptr(x), self._ptr(lb),
-                                                  self._ptr(ub), C.byref(trace.c) if trace else None, C.byref(res))
+        tail = (C.byref(ptrs), mask, C.byref(cs), self._ptr(x), self._ptr(lb), self._ptr(ub), C.byref(trace.c) if trace else None,
+                C.byref(res))
+        if isinstance(f, GridObjective):
+            rc = self._sol.lbfgsx_solver_minimize_grid(self._h, h, f.shape[0], f.shape[1], *tail)
+        else:
+            rc = self._sol.lbfgsx_solver_minimize_obj(self._h, h, n, *tail)
         del keep
         self.last = Result(res)
         L.check(rc, self.last.msg)
@@ -411,8 +470,8 @@ class _SolverBase:
         if isinstance(f, TermObjective):
             return self._minimize_obj(f, n, x, lb, ub, trace)
         if not hasattr(f, "objective"):
-            raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body) or "
-                            "DeviceObjective(fn)")
+            raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body), "
+                            "GridObjective(body, shape) or DeviceObjective(fn)")
         res = L.Result()
         a = None if f.a is None else np.ascontiguousarray(f.a, _NP[self.dtype])
         b = None if f.b is None else np.ascontiguousarray(f.b, _NP[self.dtype])
