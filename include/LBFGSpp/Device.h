@@ -104,6 +104,10 @@ class TermObjective
     const Scalar* m_host[4] = {nullptr, nullptr, nullptr, nullptr};
     double m_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::int64_t m_rows = 0, m_cols = 0;  // a GridObjective's shape; 0: the handle is bound without one
+    std::int64_t m_E = 0;                 // a GraphObjective's edges; 0: the handle is bound without any
+    const std::int32_t *m_ei = nullptr, *m_ej = nullptr;
+    bool m_edges_dev = false;
+    std::int64_t m_count[4] = {0, 0, 0, 0};  // elements of m_host[k]; 0: n
 
     TermObjective(const TermObjective&) = delete;
     TermObjective& operator=(const TermObjective&) = delete;
@@ -116,11 +120,13 @@ public:
     explicit TermObjective(const lbfgsx_objective* compiled) : m_h(const_cast<lbfgsx_objective*>(compiled)) {}
 
 protected:
-    TermObjective(int form, int K, const std::string& body, const char* who)
+    // node: a GraphObjective's node body (empty: none)
+    TermObjective(int form, int K, const std::string& body, const char* who, const std::string& node = std::string())
     {
         std::vector<char> log(16384, '\0');
         const int dt = detail::dtype_of<Scalar>::value;
-        const int rc = (form == LBFGSX_FORM_GRID)    ? lbfgsx_objective_compile_grid(&m_h, dt, body.c_str(), log.data(), log.size())
+        const int rc = (form == LBFGSX_FORM_GRAPH)   ? lbfgsx_objective_compile_graph(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
+                       : (form == LBFGSX_FORM_GRID)  ? lbfgsx_objective_compile_grid(&m_h, dt, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_CHAIN) ? lbfgsx_objective_compile_chain(&m_h, dt, K, body.c_str(), log.data(), log.size())
                                                      : lbfgsx_objective_compile(&m_h, dt, K, body.c_str(), log.data(), log.size());
         if (rc == LBFGSX_E_INVALID)
@@ -133,6 +139,13 @@ protected:
     {
         m_rows = rows;
         m_cols = cols;
+    }
+    void set_edges(std::int64_t E, const std::int32_t* ei, const std::int32_t* ej, bool on_device)
+    {
+        m_E = E;
+        m_ei = ei;
+        m_ej = ej;
+        m_edges_dev = on_device;
     }
 
 public:
@@ -154,6 +167,14 @@ public:
         if (slot < 0 || slot >= 4)
             throw std::invalid_argument("TermObjective: a term objective has at most four data arrays (slots 0..3)");
         m_host[slot] = host;
+        m_count[slot] = 0;
+        return *this;
+    }
+    // a host array of `count` elements (a GraphObjective's per-edge data has E, not n)
+    TermObjective& host_data(int slot, const Scalar* host, std::int64_t count)
+    {
+        host_data(slot, host);
+        m_count[slot] = count;
         return *this;
     }
     TermObjective& scalars(std::initializer_list<double> c) { return scalars(c.begin(), int(c.size())); }
@@ -176,11 +197,16 @@ public:
             if (m_host[k])
             {
                 void* dev = nullptr;
-                detail::check(lbfgsx_objective_upload(c, k, m_host[k], &dev));
+                if (m_count[k])
+                    detail::check(lbfgsx_objective_upload_count(c, k, m_host[k], m_count[k], &dev));
+                else
+                    detail::check(lbfgsx_objective_upload(c, k, m_host[k], &dev));
                 p[k] = dev;
             }
         }
-        if (m_rows || m_cols)
+        if (m_E || m_ei || m_ej)
+            detail::check(lbfgsx_objective_bind_graph(c, m_h, m_E, m_ei, m_ej, m_edges_dev ? 1 : 0, p, m_c, &id));
+        else if (m_rows || m_cols)
             detail::check(lbfgsx_objective_bind_grid(c, m_h, m_rows, m_cols, p, m_c, &id));
         else
             detail::check(lbfgsx_objective_bind(c, m_h, p, m_c, &id));
@@ -224,14 +250,42 @@ public:
     }
 };
 
+// An objective on a graph: x has one coordinate per node and f(x) = sum over nodes v of psi(x[v]; v) + sum over the E edges
+// of phi(x[ei[e]], x[ej[e]]; e) (include/lbfgsx.h, "graph objectives").  The edge body sees T, const T x[2] (the values at
+// ei[e] and ej[e]), T g[2], int64_t e, i, j, p0..p3 and c[8]; the node body (optional) sees T, const T x[1], T g[1], int64_t i,
+// p0..p3 and c[8].
+//     GraphObjective<double> f("const T w = p0[e] * (x[0] - x[1]); g[0] = w; g[1] = T(0) - w; return T(0.5) * (w * (x[0] - x[1]));");
+//     f.edges(E, ei, ej).host_data(0, weights, E);      solver.minimize(f, x, fx);
+// edges(): int32 arrays of E elements on the host (or on the device: on_device = true) that stay valid until minimize()
+// returns; the solver's context copies and validates them at every minimize() (a self-loop or an index outside [0, n) throws
+// std::invalid_argument with the edge named).  data, scalars and binding are a TermObjective's.  Accepted by
+// LBFGSSolver::minimize and LBFGSBSolver::minimize wherever a GridObjective is, refused where it is.
+template <typename Scalar>
+class GraphObjective : public TermObjective<Scalar>
+{
+public:
+    explicit GraphObjective(const std::string& edge_body, const std::string& node_body = std::string())
+        : TermObjective<Scalar>(LBFGSX_FORM_GRAPH, 2, edge_body, "GraphObjective: ", node_body)
+    {
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile_graph); it stays the caller's
+    explicit GraphObjective(const lbfgsx_objective* compiled) : TermObjective<Scalar>(compiled) {}
+    GraphObjective& edges(std::int64_t E, const std::int32_t* ei, const std::int32_t* ej, bool on_device = false)
+    {
+        this->set_edges(E, ei, ej, on_device);
+        return *this;
+    }
+};
+
 namespace detail {
-// the objectives compiled at run time into the fused kernels: a TermObjective, a ChainObjective or a GridObjective
+// the objectives compiled at run time into the fused kernels: a TermObjective, a ChainObjective, a GridObjective or a
+// GraphObjective
 template <typename Scalar, typename Foo>
 struct is_compiled_objective
 {
     typedef typename std::decay<Foo>::type F;
     static constexpr bool value = std::is_same<F, TermObjective<Scalar> >::value || std::is_same<F, ChainObjective<Scalar> >::value ||
-                                  std::is_same<F, GridObjective<Scalar> >::value;
+                                  std::is_same<F, GridObjective<Scalar> >::value || std::is_same<F, GraphObjective<Scalar> >::value;
 };
 }  // namespace detail
 
@@ -282,7 +336,8 @@ namespace detail {
 
 // Uniform view of the four kinds of objective `Foo` the solvers accept:
 //   BuiltinObjective<Scalar>                              -> fused device kernels
-//   TermObjective<Scalar>, ChainObjective<Scalar>, GridObjective<Scalar> -> the same kernels, compiled at run time
+//   TermObjective<Scalar>, ChainObjective<Scalar>, GridObjective<Scalar>, GraphObjective<Scalar> -> the same kernels, compiled
+//                                                            at run time
 //   Scalar f(const DeviceVector<Scalar>& x, DeviceVector<Scalar>& grad)   -> user device functor
 //   Scalar f(const Vec& x, Vec& grad) with host vectors   -> staged through host memory (compatibility)
 template <typename Scalar, typename Foo, typename HostVec>

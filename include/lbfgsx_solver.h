@@ -137,6 +137,15 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
 int lbfgsx_solver_minimize_grid(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
                                 int host_mask, const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
                                 lbfgsx_result* out);
+/* lbfgsx_solver_minimize_obj for a graph objective (include/lbfgsx.h, lbfgsx_objective_compile_graph): x has n nodes, the E
+ * edges are (ei[e], ej[e]), host arrays or device arrays (edges_on_device != 0).  counts[k] is the number of elements of
+ * p[k] where host_mask says it is a host array (n or E; NULL: n for all).  A handle of another form is refused with
+ * LBFGSX_E_INVALID, as are the edge lists lbfgsx_objective_bind_graph refuses; lbfgsx_solver_minimize_obj refuses a graph
+ * handle (it carries no edges). */
+int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t E, const int32_t* ei,
+                                 const int32_t* ej, int edges_on_device, const void* const p[4], int host_mask,
+                                 const int64_t counts[4], const double c[8], void* x, const void* lb, const void* ub,
+                                 lbfgsx_trace* trace, lbfgsx_result* out);
 
 /* ---- batched mode (BASELINE.json cfg5): many independent minimisations on one GPU ------------------------
  * Problem `id` is the extended Rosenbrock (or diag quadratic) instance generated on the device from seed

@@ -252,6 +252,12 @@ struct lbfgsx_ctx
     int term_form = 0;  // the bound handle's form (LBFGSX_FORM_*): which argument struct its kernels take (launch_args.hpp)
     int64_t term_rows = 0, term_cols = 0;  // a grid objective's shape (lbfgsx_objective_bind_grid)
     void* term_own[4] = {nullptr, nullptr, nullptr, nullptr};
+    int64_t term_own_count[4] = {0, 0, 0, 0};  // elements term_own[k] holds (lbfgsx_objective_upload_count)
+    // a graph objective's incidence list (lbfgsx_objective_bind_graph, graph_topology.hip): the context's own, built from
+    // validated indices at every bind.  graph_off: uint32[n+1], graph_inc: GraphEntry[2E]
+    int64_t graph_E = 0;
+    void* graph_off = nullptr;
+    void* graph_inc = nullptr;
 
     // L-BFGS-B work set (allocated with LBFGSX_FLAG_BOUNDED) lives in lbfgsb part
     void* lb = nullptr;

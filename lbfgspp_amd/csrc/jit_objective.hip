@@ -8,11 +8,13 @@
 // same kernel text, the same flags, the same sums.  The code object is loaded per device with hipModuleLoadData and the
 // kernels are launched with hipModuleLaunchKernel from the arguments launch_args.hpp works out for both forms.
 //
-// Three forms of objective share all of this (include/lbfgsx.h): a TERM objective (terms that do not overlap: the struct with
+// Four forms of objective share all of this (include/lbfgsx.h): a TERM objective (terms that do not overlap: the struct with
 // pack / tail / finish above), a CHAIN objective (one term starting at every coordinate: a second generated wrapper that
 // includes chain_kernels.cuh and instantiates its four kernels, which take the arguments of the four above) and a GRID
 // objective (one term per 2x2 cell of a row-major grid: a third wrapper around grid_kernels.cuh, whose struct also carries
-// the grid's shape).  A handle carries its form; the four slots of the loaded-kernel table and everything that launches
+// the grid's shape), and a GRAPH objective (one term per edge of an index list and an optional one per node: a fourth
+// wrapper around graph_kernels.cuh, whose struct also carries the context's incidence list, graph_topology.hip).  A handle
+// carries its form; the four slots of the loaded-kernel table and everything that launches
 // them are the same.
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
@@ -31,12 +33,13 @@
 
 namespace {
 
-const char* const kKernelNames[3][lbfgsx::JIT_NKERNELS] = {
+const char* const kKernelNames[4][lbfgsx::JIT_NKERNELS] = {
     {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial"},
     {"k_chain_eval", "k_chain_trial", "k_chain_b_eval", "k_chain_b_dg_maxstep_trial"},
-    {"k_grid_eval", "k_grid_trial", "k_grid_b_eval", "k_grid_b_dg_maxstep_trial"}};
-const char* const kObjStruct[3] = {"ObjTerm", "ObjChain", "ObjGrid"};
-const char* const kFormName[3] = {"term objective", "chain objective", "grid objective"};
+    {"k_grid_eval", "k_grid_trial", "k_grid_b_eval", "k_grid_b_dg_maxstep_trial"},
+    {"k_graph_eval", "k_graph_trial", "k_graph_b_eval", "k_graph_b_dg_maxstep_trial"}};
+const char* const kObjStruct[4] = {"ObjTerm", "ObjChain", "ObjGrid", "ObjGraph"};
+const char* const kFormName[4] = {"term objective", "chain objective", "grid objective", "graph objective"};
 
 // ---- hipRTC, loaded on first use (a process that never compiles an objective does not need it)
 struct Rtc
@@ -110,9 +113,13 @@ std::string kernel_dir()
 // ---- the generated translation unit
 std::string generate_chain(int dtype, int K, const char* body);
 std::string generate_grid(int dtype, const char* body);
+std::string generate_graph(int dtype, const char* node, const char* body);
 
-std::string generate(int form, int dtype, int K, const char* body)
+// node: a graph objective's node body (null or empty: none); the other forms have one body
+std::string generate(int form, int dtype, int K, const char* body, const char* node)
 {
+    if (form == LBFGSX_FORM_GRAPH)
+        return generate_graph(dtype, node, body);
     if (form == LBFGSX_FORM_CHAIN)
         return generate_chain(dtype, K, body);
     if (form == LBFGSX_FORM_GRID)
@@ -230,8 +237,69 @@ std::string generate_grid(int dtype, const char* body)
     return s;
 }
 
-bool valid_request(int form, int dtype, int K, const char* body, std::string& why)
+// the wrapper of a graph objective: the struct graph_kernels.cuh asks for (the two terms and the incidence list), and its
+// four kernels.  The leading members are TermArgs' (launch_args.hpp: GraphArgs).  Each body has its own #line name, so the
+// compile log counts lines per body
+std::string generate_graph(int dtype, const char* node, const char* body)
 {
+    const bool has_node = node && *node;
+    std::string s;
+    s += "// generated by lbfgsx_objective_compile_graph: one graph objective for the fused kernels\n";
+    s += "#include \"graph_kernels.cuh\"\n";
+    s += "namespace lbfgsx {\n";
+    s += std::string("typedef ") + (dtype == LBFGSX_F64 ? "double" : "float") + " term_scalar_t;\n";
+    s += "struct ObjGraph\n{\n";
+    s += "    typedef term_scalar_t T;\n";
+    s += "    static constexpr int K = 2;\n";
+    s += std::string("    static constexpr bool kNode = ") + (has_node ? "true" : "false") + ";\n";
+    s += "    const T* p0;\n    const T* p1;\n    const T* p2;\n    const T* p3;\n    T c[8];\n";
+    s += "    const uint32_t* off;\n    const GraphEntry* inc;\n    int64_t E;\n";
+    s += "    // the term of node i: x[0] = x[i] in, its derivative g[0] out, its value returned\n";
+    s += "    __device__ __forceinline__ T node(const T (&x)[1], T (&g)[1], int64_t i) const\n    {\n";
+    if (has_node)
+    {
+        s += "#line 1 \"node_body\"\n";
+        s += node;
+        s += "\n#line 1 \"objective_wrapper\"\n";
+    }
+    else
+        s += "        g[0] = T(0);\n        return T(0);\n";
+    s += "    }\n";
+    s += "    // the term of edge e = (i, j): x = {x[i], x[j]} in, its two partial derivatives g out, its value returned\n";
+    s += "    __device__ __forceinline__ T edge(const T (&x)[2], T (&g)[2], int64_t e, int64_t i, int64_t j) const\n    {\n";
+    s += "#line 1 \"edge_body\"\n";
+    s += body;
+    s += "\n#line 1 \"objective_wrapper\"\n";
+    s += "    }\n";
+    s += "};\n";
+    s += "typedef term_scalar_t S;\n";
+    s += "template __global__ void k_graph_eval<S, ObjGraph>(const S*, S*, int64_t, ObjGraph, RedWs, S*);\n";
+    s += "template __global__ void k_graph_trial<S, ObjGraph>(const S*, const S*, S, S*, S*, int64_t, ObjGraph, RedWs, S*, int);\n";
+    s += "template __global__ void k_graph_b_eval<S, ObjGraph>(const S*, S*, const S*, const S*, int64_t, ObjGraph, RedWs, S*);\n";
+    s += "template __global__ void k_graph_b_dg_maxstep_trial<S, ObjGraph>(const S*, const S*, const S*, const S*, const S*, S, S*, "
+         "S*, int64_t, ObjGraph, RedWs, S*, int);\n";
+    s += "}  // namespace lbfgsx\n";
+    return s;
+}
+
+bool valid_request(int form, int dtype, int K, const char* body, const char* node, std::string& why)
+{
+    if (form == LBFGSX_FORM_GRAPH)
+    {
+        if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
+            why = "graph objective: unknown dtype";
+        else if (K != 2)
+            why = "graph objective: an edge reads K = 2 coordinates";
+        else if (!body || !*body)
+            why = "graph objective: empty edge body";
+        else if (std::strstr(body, "asm"))
+            why = "graph objective: the edge body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
+        else if (node && std::strstr(node, "asm"))
+            why = "graph objective: the node body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
+        else
+            return true;
+        return false;
+    }
     if (form == LBFGSX_FORM_GRID)
     {
         if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
@@ -405,7 +473,8 @@ std::map<std::string, std::unique_ptr<lbfgsx_objective_code> >& cache()
     return m;
 }
 
-int compile_code(int form, int dtype, int K, const char* body, std::unique_ptr<lbfgsx_objective_code>& out, std::string& log)
+int compile_code(int form, int dtype, int K, const char* body, const char* node, std::unique_ptr<lbfgsx_objective_code>& out,
+                 std::string& log)
 {
     const Rtc& r = rtc();
     if (!r.error.empty())
@@ -413,7 +482,7 @@ int compile_code(int form, int dtype, int K, const char* body, std::unique_ptr<l
         log = r.error;
         return LBFGSX_E_RUNTIME;
     }
-    const std::string src = generate(form, dtype, K, body);
+    const std::string src = generate(form, dtype, K, body, node);
     // the kernel headers ask for <hip/hip_runtime.h>; hipRTC has the runtime's declarations built in, so the name resolves
     // to an empty header instead of depending on where ROCm's headers are installed
     const char* hsrc[] = {"\n"};
@@ -512,21 +581,22 @@ int jit_launch(lbfgsx_ctx* c, int which, int grid, void** params)
 
 namespace {
 
-long long objective_source(int form, int dtype, int K, const char* body, char* out, size_t len)
+long long objective_source(int form, int dtype, int K, const char* body, char* out, size_t len, const char* node = nullptr)
 {
     std::string why;
-    if (!valid_request(form, dtype, K, body, why))
+    if (!valid_request(form, dtype, K, body, node, why))
     {
         lbfgsx::set_error(why);
         return LBFGSX_E_INVALID;
     }
-    const std::string s = generate(form, dtype, K, body);
+    const std::string s = generate(form, dtype, K, body, node);
     if (out && len > 0)
         std::snprintf(out, len, "%s", s.c_str());
     return (long long) s.size() + 1;
 }
 
-int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
+int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len,
+                      const char* node = nullptr)
 {
     if (log && log_len > 0)
         log[0] = '\0';
@@ -534,13 +604,15 @@ int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const 
         return LBFGSX_E_INVALID;
     *out = nullptr;
     std::string why;
-    if (!valid_request(form, dtype, K, body, why))
+    if (!valid_request(form, dtype, K, body, node, why))
     {
         lbfgsx::set_error(why);
         put_log(log, log_len, why);
         return LBFGSX_E_INVALID;
     }
-    const std::string key = std::to_string(form) + "/" + std::to_string(dtype) + "/" + std::to_string(K) + "/" + body;
+    std::string key = std::to_string(form) + "/" + std::to_string(dtype) + "/" + std::to_string(K) + "/" + body;
+    if (form == LBFGSX_FORM_GRAPH)
+        key += std::string("\x1f") + (node ? node : "");  // both bodies
     std::lock_guard<std::mutex> lock(g_cache_mu);
     auto it = cache().find(key);
     const bool hit = it != cache().end();
@@ -548,7 +620,7 @@ int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const 
     {
         std::unique_ptr<lbfgsx_objective_code> code;
         std::string text;
-        const int rc = compile_code(form, dtype, K, body, code, text);
+        const int rc = compile_code(form, dtype, K, body, node, code, text);
         if (rc)
         {
             lbfgsx::set_error(std::string(kFormName[form]) + ": compilation failed\n" + text);
@@ -581,6 +653,10 @@ long long lbfgsx_objective_source_grid(int dtype, const char* body, char* out, s
 {
     return objective_source(LBFGSX_FORM_GRID, dtype, 4, body, out, len);
 }
+long long lbfgsx_objective_source_graph(int dtype, const char* node_body, const char* edge_body, char* out, size_t len)
+{
+    return objective_source(LBFGSX_FORM_GRAPH, dtype, 2, edge_body, out, len, node_body);
+}
 
 int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
 {
@@ -593,6 +669,11 @@ int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, con
 int lbfgsx_objective_compile_grid(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len)
 {
     return objective_compile(LBFGSX_FORM_GRID, out, dtype, 4, body, log, log_len);
+}
+int lbfgsx_objective_compile_graph(lbfgsx_objective** out, int dtype, const char* node_body, const char* edge_body, char* log,
+                                   size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_GRAPH, out, dtype, 2, edge_body, log, log_len, node_body);
 }
 
 void lbfgsx_objective_destroy(lbfgsx_objective* obj) { delete obj; }
@@ -618,21 +699,40 @@ int lbfgsx_objective_K(const lbfgsx_objective* obj) { return obj ? obj->code->K 
 int lbfgsx_objective_dtype(const lbfgsx_objective* obj) { return obj ? obj->code->dtype : LBFGSX_E_INVALID; }
 int lbfgsx_objective_form(const lbfgsx_objective* obj) { return obj ? obj->code->form : LBFGSX_E_INVALID; }
 
-int lbfgsx_objective_upload(lbfgsx_ctx* c, int slot, const void* host, void** dev)
+int lbfgsx_objective_upload_count(lbfgsx_ctx* c, int slot, const void* host, int64_t count, void** dev)
 {
     if (!c || slot < 0 || slot >= 4 || !host)
     {
         lbfgsx::set_error("lbfgsx_objective_upload: a term objective has four data arrays, slots 0..3");
         return LBFGSX_E_INVALID;
     }
+    if (count < 1)
+    {
+        lbfgsx::set_error("lbfgsx_objective_upload_count: count = " + std::to_string(count) + ": a data array has at least one element");
+        return LBFGSX_E_INVALID;
+    }
     lbfgsx::DeviceGuard dev_guard_(c->device);
+    if (c->term_own[slot] && c->term_own_count[slot] != count)
+    {
+        LBFGSX_HIP(lbfgsx::stream_sync(c->stream));
+        (void) hipFree(c->term_own[slot]);
+        c->term_own[slot] = nullptr;
+    }
     if (!c->term_own[slot])
-        LBFGSX_HIP(hipMalloc(&c->term_own[slot], size_t(c->n) * c->esz));
-    LBFGSX_HIP(lbfgsx::copy_async(c->term_own[slot], host, size_t(c->n) * c->esz, hipMemcpyHostToDevice, c->stream));
+    {
+        LBFGSX_HIP(hipMalloc(&c->term_own[slot], size_t(count) * c->esz));
+        c->term_own_count[slot] = count;
+    }
+    LBFGSX_HIP(lbfgsx::copy_async(c->term_own[slot], host, size_t(count) * c->esz, hipMemcpyHostToDevice, c->stream));
     LBFGSX_HIP(lbfgsx::stream_sync(c->stream));
     if (dev)
         *dev = c->term_own[slot];
     return LBFGSX_OK;
+}
+
+int lbfgsx_objective_upload(lbfgsx_ctx* c, int slot, const void* host, void** dev)
+{
+    return lbfgsx_objective_upload_count(c, slot, host, c ? c->n : 0, dev);
 }
 
 }  // extern "C"
@@ -651,6 +751,12 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
         c->term_np = 0;
         c->term_form = LBFGSX_FORM_TERM;
         c->term_rows = c->term_cols = 0;
+        if (c->graph_inc)
+        {
+            lbfgsx::DeviceGuard dev_guard_(c->device);
+            (void) lbfgsx::stream_sync(c->stream);  // no launch still walks the list
+            lbfgsx::graph_topology_free(c);
+        }
         if (id)
             *id = LBFGSX_OBJ_NONE;
         return LBFGSX_OK;
@@ -690,6 +796,11 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
         for (int k = 0; k < lbfgsx::JIT_NKERNELS; k++)
             c->term_fn[k] = it->second.fn[k];
     }
+    if (code->form != LBFGSX_FORM_GRAPH && c->graph_inc)
+    {
+        (void) lbfgsx::stream_sync(c->stream);  // no launch still walks the list
+        lbfgsx::graph_topology_free(c);
+    }
     c->term = &code->self;
     c->term_form = code->form;
     c->term_rows = rows;
@@ -718,6 +829,11 @@ int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void
     if (obj && obj->code->form == LBFGSX_FORM_GRID)
     {
         lbfgsx::set_error("a grid objective is bound with its shape: lbfgsx_objective_bind_grid");
+        return LBFGSX_E_INVALID;
+    }
+    if (obj && obj->code->form == LBFGSX_FORM_GRAPH)
+    {
+        lbfgsx::set_error("a graph objective is bound with its edges: lbfgsx_objective_bind_graph");
         return LBFGSX_E_INVALID;
     }
     return objective_bind(c, obj, 0, 0, p, cs, id);
@@ -761,6 +877,74 @@ int lbfgsx_objective_shape(const lbfgsx_ctx* c, int64_t* rows, int64_t* cols)
     if (cols)
         *cols = c->term_cols;
     return LBFGSX_OK;
+}
+
+int lbfgsx_objective_bind_graph(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t E, const int32_t* ei, const int32_t* ej,
+                                int edges_on_device, const void* const p[4], const double cs[8], int* id)
+{
+    if (!c || !obj)
+        return LBFGSX_E_INVALID;
+    if (obj->code->form != LBFGSX_FORM_GRAPH)
+    {
+        lbfgsx::set_error(std::string("lbfgsx_objective_bind_graph: the handle is a ") + kFormName[obj->code->form] +
+                          ", not a graph objective (lbfgsx_objective_compile_graph)");
+        return LBFGSX_E_INVALID;
+    }
+    if (obj->code->dtype != c->dtype)
+    {
+        lbfgsx::set_error("lbfgsx_objective_bind: the objective was compiled for the other dtype");
+        return LBFGSX_E_INVALID;
+    }
+    const int64_t lim = 2147483647;
+    if (E < 1 || !ei || !ej)
+    {
+        lbfgsx::set_error("graph objective: E = " + std::to_string(E) + ": a graph objective has at least one edge (E >= 1) and both index arrays");
+        return LBFGSX_E_INVALID;
+    }
+    if (E > lim)
+    {
+        lbfgsx::set_error("graph objective: E = " + std::to_string(E) + " exceeds 2^31 - 1 = " + std::to_string(lim) +
+                          ": an incidence entry holds (e << 1) | side in 32 bits");
+        return LBFGSX_E_INVALID;
+    }
+    if (c->n > lim)
+    {
+        lbfgsx::set_error("graph objective: n = " + std::to_string(c->n) + " exceeds 2^31 - 1 = " + std::to_string(lim) +
+                          ": node indices are int32");
+        return LBFGSX_E_INVALID;
+    }
+    // the list first: a context whose indices were refused keeps no graph objective bound, so nothing can be launched on them
+    c->st_valid = false;
+    c->spec_valid = false;
+    c->term = nullptr;
+    c->term_np = 0;
+    c->term_form = LBFGSX_FORM_TERM;
+    {
+        lbfgsx::DeviceGuard dev_guard_(c->device);
+        const int rc = lbfgsx::graph_topology_build(c, ei, ej, E, edges_on_device);
+        if (rc)
+            return rc;
+    }
+    const int rc = objective_bind(c, obj, 0, 0, p, cs, id);
+    if (rc)
+    {
+        lbfgsx::DeviceGuard dev_guard_(c->device);
+        lbfgsx::graph_topology_free(c);
+    }
+    return rc;
+}
+
+int lbfgsx_objective_topology(lbfgsx_ctx* c, int64_t* E, uint32_t* off, int32_t* other, uint32_t* edge_side)
+{
+    if (!c || !c->term || c->term_form != LBFGSX_FORM_GRAPH || !c->graph_inc)
+    {
+        lbfgsx::set_error("lbfgsx_objective_topology: no graph objective is bound to this context");
+        return LBFGSX_E_INVALID;
+    }
+    if (E)
+        *E = c->graph_E;
+    lbfgsx::DeviceGuard dev_guard_(c->device);
+    return lbfgsx::graph_topology_read(c, off, other, edge_side);
 }
 
 int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4])

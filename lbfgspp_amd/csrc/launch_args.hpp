@@ -116,19 +116,51 @@ struct GridArgs
     TermArgs<T> t;
     int64_t rows, cols;
 };
-// the objective argument of the bound handle's kernels, by its form: &term for a term or chain objective, &grid for a grid one
+// the by-value argument of a graph objective's kernels: layout of the generated struct ObjGraph (TermArgs, then the
+// context's incidence list: uint32 off[n+1], 8-byte entries inc[2E] (graph_entry.hpp), and E)
+struct GraphEntry;
+template <class T>
+struct GraphArgs
+{
+    TermArgs<T> t;
+    const uint32_t* off;
+    const GraphEntry* inc;
+    int64_t E;
+};
+// the objective argument of the bound handle's kernels, by its form: &term for a term or chain objective, &grid for a grid
+// one, &graph for a graph one
 template <class T>
 struct BoundArgs
 {
     TermArgs<T> term;
     GridArgs<T> grid;
+    GraphArgs<T> graph;
     void* ptr;
-    explicit BoundArgs(const lbfgsx_ctx* c) : term(term_args<T>(c)), grid{term, c->term_rows, c->term_cols}
+    explicit BoundArgs(const lbfgsx_ctx* c)
+        : term(term_args<T>(c)),
+          grid{term, c->term_rows, c->term_cols},
+          graph{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const GraphEntry*>(c->graph_inc), c->graph_E}
     {
-        ptr = (c->term_form == LBFGSX_FORM_GRID) ? static_cast<void*>(&grid) : static_cast<void*>(&term);
+        ptr = (c->term_form == LBFGSX_FORM_GRID)    ? static_cast<void*>(&grid)
+              : (c->term_form == LBFGSX_FORM_GRAPH) ? static_cast<void*>(&graph)
+                                                    : static_cast<void*>(&term);
     }
     BoundArgs(const BoundArgs&) = delete;
 };
+// what a graph objective adds to the byte model of one launch of its kernels: the offsets, the entries, and every gathered
+// value once (vectors_gathered: 1 in the evaluation kernels, 2 in the trial kernels, which gather xp and d) -- the values,
+// not the sectors that are fetched for them.  Nothing for the other forms.
+template <class T>
+inline void graph_model_add(const lbfgsx_ctx* c, int vectors_gathered)
+{
+    if (c->term_form == LBFGSX_FORM_GRAPH)
+        model_add(double(c->n + 1) * 4 + double(2 * c->graph_E) * 8 + double(2 * c->graph_E) * sizeof(T) * vectors_gathered);
+}
+// graph_topology.hip: the incidence list of the context (ctx.hpp: graph_off, graph_inc, graph_E).  build validates the
+// indices first and leaves the context without a list when an edge offends (LBFGSX_E_INVALID, the edge named)
+int graph_topology_build(lbfgsx_ctx* c, const int32_t* ei, const int32_t* ej, int64_t E, int on_device);
+int graph_topology_read(lbfgsx_ctx* c, uint32_t* off, int32_t* other, uint32_t* edge_side);
+void graph_topology_free(lbfgsx_ctx* c);
 inline bool term_bound(const lbfgsx_ctx* c, int objective) { return objective == LBFGSX_OBJ_BOUND && c->term != nullptr; }
 // one launch of loaded kernel `which` of the bound objective on the context's stream, block of kBlock threads; params as
 // hipModuleLaunchKernel takes them (one pointer per kernel argument)

@@ -34,10 +34,18 @@ struct lbfgsx_solver
                           const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) = 0;
     virtual void minimize_fn(int64_t n, lbfgsx_objective_fn fn, void* user, void* x, const void* lb, const void* ub,
                              lbfgsx_trace* tr, lbfgsx_result* out) = 0;
-    // rows, cols: the shape of a grid objective, 0 for the other forms
-    virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const void* const p[4],
-                              int host_mask, const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* tr,
-                              lbfgsx_result* out) = 0;
+    // the edges of a graph objective, and the element counts of its host data arrays (null: n each)
+    struct GraphSpec
+    {
+        int64_t E;
+        const int32_t *ei, *ej;
+        int on_device;
+        const int64_t* counts;
+    };
+    // rows, cols: the shape of a grid objective, 0 for the other forms; gr: null for every form but a graph objective
+    virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const GraphSpec* gr,
+                              const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
+                              lbfgsx_trace* tr, lbfgsx_result* out) = 0;
 };
 
 namespace {
@@ -112,13 +120,16 @@ struct CallbackObjective
 
 // a compiled term objective with its data (device pointers, or host arrays where host_mask has the slot's bit) and scalars
 template <class Scalar>
-void fill_term(TermObjective<Scalar>& f, const void* const p[4], int host_mask, const double c[8])
+void fill_term(TermObjective<Scalar>& f, const void* const p[4], int host_mask, const double c[8],
+               const int64_t* counts = nullptr)
 {
     const Scalar* dev[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int k = 0; k < 4; k++)
     {
         const Scalar* q = p ? static_cast<const Scalar*>(p[k]) : nullptr;
-        if (q && (host_mask >> k & 1))
+        if (q && (host_mask >> k & 1) && counts && counts[k] > 0)
+            f.host_data(k, q, counts[k]);
+        else if (q && (host_mask >> k & 1))
             f.host_data(k, q);
         else
             dev[k] = q;
@@ -203,12 +214,16 @@ struct LbfgsImpl : lbfgsx_solver
             throw;
         }
     }
-    void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const void* const p[4], int host_mask,
-                      const double c[8], void* x, const void*, const void*, lbfgsx_trace* tr, lbfgsx_result* out) override
+    void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const GraphSpec* gr,
+                      const void* const p[4], int host_mask, const double c[8], void* x, const void*, const void*,
+                      lbfgsx_trace* tr, lbfgsx_result* out) override
     {
         GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
-        TermObjective<Scalar>& f = shaped;
-        fill_term<Scalar>(f, p, host_mask, c);
+        GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
+        if (gr)
+            graphed.edges(gr->E, gr->ei, gr->ej, gr->on_device != 0);
+        TermObjective<Scalar>& f = gr ? static_cast<TermObjective<Scalar>&>(graphed) : shaped;
+        fill_term<Scalar>(f, p, host_mask, c, gr ? gr->counts : nullptr);
         run(f, n, x, tr, out);
     }
     template <class Foo>
@@ -311,12 +326,16 @@ struct LbfgsbImpl : lbfgsx_solver
             throw;
         }
     }
-    void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const void* const p[4], int host_mask,
-                      const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) override
+    void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const GraphSpec* gr,
+                      const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
+                      lbfgsx_trace* tr, lbfgsx_result* out) override
     {
         GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
-        TermObjective<Scalar>& f = shaped;
-        fill_term<Scalar>(f, p, host_mask, c);
+        GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
+        if (gr)
+            graphed.edges(gr->E, gr->ei, gr->ej, gr->on_device != 0);
+        TermObjective<Scalar>& f = gr ? static_cast<TermObjective<Scalar>&>(graphed) : shaped;
+        fill_term<Scalar>(f, p, host_mask, c, gr ? gr->counts : nullptr);
         run(f, n, x, lb, ub, tr, out);
     }
     template <class Foo>
@@ -896,6 +915,8 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
         const int K = lbfgsx_objective_K(obj);
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID)
             throw std::invalid_argument("a grid objective is minimised with its shape: lbfgsx_solver_minimize_grid");
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRAPH)
+            throw std::invalid_argument("a graph objective is minimised with its edges: lbfgsx_solver_minimize_graph");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_CHAIN)
         {
             if (n < K)
@@ -913,7 +934,7 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
         std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_obj: no HIP device available (this library has no CPU fallback)");
         return out->status;
     }
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, p, host_mask, c, x, lb, ub, trace, out); });
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, nullptr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 
 int lbfgsx_solver_minimize_grid(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
@@ -943,6 +964,35 @@ int lbfgsx_solver_minimize_grid(lbfgsx_solver* s, const lbfgsx_objective* obj, i
         std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_grid: no HIP device available (this library has no CPU fallback)");
         return out->status;
     }
-    return guarded(out, [&]() { s->minimize_obj(obj, int64_t(n), rows, cols, p, host_mask, c, x, lb, ub, trace, out); });
+    return guarded(out, [&]() { s->minimize_obj(obj, int64_t(n), rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out); });
+}
+
+int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t E, const int32_t* ei,
+                                 const int32_t* ej, int edges_on_device, const void* const p[4], int host_mask,
+                                 const int64_t counts[4], const double c[8], void* x, const void* lb, const void* ub,
+                                 lbfgsx_trace* trace, lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    const int bad = guarded(out, [&]() {
+        if (!s || !obj || n <= 0)
+            throw std::invalid_argument("lbfgsx_solver_minimize_graph: invalid argument");
+        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_GRAPH)
+            throw std::invalid_argument("lbfgsx_solver_minimize_graph: the handle is not a graph objective (lbfgsx_objective_compile_graph)");
+        if (lbfgsx_objective_dtype(obj) != s->dtype)
+            throw std::invalid_argument("lbfgsx_solver_minimize_graph: the objective was compiled for the other dtype");
+        if (E < 1 || !ei || !ej)
+            throw std::invalid_argument("graph objective: E = " + std::to_string(E) +
+                                        ": a graph objective has at least one edge (E >= 1) and both index arrays");
+    });
+    if (bad)
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_graph: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    const lbfgsx_solver::GraphSpec gr = {E, ei, ej, edges_on_device, counts};
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 }

@@ -7,7 +7,8 @@ Names, argument meaning and error behaviour follow yixuan/LBFGSpp:
 Exceptions: std::invalid_argument -> ValueError, std::logic_error -> ArithmeticError,
 std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device objective
 (`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`), the caller's own term compiled into the same kernels (`TermObjective(body)`,
-`ChainObjective(body)` for terms that overlap, or `GridObjective(body, shape)` for 2x2-cell terms on a grid)
+`ChainObjective(body)` for terms that overlap, `GridObjective(body, shape)` for 2x2-cell terms on a grid, or
+`GraphObjective(edge_body, edges)` for edge terms over an index list)
 or the caller's own callable, `DeviceObjective(fn)`: fn(x, grad) -> float on torch
 tensors that alias the library's device vectors.  All O(n) work of the solver runs in the HIP library, Python only passes
 pointers.  There is no CPU fallback: without the built extension or a GPU these calls raise.
@@ -180,6 +181,10 @@ class TermObjective:
         if n % self.K:
             raise ValueError("TermObjective: n = %d is not a multiple of K = %d" % (n, self.K))
 
+    def _data_sizes(self, n):
+        """the element counts a data array may have"""
+        return (n,)
+
     def __del__(self):
         try:
             core, _ = L.load()
@@ -266,6 +271,68 @@ class GridObjective(TermObjective):
 
 def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch"
+
+
+class GraphObjective(TermObjective):
+    """An objective on a graph: x has one coordinate per node, the E edges are (ei[e], ej[e]), and
+    f(x) = sum over nodes v of psi(x[v]; v) + sum over edges e of phi(x[ei[e]], x[ej[e]]; e) -- spring and finite-element
+    energies on an unstructured mesh, graph-Laplacian regularisers, XY and synchronisation energies, pairwise-comparison
+    losses (include/lbfgsx.h, "graph objectives").  edge_body sees T, const T x[2] (x at ei[e] and at ej[e], in the edge's own
+    orientation), T g[2] (to fill), int64_t e, i, j (the edge's index and its two nodes), p0..p3 and c[8] and returns the
+    edge's value; node_body (optional) sees T, const T x[1], T g[1], int64_t i, p0..p3 and c[8] and returns the node's value.
+    grad[v] is the node term's g[0], then the g_e[side] of the edges incident to v in ascending e.
+
+        springs = GraphObjective("const T d = x[0] - x[1]; const T w = p0[e] * d; g[0] = w; g[1] = T(0) - w;"
+                                 "return T(0.5) * (w * d);", edges=(ei, ej), data=(weights,),
+                                 node_body="const T r = x[0] - p1[i]; g[0] = r; return T(0.5) * (r * r);")
+
+    edges: two integer numpy arrays or torch tensors of equal length E >= 1; they are range-checked and converted to int32 on
+    the host here, and copied, validated (0 <= index < n, ei[e] != ej[e]) and turned into the incidence list on the device at
+    every minimise.  Each data[k] has n (per node) or E (per edge) elements.  set_data, set_scalars, source, compile and info
+    as for a TermObjective; usable wherever a GridObjective is, refused where one is."""
+    _NAME = "GraphObjective"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_graph", "lbfgsx_objective_source_graph"
+
+    def __init__(self, edge_body, edges, node_body=None, data=(), scalars=()):
+        try:
+            ei, ej = edges
+        except (TypeError, ValueError):
+            raise ValueError("GraphObjective: edges must be a pair (ei, ej) of integer arrays") from None
+        self.ei, self.ej = self._indices(ei, "ei"), self._indices(ej, "ej")
+        if self.ei.size != self.ej.size:
+            raise ValueError("GraphObjective: ei has %d elements and ej has %d: one pair per edge" % (self.ei.size, self.ej.size))
+        if self.ei.size < 1:
+            raise ValueError("GraphObjective: E = 0: a graph objective has at least one edge")
+        self.E = int(self.ei.size)
+        self.body, self.K = str(edge_body), 2
+        self.node_body = None if not node_body else str(node_body)
+        self._h = {}
+        self.set_data(*data)
+        self.set_scalars(*scalars)
+
+    @staticmethod
+    def _indices(a, name):
+        if _is_torch(a):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError("GraphObjective: %s must be a 1-D integer array, not %s with %d dimensions" % (name, a.dtype, a.ndim))
+        if a.size:
+            lo, hi = int(a.min()), int(a.max())
+            for v in (lo, hi):
+                if v < -2 ** 31 or v > 2 ** 31 - 1:
+                    raise ValueError("GraphObjective: %s holds %d, which does not fit a 32-bit node index" % (name, v))
+        return np.ascontiguousarray(a, np.int32)
+
+    def _form_args(self):
+        return (self.node_body.encode() if self.node_body else None,)
+
+    def _check_n(self, n):
+        if n > 2 ** 31 - 1:
+            raise ValueError("GraphObjective: n = %d exceeds 2^31 - 1: node indices are int32" % n)
+
+    def _data_sizes(self, n):
+        return (n, self.E)
 
 
 class TraceBuffer:
@@ -423,6 +490,9 @@ class _SolverBase:
         f._check_n(n)
         h = f.compile(np_dt)
         ptrs = (C.c_void_p * 4)()
+        counts = (C.c_int64 * 4)()
+        sizes = f._data_sizes(n)
+        what = " or ".join("%d" % v for v in sizes)
         keep, mask = [], 0
         for k, d in enumerate(f.data):
             if d is None:
@@ -430,17 +500,18 @@ class _SolverBase:
             if _is_torch(d):
                 torch = L.require_torch("%s with torch data" % f._NAME)
                 want = torch.float64 if self.dtype == L.F64 else torch.float32
-                if d.dim() != 1 or d.numel() != n or d.dtype != want or not d.is_cuda or d.device.index != self.device \
+                if d.dim() != 1 or d.numel() not in sizes or d.dtype != want or not d.is_cuda or d.device.index != self.device \
                         or not d.is_contiguous():
-                    raise ValueError("%s: data[%d] must be a contiguous 1-D %s tensor of %d elements on cuda:%d"
-                                     % (f._NAME, k, want, n, self.device))
+                    raise ValueError("%s: data[%d] must be a contiguous 1-D %s tensor of %s elements on cuda:%d"
+                                     % (f._NAME, k, want, what, self.device))
                 ptrs[k] = d.data_ptr()
                 keep.append(d)
             else:
                 a = np.ascontiguousarray(d, np_dt)
-                if a.ndim != 1 or a.size != n:
-                    raise ValueError("%s: data[%d] must have %d elements" % (f._NAME, k, n))
+                if a.ndim != 1 or a.size not in sizes:
+                    raise ValueError("%s: data[%d] must have %s elements" % (f._NAME, k, what))
                 ptrs[k] = a.ctypes.data
+                counts[k] = a.size
                 mask |= 1 << k
                 keep.append(a)  # the converted copy, not d: its address is what the library reads
         cs = (C.c_double * 8)(*(f.scalars + (0.0,) * (8 - len(f.scalars))))
@@ -449,7 +520,11 @@ class _SolverBase:
             torch.cuda.current_stream().synchronize()  # the data arrays are complete when the library reads them
         tail = (C.byref(ptrs), mask, C.byref(cs), self._ptr(x), self._ptr(lb), self._ptr(ub), C.byref(trace.c) if trace else None,
                 C.byref(res))
-        if isinstance(f, GridObjective):
+        if isinstance(f, GraphObjective):
+            rc = self._sol.lbfgsx_solver_minimize_graph(self._h, h, n, f.E, f.ei.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        f.ej.ctypes.data_as(C.POINTER(C.c_int32)), 0, tail[0], mask,
+                                                        C.byref(counts), *tail[2:])
+        elif isinstance(f, GridObjective):
             rc = self._sol.lbfgsx_solver_minimize_grid(self._h, h, f.shape[0], f.shape[1], *tail)
         else:
             rc = self._sol.lbfgsx_solver_minimize_obj(self._h, h, n, *tail)
@@ -471,7 +546,7 @@ class _SolverBase:
             return self._minimize_obj(f, n, x, lb, ub, trace)
         if not hasattr(f, "objective"):
             raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body), "
-                            "GridObjective(body, shape) or DeviceObjective(fn)")
+                            "GridObjective(body, shape), GraphObjective(edge_body, edges) or DeviceObjective(fn)")
         res = L.Result()
         a = None if f.a is None else np.ascontiguousarray(f.a, _NP[self.dtype])
         b = None if f.b is None else np.ascontiguousarray(f.b, _NP[self.dtype])
