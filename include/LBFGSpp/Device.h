@@ -107,6 +107,7 @@ class TermObjective
     std::int64_t m_E = 0;                 // a GraphObjective's edges; 0: the handle is bound without any
     const std::int32_t *m_ei = nullptr, *m_ej = nullptr;
     bool m_edges_dev = false;
+    const std::int32_t* m_elems = nullptr;  // a MeshObjective's connectivity table of m_E rows; null: bound without one
     std::int64_t m_count[4] = {0, 0, 0, 0};  // elements of m_host[k]; 0: n
 
     TermObjective(const TermObjective&) = delete;
@@ -120,12 +121,13 @@ public:
     explicit TermObjective(const lbfgsx_objective* compiled) : m_h(const_cast<lbfgsx_objective*>(compiled)) {}
 
 protected:
-    // node: a GraphObjective's node body (empty: none)
-    TermObjective(int form, int K, const std::string& body, const char* who, const std::string& node = std::string())
+    // node: a GraphObjective's or MeshObjective's node body (empty: none); D: a MeshObjective's unknowns per node
+    TermObjective(int form, int K, const std::string& body, const char* who, const std::string& node = std::string(), int D = 1)
     {
         std::vector<char> log(16384, '\0');
         const int dt = detail::dtype_of<Scalar>::value;
-        const int rc = (form == LBFGSX_FORM_GRAPH)   ? lbfgsx_objective_compile_graph(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
+        const int rc = (form == LBFGSX_FORM_MESH)    ? lbfgsx_objective_compile_mesh(&m_h, dt, K, D, node.c_str(), body.c_str(), log.data(), log.size())
+                       : (form == LBFGSX_FORM_GRAPH) ? lbfgsx_objective_compile_graph(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRID)  ? lbfgsx_objective_compile_grid(&m_h, dt, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_CHAIN) ? lbfgsx_objective_compile_chain(&m_h, dt, K, body.c_str(), log.data(), log.size())
                                                      : lbfgsx_objective_compile(&m_h, dt, K, body.c_str(), log.data(), log.size());
@@ -139,6 +141,12 @@ protected:
     {
         m_rows = rows;
         m_cols = cols;
+    }
+    void set_elements(std::int64_t E, const std::int32_t* elems, bool on_device)
+    {
+        m_E = E;
+        m_elems = elems;
+        m_edges_dev = on_device;
     }
     void set_edges(std::int64_t E, const std::int32_t* ei, const std::int32_t* ej, bool on_device)
     {
@@ -204,7 +212,9 @@ public:
                 p[k] = dev;
             }
         }
-        if (m_E || m_ei || m_ej)
+        if (m_elems)
+            detail::check(lbfgsx_objective_bind_mesh(c, m_h, m_E, m_elems, m_edges_dev ? 1 : 0, p, m_c, &id));
+        else if (m_E || m_ei || m_ej)
             detail::check(lbfgsx_objective_bind_graph(c, m_h, m_E, m_ei, m_ej, m_edges_dev ? 1 : 0, p, m_c, &id));
         else if (m_rows || m_cols)
             detail::check(lbfgsx_objective_bind_grid(c, m_h, m_rows, m_cols, p, m_c, &id));
@@ -277,15 +287,42 @@ public:
     }
 };
 
+// An objective on a mesh: N nodes with D unknowns each (x node-major, n = N*D), E elements of K nodes each, K in {2, 3, 4},
+// D in {1, 2, 3} (include/lbfgsx.h, "mesh objectives").  The element body sees T, K, D, const T x[K*D] (x[k*D + d]: unknown d
+// of the node in slot k), T g[K*D], int64_t e, const int64_t v[K], p0..p3 and c[8]; the node body (optional) sees T, D,
+// const T x[D], T g[D], int64_t i, p0..p3 and c[8].
+//     MeshObjective<double> f(3, 2, triangle_body);
+//     f.elements(E, tris).host_data(0, rest_area, E);      solver.minimize(f, x, fx);
+// elements(): an int32 array of E*K elements, row-major, on the host (or the device) that stays valid until minimize()
+// returns; it is copied and validated at every minimize() (std::invalid_argument with the element named).  Otherwise a
+// GraphObjective's interface; accepted wherever one is, refused where it is.
+template <typename Scalar>
+class MeshObjective : public TermObjective<Scalar>
+{
+public:
+    MeshObjective(int K, int D, const std::string& elem_body, const std::string& node_body = std::string())
+        : TermObjective<Scalar>(LBFGSX_FORM_MESH, K, elem_body, "MeshObjective: ", node_body, D)
+    {
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile_mesh); it stays the caller's
+    explicit MeshObjective(const lbfgsx_objective* compiled) : TermObjective<Scalar>(compiled) {}
+    MeshObjective& elements(std::int64_t E, const std::int32_t* elems, bool on_device = false)
+    {
+        this->set_elements(E, elems, on_device);
+        return *this;
+    }
+};
+
 namespace detail {
-// the objectives compiled at run time into the fused kernels: a TermObjective, a ChainObjective, a GridObjective or a
-// GraphObjective
+// the objectives compiled at run time into the fused kernels: a TermObjective, a ChainObjective, a GridObjective, a
+// GraphObjective or a MeshObjective
 template <typename Scalar, typename Foo>
 struct is_compiled_objective
 {
     typedef typename std::decay<Foo>::type F;
     static constexpr bool value = std::is_same<F, TermObjective<Scalar> >::value || std::is_same<F, ChainObjective<Scalar> >::value ||
-                                  std::is_same<F, GridObjective<Scalar> >::value || std::is_same<F, GraphObjective<Scalar> >::value;
+                                  std::is_same<F, GridObjective<Scalar> >::value || std::is_same<F, GraphObjective<Scalar> >::value ||
+                                  std::is_same<F, MeshObjective<Scalar> >::value;
 };
 }  // namespace detail
 
@@ -336,8 +373,8 @@ namespace detail {
 
 // Uniform view of the four kinds of objective `Foo` the solvers accept:
 //   BuiltinObjective<Scalar>                              -> fused device kernels
-//   TermObjective<Scalar>, ChainObjective<Scalar>, GridObjective<Scalar>, GraphObjective<Scalar> -> the same kernels, compiled
-//                                                            at run time
+//   TermObjective<Scalar>, ChainObjective<Scalar>, GridObjective<Scalar>, GraphObjective<Scalar>, MeshObjective<Scalar>
+//                                                         -> the same kernels, compiled at run time
 //   Scalar f(const DeviceVector<Scalar>& x, DeviceVector<Scalar>& grad)   -> user device functor
 //   Scalar f(const Vec& x, Vec& grad) with host vectors   -> staged through host memory (compatibility)
 template <typename Scalar, typename Foo, typename HostVec>

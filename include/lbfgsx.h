@@ -199,7 +199,7 @@ int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4]);
  * lbfgsx_solver_minimize_obj and the four evaluation entry points take it like a term objective's.  Binding to a context
  * with n < K is refused (any n >= K is accepted: n need not be a multiple of anything).  The compile log, the refusal of
  * asm and the line numbers are those of lbfgsx_objective_compile. */
-enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2, LBFGSX_FORM_GRAPH = 3 };
+enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2, LBFGSX_FORM_GRAPH = 3, LBFGSX_FORM_MESH = 4 };
 int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len);
 long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char* out, size_t len);
 int lbfgsx_objective_form(const lbfgsx_objective* obj);
@@ -279,8 +279,9 @@ int lbfgsx_objective_shape(const lbfgsx_ctx* c, int64_t* rows, int64_t* cols);
  * Measured (profiles/graph_objective.json; one trial evaluation at n = 1e8 f64): built-in 0.575 ms, the
  * path graph 1.10 ms, the 10000 x 10000 lattice as a graph (E = 2e8) 2.32 ms with natural labels and 16.5 ms with randomly
  * relabelled nodes, its torch callable (natural labels) 10.8 ms; building the list 15 to 30 ms.
- * Not built: vector unknowns per node, terms over more than two nodes, an edge-parallel or chunked mapping for strongly
- * skewed degrees (a node's list is walked by one thread), reordering of the nodes for locality, the lock-step batch. */
+ * Not built: an edge-parallel or chunked mapping for strongly skewed degrees (a node's list is walked by one thread),
+ * reordering of the nodes for locality, the lock-step batch.  Vector unknowns per node and terms over more than two nodes
+ * are the mesh form's (below). */
 int lbfgsx_objective_compile_graph(lbfgsx_objective** out, int dtype, const char* node_body, const char* edge_body, char* log,
                                    size_t log_len);
 long long lbfgsx_objective_source_graph(int dtype, const char* node_body, const char* edge_body, char* out, size_t len);
@@ -288,6 +289,51 @@ int lbfgsx_objective_bind_graph(lbfgsx_ctx* c, const lbfgsx_objective* obj, int6
                                 int edges_on_device, const void* const p[4], const double cs[8], int* id);
 int lbfgsx_objective_topology(lbfgsx_ctx* c, int64_t* E, uint32_t* off, int32_t* other, uint32_t* edge_side);
 int lbfgsx_objective_upload_count(lbfgsx_ctx* c, int slot, const void* host, int64_t count, void** dev);
+/* ---- mesh objectives: K-node elements, D unknowns per node ---------------------------------------------------------------
+ * N nodes with D unknowns each, D in {1, 2, 3}; x is node-major, x[v*D + d], n = N*D.  E elements of K nodes each, K in
+ * {2, 3, 4}, as one int32 array elems[E*K], row-major (a connectivity table), and
+ *     f(x) = sum over nodes v of psi(x_v; v)  +  sum over elements e of phi(x at the K nodes of e; e)
+ * -- springs in space, triangle and tetrahedron energies, FEM elasticity, mesh smoothing.  Both terms are HIP/C++ text:
+ *   elem_body sees T, constexpr int K, D, const T x[K*D] (slot-major: x[k*D + d] is unknown d of the node in slot k, in the
+ *             element's own slot order), T g[K*D] (to fill), int64_t e, const int64_t v[K] (the node indices in slot
+ *             order), p0..p3 and c[8]; it returns the element's value;
+ *   node_body (NULL or empty: none) sees T, D, const T x[D], T g[D], int64_t i, p0..p3, c[8]; it returns the node's value.
+ * The data arrays are raw device pointers the bodies index themselves (p0[e], p1[i], p2[i*D + d]).
+ * Semantics (a numpy restatement with one operation per source operation is bit-exact):
+ *   grad[v*D + d] = psi's g[d] if there is a node body, then g_e[slot*D + d] of the elements that contain v in ASCENDING
+ *             ELEMENT INDEX e (an element's nodes are pairwise distinct; an element listed twice contributes twice); the
+ *             sum starts from the first contribution (no leading 0 +); a node with no contribution gets +0;
+ *   f       = the order-independent (compensated) sum the other forms use: a node's value added once, by the node's
+ *             owner, an element's once, by the owner of the node in slot 0;
+ *   one rounding per source operation, no contraction.
+ * The thread that owns v evaluates every element that contains v and keeps the partials of v's slot, so an element's term
+ * is evaluated K times on identical inputs by the same instructions: the same bits, no floating-point atomic.  The price of
+ * the single fused launch with a reproducible sum is K times the arithmetic and K*(K-1)*D gathered values per element.
+ * (Storing the K*D contributions once and summing per destination in a second pass evaluates each body once but costs a
+ * second launch, K*D*E stores and as many gathered loads.)
+ * lbfgsx_objective_compile_mesh wraps the bodies for the four kernels of csrc/mesh_kernels.cuh, the counterparts of the
+ * graph form's, and caches by (form, both bodies, K, D, dtype); lbfgsx_objective_K returns K, lbfgsx_objective_dim D (1 for
+ * the other forms), the form is LBFGSX_FORM_MESH.  K or D out of range and the word asm in a body are refused with the
+ * value named; the compile log counts lines per body ("elem_body", "node_body").
+ * lbfgsx_objective_bind_mesh copies elems (host, or device when elems_on_device != 0) and builds on the device the list the
+ * context owns (csrc/mesh_topology.hip): uint32 off[N+1] and, for node v, the entries off[v] .. off[v+1]-1 in ascending e,
+ * each K 32-bit words: (e << 2) | slot, then the element's other nodes in ascending slot order.  VALIDATION COMES FIRST: an
+ * index outside [0, N) or two equal indices in an element return LBFGSX_E_INVALID with the smallest such e, its K indices,
+ * N and the number of offenders, and leave no objective bound.  Also refused, the values named: a handle of another form,
+ * E < 1, E > 2^30 - 1, n not a multiple of D, n > 2^31 - 1.  Rebuilt at every bind; nothing is cached by pointer.
+ * lbfgsx_objective_bind and lbfgsx_objective_bind_graph refuse a mesh handle.  lbfgsx_objective_mesh_topology copies the
+ * list to host arrays (off: N+1, words: K*E*K elements; either may be NULL) and stores E.
+ * Byte model of one launch: the built-in's streams plus (N+1)*4 bytes of offsets, K*E*4K of entries and
+ * K*E*(K-1)*D*sizeof(T) of gathered values (twice that in the trial kernels).  Registers, measurements: DESIGN.md section 1.
+ * Not built: K > 4 or D > 3, mixed element types, a chunked or element-parallel mapping for hubs, node reordering, the
+ * lock-step batch, a bench.py leg. */
+int lbfgsx_objective_compile_mesh(lbfgsx_objective** out, int dtype, int K, int D, const char* node_body, const char* elem_body,
+                                  char* log, size_t log_len);
+long long lbfgsx_objective_source_mesh(int dtype, int K, int D, const char* node_body, const char* elem_body, char* out, size_t len);
+int lbfgsx_objective_bind_mesh(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t E, const int32_t* elems, int elems_on_device,
+                               const void* const p[4], const double cs[8], int* id);
+int lbfgsx_objective_mesh_topology(lbfgsx_ctx* c, int64_t* E, uint32_t* off, uint32_t* words);
+int lbfgsx_objective_dim(const lbfgsx_objective* obj);
 /* Every entry point of this ABI makes the context's device current for its own duration and restores the caller's
  * afterwards.  Code that launches its OWN kernels on the context's vectors (a device functor, lbfgsx_vec) must run with
  * that device current too: lbfgsx_device tells which one it is, lbfgsx_device_push makes it current for the calling

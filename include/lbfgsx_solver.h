@@ -146,6 +146,15 @@ int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, 
                                  const int32_t* ej, int edges_on_device, const void* const p[4], int host_mask,
                                  const int64_t counts[4], const double c[8], void* x, const void* lb, const void* ub,
                                  lbfgsx_trace* trace, lbfgsx_result* out);
+/* lbfgsx_solver_minimize_obj for a mesh objective (include/lbfgsx.h, lbfgsx_objective_compile_mesh): x has n = N*D unknowns,
+ * node-major; elems[E*K] is the connectivity table, a host array or a device array (elems_on_device != 0).  counts[k] is the
+ * number of elements of p[k] where host_mask says it is a host array (n, N or E; NULL: n for all).  A handle of another
+ * form, E < 1 and n not a multiple of D are refused with LBFGSX_E_INVALID before a device is needed, as are the tables
+ * lbfgsx_objective_bind_mesh refuses; lbfgsx_solver_minimize_obj and lbfgsx_solver_minimize_graph refuse a mesh handle. */
+int lbfgsx_solver_minimize_mesh(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t E, const int32_t* elems,
+                                int elems_on_device, const void* const p[4], int host_mask, const int64_t counts[4],
+                                const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
+                                lbfgsx_result* out);
 
 /* ---- batched mode (BASELINE.json cfg5): many independent minimisations on one GPU ------------------------
  * Problem `id` is the extended Rosenbrock (or diag quadratic) instance generated on the device from seed

@@ -216,6 +216,14 @@ def load():
     sig(core, "lbfgsx_objective_upload_count", i32, vp, i32, vp, i64, C.POINTER(vp))
     sig(sol, "lbfgsx_solver_minimize_graph", i32, vp, vp, i64, i64, i32p, i32p, i32, C.POINTER(vp * 4), i32, C.POINTER(i64 * 4),
         C.POINTER(dbl * 8), vp, vp, vp, C.POINTER(Trace), C.POINTER(Result))
+    # mesh objectives: K nodes per element, D unknowns per node; the connectivity table travels with the binding
+    sig(core, "lbfgsx_objective_compile_mesh", i32, C.POINTER(vp), i32, i32, i32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_source_mesh", C.c_longlong, i32, i32, i32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_bind_mesh", i32, vp, vp, i64, vp, i32, C.POINTER(vp * 4), C.POINTER(dbl * 8), C.POINTER(i32))
+    sig(core, "lbfgsx_objective_mesh_topology", i32, vp, C.POINTER(i64), u32p, u32p)
+    sig(core, "lbfgsx_objective_dim", i32, vp)
+    sig(sol, "lbfgsx_solver_minimize_mesh", i32, vp, vp, i64, i64, i32p, i32, C.POINTER(vp * 4), i32, C.POINTER(i64 * 4),
+        C.POINTER(dbl * 8), vp, vp, vp, C.POINTER(Trace), C.POINTER(Result))
     _core, _solver = core, sol
     return core, sol
 

@@ -258,6 +258,10 @@ struct lbfgsx_ctx
     int64_t graph_E = 0;
     void* graph_off = nullptr;
     void* graph_inc = nullptr;
+    // a mesh objective's list lives in the same three fields (a context has one bound objective, so one list;
+    // lbfgsx_objective_bind_mesh, mesh_topology.hip): graph_off is uint32[N+1], graph_inc holds K*E entries of K 32-bit words,
+    // graph_E the elements.  mesh_K, mesh_D: the element size and the unknowns per node of that list, 0 without one
+    int mesh_K = 0, mesh_D = 0;
 
     // L-BFGS-B work set (allocated with LBFGSX_FLAG_BOUNDED) lives in lbfgsb part
     void* lb = nullptr;

@@ -13,9 +13,10 @@
 // includes chain_kernels.cuh and instantiates its four kernels, which take the arguments of the four above) and a GRID
 // objective (one term per 2x2 cell of a row-major grid: a third wrapper around grid_kernels.cuh, whose struct also carries
 // the grid's shape), and a GRAPH objective (one term per edge of an index list and an optional one per node: a fourth
-// wrapper around graph_kernels.cuh, whose struct also carries the context's incidence list, graph_topology.hip).  A handle
-// carries its form; the four slots of the loaded-kernel table and everything that launches
-// them are the same.
+// wrapper around graph_kernels.cuh, whose struct also carries the context's incidence list, graph_topology.hip).  A fifth,
+// a MESH objective (one term per element of K nodes with D unknowns each and an optional one per node), is a wrapper around
+// mesh_kernels.cuh with the list of mesh_topology.hip.  A handle carries its form; the four slots of the loaded-kernel table
+// and everything that launches them are the same.
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
 
@@ -33,13 +34,14 @@
 
 namespace {
 
-const char* const kKernelNames[4][lbfgsx::JIT_NKERNELS] = {
+const char* const kKernelNames[5][lbfgsx::JIT_NKERNELS] = {
     {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial"},
     {"k_chain_eval", "k_chain_trial", "k_chain_b_eval", "k_chain_b_dg_maxstep_trial"},
     {"k_grid_eval", "k_grid_trial", "k_grid_b_eval", "k_grid_b_dg_maxstep_trial"},
-    {"k_graph_eval", "k_graph_trial", "k_graph_b_eval", "k_graph_b_dg_maxstep_trial"}};
-const char* const kObjStruct[4] = {"ObjTerm", "ObjChain", "ObjGrid", "ObjGraph"};
-const char* const kFormName[4] = {"term objective", "chain objective", "grid objective", "graph objective"};
+    {"k_graph_eval", "k_graph_trial", "k_graph_b_eval", "k_graph_b_dg_maxstep_trial"},
+    {"k_mesh_eval", "k_mesh_trial", "k_mesh_b_eval", "k_mesh_b_dg_maxstep_trial"}};
+const char* const kObjStruct[5] = {"ObjTerm", "ObjChain", "ObjGrid", "ObjGraph", "ObjMesh"};
+const char* const kFormName[5] = {"term objective", "chain objective", "grid objective", "graph objective", "mesh objective"};
 
 // ---- hipRTC, loaded on first use (a process that never compiles an objective does not need it)
 struct Rtc
@@ -114,10 +116,14 @@ std::string kernel_dir()
 std::string generate_chain(int dtype, int K, const char* body);
 std::string generate_grid(int dtype, const char* body);
 std::string generate_graph(int dtype, const char* node, const char* body);
+std::string generate_mesh(int dtype, int K, int D, const char* node, const char* body);
 
-// node: a graph objective's node body (null or empty: none); the other forms have one body
-std::string generate(int form, int dtype, int K, const char* body, const char* node)
+// node: a graph or mesh objective's node body (null or empty: none); the other forms have one body.  D: a mesh
+// objective's unknowns per node, 1 for the other forms
+std::string generate(int form, int dtype, int K, const char* body, const char* node, int D)
 {
+    if (form == LBFGSX_FORM_MESH)
+        return generate_mesh(dtype, K, D, node, body);
     if (form == LBFGSX_FORM_GRAPH)
         return generate_graph(dtype, node, body);
     if (form == LBFGSX_FORM_CHAIN)
@@ -282,8 +288,72 @@ std::string generate_graph(int dtype, const char* node, const char* body)
     return s;
 }
 
-bool valid_request(int form, int dtype, int K, const char* body, const char* node, std::string& why)
+// the wrapper of a mesh objective: the struct mesh_kernels.cuh asks for (K, D, the two terms and the incidence list), and
+// its four kernels.  The leading members are TermArgs' (launch_args.hpp: MeshArgs).  Each body has its own #line name
+std::string generate_mesh(int dtype, int K, int D, const char* node, const char* body)
 {
+    const bool has_node = node && *node;
+    std::string s;
+    s += "// generated by lbfgsx_objective_compile_mesh: one mesh objective for the fused kernels\n";
+    s += "#include \"mesh_kernels.cuh\"\n";
+    s += "namespace lbfgsx {\n";
+    s += std::string("typedef ") + (dtype == LBFGSX_F64 ? "double" : "float") + " term_scalar_t;\n";
+    s += "struct ObjMesh\n{\n";
+    s += "    typedef term_scalar_t T;\n";
+    s += "    static constexpr int K = " + std::to_string(K) + ";\n";
+    s += "    static constexpr int D = " + std::to_string(D) + ";\n";
+    s += std::string("    static constexpr bool kNode = ") + (has_node ? "true" : "false") + ";\n";
+    s += "    const T* p0;\n    const T* p1;\n    const T* p2;\n    const T* p3;\n    T c[8];\n";
+    s += "    const uint32_t* off;\n    const uint32_t* inc;\n    int64_t E, N;\n";
+    s += "    // the term of node i: x[d] = x[i*D + d] in, its D partial derivatives g out, its value returned\n";
+    s += "    __device__ __forceinline__ T node(const T (&x)[D], T (&g)[D], int64_t i) const\n    {\n";
+    if (has_node)
+    {
+        s += "#line 1 \"node_body\"\n";
+        s += node;
+        s += "\n#line 1 \"objective_wrapper\"\n";
+    }
+    else
+        s += "        for (int d = 0; d < D; d++)\n            g[d] = T(0);\n        return T(0);\n";
+    s += "    }\n";
+    s += "    // the term of element e with nodes v[0..K): x[k*D + d] = unknown d of node v[k] in, its K*D partial derivatives g out,\n";
+    s += "    // its value returned\n";
+    s += "    __device__ __forceinline__ T elem(const T (&x)[K * D], T (&g)[K * D], int64_t e, const int64_t (&v)[K]) const\n    {\n";
+    s += "#line 1 \"elem_body\"\n";
+    s += body;
+    s += "\n#line 1 \"objective_wrapper\"\n";
+    s += "    }\n";
+    s += "};\n";
+    s += "typedef term_scalar_t S;\n";
+    s += "template __global__ void k_mesh_eval<S, ObjMesh>(const S*, S*, int64_t, ObjMesh, RedWs, S*);\n";
+    s += "template __global__ void k_mesh_trial<S, ObjMesh>(const S*, const S*, S, S*, S*, int64_t, ObjMesh, RedWs, S*, int);\n";
+    s += "template __global__ void k_mesh_b_eval<S, ObjMesh>(const S*, S*, const S*, const S*, int64_t, ObjMesh, RedWs, S*);\n";
+    s += "template __global__ void k_mesh_b_dg_maxstep_trial<S, ObjMesh>(const S*, const S*, const S*, const S*, const S*, S, S*, "
+         "S*, int64_t, ObjMesh, RedWs, S*, int);\n";
+    s += "}  // namespace lbfgsx\n";
+    return s;
+}
+
+bool valid_request(int form, int dtype, int K, const char* body, const char* node, int D, std::string& why)
+{
+    if (form == LBFGSX_FORM_MESH)
+    {
+        if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
+            why = "mesh objective: unknown dtype";
+        else if (K < 2 || K > 4)
+            why = "mesh objective: K = " + std::to_string(K) + " is not supported: an element has K = 2, 3 or 4 nodes";
+        else if (D < 1 || D > 3)
+            why = "mesh objective: D = " + std::to_string(D) + " is not supported: a node has D = 1, 2 or 3 unknowns";
+        else if (!body || !*body)
+            why = "mesh objective: empty element body";
+        else if (std::strstr(body, "asm"))
+            why = "mesh objective: the element body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
+        else if (node && std::strstr(node, "asm"))
+            why = "mesh objective: the node body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
+        else
+            return true;
+        return false;
+    }
     if (form == LBFGSX_FORM_GRAPH)
     {
         if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
@@ -446,11 +516,11 @@ struct lbfgsx_objective
     bool cache_hit = false;
 };
 
-// one compiled (form, body, K, dtype): lives until the process ends (the cache)
+// one compiled (form, body, K, D, dtype): lives until the process ends (the cache)
 struct lbfgsx_objective_code
 {
     lbfgsx_objective self;  // what a context's binding points to: it outlives every handle given to a caller
-    int form = LBFGSX_FORM_TERM, dtype = LBFGSX_F64, K = 1;
+    int form = LBFGSX_FORM_TERM, dtype = LBFGSX_F64, K = 1, D = 1;
     std::vector<char> code;
     std::string lowered[lbfgsx::JIT_NKERNELS];
     long long vgprs[lbfgsx::JIT_NKERNELS] = {0, 0, 0, 0}, scratch[lbfgsx::JIT_NKERNELS] = {0, 0, 0, 0};
@@ -473,8 +543,8 @@ std::map<std::string, std::unique_ptr<lbfgsx_objective_code> >& cache()
     return m;
 }
 
-int compile_code(int form, int dtype, int K, const char* body, const char* node, std::unique_ptr<lbfgsx_objective_code>& out,
-                 std::string& log)
+int compile_code(int form, int dtype, int K, int D, const char* body, const char* node,
+                 std::unique_ptr<lbfgsx_objective_code>& out, std::string& log)
 {
     const Rtc& r = rtc();
     if (!r.error.empty())
@@ -482,7 +552,7 @@ int compile_code(int form, int dtype, int K, const char* body, const char* node,
         log = r.error;
         return LBFGSX_E_RUNTIME;
     }
-    const std::string src = generate(form, dtype, K, body, node);
+    const std::string src = generate(form, dtype, K, body, node, D);
     // the kernel headers ask for <hip/hip_runtime.h>; hipRTC has the runtime's declarations built in, so the name resolves
     // to an empty header instead of depending on where ROCm's headers are installed
     const char* hsrc[] = {"\n"};
@@ -523,6 +593,7 @@ int compile_code(int form, int dtype, int K, const char* body, const char* node,
     code->form = form;
     code->dtype = dtype;
     code->K = K;
+    code->D = D;
     code->compile_ms = ms;
     size_t cs = 0;
     bool ok = r.code_size(prog, &cs) == HIPRTC_SUCCESS && cs > 0;
@@ -581,22 +652,23 @@ int jit_launch(lbfgsx_ctx* c, int which, int grid, void** params)
 
 namespace {
 
-long long objective_source(int form, int dtype, int K, const char* body, char* out, size_t len, const char* node = nullptr)
+long long objective_source(int form, int dtype, int K, const char* body, char* out, size_t len, const char* node = nullptr,
+                           int D = 1)
 {
     std::string why;
-    if (!valid_request(form, dtype, K, body, node, why))
+    if (!valid_request(form, dtype, K, body, node, D, why))
     {
         lbfgsx::set_error(why);
         return LBFGSX_E_INVALID;
     }
-    const std::string s = generate(form, dtype, K, body, node);
+    const std::string s = generate(form, dtype, K, body, node, D);
     if (out && len > 0)
         std::snprintf(out, len, "%s", s.c_str());
     return (long long) s.size() + 1;
 }
 
 int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len,
-                      const char* node = nullptr)
+                      const char* node = nullptr, int D = 1)
 {
     if (log && log_len > 0)
         log[0] = '\0';
@@ -604,15 +676,17 @@ int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const 
         return LBFGSX_E_INVALID;
     *out = nullptr;
     std::string why;
-    if (!valid_request(form, dtype, K, body, node, why))
+    if (!valid_request(form, dtype, K, body, node, D, why))
     {
         lbfgsx::set_error(why);
         put_log(log, log_len, why);
         return LBFGSX_E_INVALID;
     }
     std::string key = std::to_string(form) + "/" + std::to_string(dtype) + "/" + std::to_string(K) + "/" + body;
-    if (form == LBFGSX_FORM_GRAPH)
+    if (form == LBFGSX_FORM_GRAPH || form == LBFGSX_FORM_MESH)
         key += std::string("\x1f") + (node ? node : "");  // both bodies
+    if (form == LBFGSX_FORM_MESH)
+        key += "\x1f" + std::to_string(D);
     std::lock_guard<std::mutex> lock(g_cache_mu);
     auto it = cache().find(key);
     const bool hit = it != cache().end();
@@ -620,7 +694,7 @@ int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const 
     {
         std::unique_ptr<lbfgsx_objective_code> code;
         std::string text;
-        const int rc = compile_code(form, dtype, K, body, node, code, text);
+        const int rc = compile_code(form, dtype, K, D, body, node, code, text);
         if (rc)
         {
             lbfgsx::set_error(std::string(kFormName[form]) + ": compilation failed\n" + text);
@@ -657,6 +731,10 @@ long long lbfgsx_objective_source_graph(int dtype, const char* node_body, const 
 {
     return objective_source(LBFGSX_FORM_GRAPH, dtype, 2, edge_body, out, len, node_body);
 }
+long long lbfgsx_objective_source_mesh(int dtype, int K, int D, const char* node_body, const char* elem_body, char* out, size_t len)
+{
+    return objective_source(LBFGSX_FORM_MESH, dtype, K, elem_body, out, len, node_body, D);
+}
 
 int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
 {
@@ -674,6 +752,11 @@ int lbfgsx_objective_compile_graph(lbfgsx_objective** out, int dtype, const char
                                    size_t log_len)
 {
     return objective_compile(LBFGSX_FORM_GRAPH, out, dtype, 2, edge_body, log, log_len, node_body);
+}
+int lbfgsx_objective_compile_mesh(lbfgsx_objective** out, int dtype, int K, int D, const char* node_body, const char* elem_body,
+                                  char* log, size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_MESH, out, dtype, K, elem_body, log, log_len, node_body, D);
 }
 
 void lbfgsx_objective_destroy(lbfgsx_objective* obj) { delete obj; }
@@ -696,6 +779,7 @@ int lbfgsx_objective_info(const lbfgsx_objective* obj, long long out[8])
 }
 
 int lbfgsx_objective_K(const lbfgsx_objective* obj) { return obj ? obj->code->K : LBFGSX_E_INVALID; }
+int lbfgsx_objective_dim(const lbfgsx_objective* obj) { return obj ? obj->code->D : LBFGSX_E_INVALID; }
 int lbfgsx_objective_dtype(const lbfgsx_objective* obj) { return obj ? obj->code->dtype : LBFGSX_E_INVALID; }
 int lbfgsx_objective_form(const lbfgsx_objective* obj) { return obj ? obj->code->form : LBFGSX_E_INVALID; }
 
@@ -776,6 +860,12 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
             return LBFGSX_E_INVALID;
         }
     }
+    else if (code->form == LBFGSX_FORM_MESH && c->n % code->D != 0)
+    {
+        lbfgsx::set_error("mesh objective: n = " + std::to_string(c->n) + " is not a multiple of D = " + std::to_string(code->D) +
+                          ": x holds D unknowns per node");
+        return LBFGSX_E_INVALID;
+    }
     else if (code->form == LBFGSX_FORM_TERM && c->n % code->K != 0)
     {
         lbfgsx::set_error("term objective: n = " + std::to_string(c->n) + " is not a multiple of K = " + std::to_string(code->K));
@@ -796,7 +886,7 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
         for (int k = 0; k < lbfgsx::JIT_NKERNELS; k++)
             c->term_fn[k] = it->second.fn[k];
     }
-    if (code->form != LBFGSX_FORM_GRAPH && c->graph_inc)
+    if (code->form != LBFGSX_FORM_GRAPH && code->form != LBFGSX_FORM_MESH && c->graph_inc)
     {
         (void) lbfgsx::stream_sync(c->stream);  // no launch still walks the list
         lbfgsx::graph_topology_free(c);
@@ -834,6 +924,11 @@ int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void
     if (obj && obj->code->form == LBFGSX_FORM_GRAPH)
     {
         lbfgsx::set_error("a graph objective is bound with its edges: lbfgsx_objective_bind_graph");
+        return LBFGSX_E_INVALID;
+    }
+    if (obj && obj->code->form == LBFGSX_FORM_MESH)
+    {
+        lbfgsx::set_error("a mesh objective is bound with its elements: lbfgsx_objective_bind_mesh");
         return LBFGSX_E_INVALID;
     }
     return objective_bind(c, obj, 0, 0, p, cs, id);
@@ -945,6 +1040,74 @@ int lbfgsx_objective_topology(lbfgsx_ctx* c, int64_t* E, uint32_t* off, int32_t*
         *E = c->graph_E;
     lbfgsx::DeviceGuard dev_guard_(c->device);
     return lbfgsx::graph_topology_read(c, off, other, edge_side);
+}
+
+int lbfgsx_objective_bind_mesh(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t E, const int32_t* elems, int elems_on_device,
+                               const void* const p[4], const double cs[8], int* id)
+{
+    if (!c || !obj)
+        return LBFGSX_E_INVALID;
+    // whatever is refused below leaves no objective bound
+    c->st_valid = false;
+    c->spec_valid = false;
+    c->term = nullptr;
+    c->term_np = 0;
+    c->term_form = LBFGSX_FORM_TERM;
+    if (obj->code->form != LBFGSX_FORM_MESH)
+    {
+        lbfgsx::set_error(std::string("lbfgsx_objective_bind_mesh: the handle is a ") + kFormName[obj->code->form] +
+                          ", not a mesh objective (lbfgsx_objective_compile_mesh)");
+        return LBFGSX_E_INVALID;
+    }
+    if (obj->code->dtype != c->dtype)
+    {
+        lbfgsx::set_error("lbfgsx_objective_bind: the objective was compiled for the other dtype");
+        return LBFGSX_E_INVALID;
+    }
+    const int K = obj->code->K, D = obj->code->D;
+    const int64_t lim = 2147483647, elim = 1073741823;
+    std::string why;
+    if (E < 1 || !elems)
+        why = "E = " + std::to_string(E) + ": a mesh objective has at least one element (E >= 1) and its connectivity table";
+    else if (E > elim)
+        why = "E = " + std::to_string(E) + " exceeds 2^30 - 1 = " + std::to_string(elim) +
+              ": an incidence entry holds (e << 2) | slot in 32 bits";
+    else if (c->n % D != 0)
+        why = "n = " + std::to_string(c->n) + " is not a multiple of D = " + std::to_string(D) + ": x holds D unknowns per node";
+    else if (c->n > lim)
+        why = "n = " + std::to_string(c->n) + " exceeds 2^31 - 1 = " + std::to_string(lim) + ": node indices are int32";
+    if (!why.empty())
+    {
+        lbfgsx::set_error("mesh objective: " + why);
+        return LBFGSX_E_INVALID;
+    }
+    // the list first: a context whose indices were refused keeps no mesh objective bound, so nothing can be launched on them
+    {
+        lbfgsx::DeviceGuard dev_guard_(c->device);
+        const int rc = lbfgsx::mesh_topology_build(c, K, D, elems, E, elems_on_device);
+        if (rc)
+            return rc;
+    }
+    const int rc = objective_bind(c, obj, 0, 0, p, cs, id);
+    if (rc)
+    {
+        lbfgsx::DeviceGuard dev_guard_(c->device);
+        lbfgsx::graph_topology_free(c);
+    }
+    return rc;
+}
+
+int lbfgsx_objective_mesh_topology(lbfgsx_ctx* c, int64_t* E, uint32_t* off, uint32_t* words)
+{
+    if (!c || !c->term || c->term_form != LBFGSX_FORM_MESH || !c->graph_inc)
+    {
+        lbfgsx::set_error("lbfgsx_objective_mesh_topology: no mesh objective is bound to this context");
+        return LBFGSX_E_INVALID;
+    }
+    if (E)
+        *E = c->graph_E;
+    lbfgsx::DeviceGuard dev_guard_(c->device);
+    return lbfgsx::mesh_topology_read(c, off, words);
 }
 
 int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4])

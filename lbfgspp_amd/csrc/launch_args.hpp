@@ -127,22 +127,36 @@ struct GraphArgs
     const GraphEntry* inc;
     int64_t E;
 };
+// the by-value argument of a mesh objective's kernels: layout of the generated struct ObjMesh (TermArgs, then the context's
+// incidence list: uint32 off[N+1], K*E entries of K 32-bit words (mesh_topology.hip), the E elements and the N nodes)
+template <class T>
+struct MeshArgs
+{
+    TermArgs<T> t;
+    const uint32_t* off;
+    const uint32_t* inc;
+    int64_t E, N;
+};
 // the objective argument of the bound handle's kernels, by its form: &term for a term or chain objective, &grid for a grid
-// one, &graph for a graph one
+// one, &graph for a graph one, &mesh for a mesh one
 template <class T>
 struct BoundArgs
 {
     TermArgs<T> term;
     GridArgs<T> grid;
     GraphArgs<T> graph;
+    MeshArgs<T> mesh;
     void* ptr;
     explicit BoundArgs(const lbfgsx_ctx* c)
         : term(term_args<T>(c)),
           grid{term, c->term_rows, c->term_cols},
-          graph{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const GraphEntry*>(c->graph_inc), c->graph_E}
+          graph{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const GraphEntry*>(c->graph_inc), c->graph_E},
+          mesh{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const uint32_t*>(c->graph_inc), c->graph_E,
+               c->mesh_D ? c->n / c->mesh_D : 0}
     {
         ptr = (c->term_form == LBFGSX_FORM_GRID)    ? static_cast<void*>(&grid)
               : (c->term_form == LBFGSX_FORM_GRAPH) ? static_cast<void*>(&graph)
+              : (c->term_form == LBFGSX_FORM_MESH)  ? static_cast<void*>(&mesh)
                                                     : static_cast<void*>(&term);
     }
     BoundArgs(const BoundArgs&) = delete;
@@ -156,11 +170,25 @@ inline void graph_model_add(const lbfgsx_ctx* c, int vectors_gathered)
     if (c->term_form == LBFGSX_FORM_GRAPH)
         model_add(double(c->n + 1) * 4 + double(2 * c->graph_E) * 8 + double(2 * c->graph_E) * sizeof(T) * vectors_gathered);
 }
+// what a mesh objective adds: (N+1)*4 bytes of offsets, K*E entries of 4K bytes, and (K-1)*D gathered values per entry
+template <class T>
+inline void mesh_model_add(const lbfgsx_ctx* c, int vectors_gathered)
+{
+    if (c->term_form == LBFGSX_FORM_MESH)
+    {
+        const double K = c->mesh_K, D = c->mesh_D, KE = K * double(c->graph_E);
+        model_add(double(c->n / c->mesh_D + 1) * 4 + KE * 4 * K + KE * (K - 1) * D * sizeof(T) * vectors_gathered);
+    }
+}
 // graph_topology.hip: the incidence list of the context (ctx.hpp: graph_off, graph_inc, graph_E).  build validates the
 // indices first and leaves the context without a list when an edge offends (LBFGSX_E_INVALID, the edge named)
 int graph_topology_build(lbfgsx_ctx* c, const int32_t* ei, const int32_t* ej, int64_t E, int on_device);
 int graph_topology_read(lbfgsx_ctx* c, uint32_t* off, int32_t* other, uint32_t* edge_side);
 void graph_topology_free(lbfgsx_ctx* c);
+// mesh_topology.hip: the same for a mesh objective's elems[E*K], into the same fields of the context (freed by
+// graph_topology_free).  words: K*E*K uint32, off: N+1
+int mesh_topology_build(lbfgsx_ctx* c, int K, int D, const int32_t* elems, int64_t E, int on_device);
+int mesh_topology_read(lbfgsx_ctx* c, uint32_t* off, uint32_t* words);
 inline bool term_bound(const lbfgsx_ctx* c, int objective) { return objective == LBFGSX_OBJ_BOUND && c->term != nullptr; }
 // one launch of loaded kernel `which` of the bound objective on the context's stream, block of kBlock threads; params as
 // hipModuleLaunchKernel takes them (one pointer per kernel argument)

@@ -50,6 +50,7 @@ static int dg_maxstep_trial_term_t(lbfgsx_ctx* c, T step, double* r4)
     DgTrialLaunch<T> a = dg_maxstep_trial_launch<T>(c, step, c->term_np);
     BoundArgs<T> obj(c);
     graph_model_add<T>(c, 2);
+    mesh_model_add<T>(c, 2);
     void* params[] = {&a.xp, &a.g0, &a.d, &a.lb, &a.ub, &a.step, &a.x, &a.g, &a.n, obj.ptr, &a.ws, &a.out, &a.rev};
     const int rc = jit_launch(c, JIT_K_B_DG_MAXSTEP_TRIAL, a.grid, params);
     if (rc)

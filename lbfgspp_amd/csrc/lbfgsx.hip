@@ -1059,6 +1059,7 @@ static int trial_term_t(lbfgsx_ctx* c, T step, double* out2)
     lbfgsx::TrialLaunch<T> a = lbfgsx::trial_launch<T>(c, step, c->term_np);
     lbfgsx::BoundArgs<T> obj(c);
     lbfgsx::graph_model_add<T>(c, 2);
+    lbfgsx::mesh_model_add<T>(c, 2);
     void* params[] = {&a.xp, &a.d, &a.step, &a.x, &a.g, &a.n, obj.ptr, &a.ws, &a.out, &a.rev};
     const int rc = lbfgsx::jit_launch(c, lbfgsx::JIT_K_TRIAL, a.grid, params);
     if (rc)

@@ -34,13 +34,15 @@ struct lbfgsx_solver
                           const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) = 0;
     virtual void minimize_fn(int64_t n, lbfgsx_objective_fn fn, void* user, void* x, const void* lb, const void* ub,
                              lbfgsx_trace* tr, lbfgsx_result* out) = 0;
-    // the edges of a graph objective, and the element counts of its host data arrays (null: n each)
+    // the edges of a graph objective, and the element counts of its host data arrays (null: n each); elems: the
+    // connectivity table of a mesh objective (E rows) in place of ei and ej, null for a graph objective
     struct GraphSpec
     {
         int64_t E;
         const int32_t *ei, *ej;
         int on_device;
         const int64_t* counts;
+        const int32_t* elems;
     };
     // rows, cols: the shape of a grid objective, 0 for the other forms; gr: null for every form but a graph objective
     virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const GraphSpec* gr,
@@ -220,9 +222,14 @@ struct LbfgsImpl : lbfgsx_solver
     {
         GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
-        if (gr)
+        MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
+        if (gr && gr->elems)
+            meshed.elements(gr->E, gr->elems, gr->on_device != 0);
+        else if (gr)
             graphed.edges(gr->E, gr->ei, gr->ej, gr->on_device != 0);
-        TermObjective<Scalar>& f = gr ? static_cast<TermObjective<Scalar>&>(graphed) : shaped;
+        TermObjective<Scalar>& f = (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
+                                   : gr             ? static_cast<TermObjective<Scalar>&>(graphed)
+                                                    : shaped;
         fill_term<Scalar>(f, p, host_mask, c, gr ? gr->counts : nullptr);
         run(f, n, x, tr, out);
     }
@@ -332,9 +339,14 @@ struct LbfgsbImpl : lbfgsx_solver
     {
         GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
-        if (gr)
+        MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
+        if (gr && gr->elems)
+            meshed.elements(gr->E, gr->elems, gr->on_device != 0);
+        else if (gr)
             graphed.edges(gr->E, gr->ei, gr->ej, gr->on_device != 0);
-        TermObjective<Scalar>& f = gr ? static_cast<TermObjective<Scalar>&>(graphed) : shaped;
+        TermObjective<Scalar>& f = (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
+                                   : gr             ? static_cast<TermObjective<Scalar>&>(graphed)
+                                                    : shaped;
         fill_term<Scalar>(f, p, host_mask, c, gr ? gr->counts : nullptr);
         run(f, n, x, lb, ub, tr, out);
     }
@@ -917,6 +929,8 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
             throw std::invalid_argument("a grid objective is minimised with its shape: lbfgsx_solver_minimize_grid");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRAPH)
             throw std::invalid_argument("a graph objective is minimised with its edges: lbfgsx_solver_minimize_graph");
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_MESH)
+            throw std::invalid_argument("a mesh objective is minimised with its elements: lbfgsx_solver_minimize_mesh");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_CHAIN)
         {
             if (n < K)
@@ -976,6 +990,9 @@ int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, 
     const int bad = guarded(out, [&]() {
         if (!s || !obj || n <= 0)
             throw std::invalid_argument("lbfgsx_solver_minimize_graph: invalid argument");
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_MESH)
+            throw std::invalid_argument("lbfgsx_solver_minimize_graph: the handle is a mesh objective: it is minimised with its "
+                                        "elements, lbfgsx_solver_minimize_mesh");
         if (lbfgsx_objective_form(obj) != LBFGSX_FORM_GRAPH)
             throw std::invalid_argument("lbfgsx_solver_minimize_graph: the handle is not a graph objective (lbfgsx_objective_compile_graph)");
         if (lbfgsx_objective_dtype(obj) != s->dtype)
@@ -992,7 +1009,40 @@ int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, 
         std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_graph: no HIP device available (this library has no CPU fallback)");
         return out->status;
     }
-    const lbfgsx_solver::GraphSpec gr = {E, ei, ej, edges_on_device, counts};
+    const lbfgsx_solver::GraphSpec gr = {E, ei, ej, edges_on_device, counts, nullptr};
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+}
+
+int lbfgsx_solver_minimize_mesh(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t E, const int32_t* elems,
+                                int elems_on_device, const void* const p[4], int host_mask, const int64_t counts[4],
+                                const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
+                                lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    const int bad = guarded(out, [&]() {
+        if (!s || !obj || n <= 0)
+            throw std::invalid_argument("lbfgsx_solver_minimize_mesh: invalid argument");
+        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_MESH)
+            throw std::invalid_argument("lbfgsx_solver_minimize_mesh: the handle is not a mesh objective (lbfgsx_objective_compile_mesh)");
+        if (lbfgsx_objective_dtype(obj) != s->dtype)
+            throw std::invalid_argument("lbfgsx_solver_minimize_mesh: the objective was compiled for the other dtype");
+        if (E < 1 || !elems)
+            throw std::invalid_argument("mesh objective: E = " + std::to_string(E) +
+                                        ": a mesh objective has at least one element (E >= 1) and its connectivity table");
+        const int D = lbfgsx_objective_dim(obj);
+        if (n % D != 0)
+            throw std::invalid_argument("mesh objective: n = " + std::to_string(n) + " is not a multiple of D = " + std::to_string(D) +
+                                        ": x holds D unknowns per node");
+    });
+    if (bad)
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_mesh: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    const lbfgsx_solver::GraphSpec gr = {E, nullptr, nullptr, elems_on_device, counts, elems};
     return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 }

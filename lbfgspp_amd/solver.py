@@ -8,7 +8,8 @@ Exceptions: std::invalid_argument -> ValueError, std::logic_error -> ArithmeticE
 std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device objective
 (`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`), the caller's own term compiled into the same kernels (`TermObjective(body)`,
 `ChainObjective(body)` for terms that overlap, `GridObjective(body, shape)` for 2x2-cell terms on a grid, or
-`GraphObjective(edge_body, edges)` for edge terms over an index list)
+`GraphObjective(edge_body, edges)` for edge terms over an index list,
+`MeshObjective(elem_body, elements, dim)` for K-node elements with vector unknowns)
 or the caller's own callable, `DeviceObjective(fn)`: fn(x, grad) -> float on torch
 tensors that alias the library's device vectors.  All O(n) work of the solver runs in the HIP library, Python only passes
 pointers.  There is no CPU fallback: without the built extension or a GPU these calls raise.
@@ -335,6 +336,67 @@ class GraphObjective(TermObjective):
         return (n, self.E)
 
 
+class MeshObjective(TermObjective):
+    """An objective on a mesh: N nodes with D = dim unknowns each (x node-major, x[v*D + d], n = N*D), E elements of K nodes
+    each as an (E, K) connectivity table, K in {2, 3, 4}, D in {1, 2, 3}, and
+    f(x) = sum over nodes v of psi(x_v; v) + sum over elements e of phi(x at the K nodes of e; e) (include/lbfgsx.h, "mesh
+    objectives").  elem_body sees T, K, D, const T x[K*D] (x[k*D + d]: unknown d of the node in slot k), T g[K*D] (to fill),
+    int64_t e, const int64_t v[K], p0..p3 and c[8] and returns the element's value; node_body (optional) sees T, D,
+    const T x[D], T g[D], int64_t i, p0..p3, c[8].  grad[v*D + d] is the node term's g[d], then the g_e[slot*D + d] of the
+    elements that contain v in ascending e.
+
+        springs = MeshObjective("T s = T(0); for (int d = 0; d < D; d++) { const T u = x[d] - x[D + d]; s = s + u * u; }"
+                                "const T r = s - p0[e];"
+                                "for (int d = 0; d < D; d++) { const T u = x[d] - x[D + d]; g[d] = r * u; g[D + d] = T(0) - r * u; }"
+                                "return T(0.25) * (r * r);", elements=pairs, dim=3, data=(rest2,))
+
+    elements is range-checked and converted to int32 here, and copied, validated (0 <= index < N, pairwise distinct within an
+    element) and turned into the incidence list on the device at every minimise.  Each data[k] has n, N or E elements.
+    Otherwise a GraphObjective's interface; usable wherever one is, refused where one is."""
+    _NAME = "MeshObjective"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_mesh", "lbfgsx_objective_source_mesh"
+
+    def __init__(self, elem_body, elements, dim, node_body=None, data=(), scalars=()):
+        a = elements
+        if _is_torch(a):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if a.ndim != 2:
+            raise ValueError("MeshObjective: elements must be an (E, K) integer array, not one of shape %r" % (a.shape,))
+        if a.dtype.kind not in "iu":
+            raise ValueError("MeshObjective: elements must be an (E, K) integer array, not one of dtype %s" % a.dtype)
+        if a.shape[1] not in (2, 3, 4):
+            raise ValueError("MeshObjective: K = %d is not supported: an element has K = 2, 3 or 4 nodes" % a.shape[1])
+        if a.shape[0] < 1:
+            raise ValueError("MeshObjective: E = 0: a mesh objective has at least one element")
+        for v in (int(a.min()), int(a.max())):
+            if v < -2 ** 31 or v > 2 ** 31 - 1:
+                raise ValueError("MeshObjective: elements holds %d, which does not fit a 32-bit node index" % v)
+        if a.shape[0] > 2 ** 30 - 1:
+            raise ValueError("MeshObjective: E = %d exceeds 2^30 - 1" % a.shape[0])
+        if dim not in (1, 2, 3):
+            raise ValueError("MeshObjective: dim = %r is not supported: a node has D = 1, 2 or 3 unknowns" % (dim,))
+        self.elements = np.ascontiguousarray(a, np.int32)
+        self.E, self.K, self.D = int(a.shape[0]), int(a.shape[1]), int(dim)
+        self.body = str(elem_body)
+        self.node_body = None if not node_body else str(node_body)
+        self._h = {}
+        self.set_data(*data)
+        self.set_scalars(*scalars)
+
+    def _form_args(self):
+        return (self.K, self.D, self.node_body.encode() if self.node_body else None)
+
+    def _check_n(self, n):
+        if n % self.D:
+            raise ValueError("MeshObjective: n = %d is not a multiple of D = %d: x holds D unknowns per node" % (n, self.D))
+        if n > 2 ** 31 - 1:
+            raise ValueError("MeshObjective: n = %d exceeds 2^31 - 1: node indices are int32" % n)
+
+    def _data_sizes(self, n):
+        return (n, n // self.D, self.E)
+
+
 class TraceBuffer:
     """Per-evaluation record (fx and x[::stride]) for the parity tests."""
 
@@ -520,7 +582,10 @@ class _SolverBase:
             torch.cuda.current_stream().synchronize()  # the data arrays are complete when the library reads them
         tail = (C.byref(ptrs), mask, C.byref(cs), self._ptr(x), self._ptr(lb), self._ptr(ub), C.byref(trace.c) if trace else None,
                 C.byref(res))
-        if isinstance(f, GraphObjective):
+        if isinstance(f, MeshObjective):
+            rc = self._sol.lbfgsx_solver_minimize_mesh(self._h, h, n, f.E, f.elements.ctypes.data_as(C.POINTER(C.c_int32)), 0,
+                                                       tail[0], mask, C.byref(counts), *tail[2:])
+        elif isinstance(f, GraphObjective):
             rc = self._sol.lbfgsx_solver_minimize_graph(self._h, h, n, f.E, f.ei.ctypes.data_as(C.POINTER(C.c_int32)),
                                                         f.ej.ctypes.data_as(C.POINTER(C.c_int32)), 0, tail[0], mask,
                                                         C.byref(counts), *tail[2:])
@@ -546,7 +611,8 @@ class _SolverBase:
             return self._minimize_obj(f, n, x, lb, ub, trace)
         if not hasattr(f, "objective"):
             raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body), "
-                            "GridObjective(body, shape), GraphObjective(edge_body, edges) or DeviceObjective(fn)")
+                            "GridObjective(body, shape), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim) "
+                            "or DeviceObjective(fn)")
         res = L.Result()
         a = None if f.a is None else np.ascontiguousarray(f.a, _NP[self.dtype])
         b = None if f.b is None else np.ascontiguousarray(f.b, _NP[self.dtype])
