@@ -518,7 +518,9 @@ int lbfgsx_b_gram_fused_ex(lbfgsx_ctx* c, int mask, int vsel_id, int prologue, c
 /* The same pass that additionally returns the UN-ROUNDED double-double sums of the 2c x 2c block: gram_dd[2 e],
  * gram_dd[2 e + 1] = (hi, lo) of entry e = i (i + 1) / 2 + j (i >= j), 2c (2c + 1) doubles.  They let the caller form
  * the Gram of a subset through the complement identity  W_P'W_P = W_F'W_F - W_{F\P}'W_{F\P}: both sums are accurate to
- * ~2^-100, so their difference rounds to the same double as the direct sum -- and in a BOXCQP sweep the complement
+ * ~2^-100 of sum |terms| in practice -- provably, and asserted against exact sums by tests/test_bounded_sums_gpu.py, to
+ * 2 (k 2^-53)^2 sum |terms| over k rows (2^-69 at k = 3e5) --, so their difference rounds to the same double as the direct
+ * sum unless that lies as close to a rounding boundary -- and in a BOXCQP sweep the complement
  * L u U holds 10^1..10^3 rows against |P| ~ n/2.  gram and wtv may be NULL.  Default Gram kernel only. */
 int lbfgsx_b_gram_fused_dd(lbfgsx_ctx* c, int mask, int vsel_id, int prologue, const double* coef1, const double* coef2,
                            double* gram, double* wtv, double* gram_dd);
