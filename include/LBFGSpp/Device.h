@@ -109,6 +109,12 @@ class TermObjective
     bool m_edges_dev = false;
     const std::int32_t* m_elems = nullptr;  // a MeshObjective's connectivity table of m_E rows; null: bound without one
     std::int64_t m_count[4] = {0, 0, 0, 0};  // elements of m_host[k]; 0: n
+    // a LinearObjective's CSR matrix; m_rowptr null: bound without one
+    std::int64_t m_R = 0, m_nnz = 0;
+    const std::int32_t *m_rowptr = nullptr, *m_col = nullptr;
+    const Scalar* m_val = nullptr;
+    bool m_matrix_dev = false;
+    int m_lanes = 0;
 
     TermObjective(const TermObjective&) = delete;
     TermObjective& operator=(const TermObjective&) = delete;
@@ -126,7 +132,8 @@ protected:
     {
         std::vector<char> log(16384, '\0');
         const int dt = detail::dtype_of<Scalar>::value;
-        const int rc = (form == LBFGSX_FORM_MESH)    ? lbfgsx_objective_compile_mesh(&m_h, dt, K, D, node.c_str(), body.c_str(), log.data(), log.size())
+        const int rc = (form == LBFGSX_FORM_LINEAR)  ? lbfgsx_objective_compile_linear(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
+                       : (form == LBFGSX_FORM_MESH)  ? lbfgsx_objective_compile_mesh(&m_h, dt, K, D, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRAPH) ? lbfgsx_objective_compile_graph(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRID)  ? lbfgsx_objective_compile_grid(&m_h, dt, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_CHAIN) ? lbfgsx_objective_compile_chain(&m_h, dt, K, body.c_str(), log.data(), log.size())
@@ -147,6 +154,17 @@ protected:
         m_E = E;
         m_elems = elems;
         m_edges_dev = on_device;
+    }
+    void set_matrix(std::int64_t R, std::int64_t nnz, const std::int32_t* rowptr, const std::int32_t* col, const Scalar* val,
+                    bool on_device, int lanes)
+    {
+        m_R = R;
+        m_nnz = nnz;
+        m_rowptr = rowptr;
+        m_col = col;
+        m_val = val;
+        m_matrix_dev = on_device;
+        m_lanes = lanes;
     }
     void set_edges(std::int64_t E, const std::int32_t* ei, const std::int32_t* ej, bool on_device)
     {
@@ -212,7 +230,10 @@ public:
                 p[k] = dev;
             }
         }
-        if (m_elems)
+        if (m_rowptr || m_R || m_nnz)
+            detail::check(lbfgsx_objective_bind_linear(c, m_h, m_R, m_nnz, m_rowptr, m_col, m_val, m_matrix_dev ? 1 : 0, m_lanes, p,
+                                                       m_c, &id));
+        else if (m_elems)
             detail::check(lbfgsx_objective_bind_mesh(c, m_h, m_E, m_elems, m_edges_dev ? 1 : 0, p, m_c, &id));
         else if (m_E || m_ei || m_ej)
             detail::check(lbfgsx_objective_bind_graph(c, m_h, m_E, m_ei, m_ej, m_edges_dev ? 1 : 0, p, m_c, &id));
@@ -313,16 +334,44 @@ public:
     }
 };
 
+// A linear model fitted to data: f(x) = sum over coordinates j of psi(x[j]; j) + sum over the R rows of phi(z_r; r), z = A x,
+// A sparse R x n in CSR (include/lbfgsx.h, "linear-model objectives").  The row body sees T, const T z, T& dz (to assign:
+// phi'(z)), int64_t r, p0..p3 and c[8] and returns phi(z); the coordinate body (optional) is a GraphObjective's node body.
+//     LinearObjective<double> f("const T m = T(1) - p0[r] * z; const T h = m > T(0) ? m : T(0);"
+//                               "dz = T(-2) * (p0[r] * h); return h * h;", "g[0] = c[0] * x[0]; return T(0.5) * (c[0] * (x[0] * x[0]));");
+//     f.matrix(R, nnz, rowptr, col, val).host_data(0, labels, R).scalars({1e-3});      solver.minimize(f, x, fx);
+// matrix(): int32 rowptr[R+1], col[nnz] and Scalar val[nnz] on the host (or on the device: on_device = true) that stay valid
+// until minimize() returns; the solver's context copies and validates them at every minimize() (a malformed rowptr or a
+// column outside [0, n) throws std::invalid_argument with the position named).  lanes: the lanes that share a row, 0 = by the
+// library's rule.  Otherwise a GraphObjective's interface; accepted wherever one is, refused where it is.
+template <typename Scalar>
+class LinearObjective : public TermObjective<Scalar>
+{
+public:
+    explicit LinearObjective(const std::string& row_body, const std::string& coord_body = std::string())
+        : TermObjective<Scalar>(LBFGSX_FORM_LINEAR, 1, row_body, "LinearObjective: ", coord_body)
+    {
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile_linear); it stays the caller's
+    explicit LinearObjective(const lbfgsx_objective* compiled) : TermObjective<Scalar>(compiled) {}
+    LinearObjective& matrix(std::int64_t R, std::int64_t nnz, const std::int32_t* rowptr, const std::int32_t* col, const Scalar* val,
+                            bool on_device = false, int lanes = 0)
+    {
+        this->set_matrix(R, nnz, rowptr, col, val, on_device, lanes);
+        return *this;
+    }
+};
+
 namespace detail {
 // the objectives compiled at run time into the fused kernels: a TermObjective, a ChainObjective, a GridObjective, a
-// GraphObjective or a MeshObjective
+// GraphObjective, a MeshObjective or a LinearObjective
 template <typename Scalar, typename Foo>
 struct is_compiled_objective
 {
     typedef typename std::decay<Foo>::type F;
     static constexpr bool value = std::is_same<F, TermObjective<Scalar> >::value || std::is_same<F, ChainObjective<Scalar> >::value ||
                                   std::is_same<F, GridObjective<Scalar> >::value || std::is_same<F, GraphObjective<Scalar> >::value ||
-                                  std::is_same<F, MeshObjective<Scalar> >::value;
+                                  std::is_same<F, MeshObjective<Scalar> >::value || std::is_same<F, LinearObjective<Scalar> >::value;
 };
 }  // namespace detail
 

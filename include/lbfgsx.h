@@ -199,7 +199,7 @@ int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4]);
  * lbfgsx_solver_minimize_obj and the four evaluation entry points take it like a term objective's.  Binding to a context
  * with n < K is refused (any n >= K is accepted: n need not be a multiple of anything).  The compile log, the refusal of
  * asm and the line numbers are those of lbfgsx_objective_compile. */
-enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2, LBFGSX_FORM_GRAPH = 3, LBFGSX_FORM_MESH = 4 };
+enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2, LBFGSX_FORM_GRAPH = 3, LBFGSX_FORM_MESH = 4, LBFGSX_FORM_LINEAR = 5 };
 int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len);
 long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char* out, size_t len);
 int lbfgsx_objective_form(const lbfgsx_objective* obj);
@@ -334,6 +334,67 @@ int lbfgsx_objective_bind_mesh(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64
                                const void* const p[4], const double cs[8], int* id);
 int lbfgsx_objective_mesh_topology(lbfgsx_ctx* c, int64_t* E, uint32_t* off, uint32_t* words);
 int lbfgsx_objective_dim(const lbfgsx_objective* obj);
+/* ---- linear-model objectives: sparse-matrix terms phi(a_r . x) ------------------------------------------------------------
+ * x has n coordinates, the WEIGHTS; the caller gives a sparse R x n matrix A in CSR (int32 rowptr[R+1], int32 col[nnz],
+ * T val[nnz]; row r is one SAMPLE), and
+ *     f(x) = sum over coordinates j of psi(x[j]; j)  +  sum over rows r of phi(z_r; r),      z = A x
+ * -- logistic regression, least squares, non-negative least squares under L-BFGS-B, Poisson and Huber regression, L2-loss
+ * SVMs.  A row couples as many coordinates as it has entries.  Both terms are HIP/C++ text:
+ *   row_body   sees T, const T z (the row's product with x), T& dz (to assign: phi'(z)), int64_t r, p0..p3 and c[8]; it
+ *              returns phi(z).  Per-row data is indexed by the body, p0[r] (lbfgsx_objective_upload_count, count = R);
+ *   coord_body (NULL or empty: none) is a graph objective's node body: T, const T x[1], T g[1], int64_t i, p0..p3, c[8];
+ *              it returns psi.
+ * Semantics (a numpy restatement with one operation per source operation is bit-exact; tests/linear_ref.py):
+ *   z_r     L lanes share a row, L a power of two in 1..64.  Lane l takes the row's entries k0+l, k0+l+L, .. in ascending
+ *           order: s_l = val[k]*x[col[k]] for its first entry, s_l = s_l + val[k]*x[col[k]] after it; a lane with no entry
+ *           holds +0.  Then s_l = s_l + s_{l+h} for l < h, h = L/2, L/4, .., 1, and z_r = s_0.  A row's entries are taken in
+ *           the caller's order, duplicate (r, c) entries contribute twice, an empty row has z = +0 and still has its phi.
+ *           L is fixed at bind: the largest power of two <= max(1, nnz / R) (integer division), at most 64, so that a row of
+ *           average length gives a lane one or two entries; the bind call's `lanes` forces it (0: by the rule);
+ *   grad[j] psi's g[0] if there is a coordinate body, then val*w[r], w[r] = phi'(z_r), over the entries of column j in
+ *           ascending r and within one r in the caller's order (a stable sort of the CSR entries by column), started from
+ *           the first contribution; a column with none gets +0.  A column with more than C = 4096 entries is LONG (an
+ *           intercept column has R): it is cut into chunks of C consecutive entries; chunk b's partial is formed by 256
+ *           threads, thread t summing the products of the chunk's entries t, t+256, .. in ascending order from its first
+ *           (+0 if none), then s_t = s_t + s_{t+h} for t < h, h = 128 .. 1, the partial being thread 0's value; grad[j] is
+ *           psi's g[0], then the chunk partials in ascending b, started from the first contribution;
+ *   f       the order-independent (compensated) sum the other forms use, over all psi and all phi values;
+ *   one rounding per source operation, no contraction.
+ * An evaluation is two launches on one stream with no host wait between them (csrc/linear_kernels.cuh): the ROW pass
+ * (k_lin_rows; k_lin_rows_trial gathers xp[c] + step*d[c], the statement c's owner executes, never the x being written)
+ * writes w[R] and v[R] = phi(z_r) into vectors the context owns, the COLUMN pass (k_lin_eval, k_lin_trial, k_lin_b_eval,
+ * k_lin_b_dg_maxstep_trial: the arguments, tile order, reductions and completion word of the other forms' kernels) forms
+ * the gradient per owned coordinate and adds v to f.  Its grid covers the longer of n and R.  A matrix with a long column
+ * has a third launch between them, k_lin_long_cols (one block per chunk, precompiled in the library).  No float atomic.
+ * lbfgsx_objective_compile_linear caches by (form, both bodies, dtype); the form is LBFGSX_FORM_LINEAR, lbfgsx_objective_K
+ * returns 1.  The word asm in either body is refused; the compile log counts lines per body ("row_body", "coord_body").
+ * lbfgsx_objective_info's maxima cover all six kernels.
+ * lbfgsx_objective_bind_linear copies the three arrays (host pointers, or device pointers when matrix_on_device != 0; a
+ * later change of the caller's arrays has no effect) and builds on the device what the context owns
+ * (csrc/linear_topology.hip): the transposed list (uint32 colptr[n+1]; per entry its row, value and CSR position) by a
+ * stable radix sort, and the table of long columns and their chunks.  The bind issues 6 launches.  VALIDATION COMES FIRST,
+ * in the bind's first launch, the only one of a refused bind: rowptr[0] = 0, rowptr non-decreasing, rowptr[R] = nnz, every
+ * col in [0, n).  An offender returns LBFGSX_E_INVALID with the first offending position, its value, n (or R and nnz) and the
+ * number of offenders in the message and leaves no objective bound.  Also refused, the values named: a handle of another
+ * form, R < 1, nnz < 1, R, nnz or n above 2^31 - 1, lanes not 0 or a power of two <= 64.  Rebuilt at every bind; nothing is
+ * cached by pointer.  The other bind calls refuse a linear-model handle.
+ * lbfgsx_objective_linear_topology reads the list back: info = {R, nnz, L, C, long columns, chunks, 0, 0}; colptr (n+1),
+ * trow and tpos (nnz each: the row of a transposed entry and the CSR position it came from), long_col (long columns,
+ * ascending), long_chunk (long columns + 1: the first chunk of each), chunk (2 per chunk: first and past-the-last entry).
+ * Any pointer may be NULL.
+ * Byte model of one evaluation (lbfgsx_counters_ex): the built-in's streams plus, for both passes, the offsets (R+1 and n+1
+ * words), 2 nnz indices, 2 nnz values and the gathered values once each (nnz of x, or of xp and d in a trial, and nnz of w),
+ * w and v written and read, the chunk partials written and read.
+ * Not built: reusing z = A xp and A d across the trials of one line search (which would make every trial after the first
+ * O(R)), dense A, column reordering, the lock-step batch, a bench.py leg.  Measurements: DESIGN.md section 1. */
+int lbfgsx_objective_compile_linear(lbfgsx_objective** out, int dtype, const char* coord_body, const char* row_body, char* log,
+                                    size_t log_len);
+long long lbfgsx_objective_source_linear(int dtype, const char* coord_body, const char* row_body, char* out, size_t len);
+int lbfgsx_objective_bind_linear(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t R, int64_t nnz, const int32_t* rowptr,
+                                 const int32_t* col, const void* val, int matrix_on_device, int lanes, const void* const p[4],
+                                 const double cs[8], int* id);
+int lbfgsx_objective_linear_topology(lbfgsx_ctx* c, int64_t info[8], uint32_t* colptr, int32_t* trow, uint32_t* tpos,
+                                     int32_t* long_col, uint32_t* long_chunk, uint32_t* chunk);
 /* Every entry point of this ABI makes the context's device current for its own duration and restores the caller's
  * afterwards.  Code that launches its OWN kernels on the context's vectors (a device functor, lbfgsx_vec) must run with
  * that device current too: lbfgsx_device tells which one it is, lbfgsx_device_push makes it current for the calling

@@ -151,6 +151,15 @@ int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, 
  * number of elements of p[k] where host_mask says it is a host array (n, N or E; NULL: n for all).  A handle of another
  * form, E < 1 and n not a multiple of D are refused with LBFGSX_E_INVALID before a device is needed, as are the tables
  * lbfgsx_objective_bind_mesh refuses; lbfgsx_solver_minimize_obj and lbfgsx_solver_minimize_graph refuse a mesh handle. */
+/* lbfgsx_solver_minimize_obj for a linear-model objective (include/lbfgsx.h, lbfgsx_objective_compile_linear): x has n
+ * weights, the R x n matrix is rowptr / col / val in CSR, host arrays or device arrays (matrix_on_device != 0); lanes as
+ * for lbfgsx_objective_bind_linear.  counts[k]: the elements of p[k] where host_mask says it is a host array (n or R; NULL:
+ * n for all).  A handle of another form is refused with LBFGSX_E_INVALID, as are the matrices lbfgsx_objective_bind_linear
+ * refuses; lbfgsx_solver_minimize_obj refuses a linear-model handle (it carries no matrix). */
+int lbfgsx_solver_minimize_linear(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, int64_t nnz,
+                                  const int32_t* rowptr, const int32_t* col, const void* val, int matrix_on_device, int lanes,
+                                  const void* const p[4], int host_mask, const int64_t counts[4], const double c[8], void* x,
+                                  const void* lb, const void* ub, lbfgsx_trace* trace, lbfgsx_result* out);
 int lbfgsx_solver_minimize_mesh(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t E, const int32_t* elems,
                                 int elems_on_device, const void* const p[4], int host_mask, const int64_t counts[4],
                                 const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,

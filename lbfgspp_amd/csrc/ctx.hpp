@@ -245,7 +245,8 @@ struct lbfgsx_ctx
     // LBFGSX_OBJ_BOUND then evaluates it inside the fused kernels.  term_p: the caller's device arrays (term_own: the
     // context's copies of host arrays, lbfgsx_objective_upload, bound only when the caller passes them), term_c: its scalars
     const struct lbfgsx_objective* term = nullptr;
-    void* term_fn[4] = {nullptr, nullptr, nullptr, nullptr};  // its four kernels on this context's device (hipFunction_t)
+    // its four kernels on this context's device (hipFunction_t); slots 4 and 5: a linear-model objective's two row passes
+    void* term_fn[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const void* term_p[4] = {nullptr, nullptr, nullptr, nullptr};
     double term_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int term_np = 0;  // data arrays bound (byte model)
@@ -262,6 +263,20 @@ struct lbfgsx_ctx
     // lbfgsx_objective_bind_mesh, mesh_topology.hip): graph_off is uint32[N+1], graph_inc holds K*E entries of K 32-bit words,
     // graph_E the elements.  mesh_K, mesh_D: the element size and the unknowns per node of that list, 0 without one
     int mesh_K = 0, mesh_D = 0;
+    // a linear-model objective's matrix (lbfgsx_objective_bind_linear, linear_topology.hip): the context's own copy of the
+    // caller's CSR arrays, the transposed list built from them at every bind, the row pass's two output vectors and the
+    // chunk table of the long columns.  Freed with the other forms' list (graph_topology_free)
+    struct LinearTopo
+    {
+        int64_t R = 0, nnz = 0, nchunks = 0;
+        int L = 0, C = 0, nlong = 0;
+        void *rowptr = nullptr, *col = nullptr, *val = nullptr;      // int32[R+1], int32[nnz], T[nnz]
+        void *colptr = nullptr, *trow = nullptr, *tval = nullptr;    // uint32[n+1], int32[nnz], T[nnz]: sorted by column
+        void* tpos = nullptr;                                        // uint32[nnz]: the CSR position of a transposed entry
+        void *w = nullptr, *v = nullptr;                             // T[R] each: phi'(z_r), phi(z_r)
+        void *part = nullptr, *long_col = nullptr, *long_chunk = nullptr;  // T[nchunks], int32[nlong], uint32[nlong+1]
+        void* chunk = nullptr;                                       // uint32[2*nchunks]: first and past-the-last entry
+    } lin;
 
     // L-BFGS-B work set (allocated with LBFGSX_FLAG_BOUNDED) lives in lbfgsb part
     void* lb = nullptr;

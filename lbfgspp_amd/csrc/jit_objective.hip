@@ -15,8 +15,10 @@
 // the grid's shape), and a GRAPH objective (one term per edge of an index list and an optional one per node: a fourth
 // wrapper around graph_kernels.cuh, whose struct also carries the context's incidence list, graph_topology.hip).  A fifth,
 // a MESH objective (one term per element of K nodes with D unknowns each and an optional one per node), is a wrapper around
-// mesh_kernels.cuh with the list of mesh_topology.hip.  A handle carries its form; the four slots of the loaded-kernel table
-// and everything that launches them are the same.
+// mesh_kernels.cuh with the list of mesh_topology.hip.  A sixth, a LINEAR-MODEL objective (one term per row of a sparse matrix
+// product and an optional one per coordinate), is a wrapper around linear_kernels.cuh with the matrix of linear_topology.hip;
+// it alone has two more kernels, the row passes, in slots 4 and 5.  A handle carries its form; the four slots of the
+// loaded-kernel table and everything that launches them are the same.
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
 
@@ -34,14 +36,18 @@
 
 namespace {
 
-const char* const kKernelNames[5][lbfgsx::JIT_NKERNELS] = {
+const char* const kKernelNames[6][lbfgsx::JIT_NSLOTS] = {
     {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial"},
     {"k_chain_eval", "k_chain_trial", "k_chain_b_eval", "k_chain_b_dg_maxstep_trial"},
     {"k_grid_eval", "k_grid_trial", "k_grid_b_eval", "k_grid_b_dg_maxstep_trial"},
     {"k_graph_eval", "k_graph_trial", "k_graph_b_eval", "k_graph_b_dg_maxstep_trial"},
-    {"k_mesh_eval", "k_mesh_trial", "k_mesh_b_eval", "k_mesh_b_dg_maxstep_trial"}};
-const char* const kObjStruct[5] = {"ObjTerm", "ObjChain", "ObjGrid", "ObjGraph", "ObjMesh"};
-const char* const kFormName[5] = {"term objective", "chain objective", "grid objective", "graph objective", "mesh objective"};
+    {"k_mesh_eval", "k_mesh_trial", "k_mesh_b_eval", "k_mesh_b_dg_maxstep_trial"},
+    {"k_lin_eval", "k_lin_trial", "k_lin_b_eval", "k_lin_b_dg_maxstep_trial", "k_lin_rows", "k_lin_rows_trial"}};
+const char* const kObjStruct[6] = {"ObjTerm", "ObjChain", "ObjGrid", "ObjGraph", "ObjMesh", "ObjLinear"};
+const char* const kFormName[6] = {"term objective", "chain objective", "grid objective", "graph objective", "mesh objective",
+                                  "linear-model objective"};
+// the kernels of a form: the four every form has, and a linear-model objective's two row passes
+inline int kernels_of(int form) { return form == LBFGSX_FORM_LINEAR ? lbfgsx::JIT_NSLOTS : lbfgsx::JIT_NKERNELS; }
 
 // ---- hipRTC, loaded on first use (a process that never compiles an objective does not need it)
 struct Rtc
@@ -117,11 +123,14 @@ std::string generate_chain(int dtype, int K, const char* body);
 std::string generate_grid(int dtype, const char* body);
 std::string generate_graph(int dtype, const char* node, const char* body);
 std::string generate_mesh(int dtype, int K, int D, const char* node, const char* body);
+std::string generate_linear(int dtype, const char* coord, const char* body);
 
 // node: a graph or mesh objective's node body (null or empty: none); the other forms have one body.  D: a mesh
 // objective's unknowns per node, 1 for the other forms
 std::string generate(int form, int dtype, int K, const char* body, const char* node, int D)
 {
+    if (form == LBFGSX_FORM_LINEAR)
+        return generate_linear(dtype, node, body);
     if (form == LBFGSX_FORM_MESH)
         return generate_mesh(dtype, K, D, node, body);
     if (form == LBFGSX_FORM_GRAPH)
@@ -334,8 +343,74 @@ std::string generate_mesh(int dtype, int K, int D, const char* node, const char*
     return s;
 }
 
+// the wrapper of a linear-model objective: the struct linear_kernels.cuh asks for (the two terms and the matrix), its four
+// column-pass kernels and its two row passes.  The members are LinearArgs' (launch_args.hpp), in its order.  Each body has
+// its own #line name
+std::string generate_linear(int dtype, const char* coord, const char* body)
+{
+    const bool has_coord = coord && *coord;
+    std::string s;
+    s += "// generated by lbfgsx_objective_compile_linear: one linear-model objective for the fused kernels\n";
+    s += "#include \"linear_kernels.cuh\"\n";
+    s += "namespace lbfgsx {\n";
+    s += std::string("typedef ") + (dtype == LBFGSX_F64 ? "double" : "float") + " term_scalar_t;\n";
+    s += "struct ObjLinear\n{\n";
+    s += "    typedef term_scalar_t T;\n";
+    s += "    static constexpr int K = 1;\n";
+    s += std::string("    static constexpr bool kCoord = ") + (has_coord ? "true" : "false") + ";\n";
+    s += "    const T* p0;\n    const T* p1;\n    const T* p2;\n    const T* p3;\n    T c[8];\n";
+    s += "    const int32_t* rowptr;\n    const int32_t* col;\n    const T* val;\n";
+    s += "    const uint32_t* colptr;\n    const int32_t* trow;\n    const T* tval;\n";
+    s += "    T* w;\n    T* v;\n";
+    s += "    const T* part;\n    const int32_t* long_col;\n    const uint32_t* long_chunk;\n";
+    s += "    int64_t R, nnz;\n    int32_t L, C, nlong, pad_;\n";
+    s += "    // the term of coordinate i: x[0] = x[i] in, its derivative g[0] out, its value returned\n";
+    s += "    __device__ __forceinline__ T coord(const T (&x)[1], T (&g)[1], int64_t i) const\n    {\n";
+    if (has_coord)
+    {
+        s += "#line 1 \"coord_body\"\n";
+        s += coord;
+        s += "\n#line 1 \"objective_wrapper\"\n";
+    }
+    else
+        s += "        g[0] = T(0);\n        return T(0);\n";
+    s += "    }\n";
+    s += "    // the term of row r: z = the row's product with x in, its derivative dz out, its value returned\n";
+    s += "    __device__ __forceinline__ T row(const T z, T& dz, int64_t r) const\n    {\n";
+    s += "#line 1 \"row_body\"\n";
+    s += body;
+    s += "\n#line 1 \"objective_wrapper\"\n";
+    s += "    }\n";
+    s += "};\n";
+    s += "typedef term_scalar_t S;\n";
+    s += "template __global__ void k_lin_eval<S, ObjLinear>(const S*, S*, int64_t, ObjLinear, RedWs, S*);\n";
+    s += "template __global__ void k_lin_trial<S, ObjLinear>(const S*, const S*, S, S*, S*, int64_t, ObjLinear, RedWs, S*, int);\n";
+    s += "template __global__ void k_lin_b_eval<S, ObjLinear>(const S*, S*, const S*, const S*, int64_t, ObjLinear, RedWs, S*);\n";
+    s += "template __global__ void k_lin_b_dg_maxstep_trial<S, ObjLinear>(const S*, const S*, const S*, const S*, const S*, S, S*, "
+         "S*, int64_t, ObjLinear, RedWs, S*, int);\n";
+    s += "template __global__ void k_lin_rows<S, ObjLinear>(const S*, ObjLinear);\n";
+    s += "template __global__ void k_lin_rows_trial<S, ObjLinear>(const S*, const S*, S, ObjLinear);\n";
+    s += "}  // namespace lbfgsx\n";
+    return s;
+}
+
 bool valid_request(int form, int dtype, int K, const char* body, const char* node, int D, std::string& why)
 {
+    if (form == LBFGSX_FORM_LINEAR)
+    {
+        if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
+            why = "linear-model objective: unknown dtype";
+        else if (!body || !*body)
+            why = "linear-model objective: empty row body";
+        else if (std::strstr(body, "asm"))
+            why = "linear-model objective: the row body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
+        else if (node && std::strstr(node, "asm"))
+            why = "linear-model objective: the coordinate body contains 'asm': a term is plain C++ arithmetic, inline assembly is not "
+                  "accepted";
+        else
+            return true;
+        return false;
+    }
     if (form == LBFGSX_FORM_MESH)
     {
         if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
@@ -522,13 +597,13 @@ struct lbfgsx_objective_code
     lbfgsx_objective self;  // what a context's binding points to: it outlives every handle given to a caller
     int form = LBFGSX_FORM_TERM, dtype = LBFGSX_F64, K = 1, D = 1;
     std::vector<char> code;
-    std::string lowered[lbfgsx::JIT_NKERNELS];
-    long long vgprs[lbfgsx::JIT_NKERNELS] = {0, 0, 0, 0}, scratch[lbfgsx::JIT_NKERNELS] = {0, 0, 0, 0};
+    std::string lowered[lbfgsx::JIT_NSLOTS];
+    long long vgprs[lbfgsx::JIT_NSLOTS] = {0, 0, 0, 0, 0, 0}, scratch[lbfgsx::JIT_NSLOTS] = {0, 0, 0, 0, 0, 0};
     double compile_ms = 0.0;
     struct Loaded
     {
         hipModule_t mod = nullptr;
-        hipFunction_t fn[lbfgsx::JIT_NKERNELS] = {nullptr, nullptr, nullptr, nullptr};
+        hipFunction_t fn[lbfgsx::JIT_NSLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     };
     std::mutex mu;
     std::map<int, Loaded> loaded;  // per device
@@ -563,8 +638,9 @@ int compile_code(int form, int dtype, int K, int D, const char* body, const char
         log = "hiprtcCreateProgram failed";
         return LBFGSX_E_RUNTIME;
     }
-    std::string expr[lbfgsx::JIT_NKERNELS];
-    for (int k = 0; k < lbfgsx::JIT_NKERNELS; k++)
+    std::string expr[lbfgsx::JIT_NSLOTS];
+    const int nk = kernels_of(form);
+    for (int k = 0; k < nk; k++)
     {
         expr[k] = std::string("lbfgsx::") + kKernelNames[form][k] + "<lbfgsx::term_scalar_t, lbfgsx::" + kObjStruct[form] + ">";
         (void) r.add_name(prog, expr[k].c_str());
@@ -602,7 +678,7 @@ int compile_code(int form, int dtype, int K, int D, const char* body, const char
         code->code.resize(cs);
         ok = r.code(prog, code->code.data()) == HIPRTC_SUCCESS;
     }
-    for (int k = 0; ok && k < lbfgsx::JIT_NKERNELS; k++)
+    for (int k = 0; ok && k < nk; k++)
     {
         const char* low = nullptr;
         ok = r.lowered(prog, expr[k].c_str(), &low) == HIPRTC_SUCCESS && low;
@@ -683,7 +759,7 @@ int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const 
         return LBFGSX_E_INVALID;
     }
     std::string key = std::to_string(form) + "/" + std::to_string(dtype) + "/" + std::to_string(K) + "/" + body;
-    if (form == LBFGSX_FORM_GRAPH || form == LBFGSX_FORM_MESH)
+    if (form == LBFGSX_FORM_GRAPH || form == LBFGSX_FORM_MESH || form == LBFGSX_FORM_LINEAR)
         key += std::string("\x1f") + (node ? node : "");  // both bodies
     if (form == LBFGSX_FORM_MESH)
         key += "\x1f" + std::to_string(D);
@@ -735,6 +811,10 @@ long long lbfgsx_objective_source_mesh(int dtype, int K, int D, const char* node
 {
     return objective_source(LBFGSX_FORM_MESH, dtype, K, elem_body, out, len, node_body, D);
 }
+long long lbfgsx_objective_source_linear(int dtype, const char* coord_body, const char* row_body, char* out, size_t len)
+{
+    return objective_source(LBFGSX_FORM_LINEAR, dtype, 1, row_body, out, len, coord_body);
+}
 
 int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
 {
@@ -758,6 +838,11 @@ int lbfgsx_objective_compile_mesh(lbfgsx_objective** out, int dtype, int K, int 
 {
     return objective_compile(LBFGSX_FORM_MESH, out, dtype, K, elem_body, log, log_len, node_body, D);
 }
+int lbfgsx_objective_compile_linear(lbfgsx_objective** out, int dtype, const char* coord_body, const char* row_body, char* log,
+                                    size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_LINEAR, out, dtype, 1, row_body, log, log_len, coord_body);
+}
 
 void lbfgsx_objective_destroy(lbfgsx_objective* obj) { delete obj; }
 
@@ -767,11 +852,12 @@ int lbfgsx_objective_info(const lbfgsx_objective* obj, long long out[8])
         return LBFGSX_E_INVALID;
     const lbfgsx_objective_code* k = obj->code;
     out[0] = out[1] = 0;
-    for (int j = 0; j < lbfgsx::JIT_NKERNELS; j++)
+    for (int j = 0; j < kernels_of(k->form); j++)  // the maxima cover a linear-model objective's two row passes
     {
         out[0] = k->vgprs[j] > out[0] ? k->vgprs[j] : out[0];
         out[1] = k->scratch[j] > out[1] ? k->scratch[j] : out[1];
-        out[4 + j] = k->scratch[j];
+        if (j < lbfgsx::JIT_NKERNELS)
+            out[4 + j] = k->scratch[j];
     }
     out[2] = obj->cache_hit ? 1 : 0;
     out[3] = (long long) (k->compile_ms + 0.5);
@@ -835,7 +921,7 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
         c->term_np = 0;
         c->term_form = LBFGSX_FORM_TERM;
         c->term_rows = c->term_cols = 0;
-        if (c->graph_inc)
+        if (c->graph_inc || c->lin.colptr)
         {
             lbfgsx::DeviceGuard dev_guard_(c->device);
             (void) lbfgsx::stream_sync(c->stream);  // no launch still walks the list
@@ -879,14 +965,15 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
         {
             lbfgsx_objective_code::Loaded l;
             LBFGSX_HIP(hipModuleLoadData(&l.mod, code->code.data()));
-            for (int k = 0; k < lbfgsx::JIT_NKERNELS; k++)
+            for (int k = 0; k < kernels_of(code->form); k++)
                 LBFGSX_HIP(hipModuleGetFunction(&l.fn[k], l.mod, code->lowered[k].c_str()));
             it = code->loaded.emplace(c->device, l).first;
         }
-        for (int k = 0; k < lbfgsx::JIT_NKERNELS; k++)
+        for (int k = 0; k < lbfgsx::JIT_NSLOTS; k++)
             c->term_fn[k] = it->second.fn[k];
     }
-    if (code->form != LBFGSX_FORM_GRAPH && code->form != LBFGSX_FORM_MESH && c->graph_inc)
+    if (code->form != LBFGSX_FORM_GRAPH && code->form != LBFGSX_FORM_MESH && code->form != LBFGSX_FORM_LINEAR &&
+        (c->graph_inc || c->lin.colptr))
     {
         (void) lbfgsx::stream_sync(c->stream);  // no launch still walks the list
         lbfgsx::graph_topology_free(c);
@@ -929,6 +1016,11 @@ int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void
     if (obj && obj->code->form == LBFGSX_FORM_MESH)
     {
         lbfgsx::set_error("a mesh objective is bound with its elements: lbfgsx_objective_bind_mesh");
+        return LBFGSX_E_INVALID;
+    }
+    if (obj && obj->code->form == LBFGSX_FORM_LINEAR)
+    {
+        lbfgsx::set_error("a linear-model objective is bound with its matrix: lbfgsx_objective_bind_linear");
         return LBFGSX_E_INVALID;
     }
     return objective_bind(c, obj, 0, 0, p, cs, id);
@@ -1108,6 +1200,81 @@ int lbfgsx_objective_mesh_topology(lbfgsx_ctx* c, int64_t* E, uint32_t* off, uin
         *E = c->graph_E;
     lbfgsx::DeviceGuard dev_guard_(c->device);
     return lbfgsx::mesh_topology_read(c, off, words);
+}
+
+int lbfgsx_objective_bind_linear(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t R, int64_t nnz, const int32_t* rowptr,
+                                 const int32_t* col, const void* val, int matrix_on_device, int lanes, const void* const p[4],
+                                 const double cs[8], int* id)
+{
+    if (!c || !obj)
+        return LBFGSX_E_INVALID;
+    // whatever is refused below leaves no objective bound
+    c->st_valid = false;
+    c->spec_valid = false;
+    c->term = nullptr;
+    c->term_np = 0;
+    c->term_form = LBFGSX_FORM_TERM;
+    if (obj->code->form != LBFGSX_FORM_LINEAR)
+    {
+        lbfgsx::set_error(std::string("lbfgsx_objective_bind_linear: the handle is a ") + kFormName[obj->code->form] +
+                          ", not a linear-model objective (lbfgsx_objective_compile_linear)");
+        return LBFGSX_E_INVALID;
+    }
+    if (obj->code->dtype != c->dtype)
+    {
+        lbfgsx::set_error("lbfgsx_objective_bind: the objective was compiled for the other dtype");
+        return LBFGSX_E_INVALID;
+    }
+    const int64_t lim = 2147483647;
+    std::string why;
+    if (R < 1 || nnz < 1 || !rowptr || !col || !val)
+        why = "R = " + std::to_string(R) + ", nnz = " + std::to_string(nnz) +
+              ": a linear-model objective has at least one row and one entry (R >= 1, nnz >= 1) and its three CSR arrays";
+    else if (R > lim)
+        why = "R = " + std::to_string(R) + " exceeds 2^31 - 1 = " + std::to_string(lim) + ": row indices are int32";
+    else if (nnz > lim)
+        why = "nnz = " + std::to_string(nnz) + " exceeds 2^31 - 1 = " + std::to_string(lim) + ": row offsets are int32";
+    else if (c->n > lim)
+        why = "n = " + std::to_string(c->n) + " exceeds 2^31 - 1 = " + std::to_string(lim) + ": column indices are int32";
+    else if (lanes < 0 || lanes > 64 || (lanes & (lanes - 1)) != 0)
+        why = "lanes = " + std::to_string(lanes) + ": the lanes that share a row are 0 (by the rule) or a power of two in 1..64";
+    if (!why.empty())
+    {
+        lbfgsx::set_error("linear-model objective: " + why);
+        return LBFGSX_E_INVALID;
+    }
+    // the matrix first: a context whose arrays were refused keeps no objective bound, so nothing can be launched on them
+    {
+        lbfgsx::DeviceGuard dev_guard_(c->device);
+        const int rc = lbfgsx::linear_topology_build(c, R, nnz, rowptr, col, val, matrix_on_device, lanes);
+        if (rc)
+            return rc;
+    }
+    const int rc = objective_bind(c, obj, 0, 0, p, cs, id);
+    if (rc)
+    {
+        lbfgsx::DeviceGuard dev_guard_(c->device);
+        lbfgsx::graph_topology_free(c);
+    }
+    return rc;
+}
+
+int lbfgsx_objective_linear_topology(lbfgsx_ctx* c, int64_t info[8], uint32_t* colptr, int32_t* trow, uint32_t* tpos,
+                                     int32_t* long_col, uint32_t* long_chunk, uint32_t* chunk)
+{
+    if (!c || !c->term || c->term_form != LBFGSX_FORM_LINEAR || !c->lin.colptr)
+    {
+        lbfgsx::set_error("lbfgsx_objective_linear_topology: no linear-model objective is bound to this context");
+        return LBFGSX_E_INVALID;
+    }
+    if (info)
+    {
+        const int64_t v[8] = {c->lin.R, c->lin.nnz, c->lin.L, c->lin.C, c->lin.nlong, c->lin.nchunks, 0, 0};
+        for (int k = 0; k < 8; k++)
+            info[k] = v[k];
+    }
+    lbfgsx::DeviceGuard dev_guard_(c->device);
+    return lbfgsx::linear_topology_read(c, colptr, trow, tpos, long_col, long_chunk, chunk);
 }
 
 int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4])

@@ -92,6 +92,8 @@ inline DgTrialLaunch<T> dg_maxstep_trial_launch(lbfgsx_ctx* c, T step, int obj_v
 
 // ---- a term objective bound to the context (lbfgsx_objective_bind, jit_objective.hip)
 enum { JIT_K_EVAL = 0, JIT_K_TRIAL = 1, JIT_K_B_EVAL = 2, JIT_K_B_DG_MAXSTEP_TRIAL = 3, JIT_NKERNELS = 4 };
+// a linear-model objective has two more, the row passes that precede its four column-pass kernels (linear_kernels.cuh)
+enum { JIT_K_LIN_ROWS = 4, JIT_K_LIN_ROWS_TRIAL = 5, JIT_NSLOTS = 6 };
 // the by-value kernel argument: layout of the generated struct ObjTerm (four data pointers, eight scalars of type T)
 template <class T>
 struct TermArgs
@@ -137,8 +139,52 @@ struct MeshArgs
     const uint32_t* inc;
     int64_t E, N;
 };
+// the by-value argument of a linear-model objective's kernels: layout of the generated struct ObjLinear (TermArgs, then the
+// context's copy of the CSR arrays, the transposed list, the row pass's outputs and the long columns' chunk table:
+// ctx.hpp LinearTopo, linear_topology.hip)
+template <class T>
+struct LinearArgs
+{
+    TermArgs<T> t;
+    const int32_t* rowptr;
+    const int32_t* col;
+    const T* val;
+    const uint32_t* colptr;
+    const int32_t* trow;
+    const T* tval;
+    T* w;
+    T* v;
+    const T* part;
+    const int32_t* long_col;
+    const uint32_t* long_chunk;
+    int64_t R, nnz;
+    int32_t L, C, nlong, pad_;
+};
+template <class T>
+inline LinearArgs<T> linear_args(const lbfgsx_ctx* c, const TermArgs<T>& t)
+{
+    const lbfgsx_ctx::LinearTopo& l = c->lin;
+    return {t,
+            static_cast<const int32_t*>(l.rowptr),
+            static_cast<const int32_t*>(l.col),
+            static_cast<const T*>(l.val),
+            static_cast<const uint32_t*>(l.colptr),
+            static_cast<const int32_t*>(l.trow),
+            static_cast<const T*>(l.tval),
+            static_cast<T*>(l.w),
+            static_cast<T*>(l.v),
+            static_cast<const T*>(l.part),
+            static_cast<const int32_t*>(l.long_col),
+            static_cast<const uint32_t*>(l.long_chunk),
+            l.R,
+            l.nnz,
+            l.L,
+            l.C,
+            l.nlong,
+            0};
+}
 // the objective argument of the bound handle's kernels, by its form: &term for a term or chain objective, &grid for a grid
-// one, &graph for a graph one, &mesh for a mesh one
+// one, &graph for a graph one, &mesh for a mesh one, &linear for a linear-model one
 template <class T>
 struct BoundArgs
 {
@@ -146,17 +192,20 @@ struct BoundArgs
     GridArgs<T> grid;
     GraphArgs<T> graph;
     MeshArgs<T> mesh;
+    LinearArgs<T> linear;
     void* ptr;
     explicit BoundArgs(const lbfgsx_ctx* c)
         : term(term_args<T>(c)),
           grid{term, c->term_rows, c->term_cols},
           graph{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const GraphEntry*>(c->graph_inc), c->graph_E},
           mesh{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const uint32_t*>(c->graph_inc), c->graph_E,
-               c->mesh_D ? c->n / c->mesh_D : 0}
+               c->mesh_D ? c->n / c->mesh_D : 0},
+          linear(linear_args<T>(c, term))
     {
         ptr = (c->term_form == LBFGSX_FORM_GRID)    ? static_cast<void*>(&grid)
               : (c->term_form == LBFGSX_FORM_GRAPH) ? static_cast<void*>(&graph)
               : (c->term_form == LBFGSX_FORM_MESH)  ? static_cast<void*>(&mesh)
+              : (c->term_form == LBFGSX_FORM_LINEAR) ? static_cast<void*>(&linear)
                                                     : static_cast<void*>(&term);
     }
     BoundArgs(const BoundArgs&) = delete;
@@ -180,6 +229,20 @@ inline void mesh_model_add(const lbfgsx_ctx* c, int vectors_gathered)
         model_add(double(c->n / c->mesh_D + 1) * 4 + KE * 4 * K + KE * (K - 1) * D * sizeof(T) * vectors_gathered);
     }
 }
+// what a linear-model objective adds to the byte model of one evaluation (row pass, long-column launch, column pass): the
+// offsets (rowptr, colptr), the indices (col, trow) and the values (val, tval) of both passes, every gathered value once (the
+// row pass gathers vectors_gathered vectors: 1 in an evaluation, 2 in a trial, xp and d; the column pass gathers w), w and v
+// written and read, the chunk partials written and read
+template <class T>
+inline void linear_model_add(const lbfgsx_ctx* c, int vectors_gathered)
+{
+    if (c->term_form == LBFGSX_FORM_LINEAR)
+    {
+        const double R = double(c->lin.R), nnz = double(c->lin.nnz), esz = sizeof(T);
+        model_add((R + 1) * 4 + double(c->n + 1) * 4 + 2 * nnz * 4 + 2 * nnz * esz + nnz * esz * (vectors_gathered + 1) +
+                  4 * R * esz + 2 * double(c->lin.nchunks) * esz);
+    }
+}
 // graph_topology.hip: the incidence list of the context (ctx.hpp: graph_off, graph_inc, graph_E).  build validates the
 // indices first and leaves the context without a list when an edge offends (LBFGSX_E_INVALID, the edge named)
 int graph_topology_build(lbfgsx_ctx* c, const int32_t* ei, const int32_t* ej, int64_t E, int on_device);
@@ -189,9 +252,58 @@ void graph_topology_free(lbfgsx_ctx* c);
 // graph_topology_free).  words: K*E*K uint32, off: N+1
 int mesh_topology_build(lbfgsx_ctx* c, int K, int D, const int32_t* elems, int64_t E, int on_device);
 int mesh_topology_read(lbfgsx_ctx* c, uint32_t* off, uint32_t* words);
+// linear_topology.hip: the matrix of a linear-model objective (ctx.hpp: lin).  build validates the caller's CSR arrays
+// first and leaves the context without a matrix when one offends (LBFGSX_E_INVALID, the position named); lanes: 0 = by the
+// rule (linear_lanes_rule), otherwise the lanes per row.  long_launch: the launch between the two passes, none when the
+// matrix has no long column
+constexpr int kLinearChunk = 4096;  // C: a column with more entries is long and is summed in chunks of C by k_lin_long_cols
+int linear_lanes_rule(int64_t R, int64_t nnz);
+int linear_topology_build(lbfgsx_ctx* c, int64_t R, int64_t nnz, const int32_t* rowptr, const int32_t* col, const void* val,
+                          int on_device, int lanes);
+int linear_topology_read(lbfgsx_ctx* c, uint32_t* colptr, int32_t* trow, uint32_t* tpos, int32_t* long_col, uint32_t* long_chunk,
+                         uint32_t* chunk);
+void linear_topology_free(lbfgsx_ctx* c);
+int linear_long_launch(lbfgsx_ctx* c);
 inline bool term_bound(const lbfgsx_ctx* c, int objective) { return objective == LBFGSX_OBJ_BOUND && c->term != nullptr; }
 // one launch of loaded kernel `which` of the bound objective on the context's stream, block of kBlock threads; params as
 // hipModuleLaunchKernel takes them (one pointer per kernel argument)
 int jit_launch(lbfgsx_ctx* c, int which, int grid, void** params);
+
+// ---- a linear-model objective's launches ahead of its column pass, on the same stream with no host wait in between: the
+// row pass (k_lin_rows over x, or k_lin_rows_trial over xp + step*d), then the long-column launch if the matrix has a long
+// column.  Nothing for the other forms.
+inline int linear_rows_grid(const lbfgsx_ctx* c)
+{
+    const int64_t rpb = kBlock / c->lin.L, b = (c->lin.R + rpb - 1) / rpb;
+    return int(b < 1 ? 1 : (b > kGridCap ? kGridCap : b));
+}
+// the column pass strides over v[R] as well as over the n coordinates: its grid covers the longer of the two
+inline int linear_col_grid(const lbfgsx_ctx* c, int grid)
+{
+    if (c->term_form != LBFGSX_FORM_LINEAR)
+        return grid;
+    const int gr = c->grid_for(c->lin.R);
+    return gr > grid ? gr : grid;
+}
+template <class T>
+inline int linear_pre_eval(lbfgsx_ctx* c, BoundArgs<T>& obj, const T* x)
+{
+    if (c->term_form != LBFGSX_FORM_LINEAR)
+        return LBFGSX_OK;
+    linear_model_add<T>(c, 1);
+    void* params[] = {&x, obj.ptr};
+    const int rc = jit_launch(c, JIT_K_LIN_ROWS, linear_rows_grid(c), params);
+    return rc ? rc : linear_long_launch(c);
+}
+template <class T>
+inline int linear_pre_trial(lbfgsx_ctx* c, BoundArgs<T>& obj, const T* xp, const T* d, T step)
+{
+    if (c->term_form != LBFGSX_FORM_LINEAR)
+        return LBFGSX_OK;
+    linear_model_add<T>(c, 2);
+    void* params[] = {&xp, &d, &step, obj.ptr};
+    const int rc = jit_launch(c, JIT_K_LIN_ROWS_TRIAL, linear_rows_grid(c), params);
+    return rc ? rc : linear_long_launch(c);
+}
 
 }  // namespace lbfgsx

@@ -30,7 +30,10 @@ static int b_eval_term_t(lbfgsx_ctx* c, double* r3)
     BEvalLaunch<T> a = b_eval_launch<T>(c);
     BoundArgs<T> obj(c);
     void* params[] = {&a.x, &a.g, &a.lb, &a.ub, &a.n, obj.ptr, &a.ws, &a.out};
-    const int rc = jit_launch(c, JIT_K_B_EVAL, a.grid, params);
+    int rc = linear_pre_eval<T>(c, obj, a.x);
+    if (rc)
+        return rc;
+    rc = jit_launch(c, JIT_K_B_EVAL, linear_col_grid(c, a.grid), params);
     if (rc)
         return rc;
     return fetch_T<T>(c, c->sl.out(0), 3, r3);
@@ -52,7 +55,10 @@ static int dg_maxstep_trial_term_t(lbfgsx_ctx* c, T step, double* r4)
     graph_model_add<T>(c, 2);
     mesh_model_add<T>(c, 2);
     void* params[] = {&a.xp, &a.g0, &a.d, &a.lb, &a.ub, &a.step, &a.x, &a.g, &a.n, obj.ptr, &a.ws, &a.out, &a.rev};
-    const int rc = jit_launch(c, JIT_K_B_DG_MAXSTEP_TRIAL, a.grid, params);
+    int rc = linear_pre_trial<T>(c, obj, a.xp, a.d, a.step);
+    if (rc)
+        return rc;
+    rc = jit_launch(c, JIT_K_B_DG_MAXSTEP_TRIAL, linear_col_grid(c, a.grid), params);
     if (rc)
         return rc;
     return fetch_T<T>(c, c->sl.out(0), 4, r4);

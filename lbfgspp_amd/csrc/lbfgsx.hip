@@ -472,6 +472,7 @@ void lbfgsx_destroy(lbfgsx_ctx* c)
         (void) hipFree(c->term_own[k]);
     (void) hipFree(c->graph_off);
     (void) hipFree(c->graph_inc);
+    lbfgsx::linear_topology_free(c);
     (void) hipFree(c->S);
     (void) hipFree(c->Y);
     (void) hipFree(c->sc);
@@ -979,7 +980,10 @@ static int eval_term_t(lbfgsx_ctx* c, double* out3)
     lbfgsx::EvalLaunch<T> a = lbfgsx::eval_launch<T>(c);
     lbfgsx::BoundArgs<T> obj(c);
     void* params[] = {&a.x, &a.g, &a.n, obj.ptr, &a.ws, &a.out};
-    const int rc = lbfgsx::jit_launch(c, lbfgsx::JIT_K_EVAL, a.grid, params);
+    int rc = lbfgsx::linear_pre_eval<T>(c, obj, a.x);
+    if (rc)
+        return rc;
+    rc = lbfgsx::jit_launch(c, lbfgsx::JIT_K_EVAL, lbfgsx::linear_col_grid(c, a.grid), params);
     if (rc)
         return rc;
     return fetch_scalars<T>(c, c->sl.out(0), 3, out3);
@@ -1061,7 +1065,10 @@ static int trial_term_t(lbfgsx_ctx* c, T step, double* out2)
     lbfgsx::graph_model_add<T>(c, 2);
     lbfgsx::mesh_model_add<T>(c, 2);
     void* params[] = {&a.xp, &a.d, &a.step, &a.x, &a.g, &a.n, obj.ptr, &a.ws, &a.out, &a.rev};
-    const int rc = lbfgsx::jit_launch(c, lbfgsx::JIT_K_TRIAL, a.grid, params);
+    int rc = lbfgsx::linear_pre_trial<T>(c, obj, a.xp, a.d, a.step);
+    if (rc)
+        return rc;
+    rc = lbfgsx::jit_launch(c, lbfgsx::JIT_K_TRIAL, lbfgsx::linear_col_grid(c, a.grid), params);
     if (rc)
         return rc;
     return fetch_scalars<T>(c, c->sl.out(0), 2, out2);

@@ -43,6 +43,11 @@ struct lbfgsx_solver
         int on_device;
         const int64_t* counts;
         const int32_t* elems;
+        // a linear-model objective's CSR matrix in place of all of the above (rowptr null: not one): R rows, nnz entries
+        int64_t R = 0, nnz = 0;
+        const int32_t *rowptr = nullptr, *col = nullptr;
+        const void* val = nullptr;
+        int lanes = 0;
     };
     // rows, cols: the shape of a grid objective, 0 for the other forms; gr: null for every form but a graph objective
     virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const GraphSpec* gr,
@@ -223,13 +228,17 @@ struct LbfgsImpl : lbfgsx_solver
         GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
-        if (gr && gr->elems)
+        LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
+        if (gr && gr->rowptr)
+            lined.matrix(gr->R, gr->nnz, gr->rowptr, gr->col, static_cast<const Scalar*>(gr->val), gr->on_device != 0, gr->lanes);
+        else if (gr && gr->elems)
             meshed.elements(gr->E, gr->elems, gr->on_device != 0);
         else if (gr)
             graphed.edges(gr->E, gr->ei, gr->ej, gr->on_device != 0);
-        TermObjective<Scalar>& f = (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
-                                   : gr             ? static_cast<TermObjective<Scalar>&>(graphed)
-                                                    : shaped;
+        TermObjective<Scalar>& f = (gr && gr->rowptr)  ? static_cast<TermObjective<Scalar>&>(lined)
+                                   : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
+                                   : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
+                                                       : shaped;
         fill_term<Scalar>(f, p, host_mask, c, gr ? gr->counts : nullptr);
         run(f, n, x, tr, out);
     }
@@ -340,13 +349,17 @@ struct LbfgsbImpl : lbfgsx_solver
         GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
-        if (gr && gr->elems)
+        LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
+        if (gr && gr->rowptr)
+            lined.matrix(gr->R, gr->nnz, gr->rowptr, gr->col, static_cast<const Scalar*>(gr->val), gr->on_device != 0, gr->lanes);
+        else if (gr && gr->elems)
             meshed.elements(gr->E, gr->elems, gr->on_device != 0);
         else if (gr)
             graphed.edges(gr->E, gr->ei, gr->ej, gr->on_device != 0);
-        TermObjective<Scalar>& f = (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
-                                   : gr             ? static_cast<TermObjective<Scalar>&>(graphed)
-                                                    : shaped;
+        TermObjective<Scalar>& f = (gr && gr->rowptr)  ? static_cast<TermObjective<Scalar>&>(lined)
+                                   : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
+                                   : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
+                                                       : shaped;
         fill_term<Scalar>(f, p, host_mask, c, gr ? gr->counts : nullptr);
         run(f, n, x, lb, ub, tr, out);
     }
@@ -931,6 +944,8 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
             throw std::invalid_argument("a graph objective is minimised with its edges: lbfgsx_solver_minimize_graph");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_MESH)
             throw std::invalid_argument("a mesh objective is minimised with its elements: lbfgsx_solver_minimize_mesh");
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_LINEAR)
+            throw std::invalid_argument("a linear-model objective is minimised with its matrix: lbfgsx_solver_minimize_linear");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_CHAIN)
         {
             if (n < K)
@@ -1009,7 +1024,8 @@ int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, 
         std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_graph: no HIP device available (this library has no CPU fallback)");
         return out->status;
     }
-    const lbfgsx_solver::GraphSpec gr = {E, ei, ej, edges_on_device, counts, nullptr};
+    lbfgsx_solver::GraphSpec gr;
+    gr.E = E, gr.ei = ei, gr.ej = ej, gr.on_device = edges_on_device, gr.counts = counts, gr.elems = nullptr;
     return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 
@@ -1042,7 +1058,41 @@ int lbfgsx_solver_minimize_mesh(lbfgsx_solver* s, const lbfgsx_objective* obj, i
         std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_mesh: no HIP device available (this library has no CPU fallback)");
         return out->status;
     }
-    const lbfgsx_solver::GraphSpec gr = {E, nullptr, nullptr, elems_on_device, counts, elems};
+    lbfgsx_solver::GraphSpec gr;
+    gr.E = E, gr.ei = gr.ej = nullptr, gr.on_device = elems_on_device, gr.counts = counts, gr.elems = elems;
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+}
+
+int lbfgsx_solver_minimize_linear(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, int64_t nnz,
+                                  const int32_t* rowptr, const int32_t* col, const void* val, int matrix_on_device, int lanes,
+                                  const void* const p[4], int host_mask, const int64_t counts[4], const double c[8], void* x,
+                                  const void* lb, const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    const int bad = guarded(out, [&]() {
+        if (!s || !obj || n <= 0)
+            throw std::invalid_argument("lbfgsx_solver_minimize_linear: invalid argument");
+        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_LINEAR)
+            throw std::invalid_argument("lbfgsx_solver_minimize_linear: the handle is not a linear-model objective "
+                                        "(lbfgsx_objective_compile_linear)");
+        if (lbfgsx_objective_dtype(obj) != s->dtype)
+            throw std::invalid_argument("lbfgsx_solver_minimize_linear: the objective was compiled for the other dtype");
+        if (R < 1 || nnz < 1 || !rowptr || !col || !val)
+            throw std::invalid_argument("linear-model objective: R = " + std::to_string(R) + ", nnz = " + std::to_string(nnz) +
+                                        ": a linear-model objective has at least one row and one entry (R >= 1, nnz >= 1) and "
+                                        "its three CSR arrays");
+    });
+    if (bad)
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_linear: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    lbfgsx_solver::GraphSpec gr;
+    gr.E = 0, gr.ei = gr.ej = nullptr, gr.on_device = matrix_on_device, gr.counts = counts, gr.elems = nullptr;
+    gr.R = R, gr.nnz = nnz, gr.rowptr = rowptr, gr.col = col, gr.val = val, gr.lanes = lanes;
     return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 }

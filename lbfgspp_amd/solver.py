@@ -9,7 +9,8 @@ std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device ob
 (`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`), the caller's own term compiled into the same kernels (`TermObjective(body)`,
 `ChainObjective(body)` for terms that overlap, `GridObjective(body, shape)` for 2x2-cell terms on a grid, or
 `GraphObjective(edge_body, edges)` for edge terms over an index list,
-`MeshObjective(elem_body, elements, dim)` for K-node elements with vector unknowns)
+`MeshObjective(elem_body, elements, dim)` for K-node elements with vector unknowns, or
+`LinearObjective(row_body, (rowptr, col, val), n)` for a linear model over a sparse matrix)
 or the caller's own callable, `DeviceObjective(fn)`: fn(x, grad) -> float on torch
 tensors that alias the library's device vectors.  All O(n) work of the solver runs in the HIP library, Python only passes
 pointers.  There is no CPU fallback: without the built extension or a GPU these calls raise.
@@ -397,6 +398,112 @@ class MeshObjective(TermObjective):
         return (n, n // self.D, self.E)
 
 
+class LinearObjective(TermObjective):
+    """A linear model fitted to data: x are the n weights, row r of the sparse R x n matrix A is one sample, and
+    f(x) = sum over coordinates j of psi(x[j]; j) + sum over rows r of phi(z_r; r) with z = A x -- logistic regression, least
+    squares, non-negative least squares under LBFGSBSolver, Poisson and Huber regression, L2-loss SVMs (include/lbfgsx.h,
+    "linear-model objectives").  row_body sees T, const T z, T& dz (to assign: phi'(z)), int64_t r, p0..p3 and c[8] and returns
+    phi(z); coord_body (optional) is a GraphObjective's node body: T, const T x[1], T g[1], int64_t i, p0..p3, c[8], returns
+    psi.  grad[j] is the coordinate term's g[0], then val * phi'(z_r) over the entries of column j in ascending r.
+
+        svm = LinearObjective("const T m = T(1) - p0[r] * z; const T h = m > T(0) ? m : T(0);"
+                              "dz = T(-2) * (p0[r] * h); return h * h;", (rowptr, col, val), n, data=(labels,), scalars=(1e-3,),
+                              coord_body="g[0] = c[0] * x[0]; return T(0.5) * (c[0] * (x[0] * x[0]));")
+
+    The matrix is CSR: rowptr (R+1), col (nnz) and val (nnz), three numpy arrays (range-checked and converted to int32 and
+    the solver's dtype on the host) or three torch tensors on the solver's device (int32, int32 and the solver's dtype: used
+    from device memory).  They are copied, validated (rowptr starts at 0, does not decrease, ends at nnz; 0 <= col < n) and
+    transposed on the device at every minimise.  lanes: the lanes that share a row in the row pass, 0 = by the library's rule,
+    otherwise a power of two <= 64.  Each data[k] has n (per weight) or R (per sample) elements.  Otherwise a
+    GraphObjective's interface; usable wherever one is, refused where one is."""
+    _NAME = "LinearObjective"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_linear", "lbfgsx_objective_source_linear"
+
+    def __init__(self, row_body, matrix, n, coord_body=None, data=(), scalars=(), lanes=0):
+        try:
+            rowptr, col, val = matrix
+        except (TypeError, ValueError):
+            raise ValueError("LinearObjective: matrix must be a triple (rowptr, col, val) of CSR arrays") from None
+        self.n = int(n)
+        if self.n < 1 or self.n > 2 ** 31 - 1:
+            raise ValueError("LinearObjective: n = %d: a linear model has 1 .. 2^31 - 1 weights" % self.n)
+        if lanes not in (0, 1, 2, 4, 8, 16, 32, 64):
+            raise ValueError("LinearObjective: lanes = %r: the lanes that share a row are 0 (by the rule) or a power of two in "
+                             "1..64" % (lanes,))
+        self.lanes = int(lanes)
+        self.on_device = all(_is_torch(a) and a.is_cuda for a in (rowptr, col, val))
+        if self.on_device:
+            torch = L.require_torch("LinearObjective with a matrix on the device")
+            for a, name in ((rowptr, "rowptr"), (col, "col")):
+                if a.dim() != 1 or a.dtype != torch.int32 or not a.is_contiguous():
+                    raise ValueError("LinearObjective: %s on the device must be a contiguous 1-D int32 tensor" % name)
+            if val.dim() != 1 or val.dtype not in (torch.float32, torch.float64) or not val.is_contiguous():
+                raise ValueError("LinearObjective: val on the device must be a contiguous 1-D float32 or float64 tensor")
+            self.rowptr, self.col, self.val = rowptr, col, val
+            sizes = (int(rowptr.numel()), int(col.numel()), int(val.numel()))
+        else:
+            self.rowptr, self.col = self._indices(rowptr, "rowptr"), self._indices(col, "col")
+            v = val.detach().cpu().numpy() if _is_torch(val) else np.asarray(val)
+            if v.ndim != 1 or v.dtype.kind not in "fiu":
+                raise ValueError("LinearObjective: val must be a 1-D array of numbers, not %s with %d dimensions" % (v.dtype, v.ndim))
+            self.val = np.ascontiguousarray(v, np.float64 if v.dtype != np.float32 else np.float32)
+            sizes = (self.rowptr.size, self.col.size, self.val.size)
+        self.R, self.nnz = sizes[0] - 1, sizes[1]
+        if self.R < 1:
+            raise ValueError("LinearObjective: rowptr has %d elements: a matrix has at least one row (R + 1 >= 2)" % sizes[0])
+        if self.nnz < 1:
+            raise ValueError("LinearObjective: nnz = 0: a matrix has at least one entry")
+        if sizes[2] != self.nnz:
+            raise ValueError("LinearObjective: col has %d elements and val has %d: one pair per entry" % (self.nnz, sizes[2]))
+        if not self.on_device:
+            if int(self.rowptr[0]) != 0 or int(self.rowptr[-1]) != self.nnz:
+                raise ValueError("LinearObjective: rowptr[0] = %d and rowptr[R] = %d: rowptr starts at 0 and ends at nnz = %d"
+                                 % (int(self.rowptr[0]), int(self.rowptr[-1]), self.nnz))
+        self.body, self.K = str(row_body), 1
+        self.coord_body = None if not coord_body else str(coord_body)
+        self._h = {}
+        self.set_data(*data)
+        self.set_scalars(*scalars)
+
+    @staticmethod
+    def _indices(a, name):
+        if _is_torch(a):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError("LinearObjective: %s must be a 1-D integer array, not %s with %d dimensions" % (name, a.dtype, a.ndim))
+        if a.size:
+            for v in (int(a.min()), int(a.max())):
+                if v < -2 ** 31 or v > 2 ** 31 - 1:
+                    raise ValueError("LinearObjective: %s holds %d, which does not fit 32 bits" % (name, v))
+        return np.ascontiguousarray(a, np.int32)
+
+    def _form_args(self):
+        return (self.coord_body.encode() if self.coord_body else None,)
+
+    def _check_n(self, n):
+        if n != self.n:
+            raise ValueError("LinearObjective: the matrix has n = %d columns and x has %d elements" % (self.n, n))
+
+    def _data_sizes(self, n):
+        return (n, self.R)
+
+    def _matrix_args(self, solver):
+        """(rowptr, col, val as addresses, on_device, what to keep alive) for a solver of the given dtype and device"""
+        np_dt = _NP[solver.dtype]
+        if self.on_device:
+            torch = L.require_torch("LinearObjective with a matrix on the device")
+            want = torch.float64 if solver.dtype == L.F64 else torch.float32
+            val = self.val if self.val.dtype == want else self.val.to(want)
+            for a in (self.rowptr, self.col, val):
+                if a.device.index != solver.device:
+                    raise ValueError("LinearObjective: the matrix must be on cuda:%d" % solver.device)
+            torch.cuda.current_stream().synchronize()  # the arrays are complete when the library reads them
+            return self.rowptr.data_ptr(), self.col.data_ptr(), val.data_ptr(), 1, (val,)
+        val = np.ascontiguousarray(self.val, np_dt)
+        return self.rowptr.ctypes.data, self.col.ctypes.data, val.ctypes.data, 0, (val,)
+
+
 class TraceBuffer:
     """Per-evaluation record (fx and x[::stride]) for the parity tests."""
 
@@ -582,7 +689,12 @@ class _SolverBase:
             torch.cuda.current_stream().synchronize()  # the data arrays are complete when the library reads them
         tail = (C.byref(ptrs), mask, C.byref(cs), self._ptr(x), self._ptr(lb), self._ptr(ub), C.byref(trace.c) if trace else None,
                 C.byref(res))
-        if isinstance(f, MeshObjective):
+        if isinstance(f, LinearObjective):
+            rp, cp, vp, on_dev, keep_m = f._matrix_args(self)
+            rc = self._sol.lbfgsx_solver_minimize_linear(self._h, h, n, f.R, f.nnz, rp, cp, vp, on_dev, f.lanes, tail[0], mask,
+                                                         C.byref(counts), *tail[2:])
+            del keep_m
+        elif isinstance(f, MeshObjective):
             rc = self._sol.lbfgsx_solver_minimize_mesh(self._h, h, n, f.E, f.elements.ctypes.data_as(C.POINTER(C.c_int32)), 0,
                                                        tail[0], mask, C.byref(counts), *tail[2:])
         elif isinstance(f, GraphObjective):
@@ -611,8 +723,8 @@ class _SolverBase:
             return self._minimize_obj(f, n, x, lb, ub, trace)
         if not hasattr(f, "objective"):
             raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body), "
-                            "GridObjective(body, shape), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim) "
-                            "or DeviceObjective(fn)")
+                            "GridObjective(body, shape), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim), "
+                            "LinearObjective(row_body, matrix, n) or DeviceObjective(fn)")
         res = L.Result()
         a = None if f.a is None else np.ascontiguousarray(f.a, _NP[self.dtype])
         b = None if f.b is None else np.ascontiguousarray(f.b, _NP[self.dtype])
