@@ -7,7 +7,8 @@
 //     :91-92  f(x,grad), grad.norm()                -> lbfgsx_eval            (kernel K0)
 //     :106-108 drt = -grad, 1/drt.norm()            -> lbfgsx_apply_Hv with an empty history
 //     :121-123 xp = x, gradp = grad, grad.dot(drt)  -> lbfgsx_ls_begin (rotation) + dot fused into K1
-//     :127    line search                           -> LineSearch policies over lbfgsx_trial (K2)
+//     :127    line search                           -> LineSearch policies over lbfgsx_trial (K2; its first trial in the
+//                                                      post form, lbfgsx_ls_post_in_trial, when it is likely to be accepted)
 //     :130,137,159-161 norms, s, y, s.y, y.y        -> lbfgsx_post_linesearch_spec (K3 as step 0 of the recursion's launch)
 //     :162    add_correction                        -> lbfgsx_commit_correction (index rotation)
 //     :165    apply_Hv                              -> lbfgsx_apply_Hv          (one persistent launch, or 2c+1 of K1)
@@ -136,6 +137,8 @@ class LBFGSSolver
         {
             detail::Range range_iteration("lbfgs:iteration");
             detail::check(lbfgsx_ls_begin(c));
+            if (!gram)  // the first trial may run the post statements of :130-161 in its own pass (lbfgsx.h)
+                detail::check(lbfgsx_ls_post_in_trial(c, -1.0));
             const Scalar step_max = m_param.max_step;
             ev.trial_written = false;
             try

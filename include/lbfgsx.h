@@ -139,6 +139,22 @@ int lbfgsx_commit_correction(lbfgsx_ctx* c);
 int lbfgsx_post_linesearch_spec(lbfgsx_ctx* c, double a, double* gnorm2, double* xnorm2, double* sy, double* yy);
 /* instrumentation: {fused launches, directions taken over by lbfgsx_apply_Hv, pairs rejected by the kernel} */
 int lbfgsx_spec_counts(const lbfgsx_ctx* c, int64_t out[3]);
+/* Post form of the first trial.  To be called right after lbfgsx_ls_begin by a driver that will run
+ * lbfgsx_post_linesearch_spec(c, a, ...) after the search (include/LBFGS.h with the vector recursion and no reducer).  The
+ * search's first lbfgsx_trial may then run the statements that follow an accepted search in its own pass: s = x - xp and
+ * y = grad - gradp into the spare history column, g.g, x.x, s.y, y.y (LBFGS.h:130,137,159-161) and the first dot of the
+ * recursion on the new gradient, s.(a grad) (BFGSMat.h:283-288) -- 7n elements instead of the trial's 4n, and when that
+ * trial is accepted lbfgsx_post_linesearch_spec returns its sums without a pass of its own and launches the recursion from
+ * the gradient (no step 0: 11.0n instead of 14.6n elements around an accepted first trial at n = 1e8, m = 10).  A rejected
+ * first trial has moved 3n elements for nothing, so the context uses the form only when the previous search accepted its
+ * first trial, the history is non-empty, the objective goes through k_trial (a built-in one or a bound term objective; the
+ * chain, grid, graph, mesh and linear-model objectives keep the plain form) and the context is not a row shard; a search
+ * whose post-form trial is rejected goes on with plain trials and today's fused launch.  Same statements on the same
+ * operands: bit-identical results.  LBFGSX_POST_IN_TRIAL=0 (read when the context is created) switches the form off. */
+int lbfgsx_ls_post_in_trial(lbfgsx_ctx* c, double a);
+/* instrumentation: {post-form trials issued, of which accepted, persistent launches that started from the gradient,
+ * 1 if the form is enabled for this context} */
+int lbfgsx_post_in_trial_counts(const lbfgsx_ctx* c, int64_t out[4]);
 /* ---- term objectives compiled at run time -------------------------------------------------------------------------
  * An objective that is a sum of terms over K consecutive coordinates (K = 1 or 2), evaluated INSIDE the fused kernels like
  * the two built-in ones.  `body` is HIP/C++ text for one term: statements that see

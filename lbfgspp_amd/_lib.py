@@ -122,6 +122,8 @@ def load():
     sig(core, "lbfgsx_device_download", i32, i32, vp, i64, vp)
     sig(core, "lbfgsx_device_free", None, i32, vp)
     sig(core, "lbfgsx_spec_counts", i32, vp, C.POINTER(i64 * 3))
+    sig(core, "lbfgsx_ls_post_in_trial", i32, vp, dbl)
+    sig(core, "lbfgsx_post_in_trial_counts", i32, vp, C.POINTER(i64 * 4))
     sig(core, "lbfgsx_counters", i32, C.POINTER(i64 * 3), i32)
     sig(core, "lbfgsx_counters_ex", i32, C.POINTER(i64 * 8), i32)
     sig(core, "lbfgsx_poll_counts", i32, vp, C.POINTER(i64 * 2))

@@ -240,13 +240,29 @@ struct lbfgsx_ctx
     int spec_cur = 0;              // point whose gradient it used
     double spec_a = 0.0, spec_dg = 0.0;
     int64_t spec_launches = 0, spec_used = 0, spec_rejected = 0;  // instrumentation
+    // Post form of the first trial (k_trial_post, lbfgsx_ls_post_in_trial): the trial's pass also forms s, y, the four post
+    // sums and the recursion's first dot, so that an accepted first trial needs neither K3 nor step 0 of the fused launch.
+    // Used for the first trial of a search iff the driver asked for it, the previous search accepted its first trial (a
+    // rejected post-form trial has read gp and written s, y for nothing), the history is non-empty and the context is
+    // not a row shard.
+    bool post_in_trial = true;     // LBFGSX_POST_IN_TRIAL=0: never (read once, at creation)
+    bool pt_armed = false;         // lbfgsx_ls_post_in_trial was called for the search in progress
+    double pt_a = 0.0;             // the scale it gave for the recursion's start vector
+    int ls_trials = 0;             // trials evaluated by the search in progress
+    bool ls_first_ok = false;      // the previous search accepted its first trial
+    bool pt_valid = false;         // the search's only trial so far was a post-form one: pt_r holds its sums
+    int pt_buf = -1, pt_xp = -1;   // the point it wrote and the point it started from
+    double pt_r[4] = {0, 0, 0, 0};  // {g.g, x.x, s.y, y.y}
+    int64_t pt_issued = 0, pt_accepted = 0;  // instrumentation (lbfgsx_post_in_trial_counts)
+    int64_t from_g_launches = 0;   // persistent launches that started the recursion from the gradient
 
     // a term objective compiled at run time and bound to this context (lbfgsx_objective_bind, jit_objective.hip): the id
     // LBFGSX_OBJ_BOUND then evaluates it inside the fused kernels.  term_p: the caller's device arrays (term_own: the
     // context's copies of host arrays, lbfgsx_objective_upload, bound only when the caller passes them), term_c: its scalars
     const struct lbfgsx_objective* term = nullptr;
-    // its four kernels on this context's device (hipFunction_t); slots 4 and 5: a linear-model objective's two row passes
-    void* term_fn[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // its four kernels on this context's device (hipFunction_t); slots 4 and 5: a linear-model objective's two row passes;
+    // slot 6: a term objective's post form of k_trial (launch_args.hpp)
+    void* term_fn[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const void* term_p[4] = {nullptr, nullptr, nullptr, nullptr};
     double term_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int term_np = 0;  // data arrays bound (byte model)

@@ -37,7 +37,7 @@
 namespace {
 
 const char* const kKernelNames[6][lbfgsx::JIT_NSLOTS] = {
-    {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial"},
+    {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial", nullptr, nullptr, "k_trial_post"},
     {"k_chain_eval", "k_chain_trial", "k_chain_b_eval", "k_chain_b_dg_maxstep_trial"},
     {"k_grid_eval", "k_grid_trial", "k_grid_b_eval", "k_grid_b_dg_maxstep_trial"},
     {"k_graph_eval", "k_graph_trial", "k_graph_b_eval", "k_graph_b_dg_maxstep_trial"},
@@ -46,8 +46,9 @@ const char* const kKernelNames[6][lbfgsx::JIT_NSLOTS] = {
 const char* const kObjStruct[6] = {"ObjTerm", "ObjChain", "ObjGrid", "ObjGraph", "ObjMesh", "ObjLinear"};
 const char* const kFormName[6] = {"term objective", "chain objective", "grid objective", "graph objective", "mesh objective",
                                   "linear-model objective"};
-// the kernels of a form: the four every form has, and a linear-model objective's two row passes
-inline int kernels_of(int form) { return form == LBFGSX_FORM_LINEAR ? lbfgsx::JIT_NSLOTS : lbfgsx::JIT_NKERNELS; }
+// does a form have the kernel of slot k: the four every form has, a linear-model objective's two row passes, a term
+// objective's post form of k_trial (a table row names exactly the slots of its form)
+inline bool has_kernel(int form, int k) { return k >= 0 && k < lbfgsx::JIT_NSLOTS && kKernelNames[form][k] != nullptr; }
 
 // ---- hipRTC, loaded on first use (a process that never compiles an objective does not need it)
 struct Rtc
@@ -184,6 +185,8 @@ std::string generate(int form, int dtype, int K, const char* body, const char* n
     s += "typedef term_scalar_t S;\n";
     s += "template __global__ void k_eval<S, ObjTerm>(const S*, S*, int64_t, ObjTerm, RedWs, S*);\n";
     s += "template __global__ void k_trial<S, ObjTerm>(const S*, const S*, S, S*, S*, int64_t, ObjTerm, RedWs, S*, int);\n";
+    s += "template __global__ void k_trial_post<S, ObjTerm>(const S*, const S*, S, S*, S*, int64_t, ObjTerm, RedWs, S*, int, "
+         "TrialPost<S>);\n";
     s += "template __global__ void k_b_eval<S, ObjTerm>(const S*, S*, const S*, const S*, int64_t, ObjTerm, RedWs, S*);\n";
     s += "template __global__ void k_b_dg_maxstep_trial<S, ObjTerm>(const S*, const S*, const S*, const S*, const S*, S, S*, S*, "
          "int64_t, ObjTerm, RedWs, S*, int);\n";
@@ -598,12 +601,12 @@ struct lbfgsx_objective_code
     int form = LBFGSX_FORM_TERM, dtype = LBFGSX_F64, K = 1, D = 1;
     std::vector<char> code;
     std::string lowered[lbfgsx::JIT_NSLOTS];
-    long long vgprs[lbfgsx::JIT_NSLOTS] = {0, 0, 0, 0, 0, 0}, scratch[lbfgsx::JIT_NSLOTS] = {0, 0, 0, 0, 0, 0};
+    long long vgprs[lbfgsx::JIT_NSLOTS] = {0, 0, 0, 0, 0, 0, 0}, scratch[lbfgsx::JIT_NSLOTS] = {0, 0, 0, 0, 0, 0, 0};
     double compile_ms = 0.0;
     struct Loaded
     {
         hipModule_t mod = nullptr;
-        hipFunction_t fn[lbfgsx::JIT_NSLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        hipFunction_t fn[lbfgsx::JIT_NSLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     };
     std::mutex mu;
     std::map<int, Loaded> loaded;  // per device
@@ -639,9 +642,11 @@ int compile_code(int form, int dtype, int K, int D, const char* body, const char
         return LBFGSX_E_RUNTIME;
     }
     std::string expr[lbfgsx::JIT_NSLOTS];
-    const int nk = kernels_of(form);
+    const int nk = lbfgsx::JIT_NSLOTS;
     for (int k = 0; k < nk; k++)
     {
+        if (!has_kernel(form, k))
+            continue;
         expr[k] = std::string("lbfgsx::") + kKernelNames[form][k] + "<lbfgsx::term_scalar_t, lbfgsx::" + kObjStruct[form] + ">";
         (void) r.add_name(prog, expr[k].c_str());
     }
@@ -680,6 +685,8 @@ int compile_code(int form, int dtype, int K, int D, const char* body, const char
     }
     for (int k = 0; ok && k < nk; k++)
     {
+        if (!has_kernel(form, k))
+            continue;
         const char* low = nullptr;
         ok = r.lowered(prog, expr[k].c_str(), &low) == HIPRTC_SUCCESS && low;
         if (ok)
@@ -852,8 +859,10 @@ int lbfgsx_objective_info(const lbfgsx_objective* obj, long long out[8])
         return LBFGSX_E_INVALID;
     const lbfgsx_objective_code* k = obj->code;
     out[0] = out[1] = 0;
-    for (int j = 0; j < kernels_of(k->form); j++)  // the maxima cover a linear-model objective's two row passes
+    for (int j = 0; j < lbfgsx::JIT_NSLOTS; j++)  // the maxima cover the row passes and the post form of k_trial
     {
+        if (!has_kernel(k->form, j))
+            continue;
         out[0] = k->vgprs[j] > out[0] ? k->vgprs[j] : out[0];
         out[1] = k->scratch[j] > out[1] ? k->scratch[j] : out[1];
         if (j < lbfgsx::JIT_NKERNELS)
@@ -965,8 +974,9 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
         {
             lbfgsx_objective_code::Loaded l;
             LBFGSX_HIP(hipModuleLoadData(&l.mod, code->code.data()));
-            for (int k = 0; k < kernels_of(code->form); k++)
-                LBFGSX_HIP(hipModuleGetFunction(&l.fn[k], l.mod, code->lowered[k].c_str()));
+            for (int k = 0; k < lbfgsx::JIT_NSLOTS; k++)
+                if (has_kernel(code->form, k))
+                    LBFGSX_HIP(hipModuleGetFunction(&l.fn[k], l.mod, code->lowered[k].c_str()));
             it = code->loaded.emplace(c->device, l).first;
         }
         for (int k = 0; k < lbfgsx::JIT_NSLOTS; k++)

@@ -93,7 +93,10 @@ inline DgTrialLaunch<T> dg_maxstep_trial_launch(lbfgsx_ctx* c, T step, int obj_v
 // ---- a term objective bound to the context (lbfgsx_objective_bind, jit_objective.hip)
 enum { JIT_K_EVAL = 0, JIT_K_TRIAL = 1, JIT_K_B_EVAL = 2, JIT_K_B_DG_MAXSTEP_TRIAL = 3, JIT_NKERNELS = 4 };
 // a linear-model objective has two more, the row passes that precede its four column-pass kernels (linear_kernels.cuh)
-enum { JIT_K_LIN_ROWS = 4, JIT_K_LIN_ROWS_TRIAL = 5, JIT_NSLOTS = 6 };
+enum { JIT_K_LIN_ROWS = 4, JIT_K_LIN_ROWS_TRIAL = 5 };
+// a term objective has one more, the post form of k_trial (lbfgs_kernels.cuh: k_trial_post); the forms with kernels of their own
+// (chain, grid, graph, mesh, linear) have none
+enum { JIT_K_TRIAL_POST = 6, JIT_NSLOTS = 7 };
 // the by-value kernel argument: layout of the generated struct ObjTerm (four data pointers, eight scalars of type T)
 template <class T>
 struct TermArgs

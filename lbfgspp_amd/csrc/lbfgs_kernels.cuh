@@ -121,15 +121,36 @@ __global__ void __launch_bounds__(kBlock) k_eval(const T* __restrict__ x, T* __r
 // x = xp + step*d ; g = grad f(x) ; out[0] = f(x), out[1] = g.d
 // Plain (cacheable) loads of xp and d and stores of x and g, 4 vectors per stream and thread in flight: non-temporal hints
 // and 8 in flight were measured and lost (profiles/r2_trial_policy_ab.txt)
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_trial(const T* __restrict__ xp, const T* __restrict__ d, T step,
-                                                  T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj,
-                                                  RedWs ws, T* __restrict__ out, int rev)
+//
+// Post form (k_trial_post): the pass that produces x and g of a trial the search is expected to accept also runs the
+// statements that follow an accepted search (K3 and the first statement of the recursion, as step 0 of k_twoloop_persist
+// has them): s = x - xp and y = g - gp go into the spare history column, and five more sums ride along --
+//     out[2..5] = {g.g, x.x, s.y, y.y}        (LBFGS.h:130,137,159-161)
+//     *dot0     = s.(a*g)                      (the first dot of the two-loop recursion on the new gradient, BFGSMat.h:283-288)
+//     *ys_slot = s.y, *theta_slot = y.y / s.y  (BFGSMat.h:89-92)
+// Same expressions on the same operands, the same accumulators: bit-identical to the step-0 code.
+template <class T>
+struct TrialPost
+{
+    const T* gp;      // gradient at xp
+    T* s;             // spare history columns that receive s and y
+    T* y;
+    T a;              // scale of the recursion's start vector (q0 = a * g; -1 in the solvers)
+    T* ys_slot;       // sc[] slots of the spare column
+    T* theta_slot;
+    T* dot0;          // sc[] slot of the recursion's first dot
+};
+
+template <class T, class OBJ, bool POST>
+__device__ __forceinline__ void trial_pass(const T* __restrict__ xp, const T* __restrict__ d, T step, T* __restrict__ x,
+                                           T* __restrict__ g, int64_t n, const OBJ& obj, const RedWs& ws,
+                                           T* __restrict__ out, int rev, const TrialPost<T>& tp)
 {
     typedef typename AccOf<T>::type A;
     constexpr int W = Vec16<T>::W;
     constexpr int U = 4;
-    A acc[2];
+    constexpr int NRED = POST ? 7 : 2;
+    A acc[NRED];
     const int64_t nv = n / W;
     // tiles of U x kBlock vectors; both loads of every vector are issued before the first use.  The tile order
     // alternates between launches (TwoLoopArgs::rev)
@@ -138,13 +159,15 @@ __global__ void __launch_bounds__(kBlock) k_trial(const T* __restrict__ xp, cons
     for (int64_t t0 = int64_t(blockIdx.x) * tile; t0 < nv; t0 += int64_t(gridDim.x) * tile)
     {
         const int64_t base = (rev ? top - t0 : t0) + threadIdx.x;
-        Pack<T> pxp[U], pd[U];
+        Pack<T> pxp[U], pd[U], pgp[POST ? U : 1];
 #pragma unroll
         for (int u = 0; u < U; u++)
             if (base + u * kBlock < nv)
             {
                 pxp[u] = ldv(xp, base + u * kBlock);
                 pd[u] = ldv(d, base + u * kBlock);
+                if (POST)
+                    pgp[POST ? u : 0] = ldv(tp.gp, base + u * kBlock);
             }
 #pragma unroll
         for (int u = 0; u < U; u++)
@@ -162,6 +185,24 @@ __global__ void __launch_bounds__(kBlock) k_trial(const T* __restrict__ xp, cons
 #pragma unroll
                 for (int k = 0; k < W; k++)
                     acc[1].add_prod(pg.e[k], pd[u].e[k]);
+                if (POST)
+                {
+                    Pack<T> ps, py;
+#pragma unroll
+                    for (int k = 0; k < W; k++)
+                    {
+                        ps.e[k] = px.e[k] - pxp[u].e[k];
+                        py.e[k] = pg.e[k] - pgp[POST ? u : 0].e[k];
+                        const T q0 = tp.a * pg.e[k];
+                        acc[POST ? 2 : 0].add_prod(pg.e[k], pg.e[k]);
+                        acc[POST ? 3 : 0].add_prod(px.e[k], px.e[k]);
+                        acc[POST ? 4 : 0].add_prod(ps.e[k], py.e[k]);
+                        acc[POST ? 5 : 0].add_prod(py.e[k], py.e[k]);
+                        acc[POST ? 6 : 0].add_prod(ps.e[k], q0);
+                    }
+                    stv(tp.s, vi, ps);
+                    stv(tp.y, vi, py);
+                }
             }
         }
     }
@@ -174,13 +215,51 @@ __global__ void __launch_bounds__(kBlock) k_trial(const T* __restrict__ xp, cons
             obj.tail(i, n, x, g, acc[0]);
             acc[1].add_prod(g[i], d[i]);
         }
+        if (POST)
+            for (int64_t i = nv * W; i < n; i++)
+            {
+                const T si = x[i] - xp[i], yi = g[i] - tp.gp[i], q0 = tp.a * g[i];
+                tp.s[i] = si;
+                tp.y[i] = yi;
+                acc[POST ? 2 : 0].add_prod(g[i], g[i]);
+                acc[POST ? 3 : 0].add_prod(x[i], x[i]);
+                acc[POST ? 4 : 0].add_prod(si, yi);
+                acc[POST ? 5 : 0].add_prod(yi, yi);
+                acc[POST ? 6 : 0].add_prod(si, q0);
+            }
     }
-    if (grid_reduce<2>(acc, ws) && threadIdx.x == 0)
+    if (grid_reduce<NRED>(acc, ws) && threadIdx.x == 0)
     {
         out[0] = obj.finish(T(acc[0].value()));
         out[1] = T(acc[1].value());
+        if (POST)
+        {
+            const T sy = T(acc[POST ? 4 : 0].value()), yy = T(acc[POST ? 5 : 0].value());
+            out[2] = T(acc[POST ? 2 : 0].value());
+            out[3] = T(acc[POST ? 3 : 0].value());
+            out[4] = sy;
+            out[5] = yy;
+            *tp.ys_slot = sy;
+            *tp.theta_slot = yy / sy;
+            *tp.dot0 = T(acc[POST ? 6 : 0].value());
+        }
         ws_signal(ws);
     }
+}
+
+template <class T, class OBJ>
+__global__ void __launch_bounds__(kBlock) k_trial(const T* __restrict__ xp, const T* __restrict__ d, T step,
+                                                  T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj,
+                                                  RedWs ws, T* __restrict__ out, int rev)
+{
+    trial_pass<T, OBJ, false>(xp, d, step, x, g, n, obj, ws, out, rev, TrialPost<T>());
+}
+template <class T, class OBJ>
+__global__ void __launch_bounds__(kBlock) k_trial_post(const T* __restrict__ xp, const T* __restrict__ d, T step,
+                                                       T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj,
+                                                       RedWs ws, T* __restrict__ out, int rev, TrialPost<T> tp)
+{
+    trial_pass<T, OBJ, true>(xp, d, step, x, g, n, obj, ws, out, rev, tp);
 }
 
 // generic-functor path: x = xp + step*d only (user kernel evaluates f,g), and g.d
@@ -565,6 +644,9 @@ struct PersistArgs
     unsigned first_rev;    // direction parity of the first step
     int64_t ld;            // column stride of S / Y (elements)
     int pub_first;         // always 1: a step's {generation, dot} goes out before the dot's copy for the host (see zigzag)
+    int from_g;            // 1 (FUSE = false only): the recursion starts from the gradient.  The post form of k_trial has left
+                           // the first dot s.(a*g) in sc[DOT0]; step 0 then only fills the resident slots with a*g (no streamed
+                           // part, no dot, no meeting point) and step 1 forms a*g from g where it would load the stored q
 };
 
 constexpr int kSc1 = 16;  // cache-policy bit of the buffer instructions: agent scope (loads bypass L1, stores write through)
@@ -835,9 +917,20 @@ __global__ void __launch_bounds__(kHvThreads, 2)
     __shared__ T s_dotv[MEET ? kPersistMaxM + 1 : 1];       // the dots of the first loop's steps; entry cn: the latest later dot
     __shared__ T s_ys[MEET ? kPersistMaxM : 1];             // s.y of the columns, by position in pcol
     __shared__ T s_theta0;
+    // from_g: what the launch's closing signal needs (completion word, its sequence number, the host's output slots) waits
+    // in LDS, not in scalar registers held through every step (measured: 2 more spilled registers in the MEET forms).
+    // Written here by thread 0, read at the last meeting point by thread 0 of the block that closes it: the same thread of
+    // the same block, so program order is all the ordering it needs.  (One element under FUSE, which never touches it.)
+    __shared__ unsigned long long s_sig[FUSE ? 1 : 3];
     const int tid = threadIdx.x;
     if (tid < kPersistMaxM)
         s_pcol[tid] = pa.pcol[tid];
+    if (!FUSE && tid == 0)
+    {
+        s_sig[0] = (unsigned long long) ws.done;
+        s_sig[FUSE ? 0 : 1] = ws.seq;
+        s_sig[FUSE ? 0 : 2] = (unsigned long long) pf.out;
+    }
     // A launch that finds the failure word already set does nothing at all: every block sees the same word, so the grid
     // leaves uniformly and the host redoes the product with the step launches (also the hook of the fault-injection test,
     // lbfgsx_debug_persist_fault).  s_verdict doubles as the flag; FUSE rewrites it at the first meeting point.
@@ -865,8 +958,11 @@ __global__ void __launch_bounds__(kHvThreads, 2)
             s_ys[tid] = sload(s_pcol[tid]);
         if (tid == 0)
             s_theta0 = cn > 0 ? sload(m + 1 + s_pcol[0]) : T(1);
+        if (!FUSE && tid == 0 && pa.from_g)
+            s_dotv[0] = sload(DOT0);
         __syncthreads();
     }
+    const bool fromg = !FUSE && pa.from_g != 0;
     // the dot of step k / s.y of the pair at position i of the list / theta, wherever this form keeps them
     auto dslot = [&](int k) { return MEET ? (k < cn ? k : cn) : 0; };  // (static LDS stays under the 64 KB a launch may have)
     auto dotv = [&](int k) { return MEET ? s_dotv[dslot(k)] : sload(DOT0 + k); };
@@ -1059,7 +1155,7 @@ __global__ void __launch_bounds__(kHvThreads, 2)
         if (L == 0)
         {
             u = vin;
-            w = cn > 0 ? col(S, s_pcol[0]) : vin;
+            w = (cn > 0 && !fromg) ? col(S, s_pcol[0]) : vin;  // from_g: no dot in this step
         }
         else if (L < cn)
         {
@@ -1084,7 +1180,7 @@ __global__ void __launch_bounds__(kHvThreads, 2)
         {
             // the first loads of this step are in flight while the block waits for the previous step's dot
             hv_prefetch<T>(u, w, res_end, gt, gthreads, pu0, pw0);
-            if (L > (FUSE ? 1 : 0))
+            if (L > ((FUSE || fromg) ? 1 : 0))
             {
                 if (tid == 0 && !was_last)
                 {
@@ -1119,7 +1215,9 @@ __global__ void __launch_bounds__(kHvThreads, 2)
         {
             const bool rev = pa.zigzag && (((pa.first_rev + unsigned(L)) & 1u) != 0u);
             const int64_t span = nv - res_end;
-            const int64_t ntile = (span + tile - 1) / tile;
+            // from_g: step 0 stores no q0 = a*g for the streamed part -- step 1 forms it from g (g1)
+            const bool g1 = fromg && L == 1;
+            const int64_t ntile = (fromg && L == 0) ? 0 : (span + tile - 1) / tile;
             for (int64_t t0 = blockIdx.x; t0 < ntile; t0 += gridDim.x)
             {
                 const int64_t tt = rev ? ntile - 1 - t0 : t0;
@@ -1133,6 +1231,10 @@ __global__ void __launch_bounds__(kHvThreads, 2)
                 // it/s, plain accesses + agent release before arrival + acquire after 84.2, this form 87.1.
                 const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
                     const_cast<T*>(q) + W * (res_end + tt * tile), 0, int(tile * 16), 0x00020000);
+                // where the step's q comes from: q itself, or (g1) the gradient -- a wave-uniform choice of the descriptor,
+                // one load sequence into the same pq[k] (the kernel sits at its register cap)
+                const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc(
+                    const_cast<T*>(g1 ? vin : q) + W * (res_end + tt * tile), 0, int(tile * 16), 0x00020000);
                 Pack<T> pq[U], pu[U], pw[U];
 #pragma unroll
                 for (int k = 0; k < U; k++)
@@ -1144,9 +1246,15 @@ __global__ void __launch_bounds__(kHvThreads, 2)
                         pw[k] = ldv<T, true>(w, vi);
                         if (L != 0)
                             pq[k].v = __builtin_bit_cast(typename Vec16<T>::type,
-                                                         __builtin_amdgcn_raw_buffer_load_b128(rq, int((tid + k * kHvThreads) * 16), 0, kSc1));
+                                                         __builtin_amdgcn_raw_buffer_load_b128(rl, int((tid + k * kHvThreads) * 16), 0, kSc1));
                     }
                 }
+                if (g1)  // q0 = a * g (BFGSMat.h:283), the value step 0 would have stored
+#pragma unroll
+                    for (int k = 0; k < U; k++)
+#pragma unroll
+                        for (int e = 0; e < W; e++)
+                            pq[k].e[e] = a * pq[k].e[e];
 #pragma unroll
                 for (int k = 0; k < U; k++)
                 {
@@ -1170,16 +1278,18 @@ __global__ void __launch_bounds__(kHvThreads, 2)
             // producer side of the hand-off: this wave's write-through stores have reached memory before the block
             // arrives at the meeting point (grid_reduce synchronises the block before its lane 0 takes the ticket)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (blockIdx.x == 0 && tid == 0)  // scalar tail (n not a multiple of the vector width)
+            if (blockIdx.x == 0 && tid == 0 && !(fromg && L == 0))  // scalar tail (n not a multiple of the vector width)
                 for (int64_t i = nv * W; i < n; i++)
                 {
-                    T qv = (L == 0) ? a * u[i] : q[i] + c * u[i];
+                    T qv = (L == 0) ? a * u[i] : (g1 ? a * vin[i] : q[i]) + c * u[i];
                     if (div)
                         qv = qv / theta;
                     q[i] = qv;
                     acc4[0].add_prod(w[i], qv);
                 }
         }
+        if (fromg && L == 0)
+            continue;  // the step's dot is known (sc[DOT0] / s_dotv[0]): nothing to reduce, nobody to meet
         A acc[1];
         acc[0] = acc4[0];
         for (int k = 1; k < 4; k++)
@@ -1206,6 +1316,17 @@ __global__ void __launch_bounds__(kHvThreads, 2)
                 __hip_atomic_store(sc + DOT0 + L, dv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (!pa.pub_first && L < 2 * cn)  // the last dot is only read by the host
                     persist_publish(gen + 4, want, double(dv));
+                if (!FUSE && fromg && L == 2 * cn)
+                {
+                    // the same closing signal for the launch that started from the gradient (the sums went out with the trial)
+                    T* o = reinterpret_cast<T*>(s_sig[FUSE ? 0 : 2]);
+                    RedWs wsig;
+                    wsig.done = reinterpret_cast<unsigned long long*>(s_sig[0]);
+                    wsig.seq = s_sig[FUSE ? 0 : 1];
+                    __hip_atomic_store(o + 4, dv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(o + 5, T(1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    ws_signal(wsig);
+                }
                 if (FUSE && L == 2 * cn)
                 {
                     // the launch's last meeting point: everything the host reads next is known -- grad . d here, the post

@@ -363,6 +363,8 @@ static int create_fill(lbfgsx_ctx* c, int dtype, int64_t n, int m, int device, i
         c->fast_persist_out = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_FUSE_POST"))
         c->fuse_post = atoi(e) != 0;
+    if (const char* e = getenv("LBFGSX_POST_IN_TRIAL"))
+        c->post_in_trial = atoi(e) != 0;
     {
         // the persistent two-loop needs every block resident at once: occupancy * CUs
         int occ = 0;
@@ -637,6 +639,8 @@ int lbfgsx_bfgs_reset(lbfgsx_ctx* c)
     c->ptr = c->m;
     c->pending = false;
     c->spec_valid = false;
+    c->pt_valid = c->pt_armed = c->ls_first_ok = false;
+    c->ls_trials = 0;
     c->tl_step = 0;  // the traversal direction of every launch of a run is a function of the run alone
     for (int j = 0; j < c->m; j++)
         c->phys[size_t(j)] = j;
@@ -705,6 +709,7 @@ int lbfgsx_bfgs_stage_correction_host(lbfgsx_ctx* c, const void* s, const void* 
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
+    c->pt_valid = false;    // the spare column receives another pair
     if (c->gs_f32h)
     {
         set_error("lbfgsx_bfgs_stage_correction_host: this context keeps its history in f32 for the Gram-space recursion (lbfgsx_gs_set_history_dtype)");
@@ -793,6 +798,7 @@ static int apply_Hv_t(lbfgsx_ctx* c, const T* v, T a, double* dg)
         pa.first_rev = c->tl_step;
         pa.pub_first = 1;
         pa.ld = c->ld;
+        pa.from_g = 0;
         // one generation number per meeting point: the word the blocks wait for (LBFGSX_MEET=last) or the tag of the
         // 16-byte words they exchange (the default)
         c->gen_count += unsigned(2 * cn + 1);
@@ -994,6 +1000,7 @@ int lbfgsx_eval(lbfgsx_ctx* c, int objective, double* fx, double* gnorm2, double
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
+    c->pt_valid = false;
     double r[3];
     int rc = LBFGSX_E_INVALID;
     if (objective == LBFGSX_OBJ_EXT_ROSENBROCK && (c->n & 1))
@@ -1040,6 +1047,8 @@ int lbfgsx_norms(lbfgsx_ctx* c, double* gnorm2, double* xnorm2)
 int lbfgsx_ls_begin(lbfgsx_ctx* c)
 {
     c->st_valid = false;
+    c->pt_valid = c->pt_armed = false;
+    c->ls_trials = 0;
     c->xp = c->cur;
     c->lo = c->xp;
     c->trial = (c->xp + 1) % 3;
@@ -1056,6 +1065,62 @@ static int trial_t(lbfgsx_ctx* c, OBJ obj, T step, double* out2)
                        a.out, a.rev);
     LBFGSX_HIP(hipGetLastError());
     return fetch_scalars<T>(c, c->sl.out(0), 2, out2);
+}
+// the extra argument of the post form (k_trial_post): gp, the spare column and its scalar slots, the recursion's first dot
+template <class T>
+static lbfgsx::TrialPost<T> trial_post_args(lbfgsx_ctx* c)
+{
+    T* sc = P<T>(c->sc);
+    return {P<T>(c->gb[c->xp]), P<T>(c->col(c->S, c->spare)), P<T>(c->col(c->Y, c->spare)), T(c->pt_a),
+            sc + c->sl.ys(c->spare), sc + c->sl.theta(c->spare), sc + c->sl.dot(0)};
+}
+// what a post-form trial leaves in the context: out6 = {f, g.d, g.g, x.x, s.y, y.y}
+static void trial_post_done(lbfgsx_ctx* c, const double* out6)
+{
+    c->pending = false;  // the spare column holds this trial's pair; it becomes pending when the trial is accepted
+    c->pt_valid = true;
+    c->pt_buf = c->trial;
+    c->pt_xp = c->xp;
+    for (int i = 0; i < 4; i++)
+        c->pt_r[i] = out6[2 + i];
+    c->pt_issued++;
+}
+template <class T, class OBJ>
+static int trial_post_t(lbfgsx_ctx* c, OBJ obj, T step, double* out2)
+{
+    const lbfgsx::TrialLaunch<T> a = lbfgsx::trial_launch<T>(c, step, sizeof(OBJ) >= 2 * sizeof(void*) ? 2 : 0);
+    const lbfgsx::TrialPost<T> tp = trial_post_args<T>(c);
+    LBFGSX_LAUNCH((k_trial_post<T, OBJ>), dim3(a.grid), dim3(kBlock), 0, c->stream, a.xp, a.d, a.step, a.x, a.g, a.n, obj,
+                       a.ws, a.out, a.rev, tp);
+    LBFGSX_HIP(hipGetLastError());
+    double r[6];
+    const int rc = fetch_scalars<T>(c, c->sl.out(0), 6, r);
+    if (rc)
+        return rc;
+    out2[0] = r[0];
+    out2[1] = r[1];
+    trial_post_done(c, r);
+    return LBFGSX_OK;
+}
+// the post form of the kernel compiled for the context's bound term objective
+template <class T>
+static int trial_post_term_t(lbfgsx_ctx* c, T step, double* out2)
+{
+    lbfgsx::TrialLaunch<T> a = lbfgsx::trial_launch<T>(c, step, c->term_np);
+    lbfgsx::BoundArgs<T> obj(c);
+    lbfgsx::TrialPost<T> tp = trial_post_args<T>(c);
+    void* params[] = {&a.xp, &a.d, &a.step, &a.x, &a.g, &a.n, obj.ptr, &a.ws, &a.out, &a.rev, &tp};
+    int rc = lbfgsx::jit_launch(c, lbfgsx::JIT_K_TRIAL_POST, a.grid, params);
+    if (rc)
+        return rc;
+    double r[6];
+    rc = fetch_scalars<T>(c, c->sl.out(0), 6, r);
+    if (rc)
+        return rc;
+    out2[0] = r[0];
+    out2[1] = r[1];
+    trial_post_done(c, r);
+    return LBFGSX_OK;
 }
 template <class T>
 static int trial_term_t(lbfgsx_ctx* c, T step, double* out2)
@@ -1089,6 +1154,7 @@ int lbfgsx_trial(lbfgsx_ctx* c, int objective, double step, double* fx, double* 
         if (same)
         {
             c->st_hits++;
+            c->ls_trials++;
             c->tl_step++;  // the traversal order alternates between trial launches: this was one
             if (fx) *fx = c->st_f;
             if (dg) *dg = c->st_dg;
@@ -1096,13 +1162,22 @@ int lbfgsx_trial(lbfgsx_ctx* c, int objective, double step, double* fx, double* 
         }
         c->st_cooldown = 4;
     }
+    // the post form for the first trial of a search the driver armed (lbfgsx_ls_post_in_trial): the objectives that go through
+    // k_trial -- the built-in ones and a bound term objective.  The chain, grid, graph, mesh and linear-model objectives have
+    // trial kernels of their own, which keep the plain form
+    const bool post = c->pt_armed && c->ls_trials == 0 &&
+                      (objective == LBFGSX_OBJ_DIAG_QUAD || objective == LBFGSX_OBJ_EXT_ROSENBROCK ||
+                       (lbfgsx::term_bound(c, objective) && c->term_fn[lbfgsx::JIT_K_TRIAL_POST] != nullptr));
+    c->ls_trials++;
+    c->pt_valid = false;
     DISPATCH_T(c, {
         if (objective == LBFGSX_OBJ_DIAG_QUAD)
-            rc = trial_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, T(step), r);
+            rc = post ? trial_post_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, T(step), r)
+                      : trial_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, T(step), r);
         else if (objective == LBFGSX_OBJ_EXT_ROSENBROCK)
-            rc = trial_t<T>(c, ObjRosen<T>{}, T(step), r);
+            rc = post ? trial_post_t<T>(c, ObjRosen<T>{}, T(step), r) : trial_t<T>(c, ObjRosen<T>{}, T(step), r);
         else if (lbfgsx::term_bound(c, objective))
-            rc = trial_term_t<T>(c, T(step), r);
+            rc = post ? trial_post_term_t<T>(c, T(step), r) : trial_term_t<T>(c, T(step), r);
         else
             set_error("lbfgsx_trial: unknown objective");
     });
@@ -1117,6 +1192,8 @@ int lbfgsx_trial_point(lbfgsx_ctx* c, double step)
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
+    c->pt_valid = false;
+    c->ls_trials++;
     const int grid = c->grid_for(c->n);
     DISPATCH_T(c, {
         LBFGSX_LAUNCH((k_axpy_point<T>), dim3(grid), dim3(kBlock), 0, c->stream, P<T>(c->xb[c->xp]), P<T>(c->d),
@@ -1154,6 +1231,7 @@ int lbfgsx_ls_keep_trial_as_lo(lbfgsx_ctx* c)
 int lbfgsx_ls_end(lbfgsx_ctx* c, int use_lo)
 {
     c->cur = use_lo ? c->lo : c->trial;
+    c->ls_first_ok = !use_lo && c->ls_trials == 1;  // what the next search's lbfgsx_ls_post_in_trial goes by
     return LBFGSX_OK;
 }
 
@@ -1161,6 +1239,7 @@ int lbfgsx_post_linesearch(lbfgsx_ctx* c, double* gnorm2, double* xnorm2, double
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
+    c->pt_valid = false;
     if (c->gs_f32h)
     {
         set_error("lbfgsx_post_linesearch: this context keeps its history in f32 for the Gram-space recursion (lbfgsx_gs_set_history_dtype)");
@@ -1191,8 +1270,11 @@ int lbfgsx_post_linesearch(lbfgsx_ctx* c, double* gnorm2, double* xnorm2, double
 
 }  // extern "C"
 // post statements + speculative recursion in one persistent launch; returns 1 when not applicable (caller runs k_post)
+// from_g: an accepted post-form trial has run the post statements and left the recursion's first dot in sc[dot(0)] -- the
+// launch carries no step 0 (k_twoloop_persist<T, false>, PersistArgs::from_g) and r4 is not touched; 1 then means that no
+// direction was stored (lbfgsx_apply_Hv computes it)
 template <class T>
-static int post_spec_t(lbfgsx_ctx* c, T a, double* r4)
+static int post_spec_t(lbfgsx_ctx* c, T a, double* r4, bool from_g = false)
 {
     const int m = c->m;
     if (!(c->fuse_post && c->persist && c->persist_cooldown == 0 && c->persist_grid > 0 && m <= kPersistMaxM && !c->gs_f32h && c->device >= 0 &&
@@ -1222,6 +1304,7 @@ static int post_spec_t(lbfgsx_ctx* c, T a, double* r4)
     pa.first_rev = c->tl_step;
     pa.pub_first = 1;
     pa.ld = c->ld;
+    pa.from_g = from_g ? 1 : 0;
     c->gen_count += unsigned(2 * cn + 1);
     c->tl_step += unsigned(2 * cn + 1);
     T* sc = P<T>(c->sc);
@@ -1251,21 +1334,30 @@ static int post_spec_t(lbfgsx_ctx* c, T a, double* r4)
         static_cast<volatile T*>(c->outmap_host)[5] = T(0);
         lbfgsx::poll_arm(c);
     }
-    if (c->meet_all)
-        LBFGSX_LAUNCH((k_twoloop_persist<T, true, true>), dim3(c->persist_grid), dim3(kHvThreads), 0, c->stream, P<T>(c->d),
-                           P<T>(c->gb[c->cur]), a, P<T>(c->S), P<T>(c->Y), c->n, sc, pa, c->ws, c->gen_dev,
-                           reinterpret_cast<int*>(c->gen_dev + 1), pf);
+#define PERSIST_LAUNCH(FUSE, MEET)                                                                                          \
+    LBFGSX_LAUNCH((k_twoloop_persist<T, FUSE, MEET>), dim3(c->persist_grid), dim3(kHvThreads), 0, c->stream, P<T>(c->d),   \
+                  P<T>(c->gb[c->cur]), a, P<T>(c->S), P<T>(c->Y), c->n, sc, pa, c->ws, c->gen_dev,                        \
+                  reinterpret_cast<int*>(c->gen_dev + 1), pf)
+    if (from_g)
+    {
+        if (c->meet_all)
+            PERSIST_LAUNCH(false, true);
+        else
+            PERSIST_LAUNCH(false, false);
+    }
+    else if (c->meet_all)
+        PERSIST_LAUNCH(true, true);
     else
-        LBFGSX_LAUNCH((k_twoloop_persist<T, true, false>), dim3(c->persist_grid), dim3(kHvThreads), 0, c->stream, P<T>(c->d),
-                           P<T>(c->gb[c->cur]), a, P<T>(c->S), P<T>(c->Y), c->n, sc, pa, c->ws, c->gen_dev,
-                           reinterpret_cast<int*>(c->gen_dev + 1), pf);
+        PERSIST_LAUNCH(true, false);
+#undef PERSIST_LAUNCH
     LBFGSX_HIP(hipGetLastError());
+    const int fused = from_g ? 0 : 1;  // fused_timed counts the launches that carried step 0
     if (c->timing)
     {
         LBFGSX_HIP(hipEventRecord(hv.b, c->stream));
         c->ev_hv.push_back(hv);
-        c->persist_steps_timed += 2 * cn + 1;
-        c->fused_timed++;
+        c->persist_steps_timed += 2 * cn + 1;  // from_g too: the product's 2c+1 step-equivalents (step 0 ran in the trial)
+        c->fused_timed += fused;
     }
     int hflags[2] = {0, 0};  // time-out flag, verdict
     double dgv = 0.0;
@@ -1281,7 +1373,7 @@ static int post_spec_t(lbfgsx_ctx* c, T a, double* r4)
         {
             hflags[1] = int(o[5]);
             dgv = double(o[4]);
-            for (int i = 0; i < 4; i++)
+            for (int i = 0; i < 4 && !from_g; i++)
                 r4[i] = double(o[i]);
             have = true;
         }
@@ -1292,12 +1384,14 @@ static int post_spec_t(lbfgsx_ctx* c, T a, double* r4)
         // the five scalars the host needs, one synchronisation: dg = grad . d, then {g.g, x.x, s.y, y.y}
         T* h = static_cast<T*>(c->hout);
         LBFGSX_HIP(lbfgsx::copy_async(h, sc + c->sl.dot(2 * cn), sizeof(T), hipMemcpyDeviceToHost, c->stream));
-        if (!c->outmap_dev)
+        if (!c->outmap_dev && !from_g)
             LBFGSX_HIP(lbfgsx::copy_async(h + 8, sc + c->sl.out(0), 4 * sizeof(T), hipMemcpyDeviceToHost, c->stream));
         LBFGSX_HIP(lbfgsx::stream_sync(c->stream));
         dgv = double(h[0]);
-        for (int i = 0; i < 4; i++)
+        for (int i = 0; i < 4 && !from_g; i++)
             r4[i] = c->outmap_dev ? double(static_cast<const volatile T*>(c->outmap_host)[i]) : double(h[8 + i]);
+        if (from_g)
+            hflags[1] = 1;  // no verdict in this form: the host accepted the pair before the launch
     }
     if (hflags[0])
     {
@@ -1312,12 +1406,13 @@ static int post_spec_t(lbfgsx_ctx* c, T a, double* r4)
             (void) hipEventDestroy(c->ev_hv.back().b);
             c->ev_hv.pop_back();
             c->persist_steps_timed -= 2 * cn + 1;
-            c->fused_timed--;
+            c->fused_timed -= fused;
         }
         return 1;
     }
     c->persist_launches++;
     c->spec_launches++;
+    c->from_g_launches += from_g ? 1 : 0;
     c->persist_backoff = 8;  // a clean persistent launch
     if (hflags[1] == 1)
     {
@@ -1336,7 +1431,7 @@ static int post_spec_t(lbfgsx_ctx* c, T a, double* r4)
             (void) hipEventDestroy(c->ev_hv.back().b);
             c->ev_hv.pop_back();
             c->persist_steps_timed -= 2 * cn + 1;
-            c->fused_timed--;
+            c->fused_timed -= fused;
         }
     }
     return LBFGSX_OK;
@@ -1351,6 +1446,34 @@ int lbfgsx_post_linesearch_spec(lbfgsx_ctx* c, double a, double* gnorm2, double*
     double r[4];
     int rc = 1;
     c->spec_valid = false;
+    if (c->pt_valid && c->cur == c->pt_buf && c->xp == c->pt_xp)
+    {
+        // the search accepted its first trial and that trial ran in the post form: s and y are in the spare column, the
+        // sums are on the host.  What follows is the reference's order -- the caller's convergence tests, the curvature
+        // test, the commit -- with the recursion on the new gradient already on its way when the pair will be accepted
+        // (the kernel of the fused launch applies the same test to the same rounded scalars).
+        c->pt_valid = false;
+        c->pt_accepted++;
+        for (int i = 0; i < 4; i++)
+            r[i] = c->pt_r[i];
+        c->pend_sy = r[2];
+        c->pend_yy = r[3];
+        c->pending = true;
+        bool usable = false;
+        DISPATCH_T(c, { usable = a == c->pt_a && T(r[2]) > std::numeric_limits<T>::epsilon() * T(r[3]); });
+        if (usable)
+        {
+            DISPATCH_T(c, { rc = post_spec_t<T>(c, T(a), r, true); });
+            if (rc != LBFGSX_OK && rc != 1)
+                return rc;
+        }
+        if (gnorm2) *gnorm2 = r[0];
+        if (xnorm2) *xnorm2 = r[1];
+        if (sy) *sy = r[2];
+        if (yy) *yy = r[3];
+        return LBFGSX_OK;
+    }
+    c->pt_valid = false;
     DISPATCH_T(c, { rc = post_spec_t<T>(c, T(a), r); });
     if (rc == 1)
         return lbfgsx_post_linesearch(c, gnorm2, xnorm2, sy, yy);
@@ -1363,6 +1486,27 @@ int lbfgsx_post_linesearch_spec(lbfgsx_ctx* c, double a, double* gnorm2, double*
     if (xnorm2) *xnorm2 = r[1];
     if (sy) *sy = r[2];
     if (yy) *yy = r[3];
+    return LBFGSX_OK;
+}
+
+int lbfgsx_ls_post_in_trial(lbfgsx_ctx* c, double a)
+{
+    if (!c)
+        return LBFGSX_E_INVALID;
+    c->pt_a = a;
+    c->pt_armed = c->post_in_trial && c->ls_first_ok && c->ncorr > 0 && !c->gs_f32h && c->ls_trials == 0 &&
+                  c->shard_off == 0 && c->n_global == c->n;
+    return LBFGSX_OK;
+}
+
+int lbfgsx_post_in_trial_counts(const lbfgsx_ctx* c, int64_t out[4])
+{
+    if (!c || !out)
+        return LBFGSX_E_INVALID;
+    out[0] = c->pt_issued;
+    out[1] = c->pt_accepted;
+    out[2] = c->from_g_launches;
+    out[3] = c->post_in_trial ? 1 : 0;
     return LBFGSX_OK;
 }
 
