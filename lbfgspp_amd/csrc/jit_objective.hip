@@ -18,7 +18,9 @@
 // mesh_kernels.cuh with the list of mesh_topology.hip.  A sixth, a LINEAR-MODEL objective (one term per row of a sparse matrix
 // product and an optional one per coordinate), is a wrapper around linear_kernels.cuh with the matrix of linear_topology.hip;
 // it alone has two more kernels, the row passes, in slots 4 and 5.  A handle carries its form; the four slots of the
-// loaded-kernel table and everything that launches them are the same.
+// loaded-kernel table and everything that launches them are the same.  What the forms differ in -- names, kernel names, struct
+// members, the bodies' signatures, the K and D accepted, the cache key -- is one row each of kForms below; the generator, the
+// validation and the refusals are written once and read it.
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
 
@@ -36,19 +38,132 @@
 
 namespace {
 
-const char* const kKernelNames[6][lbfgsx::JIT_NSLOTS] = {
-    {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial", nullptr, nullptr, "k_trial_post"},
-    {"k_chain_eval", "k_chain_trial", "k_chain_b_eval", "k_chain_b_dg_maxstep_trial"},
-    {"k_grid_eval", "k_grid_trial", "k_grid_b_eval", "k_grid_b_dg_maxstep_trial"},
-    {"k_graph_eval", "k_graph_trial", "k_graph_b_eval", "k_graph_b_dg_maxstep_trial"},
-    {"k_mesh_eval", "k_mesh_trial", "k_mesh_b_eval", "k_mesh_b_dg_maxstep_trial"},
-    {"k_lin_eval", "k_lin_trial", "k_lin_b_eval", "k_lin_b_dg_maxstep_trial", "k_lin_rows", "k_lin_rows_trial"}};
-const char* const kObjStruct[6] = {"ObjTerm", "ObjChain", "ObjGrid", "ObjGraph", "ObjMesh", "ObjLinear"};
-const char* const kFormName[6] = {"term objective", "chain objective", "grid objective", "graph objective", "mesh objective",
-                                  "linear-model objective"};
+// ---- the forms: everything that differs between them in the generated translation unit, in the refusals and in the cache key
+// one body of a form: the method generated around the caller's text
+struct BodyDesc
+{
+    const char* comment;    // the comment above the method
+    const char* signature;  // the method, without its qualifiers
+    const char* line;       // its #line name: the compile log counts lines per body
+    const char* noun;       // what messages call it
+    const char* absent;     // an optional body: the method's text when the caller gives none; null: the body is required
+    const char* flag;       // an optional body: the struct's constant that says whether the caller gave one
+};
+struct FormDesc
+{
+    const char* name;                         // in messages
+    const char* suffix;                       // of lbfgsx_objective_compile, _source and _bind for this form
+    const char* obj;                          // the generated struct
+    const char* includes;                     // the kernel headers
+    const char* kernels[lbfgsx::JIT_NSLOTS];  // by slot; null: the form has no kernel there
+    const char* members;                      // the struct's members after TermArgs' (launch_args.hpp: the form's *Args)
+    BodyDesc second, body;                    // the optional body (no signature: the form has none), then the required one
+    const char* rest;                         // the struct's text after the two methods
+    int k_lo, k_hi, d_lo, d_hi;               // the K and D accepted
+    const char *k_refusal, *d_refusal;        // '#' stands for the value refused; null: the entry point fixes the value
+    bool key_second, key_d;                   // do the second body and D enter the cache key
+    const char* bound_with;                   // what lbfgsx_objective_bind says the form is bound with; null: it binds it
+};
+#define TERM_SIGNATURE "T term(const T (&x)[K], T (&g)[K], int64_t i) const"
+#define POINT_SIGNATURE(name) "T " name "(const T (&x)[1], T (&g)[1], int64_t i) const"
+#define POINT_ABSENT "        g[0] = T(0);\n        return T(0);\n"
+const BodyDesc kNoBody = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+const FormDesc kForms[6] = {
+    {"term objective", "", "ObjTerm", "#include \"lbfgs_kernels.cuh\"\n#include \"lbfgsb_kernels.cuh\"\n",
+     {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial", nullptr, nullptr, "k_trial_post"}, "", kNoBody,
+     {"    // one term: x[0..K) in, g[0..K) out, the term's value returned\n", TERM_SIGNATURE, "objective_body", "body", nullptr,
+      nullptr},
+     "    // the W / K terms of one 16-byte pack (W is a multiple of K: a term never straddles a pack)\n"
+     "    template <class A>\n"
+     "    __device__ __forceinline__ void pack(int64_t vi, const Pack<T>& x, Pack<T>& g, A& fx) const\n    {\n"
+     "        constexpr int W = Vec16<T>::W;\n"
+     "#pragma unroll\n"
+     "        for (int k = 0; k < W; k += K)\n        {\n"
+     "            T tx[K], tg[K];\n"
+     "#pragma unroll\n"
+     "            for (int j = 0; j < K; j++)\n                tx[j] = x.e[k + j];\n"
+     "            const T v = term(tx, tg, vi * W + k);\n"
+     "#pragma unroll\n"
+     "            for (int j = 0; j < K; j++)\n                g.e[k + j] = tg[j];\n"
+     "            fx.add(v);\n"
+     "        }\n    }\n"
+     "    __device__ __forceinline__ T finish(T sum) const { return sum; }\n"
+     "    // the coordinates past the last whole pack, called for every i of them: the term that starts at i, if one does\n"
+     "    template <class A>\n"
+     "    __device__ __forceinline__ void tail(int64_t i, int64_t n, const T* x, T* g, A& fx) const\n    {\n"
+     "        if (i % K == 0 && i + K <= n)\n        {\n"
+     "            T tx[K], tg[K];\n"
+     "            for (int j = 0; j < K; j++)\n                tx[j] = x[i + j];\n"
+     "            const T v = term(tx, tg, i);\n"
+     "            for (int j = 0; j < K; j++)\n                g[i + j] = tg[j];\n"
+     "            fx.add(v);\n"
+     "        }\n    }\n",
+     1, 2, 1, 1,
+     "K = # is not supported: a term reads K = 1 or K = 2 consecutive coordinates (a 16-byte pack of two doubles must hold whole "
+     "terms)",
+     nullptr, false, false, nullptr},
+    {"chain objective", "_chain", "ObjChain", "#include \"chain_kernels.cuh\"\n",
+     {"k_chain_eval", "k_chain_trial", "k_chain_b_eval", "k_chain_b_dg_maxstep_trial"}, "", kNoBody,
+     {"    // the term that starts at coordinate i: x[0..K) in, its K partial derivatives g[0..K) out, its value returned\n",
+      TERM_SIGNATURE, "objective_body", "body", nullptr, nullptr},
+     "", 2, 3, 1, 1,
+     "K = # is not supported: a chain term reads K = 2 or K = 3 consecutive coordinates (its halo of K - 1 values must lie inside "
+     "the neighbouring 16-byte pack of two doubles)",
+     nullptr, false, false, nullptr},
+    {"grid objective", "_grid", "ObjGrid", "#include \"grid_kernels.cuh\"\n",
+     {"k_grid_eval", "k_grid_trial", "k_grid_b_eval", "k_grid_b_dg_maxstep_trial"}, "    int64_t rows, cols;\n", kNoBody,
+     {"    // the cell whose origin is node (row, col), flat index i = row*cols + col: x = {x[row,col], x[row,col+1], x[row+1,col],\n"
+      "    // x[row+1,col+1]} in, its four partial derivatives g out, its value returned\n",
+      "T term(const T (&x)[4], T (&g)[4], int64_t i, int64_t row, int64_t col) const", "objective_body", "body", nullptr, nullptr},
+     "", 4, 4, 1, 1, "a cell reads K = 4 coordinates", nullptr, false, false, "shape"},
+    {"graph objective", "_graph", "ObjGraph", "#include \"graph_kernels.cuh\"\n",
+     {"k_graph_eval", "k_graph_trial", "k_graph_b_eval", "k_graph_b_dg_maxstep_trial"},
+     "    const uint32_t* off;\n    const GraphEntry* inc;\n    int64_t E;\n",
+     {"    // the term of node i: x[0] = x[i] in, its derivative g[0] out, its value returned\n", POINT_SIGNATURE("node"), "node_body",
+      "node body", POINT_ABSENT, "kNode"},
+     {"    // the term of edge e = (i, j): x = {x[i], x[j]} in, its two partial derivatives g out, its value returned\n",
+      "T edge(const T (&x)[2], T (&g)[2], int64_t e, int64_t i, int64_t j) const", "edge_body", "edge body", nullptr, nullptr},
+     "", 2, 2, 1, 1, "an edge reads K = 2 coordinates", nullptr, true, false, "edges"},
+    {"mesh objective", "_mesh", "ObjMesh", "#include \"mesh_kernels.cuh\"\n",
+     {"k_mesh_eval", "k_mesh_trial", "k_mesh_b_eval", "k_mesh_b_dg_maxstep_trial"},
+     "    const uint32_t* off;\n    const uint32_t* inc;\n    int64_t E, N;\n",
+     {"    // the term of node i: x[d] = x[i*D + d] in, its D partial derivatives g out, its value returned\n",
+      "T node(const T (&x)[D], T (&g)[D], int64_t i) const", "node_body", "node body",
+      "        for (int d = 0; d < D; d++)\n            g[d] = T(0);\n        return T(0);\n", "kNode"},
+     {"    // the term of element e with nodes v[0..K): x[k*D + d] = unknown d of node v[k] in, its K*D partial derivatives g out,\n"
+      "    // its value returned\n",
+      "T elem(const T (&x)[K * D], T (&g)[K * D], int64_t e, const int64_t (&v)[K]) const", "elem_body", "element body", nullptr,
+      nullptr},
+     "", 2, 4, 1, 3, "K = # is not supported: an element has K = 2, 3 or 4 nodes",
+     "D = # is not supported: a node has D = 1, 2 or 3 unknowns", true, true, "elements"},
+    {"linear-model objective", "_linear", "ObjLinear", "#include \"linear_kernels.cuh\"\n",
+     {"k_lin_eval", "k_lin_trial", "k_lin_b_eval", "k_lin_b_dg_maxstep_trial", "k_lin_rows", "k_lin_rows_trial"},
+     "    const int32_t* rowptr;\n    const int32_t* col;\n    const T* val;\n"
+     "    const uint32_t* colptr;\n    const int32_t* trow;\n    const T* tval;\n"
+     "    T* w;\n    T* v;\n"
+     "    const T* part;\n    const int32_t* long_col;\n    const uint32_t* long_chunk;\n"
+     "    int64_t R, nnz;\n    int32_t L, C, nlong, pad_;\n",
+     {"    // the term of coordinate i: x[0] = x[i] in, its derivative g[0] out, its value returned\n", POINT_SIGNATURE("coord"),
+      "coord_body", "coordinate body", POINT_ABSENT, "kCoord"},
+     {"    // the term of row r: z = the row's product with x in, its derivative dz out, its value returned\n",
+      "T row(const T z, T& dz, int64_t r) const", "row_body", "row body", nullptr, nullptr},
+     "", 1, 1, 1, 1, nullptr, nullptr, true, false, "matrix"}};
+#undef TERM_SIGNATURE
+#undef POINT_SIGNATURE
+#undef POINT_ABSENT
+// the kernels' parameter lists by slot, OBJ for the generated struct; the order the explicit instantiations are written in
+const char* const kKernelParams[lbfgsx::JIT_NSLOTS] = {
+    "const S*, S*, int64_t, OBJ, RedWs, S*",
+    "const S*, const S*, S, S*, S*, int64_t, OBJ, RedWs, S*, int",
+    "const S*, S*, const S*, const S*, int64_t, OBJ, RedWs, S*",
+    "const S*, const S*, const S*, const S*, const S*, S, S*, S*, int64_t, OBJ, RedWs, S*, int",
+    "const S*, OBJ",
+    "const S*, const S*, S, OBJ",
+    "const S*, const S*, S, S*, S*, int64_t, OBJ, RedWs, S*, int, TrialPost<S>"};
+const int kEmitOrder[lbfgsx::JIT_NSLOTS] = {0, 1, 6, 2, 3, 4, 5};
 // does a form have the kernel of slot k: the four every form has, a linear-model objective's two row passes, a term
 // objective's post form of k_trial (a table row names exactly the slots of its form)
-inline bool has_kernel(int form, int k) { return k >= 0 && k < lbfgsx::JIT_NSLOTS && kKernelNames[form][k] != nullptr; }
+inline bool has_kernel(int form, int k) { return k >= 0 && k < lbfgsx::JIT_NSLOTS && kForms[form].kernels[k] != nullptr; }
 
 // ---- hipRTC, loaded on first use (a process that never compiles an objective does not need it)
 struct Rtc
@@ -120,372 +235,80 @@ std::string kernel_dir()
 }
 
 // ---- the generated translation unit
-std::string generate_chain(int dtype, int K, const char* body);
-std::string generate_grid(int dtype, const char* body);
-std::string generate_graph(int dtype, const char* node, const char* body);
-std::string generate_mesh(int dtype, int K, int D, const char* node, const char* body);
-std::string generate_linear(int dtype, const char* coord, const char* body);
-
-// node: a graph or mesh objective's node body (null or empty: none); the other forms have one body.  D: a mesh
-// objective's unknowns per node, 1 for the other forms
-std::string generate(int form, int dtype, int K, const char* body, const char* node, int D)
+// one method of the struct around the caller's text (null or empty: the form's text for an absent body)
+void emit_body(std::string& s, const BodyDesc& b, const char* text)
 {
-    if (form == LBFGSX_FORM_LINEAR)
-        return generate_linear(dtype, node, body);
-    if (form == LBFGSX_FORM_MESH)
-        return generate_mesh(dtype, K, D, node, body);
-    if (form == LBFGSX_FORM_GRAPH)
-        return generate_graph(dtype, node, body);
-    if (form == LBFGSX_FORM_CHAIN)
-        return generate_chain(dtype, K, body);
-    if (form == LBFGSX_FORM_GRID)
-        return generate_grid(dtype, body);
+    s += b.comment;
+    s += std::string("    __device__ __forceinline__ ") + b.signature + "\n    {\n";
+    if (text && *text)
+        s += std::string("#line 1 \"") + b.line + "\"\n" + text + "\n#line 1 \"objective_wrapper\"\n";
+    else
+        s += b.absent;
+    s += "    }\n";
+}
+
+// the struct the form's kernel header asks for (the leading members are TermArgs', launch_args.hpp), and the explicit
+// instantiations of its kernels.  second: a graph, mesh or linear-model objective's optional body (null or empty: none); D: a
+// mesh objective's unknowns per node, 1 for the other forms
+std::string generate(int form, int dtype, int K, const char* body, const char* second, int D)
+{
+    const FormDesc& f = kForms[form];
     std::string s;
-    s += "// generated by lbfgsx_objective_compile: one term objective for the fused kernels\n";
-    s += "#include \"lbfgs_kernels.cuh\"\n";
-    s += "#include \"lbfgsb_kernels.cuh\"\n";
+    s += std::string("// generated by lbfgsx_objective_compile") + f.suffix + ": one " + f.name + " for the fused kernels\n";
+    s += f.includes;
     s += "namespace lbfgsx {\n";
     s += std::string("typedef ") + (dtype == LBFGSX_F64 ? "double" : "float") + " term_scalar_t;\n";
-    s += "struct ObjTerm\n{\n";
+    s += std::string("struct ") + f.obj + "\n{\n";
     s += "    typedef term_scalar_t T;\n";
     s += "    static constexpr int K = " + std::to_string(K) + ";\n";
+    if (f.d_refusal)
+        s += "    static constexpr int D = " + std::to_string(D) + ";\n";
+    if (f.second.flag)
+        s += std::string("    static constexpr bool ") + f.second.flag + " = " + (second && *second ? "true" : "false") + ";\n";
     s += "    const T* p0;\n    const T* p1;\n    const T* p2;\n    const T* p3;\n    T c[8];\n";
-    s += "    // one term: x[0..K) in, g[0..K) out, the term's value returned\n";
-    s += "    __device__ __forceinline__ T term(const T (&x)[K], T (&g)[K], int64_t i) const\n    {\n";
-    s += "#line 1 \"objective_body\"\n";
-    s += body;
-    s += "\n#line 1 \"objective_wrapper\"\n";
-    s += "    }\n";
-    s += "    // the W / K terms of one 16-byte pack (W is a multiple of K: a term never straddles a pack)\n";
-    s += "    template <class A>\n";
-    s += "    __device__ __forceinline__ void pack(int64_t vi, const Pack<T>& x, Pack<T>& g, A& fx) const\n    {\n";
-    s += "        constexpr int W = Vec16<T>::W;\n";
-    s += "#pragma unroll\n";
-    s += "        for (int k = 0; k < W; k += K)\n        {\n";
-    s += "            T tx[K], tg[K];\n";
-    s += "#pragma unroll\n";
-    s += "            for (int j = 0; j < K; j++)\n                tx[j] = x.e[k + j];\n";
-    s += "            const T v = term(tx, tg, vi * W + k);\n";
-    s += "#pragma unroll\n";
-    s += "            for (int j = 0; j < K; j++)\n                g.e[k + j] = tg[j];\n";
-    s += "            fx.add(v);\n";
-    s += "        }\n    }\n";
-    s += "    __device__ __forceinline__ T finish(T sum) const { return sum; }\n";
-    s += "    // the coordinates past the last whole pack, called for every i of them: the term that starts at i, if one does\n";
-    s += "    template <class A>\n";
-    s += "    __device__ __forceinline__ void tail(int64_t i, int64_t n, const T* x, T* g, A& fx) const\n    {\n";
-    s += "        if (i % K == 0 && i + K <= n)\n        {\n";
-    s += "            T tx[K], tg[K];\n";
-    s += "            for (int j = 0; j < K; j++)\n                tx[j] = x[i + j];\n";
-    s += "            const T v = term(tx, tg, i);\n";
-    s += "            for (int j = 0; j < K; j++)\n                g[i + j] = tg[j];\n";
-    s += "            fx.add(v);\n";
-    s += "        }\n    }\n";
+    s += f.members;
+    if (f.second.signature)
+        emit_body(s, f.second, second);
+    emit_body(s, f.body, body);
+    s += f.rest;
     s += "};\n";
     s += "typedef term_scalar_t S;\n";
-    s += "template __global__ void k_eval<S, ObjTerm>(const S*, S*, int64_t, ObjTerm, RedWs, S*);\n";
-    s += "template __global__ void k_trial<S, ObjTerm>(const S*, const S*, S, S*, S*, int64_t, ObjTerm, RedWs, S*, int);\n";
-    s += "template __global__ void k_trial_post<S, ObjTerm>(const S*, const S*, S, S*, S*, int64_t, ObjTerm, RedWs, S*, int, "
-         "TrialPost<S>);\n";
-    s += "template __global__ void k_b_eval<S, ObjTerm>(const S*, S*, const S*, const S*, int64_t, ObjTerm, RedWs, S*);\n";
-    s += "template __global__ void k_b_dg_maxstep_trial<S, ObjTerm>(const S*, const S*, const S*, const S*, const S*, S, S*, S*, "
-         "int64_t, ObjTerm, RedWs, S*, int);\n";
+    for (int k : kEmitOrder)
+        if (f.kernels[k])
+        {
+            std::string params = kKernelParams[k];
+            params.replace(params.find("OBJ"), 3, f.obj);
+            s += std::string("template __global__ void ") + f.kernels[k] + "<S, " + f.obj + ">(" + params + ");\n";
+        }
     s += "}  // namespace lbfgsx\n";
     return s;
 }
 
-// the wrapper of a chain objective: the struct chain_kernels.cuh asks for (K and term), and its four kernels
-std::string generate_chain(int dtype, int K, const char* body)
+// a refusal sentence of the table with the refused value in place of its '#'
+std::string refusal(const char* rule, int value)
 {
-    std::string s;
-    s += "// generated by lbfgsx_objective_compile_chain: one chain objective for the fused kernels\n";
-    s += "#include \"chain_kernels.cuh\"\n";
-    s += "namespace lbfgsx {\n";
-    s += std::string("typedef ") + (dtype == LBFGSX_F64 ? "double" : "float") + " term_scalar_t;\n";
-    s += "struct ObjChain\n{\n";
-    s += "    typedef term_scalar_t T;\n";
-    s += "    static constexpr int K = " + std::to_string(K) + ";\n";
-    s += "    const T* p0;\n    const T* p1;\n    const T* p2;\n    const T* p3;\n    T c[8];\n";
-    s += "    // the term that starts at coordinate i: x[0..K) in, its K partial derivatives g[0..K) out, its value returned\n";
-    s += "    __device__ __forceinline__ T term(const T (&x)[K], T (&g)[K], int64_t i) const\n    {\n";
-    s += "#line 1 \"objective_body\"\n";
-    s += body;
-    s += "\n#line 1 \"objective_wrapper\"\n";
-    s += "    }\n";
-    s += "};\n";
-    s += "typedef term_scalar_t S;\n";
-    s += "template __global__ void k_chain_eval<S, ObjChain>(const S*, S*, int64_t, ObjChain, RedWs, S*);\n";
-    s += "template __global__ void k_chain_trial<S, ObjChain>(const S*, const S*, S, S*, S*, int64_t, ObjChain, RedWs, S*, int);\n";
-    s += "template __global__ void k_chain_b_eval<S, ObjChain>(const S*, S*, const S*, const S*, int64_t, ObjChain, RedWs, S*);\n";
-    s += "template __global__ void k_chain_b_dg_maxstep_trial<S, ObjChain>(const S*, const S*, const S*, const S*, const S*, S, S*, "
-         "S*, int64_t, ObjChain, RedWs, S*, int);\n";
-    s += "}  // namespace lbfgsx\n";
-    return s;
+    std::string s = rule;
+    const size_t k = s.find('#');
+    return k == std::string::npos ? s : s.replace(k, 1, std::to_string(value));
 }
 
-// the wrapper of a grid objective: the struct grid_kernels.cuh asks for (the shape and term), and its four kernels.  The
-// leading members are TermArgs' (launch_args.hpp: GridArgs)
-std::string generate_grid(int dtype, const char* body)
+bool valid_request(int form, int dtype, int K, const char* body, const char* second, int D, std::string& why)
 {
-    std::string s;
-    s += "// generated by lbfgsx_objective_compile_grid: one grid objective for the fused kernels\n";
-    s += "#include \"grid_kernels.cuh\"\n";
-    s += "namespace lbfgsx {\n";
-    s += std::string("typedef ") + (dtype == LBFGSX_F64 ? "double" : "float") + " term_scalar_t;\n";
-    s += "struct ObjGrid\n{\n";
-    s += "    typedef term_scalar_t T;\n";
-    s += "    static constexpr int K = 4;\n";
-    s += "    const T* p0;\n    const T* p1;\n    const T* p2;\n    const T* p3;\n    T c[8];\n";
-    s += "    int64_t rows, cols;\n";
-    s += "    // the cell whose origin is node (row, col), flat index i = row*cols + col: x = {x[row,col], x[row,col+1], x[row+1,col],\n";
-    s += "    // x[row+1,col+1]} in, its four partial derivatives g out, its value returned\n";
-    s += "    __device__ __forceinline__ T term(const T (&x)[4], T (&g)[4], int64_t i, int64_t row, int64_t col) const\n    {\n";
-    s += "#line 1 \"objective_body\"\n";
-    s += body;
-    s += "\n#line 1 \"objective_wrapper\"\n";
-    s += "    }\n";
-    s += "};\n";
-    s += "typedef term_scalar_t S;\n";
-    s += "template __global__ void k_grid_eval<S, ObjGrid>(const S*, S*, int64_t, ObjGrid, RedWs, S*);\n";
-    s += "template __global__ void k_grid_trial<S, ObjGrid>(const S*, const S*, S, S*, S*, int64_t, ObjGrid, RedWs, S*, int);\n";
-    s += "template __global__ void k_grid_b_eval<S, ObjGrid>(const S*, S*, const S*, const S*, int64_t, ObjGrid, RedWs, S*);\n";
-    s += "template __global__ void k_grid_b_dg_maxstep_trial<S, ObjGrid>(const S*, const S*, const S*, const S*, const S*, S, S*, "
-         "S*, int64_t, ObjGrid, RedWs, S*, int);\n";
-    s += "}  // namespace lbfgsx\n";
-    return s;
-}
-
-// the wrapper of a graph objective: the struct graph_kernels.cuh asks for (the two terms and the incidence list), and its
-// four kernels.  The leading members are TermArgs' (launch_args.hpp: GraphArgs).  Each body has its own #line name, so the
-// compile log counts lines per body
-std::string generate_graph(int dtype, const char* node, const char* body)
-{
-    const bool has_node = node && *node;
-    std::string s;
-    s += "// generated by lbfgsx_objective_compile_graph: one graph objective for the fused kernels\n";
-    s += "#include \"graph_kernels.cuh\"\n";
-    s += "namespace lbfgsx {\n";
-    s += std::string("typedef ") + (dtype == LBFGSX_F64 ? "double" : "float") + " term_scalar_t;\n";
-    s += "struct ObjGraph\n{\n";
-    s += "    typedef term_scalar_t T;\n";
-    s += "    static constexpr int K = 2;\n";
-    s += std::string("    static constexpr bool kNode = ") + (has_node ? "true" : "false") + ";\n";
-    s += "    const T* p0;\n    const T* p1;\n    const T* p2;\n    const T* p3;\n    T c[8];\n";
-    s += "    const uint32_t* off;\n    const GraphEntry* inc;\n    int64_t E;\n";
-    s += "    // the term of node i: x[0] = x[i] in, its derivative g[0] out, its value returned\n";
-    s += "    __device__ __forceinline__ T node(const T (&x)[1], T (&g)[1], int64_t i) const\n    {\n";
-    if (has_node)
-    {
-        s += "#line 1 \"node_body\"\n";
-        s += node;
-        s += "\n#line 1 \"objective_wrapper\"\n";
-    }
-    else
-        s += "        g[0] = T(0);\n        return T(0);\n";
-    s += "    }\n";
-    s += "    // the term of edge e = (i, j): x = {x[i], x[j]} in, its two partial derivatives g out, its value returned\n";
-    s += "    __device__ __forceinline__ T edge(const T (&x)[2], T (&g)[2], int64_t e, int64_t i, int64_t j) const\n    {\n";
-    s += "#line 1 \"edge_body\"\n";
-    s += body;
-    s += "\n#line 1 \"objective_wrapper\"\n";
-    s += "    }\n";
-    s += "};\n";
-    s += "typedef term_scalar_t S;\n";
-    s += "template __global__ void k_graph_eval<S, ObjGraph>(const S*, S*, int64_t, ObjGraph, RedWs, S*);\n";
-    s += "template __global__ void k_graph_trial<S, ObjGraph>(const S*, const S*, S, S*, S*, int64_t, ObjGraph, RedWs, S*, int);\n";
-    s += "template __global__ void k_graph_b_eval<S, ObjGraph>(const S*, S*, const S*, const S*, int64_t, ObjGraph, RedWs, S*);\n";
-    s += "template __global__ void k_graph_b_dg_maxstep_trial<S, ObjGraph>(const S*, const S*, const S*, const S*, const S*, S, S*, "
-         "S*, int64_t, ObjGraph, RedWs, S*, int);\n";
-    s += "}  // namespace lbfgsx\n";
-    return s;
-}
-
-// the wrapper of a mesh objective: the struct mesh_kernels.cuh asks for (K, D, the two terms and the incidence list), and
-// its four kernels.  The leading members are TermArgs' (launch_args.hpp: MeshArgs).  Each body has its own #line name
-std::string generate_mesh(int dtype, int K, int D, const char* node, const char* body)
-{
-    const bool has_node = node && *node;
-    std::string s;
-    s += "// generated by lbfgsx_objective_compile_mesh: one mesh objective for the fused kernels\n";
-    s += "#include \"mesh_kernels.cuh\"\n";
-    s += "namespace lbfgsx {\n";
-    s += std::string("typedef ") + (dtype == LBFGSX_F64 ? "double" : "float") + " term_scalar_t;\n";
-    s += "struct ObjMesh\n{\n";
-    s += "    typedef term_scalar_t T;\n";
-    s += "    static constexpr int K = " + std::to_string(K) + ";\n";
-    s += "    static constexpr int D = " + std::to_string(D) + ";\n";
-    s += std::string("    static constexpr bool kNode = ") + (has_node ? "true" : "false") + ";\n";
-    s += "    const T* p0;\n    const T* p1;\n    const T* p2;\n    const T* p3;\n    T c[8];\n";
-    s += "    const uint32_t* off;\n    const uint32_t* inc;\n    int64_t E, N;\n";
-    s += "    // the term of node i: x[d] = x[i*D + d] in, its D partial derivatives g out, its value returned\n";
-    s += "    __device__ __forceinline__ T node(const T (&x)[D], T (&g)[D], int64_t i) const\n    {\n";
-    if (has_node)
-    {
-        s += "#line 1 \"node_body\"\n";
-        s += node;
-        s += "\n#line 1 \"objective_wrapper\"\n";
-    }
-    else
-        s += "        for (int d = 0; d < D; d++)\n            g[d] = T(0);\n        return T(0);\n";
-    s += "    }\n";
-    s += "    // the term of element e with nodes v[0..K): x[k*D + d] = unknown d of node v[k] in, its K*D partial derivatives g out,\n";
-    s += "    // its value returned\n";
-    s += "    __device__ __forceinline__ T elem(const T (&x)[K * D], T (&g)[K * D], int64_t e, const int64_t (&v)[K]) const\n    {\n";
-    s += "#line 1 \"elem_body\"\n";
-    s += body;
-    s += "\n#line 1 \"objective_wrapper\"\n";
-    s += "    }\n";
-    s += "};\n";
-    s += "typedef term_scalar_t S;\n";
-    s += "template __global__ void k_mesh_eval<S, ObjMesh>(const S*, S*, int64_t, ObjMesh, RedWs, S*);\n";
-    s += "template __global__ void k_mesh_trial<S, ObjMesh>(const S*, const S*, S, S*, S*, int64_t, ObjMesh, RedWs, S*, int);\n";
-    s += "template __global__ void k_mesh_b_eval<S, ObjMesh>(const S*, S*, const S*, const S*, int64_t, ObjMesh, RedWs, S*);\n";
-    s += "template __global__ void k_mesh_b_dg_maxstep_trial<S, ObjMesh>(const S*, const S*, const S*, const S*, const S*, S, S*, "
-         "S*, int64_t, ObjMesh, RedWs, S*, int);\n";
-    s += "}  // namespace lbfgsx\n";
-    return s;
-}
-
-// the wrapper of a linear-model objective: the struct linear_kernels.cuh asks for (the two terms and the matrix), its four
-// column-pass kernels and its two row passes.  The members are LinearArgs' (launch_args.hpp), in its order.  Each body has
-// its own #line name
-std::string generate_linear(int dtype, const char* coord, const char* body)
-{
-    const bool has_coord = coord && *coord;
-    std::string s;
-    s += "// generated by lbfgsx_objective_compile_linear: one linear-model objective for the fused kernels\n";
-    s += "#include \"linear_kernels.cuh\"\n";
-    s += "namespace lbfgsx {\n";
-    s += std::string("typedef ") + (dtype == LBFGSX_F64 ? "double" : "float") + " term_scalar_t;\n";
-    s += "struct ObjLinear\n{\n";
-    s += "    typedef term_scalar_t T;\n";
-    s += "    static constexpr int K = 1;\n";
-    s += std::string("    static constexpr bool kCoord = ") + (has_coord ? "true" : "false") + ";\n";
-    s += "    const T* p0;\n    const T* p1;\n    const T* p2;\n    const T* p3;\n    T c[8];\n";
-    s += "    const int32_t* rowptr;\n    const int32_t* col;\n    const T* val;\n";
-    s += "    const uint32_t* colptr;\n    const int32_t* trow;\n    const T* tval;\n";
-    s += "    T* w;\n    T* v;\n";
-    s += "    const T* part;\n    const int32_t* long_col;\n    const uint32_t* long_chunk;\n";
-    s += "    int64_t R, nnz;\n    int32_t L, C, nlong, pad_;\n";
-    s += "    // the term of coordinate i: x[0] = x[i] in, its derivative g[0] out, its value returned\n";
-    s += "    __device__ __forceinline__ T coord(const T (&x)[1], T (&g)[1], int64_t i) const\n    {\n";
-    if (has_coord)
-    {
-        s += "#line 1 \"coord_body\"\n";
-        s += coord;
-        s += "\n#line 1 \"objective_wrapper\"\n";
-    }
-    else
-        s += "        g[0] = T(0);\n        return T(0);\n";
-    s += "    }\n";
-    s += "    // the term of row r: z = the row's product with x in, its derivative dz out, its value returned\n";
-    s += "    __device__ __forceinline__ T row(const T z, T& dz, int64_t r) const\n    {\n";
-    s += "#line 1 \"row_body\"\n";
-    s += body;
-    s += "\n#line 1 \"objective_wrapper\"\n";
-    s += "    }\n";
-    s += "};\n";
-    s += "typedef term_scalar_t S;\n";
-    s += "template __global__ void k_lin_eval<S, ObjLinear>(const S*, S*, int64_t, ObjLinear, RedWs, S*);\n";
-    s += "template __global__ void k_lin_trial<S, ObjLinear>(const S*, const S*, S, S*, S*, int64_t, ObjLinear, RedWs, S*, int);\n";
-    s += "template __global__ void k_lin_b_eval<S, ObjLinear>(const S*, S*, const S*, const S*, int64_t, ObjLinear, RedWs, S*);\n";
-    s += "template __global__ void k_lin_b_dg_maxstep_trial<S, ObjLinear>(const S*, const S*, const S*, const S*, const S*, S, S*, "
-         "S*, int64_t, ObjLinear, RedWs, S*, int);\n";
-    s += "template __global__ void k_lin_rows<S, ObjLinear>(const S*, ObjLinear);\n";
-    s += "template __global__ void k_lin_rows_trial<S, ObjLinear>(const S*, const S*, S, ObjLinear);\n";
-    s += "}  // namespace lbfgsx\n";
-    return s;
-}
-
-bool valid_request(int form, int dtype, int K, const char* body, const char* node, int D, std::string& why)
-{
-    if (form == LBFGSX_FORM_LINEAR)
-    {
-        if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
-            why = "linear-model objective: unknown dtype";
-        else if (!body || !*body)
-            why = "linear-model objective: empty row body";
-        else if (std::strstr(body, "asm"))
-            why = "linear-model objective: the row body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
-        else if (node && std::strstr(node, "asm"))
-            why = "linear-model objective: the coordinate body contains 'asm': a term is plain C++ arithmetic, inline assembly is not "
-                  "accepted";
-        else
-            return true;
-        return false;
-    }
-    if (form == LBFGSX_FORM_MESH)
-    {
-        if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
-            why = "mesh objective: unknown dtype";
-        else if (K < 2 || K > 4)
-            why = "mesh objective: K = " + std::to_string(K) + " is not supported: an element has K = 2, 3 or 4 nodes";
-        else if (D < 1 || D > 3)
-            why = "mesh objective: D = " + std::to_string(D) + " is not supported: a node has D = 1, 2 or 3 unknowns";
-        else if (!body || !*body)
-            why = "mesh objective: empty element body";
-        else if (std::strstr(body, "asm"))
-            why = "mesh objective: the element body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
-        else if (node && std::strstr(node, "asm"))
-            why = "mesh objective: the node body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
-        else
-            return true;
-        return false;
-    }
-    if (form == LBFGSX_FORM_GRAPH)
-    {
-        if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
-            why = "graph objective: unknown dtype";
-        else if (K != 2)
-            why = "graph objective: an edge reads K = 2 coordinates";
-        else if (!body || !*body)
-            why = "graph objective: empty edge body";
-        else if (std::strstr(body, "asm"))
-            why = "graph objective: the edge body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
-        else if (node && std::strstr(node, "asm"))
-            why = "graph objective: the node body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
-        else
-            return true;
-        return false;
-    }
-    if (form == LBFGSX_FORM_GRID)
-    {
-        if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
-            why = "grid objective: unknown dtype";
-        else if (K != 4)
-            why = "grid objective: a cell reads K = 4 coordinates";
-        else if (!body || !*body)
-            why = "grid objective: empty body";
-        else if (std::strstr(body, "asm"))
-            why = "grid objective: the body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
-        else
-            return true;
-        return false;
-    }
-    if (form == LBFGSX_FORM_CHAIN)
-    {
-        if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
-            why = "chain objective: unknown dtype";
-        else if (K != 2 && K != 3)
-            why = "chain objective: K = " + std::to_string(K) + " is not supported: a chain term reads K = 2 or K = 3 consecutive "
-                  "coordinates (its halo of K - 1 values must lie inside the neighbouring 16-byte pack of two doubles)";
-        else if (!body || !*body)
-            why = "chain objective: empty body";
-        else if (std::strstr(body, "asm"))
-            why = "chain objective: the body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
-        else
-            return true;
-        return false;
-    }
+    const FormDesc& f = kForms[form];
+    const std::string name = std::string(f.name) + ": ";
+    const char* const no_asm = " contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
     if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
-        why = "term objective: unknown dtype";
-    else if (K != 1 && K != 2)
-        why = "term objective: K = " + std::to_string(K) + " is not supported: a term reads K = 1 or K = 2 consecutive coordinates "
-              "(a 16-byte pack of two doubles must hold whole terms)";
+        why = name + "unknown dtype";
+    else if (f.k_refusal && (K < f.k_lo || K > f.k_hi))
+        why = name + refusal(f.k_refusal, K);
+    else if (f.d_refusal && (D < f.d_lo || D > f.d_hi))
+        why = name + refusal(f.d_refusal, D);
     else if (!body || !*body)
-        why = "term objective: empty body";
+        why = name + "empty " + f.body.noun;
     else if (std::strstr(body, "asm"))
-        why = "term objective: the body contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
+        why = name + "the " + f.body.noun + no_asm;
+    else if (f.second.signature && second && std::strstr(second, "asm"))
+        why = name + "the " + f.second.noun + no_asm;
     else
         return true;
     return false;
@@ -647,7 +470,7 @@ int compile_code(int form, int dtype, int K, int D, const char* body, const char
     {
         if (!has_kernel(form, k))
             continue;
-        expr[k] = std::string("lbfgsx::") + kKernelNames[form][k] + "<lbfgsx::term_scalar_t, lbfgsx::" + kObjStruct[form] + ">";
+        expr[k] = std::string("lbfgsx::") + kForms[form].kernels[k] + "<lbfgsx::term_scalar_t, lbfgsx::" + kForms[form].obj + ">";
         (void) r.add_name(prog, expr[k].c_str());
     }
     const std::string inc = "-I" + kernel_dir();
@@ -698,7 +521,7 @@ int compile_code(int form, int dtype, int K, int D, const char* body, const char
     (void) r.destroy(&prog);
     if (!ok)
     {
-        log = std::string(kFormName[form]) + ": the compiled code object lacks a kernel or its descriptor";
+        log = std::string(kForms[form].name) + ": the compiled code object lacks a kernel or its descriptor";
         return LBFGSX_E_RUNTIME;
     }
     code->self.code = code.get();
@@ -726,7 +549,7 @@ int jit_launch(lbfgsx_ctx* c, int which, int grid, void** params)
     }
     counters().launches.fetch_add(1, std::memory_order_relaxed);
     if (host_trace_on())
-        host_trace(kKernelNames[c->term->code->form][which]);
+        host_trace(kForms[c->term->code->form].kernels[which]);
     LBFGSX_HIP(hipModuleLaunchKernel(fn, unsigned(grid), 1, 1, unsigned(kBlock), 1, 1, 0, c->stream, params, nullptr));
     return LBFGSX_OK;
 }
@@ -766,9 +589,9 @@ int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const 
         return LBFGSX_E_INVALID;
     }
     std::string key = std::to_string(form) + "/" + std::to_string(dtype) + "/" + std::to_string(K) + "/" + body;
-    if (form == LBFGSX_FORM_GRAPH || form == LBFGSX_FORM_MESH || form == LBFGSX_FORM_LINEAR)
+    if (kForms[form].key_second)
         key += std::string("\x1f") + (node ? node : "");  // both bodies
-    if (form == LBFGSX_FORM_MESH)
+    if (kForms[form].key_d)
         key += "\x1f" + std::to_string(D);
     std::lock_guard<std::mutex> lock(g_cache_mu);
     auto it = cache().find(key);
@@ -780,7 +603,7 @@ int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const 
         const int rc = compile_code(form, dtype, K, D, body, node, code, text);
         if (rc)
         {
-            lbfgsx::set_error(std::string(kFormName[form]) + ": compilation failed\n" + text);
+            lbfgsx::set_error(std::string(kForms[form].name) + ": compilation failed\n" + text);
             put_log(log, log_len, text);
             return rc;
         }
@@ -1005,6 +828,48 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
     return LBFGSX_OK;
 }
 
+// is the handle one of `form`; the refusal names lbfgsx_objective_bind<suffix>, the call that asked
+bool handle_is(const lbfgsx_objective* obj, int form)
+{
+    const FormDesc& f = kForms[form];
+    if (obj->code->form == form)
+        return true;
+    lbfgsx::set_error(std::string("lbfgsx_objective_bind") + f.suffix + ": the handle is a " + kForms[obj->code->form].name +
+                      ", not a " + f.name + " (lbfgsx_objective_compile" + f.suffix + ")");
+    return false;
+}
+
+// the start of a bind that builds the form's list on the context (graph, mesh, linear-model): whatever is refused, here or
+// by the caller's own checks or by the build, leaves no objective bound, so nothing can be launched on refused indices
+int bind_begin(lbfgsx_ctx* c, const lbfgsx_objective* obj, int form)
+{
+    c->st_valid = false;
+    c->spec_valid = false;
+    c->term = nullptr;
+    c->term_np = 0;
+    c->term_form = LBFGSX_FORM_TERM;
+    if (!handle_is(obj, form))
+        return LBFGSX_E_INVALID;
+    if (obj->code->dtype != c->dtype)
+    {
+        lbfgsx::set_error("lbfgsx_objective_bind: the objective was compiled for the other dtype");
+        return LBFGSX_E_INVALID;
+    }
+    return LBFGSX_OK;
+}
+
+// its end: the handle bound over the list that was built, or the list freed
+int bind_end(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void* const p[4], const double cs[8], int* id)
+{
+    const int rc = objective_bind(c, obj, 0, 0, p, cs, id);
+    if (rc)
+    {
+        lbfgsx::DeviceGuard dev_guard_(c->device);
+        lbfgsx::graph_topology_free(c);
+    }
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1013,24 +878,10 @@ int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void
 {
     if (!c)
         return LBFGSX_E_INVALID;
-    if (obj && obj->code->form == LBFGSX_FORM_GRID)
+    if (obj && kForms[obj->code->form].bound_with)
     {
-        lbfgsx::set_error("a grid objective is bound with its shape: lbfgsx_objective_bind_grid");
-        return LBFGSX_E_INVALID;
-    }
-    if (obj && obj->code->form == LBFGSX_FORM_GRAPH)
-    {
-        lbfgsx::set_error("a graph objective is bound with its edges: lbfgsx_objective_bind_graph");
-        return LBFGSX_E_INVALID;
-    }
-    if (obj && obj->code->form == LBFGSX_FORM_MESH)
-    {
-        lbfgsx::set_error("a mesh objective is bound with its elements: lbfgsx_objective_bind_mesh");
-        return LBFGSX_E_INVALID;
-    }
-    if (obj && obj->code->form == LBFGSX_FORM_LINEAR)
-    {
-        lbfgsx::set_error("a linear-model objective is bound with its matrix: lbfgsx_objective_bind_linear");
+        const FormDesc& f = kForms[obj->code->form];
+        lbfgsx::set_error(std::string("a ") + f.name + " is bound with its " + f.bound_with + ": lbfgsx_objective_bind" + f.suffix);
         return LBFGSX_E_INVALID;
     }
     return objective_bind(c, obj, 0, 0, p, cs, id);
@@ -1041,12 +892,8 @@ int lbfgsx_objective_bind_grid(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64
 {
     if (!c || !obj)
         return LBFGSX_E_INVALID;
-    if (obj->code->form != LBFGSX_FORM_GRID)
-    {
-        lbfgsx::set_error(std::string("lbfgsx_objective_bind_grid: the handle is a ") + kFormName[obj->code->form] +
-                          ", not a grid objective (lbfgsx_objective_compile_grid)");
+    if (!handle_is(obj, LBFGSX_FORM_GRID))
         return LBFGSX_E_INVALID;
-    }
     const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
     long long prod = 0;
     if (rows < 2 || cols < 2)
@@ -1081,17 +928,8 @@ int lbfgsx_objective_bind_graph(lbfgsx_ctx* c, const lbfgsx_objective* obj, int6
 {
     if (!c || !obj)
         return LBFGSX_E_INVALID;
-    if (obj->code->form != LBFGSX_FORM_GRAPH)
-    {
-        lbfgsx::set_error(std::string("lbfgsx_objective_bind_graph: the handle is a ") + kFormName[obj->code->form] +
-                          ", not a graph objective (lbfgsx_objective_compile_graph)");
-        return LBFGSX_E_INVALID;
-    }
-    if (obj->code->dtype != c->dtype)
-    {
-        lbfgsx::set_error("lbfgsx_objective_bind: the objective was compiled for the other dtype");
-        return LBFGSX_E_INVALID;
-    }
+    if (const int rc = bind_begin(c, obj, LBFGSX_FORM_GRAPH))
+        return rc;
     const int64_t lim = 2147483647;
     if (E < 1 || !ei || !ej)
     {
@@ -1110,25 +948,13 @@ int lbfgsx_objective_bind_graph(lbfgsx_ctx* c, const lbfgsx_objective* obj, int6
                           ": node indices are int32");
         return LBFGSX_E_INVALID;
     }
-    // the list first: a context whose indices were refused keeps no graph objective bound, so nothing can be launched on them
-    c->st_valid = false;
-    c->spec_valid = false;
-    c->term = nullptr;
-    c->term_np = 0;
-    c->term_form = LBFGSX_FORM_TERM;
     {
         lbfgsx::DeviceGuard dev_guard_(c->device);
         const int rc = lbfgsx::graph_topology_build(c, ei, ej, E, edges_on_device);
         if (rc)
             return rc;
     }
-    const int rc = objective_bind(c, obj, 0, 0, p, cs, id);
-    if (rc)
-    {
-        lbfgsx::DeviceGuard dev_guard_(c->device);
-        lbfgsx::graph_topology_free(c);
-    }
-    return rc;
+    return bind_end(c, obj, p, cs, id);
 }
 
 int lbfgsx_objective_topology(lbfgsx_ctx* c, int64_t* E, uint32_t* off, int32_t* other, uint32_t* edge_side)
@@ -1149,23 +975,8 @@ int lbfgsx_objective_bind_mesh(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64
 {
     if (!c || !obj)
         return LBFGSX_E_INVALID;
-    // whatever is refused below leaves no objective bound
-    c->st_valid = false;
-    c->spec_valid = false;
-    c->term = nullptr;
-    c->term_np = 0;
-    c->term_form = LBFGSX_FORM_TERM;
-    if (obj->code->form != LBFGSX_FORM_MESH)
-    {
-        lbfgsx::set_error(std::string("lbfgsx_objective_bind_mesh: the handle is a ") + kFormName[obj->code->form] +
-                          ", not a mesh objective (lbfgsx_objective_compile_mesh)");
-        return LBFGSX_E_INVALID;
-    }
-    if (obj->code->dtype != c->dtype)
-    {
-        lbfgsx::set_error("lbfgsx_objective_bind: the objective was compiled for the other dtype");
-        return LBFGSX_E_INVALID;
-    }
+    if (const int rc = bind_begin(c, obj, LBFGSX_FORM_MESH))
+        return rc;
     const int K = obj->code->K, D = obj->code->D;
     const int64_t lim = 2147483647, elim = 1073741823;
     std::string why;
@@ -1183,20 +994,13 @@ int lbfgsx_objective_bind_mesh(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64
         lbfgsx::set_error("mesh objective: " + why);
         return LBFGSX_E_INVALID;
     }
-    // the list first: a context whose indices were refused keeps no mesh objective bound, so nothing can be launched on them
     {
         lbfgsx::DeviceGuard dev_guard_(c->device);
         const int rc = lbfgsx::mesh_topology_build(c, K, D, elems, E, elems_on_device);
         if (rc)
             return rc;
     }
-    const int rc = objective_bind(c, obj, 0, 0, p, cs, id);
-    if (rc)
-    {
-        lbfgsx::DeviceGuard dev_guard_(c->device);
-        lbfgsx::graph_topology_free(c);
-    }
-    return rc;
+    return bind_end(c, obj, p, cs, id);
 }
 
 int lbfgsx_objective_mesh_topology(lbfgsx_ctx* c, int64_t* E, uint32_t* off, uint32_t* words)
@@ -1218,23 +1022,8 @@ int lbfgsx_objective_bind_linear(lbfgsx_ctx* c, const lbfgsx_objective* obj, int
 {
     if (!c || !obj)
         return LBFGSX_E_INVALID;
-    // whatever is refused below leaves no objective bound
-    c->st_valid = false;
-    c->spec_valid = false;
-    c->term = nullptr;
-    c->term_np = 0;
-    c->term_form = LBFGSX_FORM_TERM;
-    if (obj->code->form != LBFGSX_FORM_LINEAR)
-    {
-        lbfgsx::set_error(std::string("lbfgsx_objective_bind_linear: the handle is a ") + kFormName[obj->code->form] +
-                          ", not a linear-model objective (lbfgsx_objective_compile_linear)");
-        return LBFGSX_E_INVALID;
-    }
-    if (obj->code->dtype != c->dtype)
-    {
-        lbfgsx::set_error("lbfgsx_objective_bind: the objective was compiled for the other dtype");
-        return LBFGSX_E_INVALID;
-    }
+    if (const int rc = bind_begin(c, obj, LBFGSX_FORM_LINEAR))
+        return rc;
     const int64_t lim = 2147483647;
     std::string why;
     if (R < 1 || nnz < 1 || !rowptr || !col || !val)
@@ -1253,20 +1042,13 @@ int lbfgsx_objective_bind_linear(lbfgsx_ctx* c, const lbfgsx_objective* obj, int
         lbfgsx::set_error("linear-model objective: " + why);
         return LBFGSX_E_INVALID;
     }
-    // the matrix first: a context whose arrays were refused keeps no objective bound, so nothing can be launched on them
     {
         lbfgsx::DeviceGuard dev_guard_(c->device);
         const int rc = lbfgsx::linear_topology_build(c, R, nnz, rowptr, col, val, matrix_on_device, lanes);
         if (rc)
             return rc;
     }
-    const int rc = objective_bind(c, obj, 0, 0, p, cs, id);
-    if (rc)
-    {
-        lbfgsx::DeviceGuard dev_guard_(c->device);
-        lbfgsx::graph_topology_free(c);
-    }
-    return rc;
+    return bind_end(c, obj, p, cs, id);
 }
 
 int lbfgsx_objective_linear_topology(lbfgsx_ctx* c, int64_t info[8], uint32_t* colptr, int32_t* trow, uint32_t* tpos,

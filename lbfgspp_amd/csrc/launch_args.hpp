@@ -213,37 +213,30 @@ struct BoundArgs
     }
     BoundArgs(const BoundArgs&) = delete;
 };
-// what a graph objective adds to the byte model of one launch of its kernels: the offsets, the entries, and every gathered
-// value once (vectors_gathered: 1 in the evaluation kernels, 2 in the trial kernels, which gather xp and d) -- the values,
-// not the sectors that are fetched for them.  Nothing for the other forms.
+// what the bound objective's lists add to the byte model, by its form; nothing for a term, chain or grid objective.
+// vectors_gathered: 1 in an evaluation, 2 in a trial, which gathers xp and d -- the values, not the sectors fetched for them.
+//   graph   one launch: the offsets, the 2E entries of 8 bytes, and every gathered value once
+//   mesh    one launch: (N+1)*4 bytes of offsets, K*E entries of 4K bytes, and (K-1)*D gathered values per entry
+//   linear  one evaluation (row pass, long-column launch, column pass): the offsets (rowptr, colptr), the indices (col, trow)
+//           and the values (val, tval) of both passes, every gathered value once (the row pass gathers vectors_gathered
+//           vectors, the column pass gathers w), w and v written and read, the chunk partials written and read
+// A trial launch adds it at its call site; an evaluation adds only a linear-model objective's, in linear_pre_eval.
 template <class T>
-inline void graph_model_add(const lbfgsx_ctx* c, int vectors_gathered)
+inline void objective_model_add(const lbfgsx_ctx* c, int vectors_gathered)
 {
+    const double esz = sizeof(T), vg = vectors_gathered;
     if (c->term_form == LBFGSX_FORM_GRAPH)
-        model_add(double(c->n + 1) * 4 + double(2 * c->graph_E) * 8 + double(2 * c->graph_E) * sizeof(T) * vectors_gathered);
-}
-// what a mesh objective adds: (N+1)*4 bytes of offsets, K*E entries of 4K bytes, and (K-1)*D gathered values per entry
-template <class T>
-inline void mesh_model_add(const lbfgsx_ctx* c, int vectors_gathered)
-{
-    if (c->term_form == LBFGSX_FORM_MESH)
+        model_add(double(c->n + 1) * 4 + double(2 * c->graph_E) * 8 + double(2 * c->graph_E) * esz * vg);
+    else if (c->term_form == LBFGSX_FORM_MESH)
     {
         const double K = c->mesh_K, D = c->mesh_D, KE = K * double(c->graph_E);
-        model_add(double(c->n / c->mesh_D + 1) * 4 + KE * 4 * K + KE * (K - 1) * D * sizeof(T) * vectors_gathered);
+        model_add(double(c->n / c->mesh_D + 1) * 4 + KE * 4 * K + KE * (K - 1) * D * esz * vg);
     }
-}
-// what a linear-model objective adds to the byte model of one evaluation (row pass, long-column launch, column pass): the
-// offsets (rowptr, colptr), the indices (col, trow) and the values (val, tval) of both passes, every gathered value once (the
-// row pass gathers vectors_gathered vectors: 1 in an evaluation, 2 in a trial, xp and d; the column pass gathers w), w and v
-// written and read, the chunk partials written and read
-template <class T>
-inline void linear_model_add(const lbfgsx_ctx* c, int vectors_gathered)
-{
-    if (c->term_form == LBFGSX_FORM_LINEAR)
+    else if (c->term_form == LBFGSX_FORM_LINEAR)
     {
-        const double R = double(c->lin.R), nnz = double(c->lin.nnz), esz = sizeof(T);
-        model_add((R + 1) * 4 + double(c->n + 1) * 4 + 2 * nnz * 4 + 2 * nnz * esz + nnz * esz * (vectors_gathered + 1) +
-                  4 * R * esz + 2 * double(c->lin.nchunks) * esz);
+        const double R = double(c->lin.R), nnz = double(c->lin.nnz);
+        model_add((R + 1) * 4 + double(c->n + 1) * 4 + 2 * nnz * 4 + 2 * nnz * esz + nnz * esz * (vg + 1) + 4 * R * esz +
+                  2 * double(c->lin.nchunks) * esz);
     }
 }
 // graph_topology.hip: the incidence list of the context (ctx.hpp: graph_off, graph_inc, graph_E).  build validates the
@@ -293,7 +286,7 @@ inline int linear_pre_eval(lbfgsx_ctx* c, BoundArgs<T>& obj, const T* x)
 {
     if (c->term_form != LBFGSX_FORM_LINEAR)
         return LBFGSX_OK;
-    linear_model_add<T>(c, 1);
+    objective_model_add<T>(c, 1);
     void* params[] = {&x, obj.ptr};
     const int rc = jit_launch(c, JIT_K_LIN_ROWS, linear_rows_grid(c), params);
     return rc ? rc : linear_long_launch(c);
@@ -303,7 +296,6 @@ inline int linear_pre_trial(lbfgsx_ctx* c, BoundArgs<T>& obj, const T* xp, const
 {
     if (c->term_form != LBFGSX_FORM_LINEAR)
         return LBFGSX_OK;
-    linear_model_add<T>(c, 2);
     void* params[] = {&xp, &d, &step, obj.ptr};
     const int rc = jit_launch(c, JIT_K_LIN_ROWS_TRIAL, linear_rows_grid(c), params);
     return rc ? rc : linear_long_launch(c);

@@ -52,8 +52,7 @@ static int dg_maxstep_trial_term_t(lbfgsx_ctx* c, T step, double* r4)
 {
     DgTrialLaunch<T> a = dg_maxstep_trial_launch<T>(c, step, c->term_np);
     BoundArgs<T> obj(c);
-    graph_model_add<T>(c, 2);
-    mesh_model_add<T>(c, 2);
+    objective_model_add<T>(c, 2);
     void* params[] = {&a.xp, &a.g0, &a.d, &a.lb, &a.ub, &a.step, &a.x, &a.g, &a.n, obj.ptr, &a.ws, &a.out, &a.rev};
     int rc = linear_pre_trial<T>(c, obj, a.xp, a.d, a.step);
     if (rc)

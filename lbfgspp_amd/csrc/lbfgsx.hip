@@ -1127,8 +1127,7 @@ static int trial_term_t(lbfgsx_ctx* c, T step, double* out2)
 {
     lbfgsx::TrialLaunch<T> a = lbfgsx::trial_launch<T>(c, step, c->term_np);
     lbfgsx::BoundArgs<T> obj(c);
-    lbfgsx::graph_model_add<T>(c, 2);
-    lbfgsx::mesh_model_add<T>(c, 2);
+    lbfgsx::objective_model_add<T>(c, 2);
     void* params[] = {&a.xp, &a.d, &a.step, &a.x, &a.g, &a.n, obj.ptr, &a.ws, &a.out, &a.rev};
     int rc = lbfgsx::linear_pre_trial<T>(c, obj, a.xp, a.d, a.step);
     if (rc)

@@ -31,8 +31,7 @@
 //
 // Every index read here was validated at bind: 0 <= col < n, 0 <= trow < R, list positions in [0, nnz).
 #pragma once
-#include "lbfgs_kernels.cuh"
-#include "lbfgsb_kernels.cuh"
+#include "own_frame.cuh"
 
 namespace lbfgsx {
 
@@ -121,15 +120,6 @@ __global__ void __launch_bounds__(kBlock) k_lin_rows_trial(const T* __restrict__
 }
 
 // ---------------------------------------------------------------- the column pass
-// the W + 1 offsets of the pack at b = vi*W (colptr has n + 1 elements, b + W <= n)
-template <int W>
-__device__ __forceinline__ void lin_offsets(const uint32_t* __restrict__ off, int64_t b, uint32_t (&o)[W + 1])
-{
-#pragma unroll
-    for (int k = 0; k <= W; k++)
-        o[k] = off[b + k];
-}
-
 // coordinate j with value xj and transposed entries [lo, hi): its gradient, returned; psi's value goes to fx
 template <class T, class OBJ, class A>
 __device__ __forceinline__ T lin_coord(const OBJ& obj, int64_t j, T xj, uint32_t lo, uint32_t hi, A& fx)
@@ -222,174 +212,56 @@ __device__ __forceinline__ void lin_row_values(const OBJ& obj, A& fx)
             fx.add(v[r]);
 }
 
-// ---------------------------------------------------------------- k_eval's counterpart
-// out[0] = f(x), out[1] = g.g, out[2] = x.x
+// the frame's family (own_frame.cuh): n coordinates, the transposed list at colptr, and every row's value as the extra pass
+struct LinFamily
+{
+    static constexpr int D = 1, U = kLinTrialU;
+    template <class OBJ>
+    static __device__ __forceinline__ int64_t nodes(const OBJ&, int64_t n)
+    {
+        return n;
+    }
+    template <class OBJ>
+    static __device__ __forceinline__ const uint32_t* off(const OBJ& obj)
+    {
+        return obj.colptr;
+    }
+    template <class T, class OBJ, class LD, class A>
+    static __device__ __forceinline__ void node(const OBJ& obj, int64_t j, const T (&xj)[1], uint32_t lo, uint32_t hi, LD, A& fx,
+                                                T (&gj)[1])
+    {
+        gj[0] = lin_coord<T>(obj, j, xj[0], lo, hi, fx);
+    }
+    template <class T, class OBJ, class A>
+    static __device__ __forceinline__ void extra(const OBJ& obj, A& fx)
+    {
+        lin_row_values<T>(obj, fx);
+    }
+};
+
 template <class T, class OBJ>
 __global__ void __launch_bounds__(kBlock) k_lin_eval(const T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
                                                      T* __restrict__ out)
 {
-    typedef typename AccOf<T>::type A;
-    constexpr int W = Vec16<T>::W;
-    A acc[3];
-    const int64_t nv = n / W;
-    const int64_t stride = int64_t(gridDim.x) * kBlock;
-    for (int64_t vi = int64_t(blockIdx.x) * kBlock + threadIdx.x; vi < nv; vi += stride)
-    {
-        const Pack<T> px = ldv(x, vi);
-        uint32_t o[W + 1];
-        lin_offsets<W>(obj.colptr, vi * W, o);
-        Pack<T> pg;
-#pragma unroll
-        for (int k = 0; k < W; k++)
-            pg.e[k] = lin_coord<T>(obj, vi * W + k, px.e[k], o[k], o[k + 1], acc[0]);
-        stv(g, vi, pg);
-#pragma unroll
-        for (int k = 0; k < W; k++)
-        {
-            acc[1].add_prod(pg.e[k], pg.e[k]);
-            acc[2].add_prod(px.e[k], px.e[k]);
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int64_t i = nv * W; i < n; i++)
-        {
-            const T gi = lin_coord<T>(obj, i, x[i], obj.colptr[i], obj.colptr[i + 1], acc[0]);
-            g[i] = gi;
-            acc[1].add_prod(gi, gi);
-            acc[2].add_prod(x[i], x[i]);
-        }
-    lin_row_values<T>(obj, acc[0]);
-    if (grid_reduce<3>(acc, ws) && threadIdx.x == 0)
-    {
-        out[0] = T(acc[0].value());
-        out[1] = T(acc[1].value());
-        out[2] = T(acc[2].value());
-    }
+    own_eval<T, LinFamily, OBJ, false>(x, g, nullptr, nullptr, n, obj, ws, out);
 }
 
-// ---------------------------------------------------------------- k_trial's counterpart
-// x = xp + step*d ; g = grad f(x) ; out[0] = f(x), out[1] = g.d
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_lin_trial(const T* __restrict__ xp, const T* __restrict__ d, T step,
-                                                      T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                      T* __restrict__ out, int rev)
-{
-    typedef typename AccOf<T>::type A;
-    constexpr int W = Vec16<T>::W;
-    constexpr int U = kLinTrialU;
-    A acc[2];
-    const int64_t nv = n / W;
-    const int64_t tile = int64_t(kBlock) * U;
-    const int64_t top = ((nv + tile - 1) / tile - 1) * tile;
-    for (int64_t t0 = int64_t(blockIdx.x) * tile; t0 < nv; t0 += int64_t(gridDim.x) * tile)
-    {
-        const int64_t base = (rev ? top - t0 : t0) + threadIdx.x;
-        Pack<T> pxp[U], pd[U];
-        uint32_t o[U][W + 1];
-#pragma unroll
-        for (int u = 0; u < U; u++)
-        {
-            const int64_t vi = base + u * kBlock;
-            if (vi < nv)
-            {
-                pxp[u] = ldv(xp, vi);
-                pd[u] = ldv(d, vi);
-                lin_offsets<W>(obj.colptr, vi * W, o[u]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++)
-        {
-            const int64_t vi = base + u * kBlock;
-            if (vi < nv)
-            {
-                Pack<T> px, pg;
-#pragma unroll
-                for (int k = 0; k < W; k++)
-                    px.e[k] = pxp[u].e[k] + step * pd[u].e[k];
-#pragma unroll
-                for (int k = 0; k < W; k++)
-                    pg.e[k] = lin_coord<T>(obj, vi * W + k, px.e[k], o[u][k], o[u][k + 1], acc[0]);
-                stv(x, vi, px);
-                stv(g, vi, pg);
-#pragma unroll
-                for (int k = 0; k < W; k++)
-                    acc[1].add_prod(pg.e[k], pd[u].e[k]);
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int64_t i = nv * W; i < n; i++)
-        {
-            const T xi = xp[i] + step * d[i];
-            x[i] = xi;
-            const T gi = lin_coord<T>(obj, i, xi, obj.colptr[i], obj.colptr[i + 1], acc[0]);
-            g[i] = gi;
-            acc[1].add_prod(gi, d[i]);
-        }
-    lin_row_values<T>(obj, acc[0]);
-    if (grid_reduce<2>(acc, ws) && threadIdx.x == 0)
-    {
-        out[0] = T(acc[0].value());
-        out[1] = T(acc[1].value());
-        ws_signal(ws);
-    }
-}
-
-// ---------------------------------------------------------------- k_b_eval's counterpart
-// out[0] = f(x), out[1] = x.x, out[2] = ||P(x-g)-x||_inf
 template <class T, class OBJ>
 __global__ void __launch_bounds__(kBlock) k_lin_b_eval(const T* __restrict__ x, T* __restrict__ g, const T* __restrict__ lb,
                                                        const T* __restrict__ ub, int64_t n, OBJ obj, RedWs ws,
                                                        T* __restrict__ out)
 {
-    typedef typename AccOf<T>::type A;
-    constexpr int W = Vec16<T>::W;
-    A acc[2];
-    double pg = 0.0;
-    const int64_t nv = n / W;
-    const int64_t stride = int64_t(gridDim.x) * kBlock;
-    for (int64_t vi = int64_t(blockIdx.x) * kBlock + threadIdx.x; vi < nv; vi += stride)
-    {
-        const Pack<T> px = ldv(x, vi), pl = ldv(lb, vi), pu = ldv(ub, vi);
-        uint32_t o[W + 1];
-        lin_offsets<W>(obj.colptr, vi * W, o);
-        Pack<T> pgv;
-#pragma unroll
-        for (int k = 0; k < W; k++)
-            pgv.e[k] = lin_coord<T>(obj, vi * W + k, px.e[k], o[k], o[k + 1], acc[0]);
-        stv(g, vi, pgv);
-#pragma unroll
-        for (int k = 0; k < W; k++)
-        {
-            acc[1].add_prod(px.e[k], px.e[k]);
-            pg = fmax(pg, double(projg_term(px.e[k], pgv.e[k], pl.e[k], pu.e[k])));
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int64_t i = nv * W; i < n; i++)
-        {
-            const T gi = lin_coord<T>(obj, i, x[i], obj.colptr[i], obj.colptr[i + 1], acc[0]);
-            g[i] = gi;
-            acc[1].add_prod(x[i], x[i]);
-            pg = fmax(pg, double(projg_term(x[i], gi, lb[i], ub[i])));
-        }
-    lin_row_values<T>(obj, acc[0]);
-    ext_publish<false>(pg, ws, 4);
-    if (grid_reduce<2>(acc, ws))
-    {
-        const double pgmax = ext_collect<false>(ws, 4);
-        if (threadIdx.x == 0)
-        {
-            out[0] = T(acc[0].value());
-            out[1] = T(acc[1].value());
-            out[2] = T(pgmax);
-        }
-    }
+    own_eval<T, LinFamily, OBJ, true>(x, g, lb, ub, n, obj, ws, out);
 }
 
-// ---------------------------------------------------------------- k_b_dg_maxstep_trial's counterpart
-// out[0] = g0.d, out[1] = step_max, out[2] = f(x), out[3] = grad(x).d at x = xp + step*d
+template <class T, class OBJ>
+__global__ void __launch_bounds__(kBlock) k_lin_trial(const T* __restrict__ xp, const T* __restrict__ d, T step,
+                                                      T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
+                                                      T* __restrict__ out, int rev)
+{
+    own_trial<T, LinFamily, OBJ, false>(xp, nullptr, d, nullptr, nullptr, step, x, g, n, obj, ws, out, rev);
+}
+
 template <class T, class OBJ>
 __global__ void __launch_bounds__(kBlock) k_lin_b_dg_maxstep_trial(const T* __restrict__ xp, const T* __restrict__ g0,
                                                                    const T* __restrict__ d, const T* __restrict__ lb,
@@ -397,89 +269,7 @@ __global__ void __launch_bounds__(kBlock) k_lin_b_dg_maxstep_trial(const T* __re
                                                                    T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
                                                                    T* __restrict__ out, int rev)
 {
-    typedef typename AccOf<T>::type A;
-    constexpr int W = Vec16<T>::W;
-    constexpr int U = kLinTrialU;
-    A acc[3];  // f's sum, grad(x).d, g0.d
-    double smin = __longlong_as_double(0x7FF0000000000000ll);
-    auto feas = [&](T xi, T di, T lo, T up) __attribute__((always_inline)) {
-        if (di > T(0))
-            smin = fmin(smin, double((up - xi) / di) + 0.0);
-        else if (di < T(0))
-            smin = fmin(smin, double((lo - xi) / di) + 0.0);
-    };
-    const int64_t nv = n / W;
-    const int64_t tile = int64_t(kBlock) * U;
-    const int64_t top = ((nv + tile - 1) / tile - 1) * tile;
-    for (int64_t t0 = int64_t(blockIdx.x) * tile; t0 < nv; t0 += int64_t(gridDim.x) * tile)
-    {
-        const int64_t base = (rev ? top - t0 : t0) + threadIdx.x;
-        Pack<T> pxp[U], pd[U], pg0[U], plo[U], pup[U];
-        uint32_t o[U][W + 1];
-#pragma unroll
-        for (int u = 0; u < U; u++)
-        {
-            const int64_t vi = base + u * kBlock;
-            if (vi < nv)
-            {
-                pxp[u] = ldv<T>(xp, vi);
-                pd[u] = ldv<T>(d, vi);
-                pg0[u] = ldv<T>(g0, vi);
-                plo[u] = ldv<T>(lb, vi);
-                pup[u] = ldv<T>(ub, vi);
-                lin_offsets<W>(obj.colptr, vi * W, o[u]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++)
-        {
-            const int64_t vi = base + u * kBlock;
-            if (vi < nv)
-            {
-                Pack<T> px, pg;
-#pragma unroll
-                for (int k = 0; k < W; k++)
-                {
-                    px.e[k] = pxp[u].e[k] + step * pd[u].e[k];
-                    acc[2].add_prod(pg0[u].e[k], pd[u].e[k]);
-                    feas(pxp[u].e[k], pd[u].e[k], plo[u].e[k], pup[u].e[k]);
-                }
-#pragma unroll
-                for (int k = 0; k < W; k++)
-                    pg.e[k] = lin_coord<T>(obj, vi * W + k, px.e[k], o[u][k], o[u][k + 1], acc[0]);
-                stv<T>(x, vi, px);
-                stv<T>(g, vi, pg);
-#pragma unroll
-                for (int k = 0; k < W; k++)
-                    acc[1].add_prod(pg.e[k], pd[u].e[k]);
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int64_t i = nv * W; i < n; i++)
-        {
-            acc[2].add_prod(g0[i], d[i]);
-            feas(xp[i], d[i], lb[i], ub[i]);
-            const T xi = xp[i] + step * d[i];
-            x[i] = xi;
-            const T gi = lin_coord<T>(obj, i, xi, obj.colptr[i], obj.colptr[i + 1], acc[0]);
-            g[i] = gi;
-            acc[1].add_prod(gi, d[i]);
-        }
-    lin_row_values<T>(obj, acc[0]);
-    ext_publish<true>(smin, ws, 6);
-    if (grid_reduce<3>(acc, ws))
-    {
-        const double smin_all = ext_collect<true>(ws, 6);
-        if (threadIdx.x == 0)
-        {
-            out[0] = T(acc[2].value());
-            out[1] = T(smin_all);
-            out[2] = T(acc[0].value());
-            out[3] = T(acc[1].value());
-            ws_signal(ws);
-        }
-    }
+    own_trial<T, LinFamily, OBJ, true>(xp, g0, d, lb, ub, step, x, g, n, obj, ws, out, rev);
 }
 
 }  // namespace lbfgsx

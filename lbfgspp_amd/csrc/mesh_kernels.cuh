@@ -25,8 +25,7 @@
 // the trial kernels a gathered value is xp[u] + step*d[u], never a read of the x this launch writes.  Every index read from
 // the list was validated at bind, every list position lies in [0, K*E).
 #pragma once
-#include "lbfgs_kernels.cuh"
-#include "lbfgsb_kernels.cuh"
+#include "own_frame.cuh"
 
 namespace lbfgsx {
 
@@ -50,15 +49,6 @@ struct alignas(K == 3 ? 4 : 4 * K) MeshEntry
 {
     uint32_t w[K];
 };
-
-// the W + 1 offsets of the node group at b = vi*W (off has N + 1 elements, b + W <= N)
-template <int W>
-__device__ __forceinline__ void mesh_offsets(const uint32_t* __restrict__ off, int64_t b, uint32_t (&o)[W + 1])
-{
-#pragma unroll
-    for (int k = 0; k <= W; k++)
-        o[k] = off[b + k];
-}
 
 // node v with values xv and entries [lo, hi): its D partial derivatives go to gv; its node value and the values of the
 // elements it is slot 0 of go to fx.  ld(i) = x[i] -- from memory in the evaluation kernels, recomputed from xp and d in
@@ -142,122 +132,30 @@ __device__ __forceinline__ void mesh_node(const OBJ& obj, int64_t v, const T (&x
     }
 }
 
-// the W nodes of group vi: their values from the D packs px, their gradients into the D packs pg
-template <class T, class OBJ, class LD, class A>
-__device__ __forceinline__ void mesh_group_nodes(const OBJ& obj, int64_t vi, const Pack<T> (&px)[OBJ::D],
-                                                 const uint32_t (&o)[Vec16<T>::W + 1], LD ld, A& fx, Pack<T> (&pg)[OBJ::D])
+// the frame's family (own_frame.cuh): N nodes of D unknowns, the list at off, no extra pass
+template <class OBJ>
+struct MeshFamily
 {
-    constexpr int W = Vec16<T>::W, D = OBJ::D;
-#pragma unroll
-    for (int k = 0; k < W; k++)
+    static constexpr int D = OBJ::D, U = MeshTrialU<D>::value;
+    static __device__ __forceinline__ int64_t nodes(const OBJ& obj, int64_t) { return obj.N; }
+    static __device__ __forceinline__ const uint32_t* off(const OBJ& obj) { return obj.off; }
+    template <class T, class LD, class A>
+    static __device__ __forceinline__ void node(const OBJ& obj, int64_t v, const T (&xv)[D], uint32_t lo, uint32_t hi, LD ld,
+                                                A& fx, T (&gv)[D])
     {
-        T xv[D], gv[D];
-#pragma unroll
-        for (int d = 0; d < D; d++)
-            xv[d] = px[(k * D + d) / W].e[(k * D + d) % W];
-        mesh_node<T>(obj, vi * W + k, xv, o[k], o[k + 1], ld, fx, gv);
-#pragma unroll
-        for (int d = 0; d < D; d++)
-            pg[(k * D + d) / W].e[(k * D + d) % W] = gv[d];
+        mesh_node<T>(obj, v, xv, lo, hi, ld, fx, gv);
     }
-}
-
-// the N mod W trailing nodes, one at a time (thread 0 of block 0): xv = value(i), g written, done(i, g_i) per unknown
-template <class T, class OBJ, class LD, class A, class XV, class DONE>
-__device__ __forceinline__ void mesh_tail(const OBJ& obj, int64_t first, T* __restrict__ g, LD ld, A& fx, XV value, DONE done)
-{
-    constexpr int D = OBJ::D;
-    for (int64_t v = first; v < obj.N; v++)
+    template <class T, class A>
+    static __device__ __forceinline__ void extra(const OBJ&, A&)
     {
-        T xv[D], gv[D];
-#pragma unroll
-        for (int k = 0; k < D; k++)
-            xv[k] = value(v * D + k);
-        mesh_node<T>(obj, v, xv, obj.off[v], obj.off[v + 1], ld, fx, gv);
-#pragma unroll
-        for (int k = 0; k < D; k++)
-        {
-            g[v * D + k] = gv[k];
-            done(v * D + k, xv[k], gv[k]);
-        }
     }
-}
-
-// ---------------------------------------------------------------- k_graph_eval's and k_graph_b_eval's counterparts
-// BOUNDED false: out[0] = f(x), out[1] = g.g, out[2] = x.x;  true: out[0] = f(x), out[1] = x.x, out[2] = ||P(x-g)-x||_inf
-template <class T, class OBJ, bool BOUNDED>
-__device__ __forceinline__ void mesh_eval(const T* __restrict__ x, T* __restrict__ g, const T* __restrict__ lb,
-                                          const T* __restrict__ ub, OBJ obj, RedWs ws, T* __restrict__ out)
-{
-    typedef typename AccOf<T>::type A;
-    constexpr int W = Vec16<T>::W, D = OBJ::D;
-    constexpr int NA = BOUNDED ? 2 : 3, XX = NA - 1;  // acc[0]: f's sum, acc[XX]: x.x, acc[1] of three: g.g
-    A acc[NA];
-    double pgm = 0.0;
-    const int64_t nv = obj.N / W;
-    const int64_t stride = int64_t(gridDim.x) * kBlock;
-    auto ld = [&](int64_t i) { return x[i]; };
-    auto done = [&](int64_t i, T xi, T gi) __attribute__((always_inline)) {
-        acc[XX].add_prod(xi, xi);
-        if constexpr (BOUNDED)
-            pgm = fmax(pgm, double(projg_term(xi, gi, lb[i], ub[i])));
-        else
-            acc[1].add_prod(gi, gi);
-    };
-    for (int64_t vi = int64_t(blockIdx.x) * kBlock + threadIdx.x; vi < nv; vi += stride)
-    {
-        Pack<T> px[D], pl[D], pu[D], pg[D];
-#pragma unroll
-        for (int j = 0; j < D; j++)
-        {
-            px[j] = ldv(x, vi * D + j);
-            if constexpr (BOUNDED)
-            {
-                pl[j] = ldv(lb, vi * D + j);
-                pu[j] = ldv(ub, vi * D + j);
-            }
-        }
-        uint32_t o[W + 1];
-        mesh_offsets<W>(obj.off, vi * W, o);
-        mesh_group_nodes<T>(obj, vi, px, o, ld, acc[0], pg);
-#pragma unroll
-        for (int j = 0; j < D; j++)
-        {
-            stv(g, vi * D + j, pg[j]);
-#pragma unroll
-            for (int k = 0; k < W; k++)
-            {
-                acc[XX].add_prod(px[j].e[k], px[j].e[k]);
-                if constexpr (BOUNDED)
-                    pgm = fmax(pgm, double(projg_term(px[j].e[k], pg[j].e[k], pl[j].e[k], pu[j].e[k])));
-                else
-                    acc[1].add_prod(pg[j].e[k], pg[j].e[k]);
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        mesh_tail<T>(obj, nv * W, g, ld, acc[0], ld, done);
-    if constexpr (BOUNDED)
-        ext_publish<false>(pgm, ws, 4);
-    if (grid_reduce<NA>(acc, ws))
-    {
-        double pgmax = 0.0;
-        if constexpr (BOUNDED)
-            pgmax = ext_collect<false>(ws, 4);
-        if (threadIdx.x == 0)
-        {
-            out[0] = T(acc[0].value());
-            out[1] = T(acc[1].value());
-            out[2] = BOUNDED ? T(pgmax) : T(acc[XX].value());
-        }
-    }
-}
+};
 
 template <class T, class OBJ>
 __global__ void __launch_bounds__(kBlock) k_mesh_eval(const T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
                                                       T* __restrict__ out)
 {
-    mesh_eval<T, OBJ, false>(x, g, nullptr, nullptr, obj, ws, out);
+    own_eval<T, MeshFamily<OBJ>, OBJ, false>(x, g, nullptr, nullptr, n, obj, ws, out);
 }
 
 template <class T, class OBJ>
@@ -265,124 +163,7 @@ __global__ void __launch_bounds__(kBlock) k_mesh_b_eval(const T* __restrict__ x,
                                                         const T* __restrict__ ub, int64_t n, OBJ obj, RedWs ws,
                                                         T* __restrict__ out)
 {
-    mesh_eval<T, OBJ, true>(x, g, lb, ub, obj, ws, out);
-}
-
-// ---------------------------------------------------------------- k_graph_trial's and k_graph_b_dg_maxstep_trial's counterparts
-// x = xp + step*d ; g = grad f(x).  BOUNDED false: out[0] = f(x), out[1] = g.d;
-// true: out[0] = g0.d, out[1] = step_max, out[2] = f(x), out[3] = grad(x).d
-template <class T, class OBJ, bool BOUNDED>
-__device__ __forceinline__ void mesh_trial(const T* __restrict__ xp, const T* __restrict__ g0, const T* __restrict__ d,
-                                           const T* __restrict__ lb, const T* __restrict__ ub, T step, T* __restrict__ x,
-                                           T* __restrict__ g, OBJ obj, RedWs ws, T* __restrict__ out, int rev)
-{
-    typedef typename AccOf<T>::type A;
-    constexpr int W = Vec16<T>::W, D = OBJ::D;
-    constexpr int U = MeshTrialU<D>::value;
-    constexpr int NA = BOUNDED ? 3 : 2;
-    A acc[NA];  // f's sum, grad(x).d, g0.d
-    double smin = __longlong_as_double(0x7FF0000000000000ll);
-    auto feas = [&](T xi, T di, T lo, T up) __attribute__((always_inline)) {
-        if (di > T(0))
-            smin = fmin(smin, double((up - xi) / di) + 0.0);
-        else if (di < T(0))
-            smin = fmin(smin, double((lo - xi) / di) + 0.0);
-    };
-    const int64_t nv = obj.N / W;
-    const int64_t tile = int64_t(kBlock) * U;
-    const int64_t top = ((nv + tile - 1) / tile - 1) * tile;
-    auto ld = [&](int64_t i) { return xp[i] + step * d[i]; };
-    for (int64_t t0 = int64_t(blockIdx.x) * tile; t0 < nv; t0 += int64_t(gridDim.x) * tile)
-    {
-        const int64_t base = (rev ? top - t0 : t0) + threadIdx.x;
-        Pack<T> pxp[U][D], pd[U][D], pg0[U][D], plo[U][D], pup[U][D];
-        uint32_t o[U][W + 1];
-#pragma unroll
-        for (int u = 0; u < U; u++)
-        {
-            const int64_t vi = base + u * kBlock;
-            if (vi < nv)
-            {
-#pragma unroll
-                for (int j = 0; j < D; j++)
-                {
-                    pxp[u][j] = ldv<T>(xp, vi * D + j);
-                    pd[u][j] = ldv<T>(d, vi * D + j);
-                    if constexpr (BOUNDED)
-                    {
-                        pg0[u][j] = ldv<T>(g0, vi * D + j);
-                        plo[u][j] = ldv<T>(lb, vi * D + j);
-                        pup[u][j] = ldv<T>(ub, vi * D + j);
-                    }
-                }
-                mesh_offsets<W>(obj.off, vi * W, o[u]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++)
-        {
-            const int64_t vi = base + u * kBlock;
-            if (vi < nv)
-            {
-                Pack<T> px[D], pg[D];
-#pragma unroll
-                for (int j = 0; j < D; j++)
-#pragma unroll
-                    for (int k = 0; k < W; k++)
-                    {
-                        px[j].e[k] = pxp[u][j].e[k] + step * pd[u][j].e[k];
-                        if constexpr (BOUNDED)
-                        {
-                            acc[NA - 1].add_prod(pg0[u][j].e[k], pd[u][j].e[k]);
-                            feas(pxp[u][j].e[k], pd[u][j].e[k], plo[u][j].e[k], pup[u][j].e[k]);
-                        }
-                    }
-                mesh_group_nodes<T>(obj, vi, px, o[u], ld, acc[0], pg);
-#pragma unroll
-                for (int j = 0; j < D; j++)
-                {
-                    stv<T>(x, vi * D + j, px[j]);
-                    stv<T>(g, vi * D + j, pg[j]);
-#pragma unroll
-                    for (int k = 0; k < W; k++)
-                        acc[1].add_prod(pg[j].e[k], pd[u][j].e[k]);
-                }
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        mesh_tail<T>(
-            obj, nv * W, g, ld, acc[0],
-            [&](int64_t i) __attribute__((always_inline)) {
-                if constexpr (BOUNDED)
-                {
-                    acc[NA - 1].add_prod(g0[i], d[i]);
-                    feas(xp[i], d[i], lb[i], ub[i]);
-                }
-                const T xi = xp[i] + step * d[i];
-                x[i] = xi;
-                return xi;
-            },
-            [&](int64_t i, T, T gi) __attribute__((always_inline)) { acc[1].add_prod(gi, d[i]); });
-    if constexpr (BOUNDED)
-        ext_publish<true>(smin, ws, 6);
-    if (grid_reduce<NA>(acc, ws))
-    {
-        double smin_all = 0.0;
-        if constexpr (BOUNDED)
-            smin_all = ext_collect<true>(ws, 6);
-        if (threadIdx.x == 0)
-        {
-            if constexpr (BOUNDED)
-            {
-                out[0] = T(acc[2].value());
-                out[1] = T(smin_all);
-            }
-            out[BOUNDED ? 2 : 0] = T(acc[0].value());
-            out[BOUNDED ? 3 : 1] = T(acc[1].value());
-            ws_signal(ws);
-        }
-    }
+    own_eval<T, MeshFamily<OBJ>, OBJ, true>(x, g, lb, ub, n, obj, ws, out);
 }
 
 template <class T, class OBJ>
@@ -390,7 +171,7 @@ __global__ void __launch_bounds__(kBlock) k_mesh_trial(const T* __restrict__ xp,
                                                        T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
                                                        T* __restrict__ out, int rev)
 {
-    mesh_trial<T, OBJ, false>(xp, nullptr, d, nullptr, nullptr, step, x, g, obj, ws, out, rev);
+    own_trial<T, MeshFamily<OBJ>, OBJ, false>(xp, nullptr, d, nullptr, nullptr, step, x, g, n, obj, ws, out, rev);
 }
 
 template <class T, class OBJ>
@@ -400,7 +181,7 @@ __global__ void __launch_bounds__(kBlock) k_mesh_b_dg_maxstep_trial(const T* __r
                                                                     T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
                                                                     T* __restrict__ out, int rev)
 {
-    mesh_trial<T, OBJ, true>(xp, g0, d, lb, ub, step, x, g, obj, ws, out, rev);
+    own_trial<T, MeshFamily<OBJ>, OBJ, true>(xp, g0, d, lb, ub, step, x, g, n, obj, ws, out, rev);
 }
 
 }  // namespace lbfgsx

@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""Registers, scratch and occupancy of the graph, mesh and linear-model kernels in two trees, side by side
+(profiles/own_frame_kernel_resources.tsv).  No GPU is needed: the generated sources are compiled for gfx950 here.
+
+Each tree (a built checkout: the parent commit's and this one) is asked, in a process of its own, for the generated
+translation unit -- source() -- of
+    graph    ASYM_EDGE with and without NODE                                   (tests/graph_ref.py)
+    mesh     every (K, D) with the bodies tests/test_mesh_objective_cpu.py compiles (tests/mesh_ref.py)
+    linear   LOGISTIC with and without RIDGE                                   (tests/linear_ref.py)
+at f64 and f32.  Each is compiled against its own tree's lbfgspp_amd/csrc with the library's flags,
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off --cuda-device-only -S -Rpass-analysis=kernel-resource-usage
+and the compiler's remarks give VGPRs, scratch bytes per lane and occupancy (waves per SIMD) per kernel.
+
+The script fails when a kernel of this tree has scratch or a lower occupancy than the parent's.
+
+    python scripts/measure_own_frame_resources.py --parent <built checkout of the parent commit> [--out profiles/...tsv]
+"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only", "-S",
+         "-Rpass-analysis=kernel-resource-usage"]
+
+
+def emit_sources(tree):
+    """{case: source} of one tree, by that tree's own library"""
+    for p in (tree, os.path.join(tree, "tests")):
+        sys.path.insert(0, p)
+    import numpy as np
+
+    import graph_ref as GR
+    import linear_ref as LR
+    import lbfgspp_amd as A
+    import mesh_ref as MR
+    out = {}
+    one_edge = (np.array([0]), np.array([1]))
+    one_entry = (np.array([0, 1], np.int32), np.array([0], np.int32), np.array([1.0]))
+    for dname, dtype in (("f64", np.float64), ("f32", np.float32)):
+        for name, node in (("asym+node", GR.NODE), ("asym", None)):
+            out["graph/%s/%s" % (name, dname)] = A.GraphObjective(GR.ASYM_EDGE, edges=one_edge, node_body=node).source(dtype)
+        for K in (2, 3, 4):
+            for D in (1, 2, 3):
+                bodies = list(MR.GENERIC_BODIES)
+                bodies += {(3, 1): [("triple", MR.ALIAS_I + MR.TRIPLE, None)], (3, 2): [("triangle", MR.TRIANGLE, MR.TIE_NODE)],
+                           (4, 3): [("volume", MR.VOLUME, None)]}.get((K, D), [])
+                for name, elem, node in bodies:
+                    out["mesh/K%dD%d/%s/%s" % (K, D, name, dname)] = A.MeshObjective(elem, MR.strip(K, K), D, node_body=node).source(dtype)
+        for name, coord in (("logistic+ridge", LR.RIDGE), ("logistic", None)):
+            out["linear/%s/%s" % (name, dname)] = A.LinearObjective(LR.LOGISTIC, one_entry, 1, coord_body=coord).source(dtype)
+    return out
+
+
+def kernel_name(mangled):
+    m = re.search(r"(\d+)k_", mangled)
+    return mangled[m.end(1):m.end(1) + int(m.group(1))] if m else mangled
+
+
+def resources(job):
+    """{kernel: (vgprs, scratch, occupancy)} of one source compiled against one tree's kernel headers"""
+    src, csrc = job
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "objective_wrapper.hip")
+        with open(path, "w") as f:
+            f.write(src)
+        r = subprocess.run([HIPCC] + FLAGS + ["-I", csrc, path, "-o", os.path.join(d, "out.s")], stderr=subprocess.PIPE, text=True)
+        if r.returncode:
+            raise SystemExit(r.stderr[-4000:])
+    out, name = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark: (?:.*?\s)?(Function Name|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\S+)", line)
+        if not m:
+            continue
+        if m.group(1) == "Function Name":
+            name = kernel_name(m.group(2))
+            out[name] = {}
+        elif name:
+            out[name][m.group(1).split(" ")[0]] = int(m.group(2))
+    return {k: (v["VGPRs"], v["ScratchSize"], v["Occupancy"]) for k, v in out.items() if k.startswith("k_")}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", help="built checkout of the parent commit")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "own_frame_kernel_resources.tsv"))
+    ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
+    ap.add_argument("--emit-sources", metavar="TREE", help="print the sources of TREE as JSON and nothing else")
+    args = ap.parse_args()
+    if args.emit_sources:
+        json.dump(emit_sources(args.emit_sources), sys.stdout)
+        return
+    if not args.parent:
+        ap.error("--parent is required")
+    trees = {"parent": os.path.abspath(args.parent), "head": ROOT}
+    srcs = {k: json.loads(subprocess.run([sys.executable, os.path.abspath(__file__), "--emit-sources", t], cwd=t, check=True,
+                                         stdout=subprocess.PIPE, text=True).stdout) for k, t in trees.items()}
+    assert sorted(srcs["parent"]) == sorted(srcs["head"])
+    cases = sorted(srcs["head"])
+    jobs = [(srcs[k][c], os.path.join(trees[k], "lbfgspp_amd", "csrc")) for c in cases for k in ("parent", "head")]
+    with ThreadPoolExecutor(max_workers=args.jobs) as ex:
+        res = list(ex.map(resources, jobs))
+    bad = []
+    with open(args.out, "w") as f:
+        f.write("# VGPRs, scratch bytes per lane and occupancy (waves per SIMD) of every graph, mesh and linear-model kernel, from the\n"
+                "# compiler's kernel-resource-usage remarks: the parent commit and the kernels on own_frame.cuh, side by side\n"
+                "# (scripts/measure_own_frame_resources.py; case = form/bodies/dtype)\n")
+        f.write("case\tkernel\tvgpr_parent\tvgpr_head\tscratch_parent\tscratch_head\toccupancy_parent\toccupancy_head\tsame_source\n")
+        for i, c in enumerate(cases):
+            parent, head = res[2 * i], res[2 * i + 1]
+            assert sorted(parent) == sorted(head), (c, sorted(parent), sorted(head))
+            for k in sorted(head):
+                p, h = parent[k], head[k]
+                f.write("%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%s\n" % (c, k, p[0], h[0], p[1], h[1], p[2], h[2],
+                                                                    "yes" if srcs["parent"][c] == srcs["head"][c] else "no"))
+                if h[1] != 0 or h[2] < p[2]:
+                    bad.append("%s %s: scratch %d, occupancy %d against the parent's %d" % (c, k, h[1], h[2], p[2]))
+    print("wrote %s: %d cases" % (args.out, len(cases)))
+    if bad:
+        sys.exit("\n".join(bad))
+
+
+if __name__ == "__main__":
+    main()

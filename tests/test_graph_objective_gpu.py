@@ -35,8 +35,10 @@ def _size_list(dtype):
     W = PACK[dtype]
     tile = 256 * TRIAL_U  # packs
     # around a wave, a block and one and two trial tiles, with and without tail coordinates; about five tiles: several blocks,
-    # and both tile orders cross tile borders
-    return [2, 3, 64 * W - 1, 64 * W + 1, 256 * W + W + 1, tile * W + 3, 2 * tile * W + W + 1, 5 * tile * W + W + 1]
+    # and both tile orders cross tile borders.  2 and 3 have no whole pack at f32 (at f64 W = 2 and an edge needs two nodes:
+    # there is no smaller graph); 3 and 64 W + 1 have exactly one coordinate past the last pack; tile W + 1 is one node past
+    # one trial tile
+    return [2, 3, 64 * W - 1, 64 * W + 1, 256 * W + W + 1, tile * W + 1, tile * W + 3, 2 * tile * W + W + 1, 5 * tile * W + W + 1]
 
 
 def _sizes():
@@ -459,10 +461,16 @@ def test_graph_solve_issues_the_launches_per_iteration_of_a_chain_solve(A):
             c0 = _counters(core)
             niter, fx = s.minimize(f, x)
             c1 = _counters(core)
-            out[name, iters] = (niter, s.last.nfev, fx, c1[0] - c0[0])
+            out[name, iters] = (niter, s.last.nfev, fx, c1[0] - c0[0], c1[3] - c0[3])
     print(out)
     for iters in (10, 20):
         assert out["graph", iters][:3] == out["chain", iters][:3] and out["graph", iters][0] == iters
+        # the byte model (launch_args.hpp): a trial launch reads xp and d, writes x and grad and reads the one data array; a
+        # graph's adds the n + 1 offsets, the 2E entries of 8 bytes and 2E gathered values of xp and of d.  Every evaluation
+        # but the first is a trial launch
+        trials, E = out["graph", iters][1] - 1, n - 1
+        assert out["chain", iters][4] == trials * (n * 8 * 5)
+        assert out["graph", iters][4] == trials * (n * 8 * 5 + (n + 1) * 4 + 2 * E * 8 + 2 * E * 8 * 2)
     build = out["graph", 10][3] - out["chain", 10][3]
     assert 0 < build <= 8 and out["graph", 20][3] - out["chain", 20][3] == build
     assert out["graph", 20][3] - out["graph", 10][3] == out["chain", 20][3] - out["chain", 10][3] > 0

@@ -51,12 +51,16 @@ def _problem(name, dtype):
         return LR.random_rows(700, 1031, 40, 7, dt)
     if name == "wide":
         return LR.random_rows(300, _wide_n(dtype), 12, 8, dt)
+    if name == "tile":  # one coordinate past one trial tile of the column pass, R < n: the grid is chosen by n
+        return LR.random_rows(200, 256 * LR.TRIAL_U * PACK[dtype] + 1, 12, 9, dt)
     return LR.long_columns(dt)
 
 
-LANES = {"single": (0, 2), "tiny": (0, 4), "random": (0, 1, 2, 8, 64), "wide": (0,), "long": (0,)}
+# single: n = 1, no whole pack; tiny (n = 5, R = 3) and long (n = 37, R = 9000): one coordinate past the last pack, the grid
+# chosen by n and by R
+LANES = {"single": (0, 2), "tiny": (0, 4), "random": (0, 1, 2, 8, 64), "wide": (0,), "tile": (0,), "long": (0,)}
 CASES = [pytest.param(dt, name, id="%s-%s" % ("f64" if dt == O.F64 else "f32", name))
-         for dt in (O.F64, O.F32) for name in ("single", "tiny", "random", "wide", "long")]
+         for dt in (O.F64, O.F32) for name in ("single", "tiny", "random", "wide", "tile", "long")]
 
 
 @pytest.fixture(scope="module")
@@ -395,11 +399,26 @@ def _regression(R_, n, seed, per_row=8):
     return rng, (rowptr, col, val), dense
 
 
+def _model_bytes(core):
+    cnt = (C.c_int64 * 8)()
+    assert core.lbfgsx_counters_ex(C.byref(cnt), 0) == 0
+    return cnt[3]
+
+
 def _solve(A, solver, f, n, eps, cap=3000):
     x = np.zeros(n)
     if solver == "lbfgs":
         s = A.LBFGSSolver(A.LBFGSParam(m=10, epsilon=eps, epsilon_rel=eps, past=0, max_iterations=cap), linesearch=A.LS_MORE_THUENTE)
+        core, _ = A.load()
+        before = _model_bytes(core)
         niter, fx = s.minimize(f, x)
+        # the byte model (launch_args.hpp).  An evaluation of a linear-model objective: the offsets of both passes, their
+        # indices and values, the gathered values (vg vectors in the row pass, w in the column pass), w and v written and read;
+        # no column is long here.  A trial launch also reads xp and d, writes x and grad and reads the data arrays.  The first
+        # evaluation is lbfgsx_eval (vg = 1), every other one a trial (vg = 2: xp and d)
+        assert f.R <= LR.C_DEFAULT
+        lin = lambda vg: (f.R + 1) * 4 + (n + 1) * 4 + 2 * f.nnz * 4 + 2 * f.nnz * 8 + f.nnz * 8 * (vg + 1) + 4 * f.R * 8
+        assert _model_bytes(core) - before == lin(1) + (s.last.nfev - 1) * (n * 8 * (4 + len(f.data)) + lin(2))
     else:
         s = A.LBFGSBSolver(A.LBFGSBParam(m=10, epsilon=eps, epsilon_rel=eps, past=0, max_iterations=cap))
         niter, fx = s.minimize(f, x, np.full(n, -50.0), np.full(n, 50.0))

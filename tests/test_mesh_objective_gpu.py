@@ -34,11 +34,14 @@ PACK = {O.F64: 2, O.F32: 4}  # W: the nodes a thread owns (the values of a 16-by
 def _node_counts(dtype, K, D, full):
     W = PACK[dtype]
     tile = 256 * MR.TRIAL_U[D]  # node packs
+    # K < W at f32 for K = 2 and 3: no whole group of nodes (at f64 W = 2 <= K: there is no smaller mesh); 64 W + 1 has exactly
+    # one node past the last group; tile W + 1 is one node past one trial tile
     if not full:
-        return [K, 64 * W + 1, tile * W + 3]
+        return [K, 64 * W + 1, tile * W + 1, tile * W + 3]
     # around a wave, a block and one and two trial tiles, with and without tail nodes; about five tiles: several blocks, and
     # both tile orders cross tile borders
-    return [K, K + 1, 64 * W - 1, 64 * W + 1, 256 * W + W + 1, tile * W + 3, 2 * tile * W + W + 1, 5 * tile * W + W + 1]
+    return [K, K + 1, 64 * W - 1, 64 * W + 1, 256 * W + W + 1, tile * W + 1, tile * W + 3, 2 * tile * W + W + 1,
+            5 * tile * W + W + 1]
 
 
 def _shapes():
@@ -503,10 +506,16 @@ def test_mesh_solve_issues_the_launches_per_iteration_of_a_graph_solve(A):
             c0 = _counters(core)
             niter, fx = s.minimize(f, x)
             c1 = _counters(core)
-            out[name, iters] = (niter, s.last.nfev, fx, c1[0] - c0[0])
+            out[name, iters] = (niter, s.last.nfev, fx, c1[0] - c0[0], c1[3] - c0[3])
     print(out)
     for iters in (10, 20):
         assert out["mesh", iters][:3] == out["graph", iters][:3] and out["mesh", iters][0] == iters
+        # the byte model (launch_args.hpp): a trial launch reads xp and d, writes x and grad and reads the one data array; a
+        # mesh's adds the N + 1 offsets, the K E entries of 4 K bytes and (K - 1) D gathered values of xp and of d per entry
+        # -- at K = 2, D = 1 what the graph's adds.  Every evaluation but the first is a trial launch
+        trials, E, K, D = out["mesh", iters][1] - 1, n - 1, 2, 1
+        assert out["mesh", iters][4] == trials * (n * 8 * 5 + (n // D + 1) * 4 + K * E * 4 * K + K * E * (K - 1) * D * 8 * 2)
+        assert out["mesh", iters][4] == out["graph", iters][4]
     assert out["mesh", 20][3] - out["mesh", 10][3] == out["graph", 20][3] - out["graph", 10][3] > 0
     assert out["mesh", 10][3] == out["graph", 10][3]  # the bind's launches too
 
