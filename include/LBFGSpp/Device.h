@@ -132,7 +132,8 @@ protected:
     {
         std::vector<char> log(16384, '\0');
         const int dt = detail::dtype_of<Scalar>::value;
-        const int rc = (form == LBFGSX_FORM_LINEAR)  ? lbfgsx_objective_compile_linear(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
+        const int rc = (form == LBFGSX_FORM_LINEAR_MULTI) ? lbfgsx_objective_compile_linear_multi(&m_h, dt, D, node.c_str(), body.c_str(), log.data(), log.size())
+                       : (form == LBFGSX_FORM_LINEAR)  ? lbfgsx_objective_compile_linear(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_MESH)  ? lbfgsx_objective_compile_mesh(&m_h, dt, K, D, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRAPH) ? lbfgsx_objective_compile_graph(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRID)  ? lbfgsx_objective_compile_grid(&m_h, dt, body.c_str(), log.data(), log.size())
@@ -362,16 +363,45 @@ public:
     }
 };
 
+// A linear model with D outputs per sample: x holds an F x D weight matrix, feature-major (x[j*D + c], n = F*D), A is a sparse
+// R x F CSR matrix, Z = A X and f(x) = sum over coordinates i of psi(x[i]; i) + sum over rows r of phi(Z[r, 0..D); r)
+// (include/lbfgsx.h, "multi-output linear-model objectives"): softmax regression, multi-class SVMs, multi-target least
+// squares.  D = 1 .. 16.  The row body sees T, D, const T z[D], T dz[D] (to fill), int64_t r, p0..p3 and c[8] and returns phi;
+// the coordinate body (optional) is a LinearObjective's, per coordinate i = j*D + c.
+//     MultiLinearObjective<double> f(3, "T s = T(0);\n#pragma unroll\nfor (int c = 0; c < D; c++) { dz[c] = z[c] - p0[r * D + c];"
+//                                       " s = s + dz[c] * dz[c]; } return T(0.5) * s;");
+//     f.matrix(R, nnz, rowptr, col, val).host_data(0, targets, R * 3);      solver.minimize(f, x, fx);
+// matrix(): a LinearObjective's, with col in [0, F); x.size() not a multiple of D throws std::invalid_argument.  Accepted
+// wherever a LinearObjective is, refused where it is.
+template <typename Scalar>
+class MultiLinearObjective : public TermObjective<Scalar>
+{
+public:
+    MultiLinearObjective(int D, const std::string& row_body, const std::string& coord_body = std::string())
+        : TermObjective<Scalar>(LBFGSX_FORM_LINEAR_MULTI, 1, row_body, "MultiLinearObjective: ", coord_body, D)
+    {
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile_linear_multi); it stays the caller's
+    explicit MultiLinearObjective(const lbfgsx_objective* compiled) : TermObjective<Scalar>(compiled) {}
+    MultiLinearObjective& matrix(std::int64_t R, std::int64_t nnz, const std::int32_t* rowptr, const std::int32_t* col,
+                                 const Scalar* val, bool on_device = false, int lanes = 0)
+    {
+        this->set_matrix(R, nnz, rowptr, col, val, on_device, lanes);
+        return *this;
+    }
+};
+
 namespace detail {
 // the objectives compiled at run time into the fused kernels: a TermObjective, a ChainObjective, a GridObjective, a
-// GraphObjective, a MeshObjective or a LinearObjective
+// GraphObjective, a MeshObjective, a LinearObjective or a MultiLinearObjective
 template <typename Scalar, typename Foo>
 struct is_compiled_objective
 {
     typedef typename std::decay<Foo>::type F;
     static constexpr bool value = std::is_same<F, TermObjective<Scalar> >::value || std::is_same<F, ChainObjective<Scalar> >::value ||
                                   std::is_same<F, GridObjective<Scalar> >::value || std::is_same<F, GraphObjective<Scalar> >::value ||
-                                  std::is_same<F, MeshObjective<Scalar> >::value || std::is_same<F, LinearObjective<Scalar> >::value;
+                                  std::is_same<F, MeshObjective<Scalar> >::value || std::is_same<F, LinearObjective<Scalar> >::value ||
+                                  std::is_same<F, MultiLinearObjective<Scalar> >::value;
 };
 }  // namespace detail
 

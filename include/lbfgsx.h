@@ -215,7 +215,8 @@ int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4]);
  * lbfgsx_solver_minimize_obj and the four evaluation entry points take it like a term objective's.  Binding to a context
  * with n < K is refused (any n >= K is accepted: n need not be a multiple of anything).  The compile log, the refusal of
  * asm and the line numbers are those of lbfgsx_objective_compile. */
-enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2, LBFGSX_FORM_GRAPH = 3, LBFGSX_FORM_MESH = 4, LBFGSX_FORM_LINEAR = 5 };
+enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2, LBFGSX_FORM_GRAPH = 3, LBFGSX_FORM_MESH = 4, LBFGSX_FORM_LINEAR = 5,
+       LBFGSX_FORM_LINEAR_MULTI = 6 };
 int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len);
 long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char* out, size_t len);
 int lbfgsx_objective_form(const lbfgsx_objective* obj);
@@ -402,7 +403,8 @@ int lbfgsx_objective_dim(const lbfgsx_objective* obj);
  * words), 2 nnz indices, 2 nnz values and the gathered values once each (nnz of x, or of xp and d in a trial, and nnz of w),
  * w and v written and read, the chunk partials written and read.
  * Not built: reusing z = A xp and A d across the trials of one line search (which would make every trial after the first
- * O(R)), dense A, column reordering, the lock-step batch, a bench.py leg.  Measurements: DESIGN.md section 1. */
+ * O(R)), dense A, column reordering, the lock-step batch, a bench.py leg.  (Several outputs per row are the next section's
+ * form.)  Measurements: DESIGN.md section 1. */
 int lbfgsx_objective_compile_linear(lbfgsx_objective** out, int dtype, const char* coord_body, const char* row_body, char* log,
                                     size_t log_len);
 long long lbfgsx_objective_source_linear(int dtype, const char* coord_body, const char* row_body, char* out, size_t len);
@@ -411,6 +413,43 @@ int lbfgsx_objective_bind_linear(lbfgsx_ctx* c, const lbfgsx_objective* obj, int
                                  const double cs[8], int* id);
 int lbfgsx_objective_linear_topology(lbfgsx_ctx* c, int64_t info[8], uint32_t* colptr, int32_t* trow, uint32_t* tpos,
                                      int32_t* long_col, uint32_t* long_chunk, uint32_t* chunk);
+/* ---- multi-output linear-model objectives: D outputs per row, phi(a_r . X) ---------------------------------------------------
+ * x holds an F x D WEIGHT MATRIX X, feature-major: x[j*D + c], n = F*D.  A is the caller's sparse R x F CSR matrix and
+ *     Z = A X  (R x D),      f(x) = sum over coordinates i of psi(x[i]; i)  +  sum over rows r of phi(Z[r, 0..D); r)
+ * -- multinomial (softmax) logistic regression, multi-class SVMs, multi-target least squares, non-negative matrix regression
+ * under L-BFGS-B.  D is a compile-time constant of the generated struct, 1 <= D <= 16 ("D = # is not supported: a row has
+ * D = 1 .. 16 outputs").
+ *   row_body   sees T, constexpr int D, const T z[D], T dz[D] (to fill with dphi/dz_c), int64_t r, p0..p3 and c[8]; it
+ *              returns phi.  Loops over D unroll fully with #pragma unroll;
+ *   coord_body (NULL or empty: none) is the scalar form's, per coordinate i = j*D + c: const T x[1], T g[1], int64_t i; D is
+ *              visible, so the body can recover j = i / D and c = i % D.
+ * Semantics (bit-exact numpy restatement: tests/multilinear_ref.py): Z[r, c] is the scalar form's row sum for each c on its
+ * own (lane l: s_l[c] = val[k]*x[col[k]*D + c] for its first entry, s_l[c] = s_l[c] + .. after it, +0 without one; then the
+ * halvings; L by the same rule from nnz / R, or `lanes`).  grad[j*D + c] is psi's g[0] if there is a coordinate body, then
+ * tval[q]*w[trow[q]*D + c], w[r*D + c] = dz[c], over column j's transposed entries in ascending q, started from the first
+ * contribution, +0 without any.  A column with more than C = 4096 entries is long, as in the scalar form: per chunk b and
+ * output c the partial part[b*D + c] is formed by the scalar form's 256-thread rule over w[trow[q]*D + c], and the owner adds
+ * a column's partials in ascending b.  f, roundings and the trial's gather of xp[i] + step*d[i]: the scalar form's.
+ * Kernels (csrc/linear_multi_kernels.cuh): the row pass k_linm_rows / k_linm_rows_trial (L lanes per row, D accumulators per
+ * lane, 16-byte loads of a feature's weight row when D*sizeof(T) is a multiple of 16, D cross-lane moves per halving, no LDS,
+ * no atomic), the column pass k_linm_eval, k_linm_trial, k_linm_b_eval, k_linm_b_dg_maxstep_trial (a thread owns one 16-byte
+ * pack of consecutive coordinates; coordinate i walks the list of feature i / D, so a pack may straddle two features), and
+ * k_lin_long_cols_multi, one block per (chunk, output), precompiled, the third launch only when the matrix has a long column.
+ * lbfgsx_objective_compile_linear_multi caches by (form, both bodies, dtype, D); the form is LBFGSX_FORM_LINEAR_MULTI,
+ * lbfgsx_objective_K returns 1 and lbfgsx_objective_dim D.  The handle is bound with lbfgsx_objective_bind_linear (and minimised
+ * with lbfgsx_solver_minimize_linear), which accept a handle of either linear form; for this one they refuse n % D != 0 with
+ * both values named, validate col against F = n / D, size w to R*D and the chunk partials to chunks*D, and
+ * lbfgsx_objective_linear_topology reports D in info[6] (0 for the scalar form) with colptr of F + 1 elements.  Every other
+ * bind call refuses the handle, as they refuse a scalar one; so do the Gram-space recursion, row shards and the lock-step batch.
+ * Byte model of one evaluation: the scalar form's with every count of gathered x, xp, d and w, of w written and read and of
+ * the chunk partials multiplied by D; offsets (R+1 and F+1 words), indices and matrix values are counted once.  The D
+ * coordinates of a feature read its entries again; those re-reads are cache hits and are not modelled.
+ * Not built: D > 16, reusing Z across a line search's trials, dense A, mixed per-row output counts, the lock-step batch, a
+ * bench.py leg.  Registers, measurements: DESIGN.md section 1. */
+int lbfgsx_objective_compile_linear_multi(lbfgsx_objective** out, int dtype, int D, const char* coord_body, const char* row_body,
+                                          char* log, size_t log_len);
+long long lbfgsx_objective_source_linear_multi(int dtype, int D, const char* coord_body, const char* row_body, char* out,
+                                               size_t len);
 /* Every entry point of this ABI makes the context's device current for its own duration and restores the caller's
  * afterwards.  Code that launches its OWN kernels on the context's vectors (a device functor, lbfgsx_vec) must run with
  * that device current too: lbfgsx_device tells which one it is, lbfgsx_device_push makes it current for the calling

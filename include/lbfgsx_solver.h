@@ -155,7 +155,9 @@ int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, 
  * weights, the R x n matrix is rowptr / col / val in CSR, host arrays or device arrays (matrix_on_device != 0); lanes as
  * for lbfgsx_objective_bind_linear.  counts[k]: the elements of p[k] where host_mask says it is a host array (n or R; NULL:
  * n for all).  A handle of another form is refused with LBFGSX_E_INVALID, as are the matrices lbfgsx_objective_bind_linear
- * refuses; lbfgsx_solver_minimize_obj refuses a linear-model handle (it carries no matrix). */
+ * refuses; lbfgsx_solver_minimize_obj refuses a linear-model handle (it carries no matrix).  A multi-output handle
+ * (lbfgsx_objective_compile_linear_multi, D outputs per row) is taken here too: x holds the F x D weight matrix, n = F*D, the
+ * matrix is R x F, and n not a multiple of D is refused with both values named before a device is needed. */
 int lbfgsx_solver_minimize_linear(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, int64_t nnz,
                                   const int32_t* rowptr, const int32_t* col, const void* val, int matrix_on_device, int lanes,
                                   const void* const p[4], int host_mask, const int64_t counts[4], const double c[8], void* x,

@@ -229,6 +229,8 @@ def load():
     # linear-model objectives: two bodies; the CSR matrix travels with the binding
     sig(core, "lbfgsx_objective_compile_linear", i32, C.POINTER(vp), i32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t)
     sig(core, "lbfgsx_objective_source_linear", C.c_longlong, i32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_compile_linear_multi", i32, C.POINTER(vp), i32, i32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_source_linear_multi", C.c_longlong, i32, i32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t)
     sig(core, "lbfgsx_objective_bind_linear", i32, vp, vp, i64, i64, vp, vp, vp, i32, i32, C.POINTER(vp * 4),
         C.POINTER(dbl * 8), C.POINTER(i32))
     sig(core, "lbfgsx_objective_linear_topology", i32, vp, C.POINTER(i64 * 8), u32p, i32p, u32p, i32p, u32p, u32p)

@@ -281,11 +281,13 @@ struct lbfgsx_ctx
     int mesh_K = 0, mesh_D = 0;
     // a linear-model objective's matrix (lbfgsx_objective_bind_linear, linear_topology.hip): the context's own copy of the
     // caller's CSR arrays, the transposed list built from them at every bind, the row pass's two output vectors and the
-    // chunk table of the long columns.  Freed with the other forms' list (graph_topology_free)
+    // chunk table of the long columns.  Freed with the other forms' list (graph_topology_free).  A multi-output linear-model
+    // objective's matrix lives here too: D > 0 is its outputs per row, the matrix then has n / D columns, w holds R*D
+    // elements and part nchunks*D (0: the scalar form, where the comments below hold as written)
     struct LinearTopo
     {
         int64_t R = 0, nnz = 0, nchunks = 0;
-        int L = 0, C = 0, nlong = 0;
+        int L = 0, C = 0, nlong = 0, D = 0;
         void *rowptr = nullptr, *col = nullptr, *val = nullptr;      // int32[R+1], int32[nnz], T[nnz]
         void *colptr = nullptr, *trow = nullptr, *tval = nullptr;    // uint32[n+1], int32[nnz], T[nnz]: sorted by column
         void* tpos = nullptr;                                        // uint32[nnz]: the CSR position of a transposed entry

@@ -17,7 +17,9 @@
 // a MESH objective (one term per element of K nodes with D unknowns each and an optional one per node), is a wrapper around
 // mesh_kernels.cuh with the list of mesh_topology.hip.  A sixth, a LINEAR-MODEL objective (one term per row of a sparse matrix
 // product and an optional one per coordinate), is a wrapper around linear_kernels.cuh with the matrix of linear_topology.hip;
-// it alone has two more kernels, the row passes, in slots 4 and 5.  A handle carries its form; the four slots of the
+// it has two more kernels, the row passes, in slots 4 and 5; so has the seventh, a MULTI-OUTPUT LINEAR-MODEL objective (D
+// outputs per row, x an F x D matrix), a wrapper around linear_multi_kernels.cuh over the same matrix and the same argument
+// struct, bound by the same call.  A handle carries its form; the four slots of the
 // loaded-kernel table and everything that launches them are the same.  What the forms differ in -- names, kernel names, struct
 // members, the bodies' signatures, the K and D accepted, the cache key -- is one row each of kForms below; the generator, the
 // validation and the refusals are written once and read it.
@@ -63,12 +65,20 @@ struct FormDesc
     const char *k_refusal, *d_refusal;        // '#' stands for the value refused; null: the entry point fixes the value
     bool key_second, key_d;                   // do the second body and D enter the cache key
     const char* bound_with;                   // what lbfgsx_objective_bind says the form is bound with; null: it binds it
+    const char* bind_suffix;                  // of the call that binds it, where that is another form's; null: suffix
 };
 #define TERM_SIGNATURE "T term(const T (&x)[K], T (&g)[K], int64_t i) const"
 #define POINT_SIGNATURE(name) "T " name "(const T (&x)[1], T (&g)[1], int64_t i) const"
 #define POINT_ABSENT "        g[0] = T(0);\n        return T(0);\n"
+// the members of both linear-model forms (launch_args.hpp: LinearArgs)
+#define LINEAR_MEMBERS                                                                             \
+    "    const int32_t* rowptr;\n    const int32_t* col;\n    const T* val;\n"                      \
+    "    const uint32_t* colptr;\n    const int32_t* trow;\n    const T* tval;\n"                   \
+    "    T* w;\n    T* v;\n"                                                                       \
+    "    const T* part;\n    const int32_t* long_col;\n    const uint32_t* long_chunk;\n"           \
+    "    int64_t R, nnz;\n    int32_t L, C, nlong, pad_;\n"
 const BodyDesc kNoBody = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-const FormDesc kForms[6] = {
+const FormDesc kForms[7] = {
     {"term objective", "", "ObjTerm", "#include \"lbfgs_kernels.cuh\"\n#include \"lbfgsb_kernels.cuh\"\n",
      {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial", nullptr, nullptr, "k_trial_post"}, "", kNoBody,
      {"    // one term: x[0..K) in, g[0..K) out, the term's value returned\n", TERM_SIGNATURE, "objective_body", "body", nullptr,
@@ -138,16 +148,22 @@ const FormDesc kForms[6] = {
      "D = # is not supported: a node has D = 1, 2 or 3 unknowns", true, true, "elements"},
     {"linear-model objective", "_linear", "ObjLinear", "#include \"linear_kernels.cuh\"\n",
      {"k_lin_eval", "k_lin_trial", "k_lin_b_eval", "k_lin_b_dg_maxstep_trial", "k_lin_rows", "k_lin_rows_trial"},
-     "    const int32_t* rowptr;\n    const int32_t* col;\n    const T* val;\n"
-     "    const uint32_t* colptr;\n    const int32_t* trow;\n    const T* tval;\n"
-     "    T* w;\n    T* v;\n"
-     "    const T* part;\n    const int32_t* long_col;\n    const uint32_t* long_chunk;\n"
-     "    int64_t R, nnz;\n    int32_t L, C, nlong, pad_;\n",
+     LINEAR_MEMBERS,
      {"    // the term of coordinate i: x[0] = x[i] in, its derivative g[0] out, its value returned\n", POINT_SIGNATURE("coord"),
       "coord_body", "coordinate body", POINT_ABSENT, "kCoord"},
      {"    // the term of row r: z = the row's product with x in, its derivative dz out, its value returned\n",
       "T row(const T z, T& dz, int64_t r) const", "row_body", "row body", nullptr, nullptr},
-     "", 1, 1, 1, 1, nullptr, nullptr, true, false, "matrix"}};
+     "", 1, 1, 1, 1, nullptr, nullptr, true, false, "matrix"},
+    {"multi-output linear-model objective", "_linear_multi", "ObjLinearMulti", "#include \"linear_multi_kernels.cuh\"\n",
+     {"k_linm_eval", "k_linm_trial", "k_linm_b_eval", "k_linm_b_dg_maxstep_trial", "k_linm_rows", "k_linm_rows_trial"},
+     LINEAR_MEMBERS,
+     {"    // the term of coordinate i = j*D + c: x[0] = x[i] in, its derivative g[0] out, its value returned\n", POINT_SIGNATURE("coord"),
+      "coord_body", "coordinate body", POINT_ABSENT, "kCoord"},
+     {"    // the term of row r: z[c] = the row's product with column c of the F x D matrix x in, its D partial derivatives dz out,\n"
+      "    // its value returned\n",
+      "T row(const T (&z)[D], T (&dz)[D], int64_t r) const", "row_body", "row body", nullptr, nullptr},
+     "", 1, 1, 1, 16, nullptr, "D = # is not supported: a row has D = 1 .. 16 outputs", true, true, "matrix", "_linear"}};
+#undef LINEAR_MEMBERS
 #undef TERM_SIGNATURE
 #undef POINT_SIGNATURE
 #undef POINT_ABSENT
@@ -645,6 +661,11 @@ long long lbfgsx_objective_source_linear(int dtype, const char* coord_body, cons
 {
     return objective_source(LBFGSX_FORM_LINEAR, dtype, 1, row_body, out, len, coord_body);
 }
+long long lbfgsx_objective_source_linear_multi(int dtype, int D, const char* coord_body, const char* row_body, char* out,
+                                               size_t len)
+{
+    return objective_source(LBFGSX_FORM_LINEAR_MULTI, dtype, 1, row_body, out, len, coord_body, D);
+}
 
 int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
 {
@@ -672,6 +693,11 @@ int lbfgsx_objective_compile_linear(lbfgsx_objective** out, int dtype, const cha
                                     size_t log_len)
 {
     return objective_compile(LBFGSX_FORM_LINEAR, out, dtype, 1, row_body, log, log_len, coord_body);
+}
+int lbfgsx_objective_compile_linear_multi(lbfgsx_objective** out, int dtype, int D, const char* coord_body, const char* row_body,
+                                          char* log, size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_LINEAR_MULTI, out, dtype, 1, row_body, log, log_len, coord_body, D);
 }
 
 void lbfgsx_objective_destroy(lbfgsx_objective* obj) { delete obj; }
@@ -805,7 +831,7 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
         for (int k = 0; k < lbfgsx::JIT_NSLOTS; k++)
             c->term_fn[k] = it->second.fn[k];
     }
-    if (code->form != LBFGSX_FORM_GRAPH && code->form != LBFGSX_FORM_MESH && code->form != LBFGSX_FORM_LINEAR &&
+    if (code->form != LBFGSX_FORM_GRAPH && code->form != LBFGSX_FORM_MESH && !lbfgsx::form_is_linear(code->form) &&
         (c->graph_inc || c->lin.colptr))
     {
         (void) lbfgsx::stream_sync(c->stream);  // no launch still walks the list
@@ -881,7 +907,8 @@ int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void
     if (obj && kForms[obj->code->form].bound_with)
     {
         const FormDesc& f = kForms[obj->code->form];
-        lbfgsx::set_error(std::string("a ") + f.name + " is bound with its " + f.bound_with + ": lbfgsx_objective_bind" + f.suffix);
+        lbfgsx::set_error(std::string("a ") + f.name + " is bound with its " + f.bound_with + ": lbfgsx_objective_bind" +
+                          (f.bind_suffix ? f.bind_suffix : f.suffix));
         return LBFGSX_E_INVALID;
     }
     return objective_bind(c, obj, 0, 0, p, cs, id);
@@ -1022,8 +1049,12 @@ int lbfgsx_objective_bind_linear(lbfgsx_ctx* c, const lbfgsx_objective* obj, int
 {
     if (!c || !obj)
         return LBFGSX_E_INVALID;
-    if (const int rc = bind_begin(c, obj, LBFGSX_FORM_LINEAR))
+    // either linear form: a multi-output handle has D = its outputs per row and a matrix of F = n / D columns
+    const bool multi = obj->code->form == LBFGSX_FORM_LINEAR_MULTI;
+    if (const int rc = bind_begin(c, obj, multi ? LBFGSX_FORM_LINEAR_MULTI : LBFGSX_FORM_LINEAR))
         return rc;
+    const int D = multi ? obj->code->D : 1;
+    const std::string name = std::string(kForms[obj->code->form].name) + ": ";
     const int64_t lim = 2147483647;
     std::string why;
     if (R < 1 || nnz < 1 || !rowptr || !col || !val)
@@ -1037,14 +1068,17 @@ int lbfgsx_objective_bind_linear(lbfgsx_ctx* c, const lbfgsx_objective* obj, int
         why = "n = " + std::to_string(c->n) + " exceeds 2^31 - 1 = " + std::to_string(lim) + ": column indices are int32";
     else if (lanes < 0 || lanes > 64 || (lanes & (lanes - 1)) != 0)
         why = "lanes = " + std::to_string(lanes) + ": the lanes that share a row are 0 (by the rule) or a power of two in 1..64";
+    else if (c->n % D != 0)
+        why = "n = " + std::to_string(c->n) + " is not a multiple of D = " + std::to_string(D) +
+              ": x holds the D weights of each feature";
     if (!why.empty())
     {
-        lbfgsx::set_error("linear-model objective: " + why);
+        lbfgsx::set_error(name + why);
         return LBFGSX_E_INVALID;
     }
     {
         lbfgsx::DeviceGuard dev_guard_(c->device);
-        const int rc = lbfgsx::linear_topology_build(c, R, nnz, rowptr, col, val, matrix_on_device, lanes);
+        const int rc = lbfgsx::linear_topology_build(c, R, nnz, rowptr, col, val, matrix_on_device, lanes, multi ? D : 0);
         if (rc)
             return rc;
     }
@@ -1054,14 +1088,14 @@ int lbfgsx_objective_bind_linear(lbfgsx_ctx* c, const lbfgsx_objective* obj, int
 int lbfgsx_objective_linear_topology(lbfgsx_ctx* c, int64_t info[8], uint32_t* colptr, int32_t* trow, uint32_t* tpos,
                                      int32_t* long_col, uint32_t* long_chunk, uint32_t* chunk)
 {
-    if (!c || !c->term || c->term_form != LBFGSX_FORM_LINEAR || !c->lin.colptr)
+    if (!c || !c->term || !lbfgsx::form_is_linear(c->term_form) || !c->lin.colptr)
     {
         lbfgsx::set_error("lbfgsx_objective_linear_topology: no linear-model objective is bound to this context");
         return LBFGSX_E_INVALID;
     }
     if (info)
     {
-        const int64_t v[8] = {c->lin.R, c->lin.nnz, c->lin.L, c->lin.C, c->lin.nlong, c->lin.nchunks, 0, 0};
+        const int64_t v[8] = {c->lin.R, c->lin.nnz, c->lin.L, c->lin.C, c->lin.nlong, c->lin.nchunks, c->lin.D, 0};
         for (int k = 0; k < 8; k++)
             info[k] = v[k];
     }

@@ -186,8 +186,10 @@ inline LinearArgs<T> linear_args(const lbfgsx_ctx* c, const TermArgs<T>& t)
             l.nlong,
             0};
 }
+// the two forms that bind a CSR matrix: a linear-model objective and a multi-output one
+inline bool form_is_linear(int form) { return form == LBFGSX_FORM_LINEAR || form == LBFGSX_FORM_LINEAR_MULTI; }
 // the objective argument of the bound handle's kernels, by its form: &term for a term or chain objective, &grid for a grid
-// one, &graph for a graph one, &mesh for a mesh one, &linear for a linear-model one
+// one, &graph for a graph one, &mesh for a mesh one, &linear for a linear-model one of either form
 template <class T>
 struct BoundArgs
 {
@@ -208,7 +210,7 @@ struct BoundArgs
         ptr = (c->term_form == LBFGSX_FORM_GRID)    ? static_cast<void*>(&grid)
               : (c->term_form == LBFGSX_FORM_GRAPH) ? static_cast<void*>(&graph)
               : (c->term_form == LBFGSX_FORM_MESH)  ? static_cast<void*>(&mesh)
-              : (c->term_form == LBFGSX_FORM_LINEAR) ? static_cast<void*>(&linear)
+              : form_is_linear(c->term_form)        ? static_cast<void*>(&linear)
                                                     : static_cast<void*>(&term);
     }
     BoundArgs(const BoundArgs&) = delete;
@@ -220,6 +222,9 @@ struct BoundArgs
 //   linear  one evaluation (row pass, long-column launch, column pass): the offsets (rowptr, colptr), the indices (col, trow)
 //           and the values (val, tval) of both passes, every gathered value once (the row pass gathers vectors_gathered
 //           vectors, the column pass gathers w), w and v written and read, the chunk partials written and read
+//   multi-output linear  the same with every gathered value of x, xp, d and w, w written and read and the chunk partials
+//           counted D times (F + 1 column offsets); offsets, indices and matrix values once: the D coordinates of a feature
+//           read the same entries again, which are cache hits and are not modelled
 // A trial launch adds it at its call site; an evaluation adds only a linear-model objective's, in linear_pre_eval.
 template <class T>
 inline void objective_model_add(const lbfgsx_ctx* c, int vectors_gathered)
@@ -232,11 +237,11 @@ inline void objective_model_add(const lbfgsx_ctx* c, int vectors_gathered)
         const double K = c->mesh_K, D = c->mesh_D, KE = K * double(c->graph_E);
         model_add(double(c->n / c->mesh_D + 1) * 4 + KE * 4 * K + KE * (K - 1) * D * esz * vg);
     }
-    else if (c->term_form == LBFGSX_FORM_LINEAR)
+    else if (form_is_linear(c->term_form))
     {
-        const double R = double(c->lin.R), nnz = double(c->lin.nnz);
-        model_add((R + 1) * 4 + double(c->n + 1) * 4 + 2 * nnz * 4 + 2 * nnz * esz + nnz * esz * (vg + 1) + 4 * R * esz +
-                  2 * double(c->lin.nchunks) * esz);
+        const double R = double(c->lin.R), nnz = double(c->lin.nnz), D = c->lin.D ? c->lin.D : 1;
+        model_add((R + 1) * 4 + (double(c->n) / D + 1) * 4 + 2 * nnz * 4 + 2 * nnz * esz + nnz * esz * (vg + 1) * D +
+                  2 * R * esz * D + 2 * R * esz + 2 * double(c->lin.nchunks) * esz * D);
     }
 }
 // graph_topology.hip: the incidence list of the context (ctx.hpp: graph_off, graph_inc, graph_E).  build validates the
@@ -251,11 +256,12 @@ int mesh_topology_read(lbfgsx_ctx* c, uint32_t* off, uint32_t* words);
 // linear_topology.hip: the matrix of a linear-model objective (ctx.hpp: lin).  build validates the caller's CSR arrays
 // first and leaves the context without a matrix when one offends (LBFGSX_E_INVALID, the position named); lanes: 0 = by the
 // rule (linear_lanes_rule), otherwise the lanes per row.  long_launch: the launch between the two passes, none when the
-// matrix has no long column
+// matrix has no long column.  D: the outputs per row of a multi-output objective (the matrix then has n / D columns), 0 for
+// the scalar form
 constexpr int kLinearChunk = 4096;  // C: a column with more entries is long and is summed in chunks of C by k_lin_long_cols
 int linear_lanes_rule(int64_t R, int64_t nnz);
 int linear_topology_build(lbfgsx_ctx* c, int64_t R, int64_t nnz, const int32_t* rowptr, const int32_t* col, const void* val,
-                          int on_device, int lanes);
+                          int on_device, int lanes, int D = 0);
 int linear_topology_read(lbfgsx_ctx* c, uint32_t* colptr, int32_t* trow, uint32_t* tpos, int32_t* long_col, uint32_t* long_chunk,
                          uint32_t* chunk);
 void linear_topology_free(lbfgsx_ctx* c);
@@ -276,7 +282,7 @@ inline int linear_rows_grid(const lbfgsx_ctx* c)
 // the column pass strides over v[R] as well as over the n coordinates: its grid covers the longer of the two
 inline int linear_col_grid(const lbfgsx_ctx* c, int grid)
 {
-    if (c->term_form != LBFGSX_FORM_LINEAR)
+    if (!form_is_linear(c->term_form))
         return grid;
     const int gr = c->grid_for(c->lin.R);
     return gr > grid ? gr : grid;
@@ -284,7 +290,7 @@ inline int linear_col_grid(const lbfgsx_ctx* c, int grid)
 template <class T>
 inline int linear_pre_eval(lbfgsx_ctx* c, BoundArgs<T>& obj, const T* x)
 {
-    if (c->term_form != LBFGSX_FORM_LINEAR)
+    if (!form_is_linear(c->term_form))
         return LBFGSX_OK;
     objective_model_add<T>(c, 1);
     void* params[] = {&x, obj.ptr};
@@ -294,7 +300,7 @@ inline int linear_pre_eval(lbfgsx_ctx* c, BoundArgs<T>& obj, const T* x)
 template <class T>
 inline int linear_pre_trial(lbfgsx_ctx* c, BoundArgs<T>& obj, const T* xp, const T* d, T step)
 {
-    if (c->term_form != LBFGSX_FORM_LINEAR)
+    if (!form_is_linear(c->term_form))
         return LBFGSX_OK;
     void* params[] = {&xp, &d, &step, obj.ptr};
     const int rc = jit_launch(c, JIT_K_LIN_ROWS_TRIAL, linear_rows_grid(c), params);

@@ -1,6 +1,7 @@
 // lbfgspp_amd/csrc/linear_topology.hip -- the matrix of a linear-model objective, prepared on the device at bind
 // (include/lbfgsx.h, "linear-model objectives"; walked by linear_kernels.cuh), and the one kernel of the form that holds no
-// caller text, k_lin_long_cols.
+// caller text, k_lin_long_cols.  A multi-output objective (linear_multi_kernels.cuh) has the same build over the F = n / D
+// columns of its matrix (n below is then F), w of R*D elements, D partials per chunk and k_lin_long_cols_multi.
 //
 //   1. the caller's rowptr[R+1], col[nnz], val[nnz] (host or device) are copied into arrays the context owns;
 //   2. k_lin_validate, the only launch of a refused bind, reduces the count of offending positions and the smallest one:
@@ -168,6 +169,35 @@ __global__ void __launch_bounds__(kBlock) k_lin_long_cols(const uint32_t* __rest
         part[blockIdx.x] = sh[0];
 }
 
+// The same per output c of a multi-output objective: one block per (chunk b, output c), blockIdx.x = b*D + c, over
+// w[trow[q]*D + c], into part[b*D + c].
+template <class T>
+__global__ void __launch_bounds__(kBlock) k_lin_long_cols_multi(const uint32_t* __restrict__ chunk,
+                                                                const int32_t* __restrict__ trow, const T* __restrict__ tval,
+                                                                const T* __restrict__ w, T* __restrict__ part, int D)
+{
+    __shared__ T sh[kBlock];
+    const unsigned b = blockIdx.x / unsigned(D), c = blockIdx.x % unsigned(D);
+    const uint32_t beg = chunk[2 * b], end = chunk[2 * b + 1];
+    T s = T(0);
+    bool has = false;
+    for (int64_t q = int64_t(beg) + threadIdx.x; q < int64_t(end); q += kBlock)
+    {
+        const T prod = tval[q] * w[int64_t(trow[q]) * D + c];
+        s = has ? s + prod : prod;
+        has = true;
+    }
+    sh[threadIdx.x] = s;
+    for (int h = kBlock / 2; h >= 1; h >>= 1)
+    {
+        __syncthreads();
+        if (int(threadIdx.x) < h)
+            sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + h];
+    }
+    if (threadIdx.x == 0)
+        part[blockIdx.x] = sh[0];
+}
+
 // device buffers of one build, freed when it ends
 struct Temps
 {
@@ -196,10 +226,12 @@ int grid_of(int64_t items)
 hipError_t own(void** out, size_t bytes) { return hipMalloc(out, bytes ? bytes : 1); }
 
 int build(lbfgsx_ctx* c, int64_t R, int64_t nnz, const int32_t* rowptr, const int32_t* col, const void* val, int on_device,
-          int lanes)
+          int lanes, int D)
 {
     lbfgsx_ctx::LinearTopo& l = c->lin;
-    const int64_t n = c->n;
+    const int64_t n = D ? c->n / D : c->n;  // the matrix's columns
+    const size_t Dw = size_t(D ? D : 1);    // the elements of w per row and of part per chunk
+    const std::string name = D ? "multi-output linear-model objective: " : "linear-model objective: ";
     const size_t esz = size_t(c->esz);
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     Temps t;
@@ -230,16 +262,20 @@ int build(lbfgsx_ctx* c, int64_t R, int64_t nnz, const int32_t* rowptr, const in
         if (p <= R)
             what = "rowptr[" + std::to_string(p) + "] = " + std::to_string(v) + " with R = " + std::to_string(R) + ", nnz = " +
                    std::to_string(nnz) + ": rowptr starts at 0, does not decrease and ends at nnz";
+        else if (D)
+            what = "col[" + std::to_string(p - R - 1) + "] = " + std::to_string(v) + " with F = n / D = " + std::to_string(c->n) +
+                   " / " + std::to_string(D) + " = " + std::to_string(n) + ": a column index lies in [0, F)";
         else
             what = "col[" + std::to_string(p - R - 1) + "] = " + std::to_string(v) + " with n = " + std::to_string(n) +
                    ": a column index lies in [0, n)";
-        set_error("linear-model objective: " + what + "; " + std::to_string(got[0]) + " of the " + std::to_string(R + 1 + nnz) +
+        set_error(name + what + "; " + std::to_string(got[0]) + " of the " + std::to_string(R + 1 + nnz) +
                   " positions of rowptr and col offend, this is the first");
         return LBFGSX_E_INVALID;
     }
     l.R = R;
     l.nnz = nnz;
     l.C = kLinearChunk;
+    l.D = D;
     l.L = lanes ? lanes : linear_lanes_rule(R, nnz);
     // the transposed list
     uint32_t *kin = nullptr, *kout = nullptr, *vin = nullptr;
@@ -250,7 +286,7 @@ int build(lbfgsx_ctx* c, int64_t R, int64_t nnz, const int32_t* rowptr, const in
     LBFGSX_HIP(own(&l.colptr, size_t(n + 1) * 4));
     LBFGSX_HIP(own(&l.trow, size_t(nnz) * 4));
     LBFGSX_HIP(own(&l.tval, size_t(nnz) * esz));
-    LBFGSX_HIP(own(&l.w, size_t(R) * esz));
+    LBFGSX_HIP(own(&l.w, size_t(R) * Dw * esz));
     LBFGSX_HIP(own(&l.v, size_t(R) * esz));
     uint32_t* tpos = static_cast<uint32_t*>(l.tpos);
     uint32_t* colptr = static_cast<uint32_t*>(l.colptr);
@@ -284,7 +320,7 @@ int build(lbfgsx_ctx* c, int64_t R, int64_t nnz, const int32_t* rowptr, const in
     LBFGSX_HIP(stream_sync(c->stream));
     if (nlong > cap)
     {
-        set_error("linear-model objective: more long columns than nnz / (C + 1) allows: the list is inconsistent");
+        set_error(name + "more long columns than nnz / (C + 1) allows: the list is inconsistent");
         return LBFGSX_E_LOGIC;
     }
     l.nlong = int(nlong);
@@ -316,7 +352,7 @@ int build(lbfgsx_ctx* c, int64_t R, int64_t nnz, const int32_t* rowptr, const in
         LBFGSX_HIP(own(&l.long_col, lcol.size() * 4));
         LBFGSX_HIP(own(&l.long_chunk, lchunk.size() * 4));
         LBFGSX_HIP(own(&l.chunk, chunk.size() * 4));
-        LBFGSX_HIP(own(&l.part, size_t(l.nchunks) * esz));
+        LBFGSX_HIP(own(&l.part, size_t(l.nchunks) * Dw * esz));
         LBFGSX_HIP(copy_async(l.long_col, lcol.data(), lcol.size() * 4, hipMemcpyHostToDevice, c->stream));
         LBFGSX_HIP(copy_async(l.long_chunk, lchunk.data(), lchunk.size() * 4, hipMemcpyHostToDevice, c->stream));
         LBFGSX_HIP(copy_async(l.chunk, chunk.data(), chunk.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -349,11 +385,11 @@ void linear_topology_free(lbfgsx_ctx* c)
 }
 
 int linear_topology_build(lbfgsx_ctx* c, int64_t R, int64_t nnz, const int32_t* rowptr, const int32_t* col, const void* val,
-                          int on_device, int lanes)
+                          int on_device, int lanes, int D)
 {
     LBFGSX_HIP(stream_sync(c->stream));  // no launch of an earlier binding still walks the list this call frees
     graph_topology_free(c);
-    const int rc = build(c, R, nnz, rowptr, col, val, on_device, lanes);
+    const int rc = build(c, R, nnz, rowptr, col, val, on_device, lanes, D);
     if (rc)
     {
         (void) stream_sync(c->stream);
@@ -367,7 +403,7 @@ int linear_topology_read(lbfgsx_ctx* c, uint32_t* colptr, int32_t* trow, uint32_
 {
     const lbfgsx_ctx::LinearTopo& l = c->lin;
     if (colptr)
-        LBFGSX_HIP(copy_async(colptr, l.colptr, size_t(c->n + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+        LBFGSX_HIP(copy_async(colptr, l.colptr, size_t((l.D ? c->n / l.D : c->n) + 1) * 4, hipMemcpyDeviceToHost, c->stream));
     if (trow)
         LBFGSX_HIP(copy_async(trow, l.trow, size_t(l.nnz) * 4, hipMemcpyDeviceToHost, c->stream));
     if (tpos)
@@ -392,6 +428,17 @@ int linear_long_launch(lbfgsx_ctx* c)
         return LBFGSX_OK;
     const uint32_t* chunk = static_cast<const uint32_t*>(l.chunk);
     const int32_t* trow = static_cast<const int32_t*>(l.trow);
+    if (l.D)
+    {
+        const unsigned blocks = unsigned(l.nchunks) * unsigned(l.D);
+        if (c->dtype == LBFGSX_F64)
+            LBFGSX_LAUNCH((k_lin_long_cols_multi<double>), dim3(blocks), dim3(kBlock), 0, c->stream, chunk, trow,
+                          static_cast<const double*>(l.tval), static_cast<const double*>(l.w), static_cast<double*>(l.part), l.D);
+        else
+            LBFGSX_LAUNCH((k_lin_long_cols_multi<float>), dim3(blocks), dim3(kBlock), 0, c->stream, chunk, trow,
+                          static_cast<const float*>(l.tval), static_cast<const float*>(l.w), static_cast<float*>(l.part), l.D);
+        return LBFGSX_OK;
+    }
     if (c->dtype == LBFGSX_F64)
         LBFGSX_LAUNCH((k_lin_long_cols<double>), dim3(unsigned(l.nchunks)), dim3(kBlock), 0, c->stream, chunk, trow,
                       static_cast<const double*>(l.tval), static_cast<const double*>(l.w), static_cast<double*>(l.part));

@@ -1,5 +1,6 @@
 // lbfgspp_amd/csrc/own_frame.cuh -- the frame of the owner-computes gather kernels: the four evaluation kernels of a GRAPH,
-// a MESH and a LINEAR-MODEL objective (graph_kernels.cuh, mesh_kernels.cuh, the column pass of linear_kernels.cuh) are
+// a MESH and a LINEAR-MODEL objective (graph_kernels.cuh, mesh_kernels.cuh, the column pass of linear_kernels.cuh and of
+// linear_multi_kernels.cuh) are
 // own_eval and own_trial, bounded or not, around the family's walk of one node's list.
 //
 // Ownership.  x holds D unknowns per node, node-major.  A thread owns W = 16 / sizeof(T) consecutive nodes: exactly D whole
@@ -12,6 +13,9 @@
 //     static constexpr int D = unknowns per node;  U = the tile depth of the two trial kernels
 //     int64_t nodes(const OBJ&, int64_t n)                      the nodes of a problem of n unknowns
 //     const uint32_t* off(const OBJ&)                           the offsets of the nodes' lists, nodes + 1 of them
+//     or  static constexpr bool kRange = true;  void range(obj, v, lo, hi)   a family whose nodes share lists (the multi-output
+//                                                               linear model: D coordinates walk one feature's list): node
+//                                                               v's entries [lo, hi), in place of off[v] and off[v + 1]
 //     void node<T>(obj, v, xv[D], lo, hi, ld, fx, gv[D])        node v with values xv and entries [lo, hi): its D partial
 //                                                               derivatives to gv, what it owns of f to fx; ld(i) = x[i]
 //     void extra<T>(obj, fx)                                    what else the launch adds to f, after the tail
@@ -21,21 +25,49 @@
 
 namespace lbfgsx {
 
-// the W + 1 offsets of the node group at b = vi*W (off has nodes + 1 elements, b + W <= nodes)
-template <int W>
-__device__ __forceinline__ void own_offsets(const uint32_t* __restrict__ off, int64_t b, uint32_t (&o)[W + 1])
+// does family F give a node's (lo, hi) itself (F::kRange); the default is the load from F::off
+template <class F, class = void>
+struct OwnRange
 {
+    static constexpr bool value = false;
+};
+template <class F>
+struct OwnRange<F, decltype(void(F::kRange))>
+{
+    static constexpr bool value = F::kRange;
+};
+// the offsets a thread holds for its W nodes: W + 1 consecutive ones, or a (lo, hi) pair per node
+template <class F, int W>
+constexpr int own_noff = OwnRange<F>::value ? 2 * W : W + 1;
+
+// the offsets of the node group at b = vi*W (off has nodes + 1 elements, b + W <= nodes): node k's entries are
+// [o[k], o[k + 1]), or [o[2k], o[2k + 1]) from F::range
+template <class F, int W, class OBJ>
+__device__ __forceinline__ void own_offsets(const OBJ& obj, int64_t b, uint32_t (&o)[own_noff<F, W>])
+{
+    if constexpr (OwnRange<F>::value)
+    {
 #pragma unroll
-    for (int k = 0; k <= W; k++)
-        o[k] = off[b + k];
+        for (int k = 0; k < W; k++)
+            F::range(obj, b + k, o[2 * k], o[2 * k + 1]);
+    }
+    else
+    {
+        const uint32_t* __restrict__ off = F::off(obj);
+#pragma unroll
+        for (int k = 0; k <= W; k++)
+            o[k] = off[b + k];
+    }
 }
 
 // the W nodes of group vi: their values from the D packs px, their gradients into the D packs pg
 template <class T, class F, class OBJ, class LD, class A>
 __device__ __forceinline__ void own_group_nodes(const OBJ& obj, int64_t vi, const Pack<T> (&px)[F::D],
-                                                const uint32_t (&o)[Vec16<T>::W + 1], LD ld, A& fx, Pack<T> (&pg)[F::D])
+                                                const uint32_t (&o)[own_noff<F, Vec16<T>::W>], LD ld, A& fx,
+                                                Pack<T> (&pg)[F::D])
 {
     constexpr int W = Vec16<T>::W, D = F::D;
+    constexpr int S = OwnRange<F>::value ? 2 : 1;  // o's stride from one node to the next
 #pragma unroll
     for (int k = 0; k < W; k++)
     {
@@ -43,7 +75,7 @@ __device__ __forceinline__ void own_group_nodes(const OBJ& obj, int64_t vi, cons
 #pragma unroll
         for (int d = 0; d < D; d++)
             xv[d] = px[(k * D + d) / W].e[(k * D + d) % W];
-        F::template node<T>(obj, vi * W + k, xv, o[k], o[k + 1], ld, fx, gv);
+        F::template node<T>(obj, vi * W + k, xv, o[S * k], o[S * k + 1], ld, fx, gv);
 #pragma unroll
         for (int d = 0; d < D; d++)
             pg[(k * D + d) / W].e[(k * D + d) % W] = gv[d];
@@ -56,14 +88,22 @@ __device__ __forceinline__ void own_tail(const OBJ& obj, int64_t first, int64_t 
                                          XV value, DONE done)
 {
     constexpr int D = F::D;
-    const uint32_t* __restrict__ off = F::off(obj);
     for (int64_t v = first; v < nodes; v++)
     {
         T xv[D], gv[D];
 #pragma unroll
         for (int k = 0; k < D; k++)
             xv[k] = value(v * D + k);
-        F::template node<T>(obj, v, xv, off[v], off[v + 1], ld, fx, gv);
+        uint32_t lo, hi;
+        if constexpr (OwnRange<F>::value)
+            F::range(obj, v, lo, hi);
+        else
+        {
+            const uint32_t* __restrict__ off = F::off(obj);
+            lo = off[v];
+            hi = off[v + 1];
+        }
+        F::template node<T>(obj, v, xv, lo, hi, ld, fx, gv);
 #pragma unroll
         for (int k = 0; k < D; k++)
         {
@@ -109,8 +149,8 @@ __device__ __forceinline__ void own_eval(const T* __restrict__ x, T* __restrict_
                 pu[j] = ldv(ub, vi * D + j);
             }
         }
-        uint32_t o[W + 1];
-        own_offsets<W>(F::off(obj), vi * W, o);
+        uint32_t o[own_noff<F, W>];
+        own_offsets<F, W>(obj, vi * W, o);
         own_group_nodes<T, F>(obj, vi, px, o, ld, acc[0], pg);
 #pragma unroll
         for (int j = 0; j < D; j++)
@@ -174,7 +214,7 @@ __device__ __forceinline__ void own_trial(const T* __restrict__ xp, const T* __r
     {
         const int64_t base = (rev ? top - t0 : t0) + threadIdx.x;
         Pack<T> pxp[U][D], pd[U][D], pg0[U][D], plo[U][D], pup[U][D];
-        uint32_t o[U][W + 1];
+        uint32_t o[U][own_noff<F, W>];
 #pragma unroll
         for (int u = 0; u < U; u++)
         {
@@ -193,7 +233,7 @@ __device__ __forceinline__ void own_trial(const T* __restrict__ xp, const T* __r
                         pup[u][j] = ldv<T>(ub, vi * D + j);
                     }
                 }
-                own_offsets<W>(F::off(obj), vi * W, o[u]);
+                own_offsets<F, W>(obj, vi * W, o[u]);
             }
         }
 #pragma unroll

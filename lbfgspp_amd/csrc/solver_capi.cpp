@@ -946,6 +946,9 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
             throw std::invalid_argument("a mesh objective is minimised with its elements: lbfgsx_solver_minimize_mesh");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_LINEAR)
             throw std::invalid_argument("a linear-model objective is minimised with its matrix: lbfgsx_solver_minimize_linear");
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_LINEAR_MULTI)
+            throw std::invalid_argument("a multi-output linear-model objective is minimised with its matrix: "
+                                        "lbfgsx_solver_minimize_linear");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_CHAIN)
         {
             if (n < K)
@@ -1072,9 +1075,14 @@ int lbfgsx_solver_minimize_linear(lbfgsx_solver* s, const lbfgsx_objective* obj,
     const int bad = guarded(out, [&]() {
         if (!s || !obj || n <= 0)
             throw std::invalid_argument("lbfgsx_solver_minimize_linear: invalid argument");
-        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_LINEAR)
+        const bool multi = lbfgsx_objective_form(obj) == LBFGSX_FORM_LINEAR_MULTI;
+        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_LINEAR && !multi)
             throw std::invalid_argument("lbfgsx_solver_minimize_linear: the handle is not a linear-model objective "
                                         "(lbfgsx_objective_compile_linear)");
+        if (multi && n % lbfgsx_objective_dim(obj) != 0)
+            throw std::invalid_argument("multi-output linear-model objective: n = " + std::to_string(n) +
+                                        " is not a multiple of D = " + std::to_string(lbfgsx_objective_dim(obj)) +
+                                        ": x holds the D weights of each feature");
         if (lbfgsx_objective_dtype(obj) != s->dtype)
             throw std::invalid_argument("lbfgsx_solver_minimize_linear: the objective was compiled for the other dtype");
         if (R < 1 || nnz < 1 || !rowptr || !col || !val)

@@ -10,7 +10,8 @@ std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device ob
 `ChainObjective(body)` for terms that overlap, `GridObjective(body, shape)` for 2x2-cell terms on a grid, or
 `GraphObjective(edge_body, edges)` for edge terms over an index list,
 `MeshObjective(elem_body, elements, dim)` for K-node elements with vector unknowns, or
-`LinearObjective(row_body, (rowptr, col, val), n)` for a linear model over a sparse matrix)
+`LinearObjective(row_body, (rowptr, col, val), n)` for a linear model over a sparse matrix, or
+`MultiLinearObjective(row_body, (rowptr, col, val), features, outputs)` for one with several outputs per row)
 or the caller's own callable, `DeviceObjective(fn)`: fn(x, grad) -> float on torch
 tensors that alias the library's device vectors.  All O(n) work of the solver runs in the HIP library, Python only passes
 pointers.  There is no CPU fallback: without the built extension or a GPU these calls raise.
@@ -504,6 +505,49 @@ class LinearObjective(TermObjective):
         return self.rowptr.ctypes.data, self.col.ctypes.data, val.ctypes.data, 0, (val,)
 
 
+class MultiLinearObjective(LinearObjective):
+    """A linear model with D = outputs values per sample: x holds an F x D weight matrix, feature-major (x[j*D + c],
+    n = features * outputs), A is a sparse R x F CSR matrix, Z = A X, and
+    f(x) = sum over coordinates i of psi(x[i]; i) + sum over rows r of phi(Z[r, 0..D); r) -- multinomial (softmax) logistic
+    regression, multi-class SVMs, multi-target least squares, non-negative matrix regression under LBFGSBSolver
+    (include/lbfgsx.h, "multi-output linear-model objectives").  row_body sees T, constexpr int D, const T z[D], T dz[D] (to
+    fill with dphi/dz_c), int64_t r, p0..p3 and c[8] and returns phi; coord_body (optional) is a LinearObjective's, per
+    coordinate i = j*D + c (D is visible).  grad[j*D + c] is the coordinate term's g[0], then val * dz_r[c] over the entries of
+    column j in ascending r.
+
+        lsq = MultiLinearObjective("T s = T(0);\n#pragma unroll\nfor (int c = 0; c < D; c++) {"
+                                   " dz[c] = z[c] - p0[r * D + c]; s = s + dz[c] * dz[c]; } return T(0.5) * s;",
+                                   (rowptr, col, val), features=F, outputs=3, data=(targets.ravel(),))
+
+    1 <= outputs <= 16.  The matrix is a LinearObjective's with 0 <= col < features.  Each data[k] has n, features, R or
+    R * D elements (an R x D table of targets, p0[r * D + c]).  Otherwise a
+    LinearObjective's interface; usable wherever one is, refused where one is."""
+    _NAME = "MultiLinearObjective"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_linear_multi", "lbfgsx_objective_source_linear_multi"
+
+    def __init__(self, row_body, matrix, features, outputs, coord_body=None, data=(), scalars=(), lanes=0):
+        self.D, self.F = int(outputs), int(features)
+        if self.D < 1 or self.D > 16:
+            raise ValueError("MultiLinearObjective: D = %d is not supported: a row has D = 1 .. 16 outputs" % self.D)
+        if self.F < 1:
+            raise ValueError("MultiLinearObjective: features = %d: a model has at least one feature" % self.F)
+        super().__init__(row_body, matrix, self.F * self.D, coord_body, data, scalars, lanes)
+
+    def _form_args(self):
+        return (self.D, self.coord_body.encode() if self.coord_body else None)
+
+    def _check_n(self, n):
+        if n % self.D:
+            raise ValueError("MultiLinearObjective: n = %d is not a multiple of D = %d: x holds the D weights of each feature"
+                             % (n, self.D))
+        if n != self.n:
+            raise ValueError("MultiLinearObjective: the model has n = %d * %d = %d weights and x has %d elements"
+                             % (self.F, self.D, self.n, n))
+
+    def _data_sizes(self, n):
+        return (n, self.F, self.R, self.R * self.D)
+
+
 class TraceBuffer:
     """Per-evaluation record (fx and x[::stride]) for the parity tests."""
 
@@ -724,7 +768,7 @@ class _SolverBase:
         if not hasattr(f, "objective"):
             raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body), "
                             "GridObjective(body, shape), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim), "
-                            "LinearObjective(row_body, matrix, n) or DeviceObjective(fn)")
+                            "LinearObjective(row_body, matrix, n), MultiLinearObjective(row_body, matrix, features, outputs) or DeviceObjective(fn)")
         res = L.Result()
         a = None if f.a is None else np.ascontiguousarray(f.a, _NP[self.dtype])
         b = None if f.b is None else np.ascontiguousarray(f.b, _NP[self.dtype])
