@@ -115,6 +115,10 @@ class TermObjective
     const Scalar* m_val = nullptr;
     bool m_matrix_dev = false;
     int m_lanes = 0;
+    // a DenseLinearObjective's matrix (m_R rows, m_matrix_dev, m_lanes as above); m_A null: bound without one
+    const Scalar* m_A = nullptr;
+    std::int64_t m_lda = 0;
+    bool m_dense = false;
 
     TermObjective(const TermObjective&) = delete;
     TermObjective& operator=(const TermObjective&) = delete;
@@ -132,7 +136,8 @@ protected:
     {
         std::vector<char> log(16384, '\0');
         const int dt = detail::dtype_of<Scalar>::value;
-        const int rc = (form == LBFGSX_FORM_LINEAR_MULTI) ? lbfgsx_objective_compile_linear_multi(&m_h, dt, D, node.c_str(), body.c_str(), log.data(), log.size())
+        const int rc = (form == LBFGSX_FORM_DENSE) ? lbfgsx_objective_compile_dense(&m_h, dt, D, node.c_str(), body.c_str(), log.data(), log.size())
+                       : (form == LBFGSX_FORM_LINEAR_MULTI) ? lbfgsx_objective_compile_linear_multi(&m_h, dt, D, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_LINEAR)  ? lbfgsx_objective_compile_linear(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_MESH)  ? lbfgsx_objective_compile_mesh(&m_h, dt, K, D, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRAPH) ? lbfgsx_objective_compile_graph(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
@@ -164,6 +169,15 @@ protected:
         m_rowptr = rowptr;
         m_col = col;
         m_val = val;
+        m_matrix_dev = on_device;
+        m_lanes = lanes;
+    }
+    void set_dense(std::int64_t R, const Scalar* A, std::int64_t lda, bool on_device, int lanes)
+    {
+        m_dense = true;
+        m_R = R;
+        m_A = A;
+        m_lda = lda;
         m_matrix_dev = on_device;
         m_lanes = lanes;
     }
@@ -231,7 +245,9 @@ public:
                 p[k] = dev;
             }
         }
-        if (m_rowptr || m_R || m_nnz)
+        if (m_dense)
+            detail::check(lbfgsx_objective_bind_dense(c, m_h, m_R, m_A, m_lda, m_matrix_dev ? 1 : 0, m_lanes, p, m_c, &id));
+        else if (m_rowptr || m_R || m_nnz)
             detail::check(lbfgsx_objective_bind_linear(c, m_h, m_R, m_nnz, m_rowptr, m_col, m_val, m_matrix_dev ? 1 : 0, m_lanes, p,
                                                        m_c, &id));
         else if (m_elems)
@@ -391,9 +407,36 @@ public:
     }
 };
 
+// The multi-output linear model over a DENSE matrix: x holds an F x D weight matrix, feature-major (x[j*D + c], n = F*D), A is
+// R x F, row-major with a row stride of lda >= F elements, Z = A X and f(x) = sum over coordinates i of psi(x[i]; i) + sum over
+// rows r of phi(Z[r, 0..D); r) (include/lbfgsx.h, "dense linear-model objectives"): logistic, softmax, Poisson and
+// least-squares regression on tabular features, NNLS under LBFGSBSolver.  D = 1 .. 16; the bodies are a
+// MultiLinearObjective's (D = 1: z[0], dz[0]).
+//     DenseLinearObjective<double> f(1, "const T m = p0[r] * z[0]; ... return ...;", "g[0] = c[0] * x[0]; return T(0.5) * (c[0] * (x[0] * x[0]));");
+//     f.matrix(R, A, F).host_data(0, labels, R).scalars({1e-3});      solver.minimize(f, x, fx);
+// matrix(): a host array, copied to the device at every minimize(), or a device array (on_device = true) that is used in
+// place, NOT copied: it stays alive and unchanged until minimize() returns.  lda < x.size() / D, R < 1 and x.size() not a
+// multiple of D throw std::invalid_argument.  Accepted wherever a MultiLinearObjective is, refused where it is.
+template <typename Scalar>
+class DenseLinearObjective : public TermObjective<Scalar>
+{
+public:
+    DenseLinearObjective(int D, const std::string& row_body, const std::string& coord_body = std::string())
+        : TermObjective<Scalar>(LBFGSX_FORM_DENSE, 1, row_body, "DenseLinearObjective: ", coord_body, D)
+    {
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile_dense); it stays the caller's
+    explicit DenseLinearObjective(const lbfgsx_objective* compiled) : TermObjective<Scalar>(compiled) {}
+    DenseLinearObjective& matrix(std::int64_t R, const Scalar* A, std::int64_t lda, bool on_device = false, int lanes = 0)
+    {
+        this->set_dense(R, A, lda, on_device, lanes);
+        return *this;
+    }
+};
+
 namespace detail {
 // the objectives compiled at run time into the fused kernels: a TermObjective, a ChainObjective, a GridObjective, a
-// GraphObjective, a MeshObjective, a LinearObjective or a MultiLinearObjective
+// GraphObjective, a MeshObjective, a LinearObjective, a MultiLinearObjective or a DenseLinearObjective
 template <typename Scalar, typename Foo>
 struct is_compiled_objective
 {
@@ -401,7 +444,8 @@ struct is_compiled_objective
     static constexpr bool value = std::is_same<F, TermObjective<Scalar> >::value || std::is_same<F, ChainObjective<Scalar> >::value ||
                                   std::is_same<F, GridObjective<Scalar> >::value || std::is_same<F, GraphObjective<Scalar> >::value ||
                                   std::is_same<F, MeshObjective<Scalar> >::value || std::is_same<F, LinearObjective<Scalar> >::value ||
-                                  std::is_same<F, MultiLinearObjective<Scalar> >::value;
+                                  std::is_same<F, MultiLinearObjective<Scalar> >::value ||
+                                  std::is_same<F, DenseLinearObjective<Scalar> >::value;
 };
 }  // namespace detail
 

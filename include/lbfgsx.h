@@ -216,7 +216,7 @@ int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4]);
  * with n < K is refused (any n >= K is accepted: n need not be a multiple of anything).  The compile log, the refusal of
  * asm and the line numbers are those of lbfgsx_objective_compile. */
 enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2, LBFGSX_FORM_GRAPH = 3, LBFGSX_FORM_MESH = 4, LBFGSX_FORM_LINEAR = 5,
-       LBFGSX_FORM_LINEAR_MULTI = 6 };
+       LBFGSX_FORM_LINEAR_MULTI = 6, LBFGSX_FORM_DENSE = 7 };
 int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len);
 long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char* out, size_t len);
 int lbfgsx_objective_form(const lbfgsx_objective* obj);
@@ -403,8 +403,8 @@ int lbfgsx_objective_dim(const lbfgsx_objective* obj);
  * words), 2 nnz indices, 2 nnz values and the gathered values once each (nnz of x, or of xp and d in a trial, and nnz of w),
  * w and v written and read, the chunk partials written and read.
  * Not built: reusing z = A xp and A d across the trials of one line search (which would make every trial after the first
- * O(R)), dense A, column reordering, the lock-step batch, a bench.py leg.  (Several outputs per row are the next section's
- * form.)  Measurements: DESIGN.md section 1. */
+ * O(R)), column reordering, the lock-step batch, a bench.py leg.  (Several outputs per row are the next section's form, a
+ * dense matrix the one after it.)  Measurements: DESIGN.md section 1. */
 int lbfgsx_objective_compile_linear(lbfgsx_objective** out, int dtype, const char* coord_body, const char* row_body, char* log,
                                     size_t log_len);
 long long lbfgsx_objective_source_linear(int dtype, const char* coord_body, const char* row_body, char* out, size_t len);
@@ -444,12 +444,65 @@ int lbfgsx_objective_linear_topology(lbfgsx_ctx* c, int64_t info[8], uint32_t* c
  * Byte model of one evaluation: the scalar form's with every count of gathered x, xp, d and w, of w written and read and of
  * the chunk partials multiplied by D; offsets (R+1 and F+1 words), indices and matrix values are counted once.  The D
  * coordinates of a feature read its entries again; those re-reads are cache hits and are not modelled.
- * Not built: D > 16, reusing Z across a line search's trials, dense A, mixed per-row output counts, the lock-step batch, a
- * bench.py leg.  Registers, measurements: DESIGN.md section 1. */
+ * Not built: D > 16, reusing Z across a line search's trials, mixed per-row output counts, the lock-step batch, a
+ * bench.py leg.  (A dense matrix is the next section's form.)  Registers, measurements: DESIGN.md section 1. */
 int lbfgsx_objective_compile_linear_multi(lbfgsx_objective** out, int dtype, int D, const char* coord_body, const char* row_body,
                                           char* log, size_t log_len);
 long long lbfgsx_objective_source_linear_multi(int dtype, int D, const char* coord_body, const char* row_body, char* out,
                                                size_t len);
+/* ---- dense linear-model objectives: the multi-output form over a dense row-major matrix ---------------------------------------
+ * x holds an F x D weight matrix X, feature-major (x[j*D + c], n = F*D), A is the caller's DENSE R x F matrix, row-major with a
+ * row stride of lda >= F elements, of the solver's dtype, and
+ *     Z = A X  (R x D),      f(x) = sum over coordinates i of psi(x[i]; i)  +  sum over rows r of phi(Z[r, 0..D); r)
+ * -- logistic, softmax, Poisson and least-squares regression on tabular features, NNLS under L-BFGS-B.  1 <= D <= 16 ("D = #
+ * is not supported: a row has D = 1 .. 16 outputs").  The bodies are exactly the multi-output form's: row_body sees T,
+ * constexpr int D, const T z[D], T dz[D], int64_t r, p0..p3, c[8] and returns phi; coord_body (NULL or empty: none) sees
+ * const T x[1], T g[1], int64_t i.  D = 1 is the scalar model, written z[0] / dz[0]; there is no scalar-signature form.
+ * Semantics (bit-exact numpy restatement: tests/dense_ref.py; one rounding per source operation, no contraction):
+ *   Z[r, c]   the sparse forms' row rule on the dense row: L lanes share a row, lane l takes columns l, l+L, .. in ascending
+ *             order, s_l[c] = A[r,k]*x[k*D + c] for its first column and s_l[c] = s_l[c] + .. after it, +0 without one; then
+ *             s_l = s_l + s_{l+h} for l < h, h = L/2 .. 1, and Z[r, c] = s_0[c].  L is the largest power of two <= F, at most
+ *             64 (the sparse rule with nnz / R = F), or `lanes`.  The same matrix given to the sparse forms as CSR with every
+ *             entry stored, and the same lanes, gives the same bits in z, w, v and f.
+ *   grad      rows are cut into chunks of C = 256 consecutive rows (the last one shorter); part[b*n + j*D + c] is the sum over
+ *             the rows r of chunk b, in ascending r, of A[r,j]*w[r*D + c], w[r*D + c] = dz[c], started from the first
+ *             product; grad[j*D + c] is psi's g[0] if there is a coordinate body, then the partials in ascending b, started
+ *             from the first contribution.  C is part of the semantics, a constant (never data-dependent), reported in info[4].
+ *   f         the order-independent compensated sum of the other forms over all psi and phi values.
+ *   trial     the weight used is xp[i] + step*d[i], the statement i's owner executes, never a read of the x the launch writes.
+ * Kernels (csrc/linear_dense_kernels.cuh), three launches per evaluation on one stream, no host wait: the row pass
+ * k_dense_rows / k_dense_rows_trial (kBlock / L rows per block step, the lanes of a row read consecutive elements, D
+ * accumulators per lane, cross-lane halvings, no LDS, no atomic), the partial pass k_dense_partials (A read a second time,
+ * column-wise without a strided access: a thread owns a 16-byte pack of consecutive columns and walks the C rows of a chunk
+ * with W*D accumulators; small F packs several chunks into a block) and the column pass k_dense_eval, k_dense_trial,
+ * k_dense_b_eval, k_dense_b_dg_maxstep_trial (a thread owns a 16-byte pack of coordinates and adds their partials).
+ * k_dense_partials holds no caller text but is instantiated in the generated unit, which keeps D a compile-time constant.
+ * lbfgsx_objective_compile_dense caches by (form, both bodies, dtype, D); the form is LBFGSX_FORM_DENSE, lbfgsx_objective_K
+ * returns 1 and lbfgsx_objective_dim D.
+ * lbfgsx_objective_bind_dense: F = n / D.  A HOST matrix (a_on_device = 0) is copied to the device compactly; the context owns
+ * the copy and frees it with the other forms' lists.  A DEVICE matrix is used IN PLACE and is NOT copied: the caller keeps it
+ * alive and unchanged while the objective is bound (a second copy is what would make dense data infeasible).  Refused with
+ * LBFGSX_E_INVALID, the values named, nothing bound, no launch: a handle of another form, R < 1, A null, n % D != 0, lda < F,
+ * R or F above 2^31 - 1, lanes not 0 or a power of two <= 64.  Every other bind call refuses a dense handle, and this one
+ * theirs; lbfgsx_solver_minimize_obj and _linear refuse it; so do the Gram-space recursion, row shards and the lock-step batch.
+ * lbfgsx_objective_dense_info: info = {R, F, D, L, C, chunks, lda, 1 if the context owns a copy of A}.
+ * lbfgsx_objective_dense_read: w (R*D), v (R) and part (chunks*n) of the last evaluation, host arrays, any of them NULL.
+ * Byte model of one evaluation (lbfgsx_counters_ex), with s = sizeof(T): the built-in's streams, plus 2 R F s for A (read by
+ * the row pass and by the partial pass), n s of weights for the row pass (2 n s in a trial), R D s of w written and R D s
+ * read, R s of v written and R s read, chunks n s of partials written and the same read.  The row pass's re-reads of x and
+ * the partial pass's re-reads of w are served by the caches and are not modelled.  Launches per evaluation: 3; per bind: the
+ * upload only.
+ * Not built: a single-sweep kernel that forms Z and A^T w from one read of A, reuse of A xp and A d across a line search's
+ * trials, the matrix cores (no default path runs an MFMA, and the bit contract forbids reordering the sums), D > 16,
+ * column-major A, mixed dense + sparse blocks, the lock-step batch, a bench.py leg.  Registers, measurements: DESIGN.md
+ * section 1. */
+int lbfgsx_objective_compile_dense(lbfgsx_objective** out, int dtype, int D, const char* coord_body, const char* row_body, char* log,
+                                   size_t log_len);
+long long lbfgsx_objective_source_dense(int dtype, int D, const char* coord_body, const char* row_body, char* out, size_t len);
+int lbfgsx_objective_bind_dense(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t R, const void* A, int64_t lda, int a_on_device,
+                                int lanes, const void* const p[4], const double cs[8], int* id);
+int lbfgsx_objective_dense_info(lbfgsx_ctx* c, int64_t info[8]);
+int lbfgsx_objective_dense_read(lbfgsx_ctx* c, void* w, void* v, void* part);
 /* Every entry point of this ABI makes the context's device current for its own duration and restores the caller's
  * afterwards.  Code that launches its OWN kernels on the context's vectors (a device functor, lbfgsx_vec) must run with
  * that device current too: lbfgsx_device tells which one it is, lbfgsx_device_push makes it current for the calling

@@ -162,6 +162,16 @@ int lbfgsx_solver_minimize_linear(lbfgsx_solver* s, const lbfgsx_objective* obj,
                                   const int32_t* rowptr, const int32_t* col, const void* val, int matrix_on_device, int lanes,
                                   const void* const p[4], int host_mask, const int64_t counts[4], const double c[8], void* x,
                                   const void* lb, const void* ub, lbfgsx_trace* trace, lbfgsx_result* out);
+/* The same for a dense linear-model objective (lbfgsx_objective_compile_dense, include/lbfgsx.h "dense linear-model
+ * objectives"): x holds the F x D weight matrix, n = F*D, A is R x F, row-major with a row stride of lda >= F elements of the
+ * solver's dtype, a host array (copied) or a device array used in place (a_on_device != 0); lanes and counts as for
+ * lbfgsx_solver_minimize_linear (a data array has n, F, R or R*D elements).  A handle of another form, n not a multiple of D
+ * (both named), R < 1, A null and lda < F are refused with LBFGSX_E_INVALID before a device is needed;
+ * lbfgsx_solver_minimize_obj and lbfgsx_solver_minimize_linear refuse a dense handle. */
+int lbfgsx_solver_minimize_dense(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, const void* A, int64_t lda,
+                                 int a_on_device, int lanes, const void* const p[4], int host_mask, const int64_t counts[4],
+                                 const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
+                                 lbfgsx_result* out);
 int lbfgsx_solver_minimize_mesh(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t E, const int32_t* elems,
                                 int elems_on_device, const void* const p[4], int host_mask, const int64_t counts[4],
                                 const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,

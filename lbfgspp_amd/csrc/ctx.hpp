@@ -261,8 +261,8 @@ struct lbfgsx_ctx
     // context's copies of host arrays, lbfgsx_objective_upload, bound only when the caller passes them), term_c: its scalars
     const struct lbfgsx_objective* term = nullptr;
     // its four kernels on this context's device (hipFunction_t); slots 4 and 5: a linear-model objective's two row passes;
-    // slot 6: a term objective's post form of k_trial (launch_args.hpp)
-    void* term_fn[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // slot 6: a term objective's post form of k_trial; slot 7: a dense linear-model objective's partial pass (launch_args.hpp)
+    void* term_fn[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const void* term_p[4] = {nullptr, nullptr, nullptr, nullptr};
     double term_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int term_np = 0;  // data arrays bound (byte model)
@@ -295,6 +295,18 @@ struct lbfgsx_ctx
         void *part = nullptr, *long_col = nullptr, *long_chunk = nullptr;  // T[nchunks], int32[nlong], uint32[nlong+1]
         void* chunk = nullptr;                                       // uint32[2*nchunks]: first and past-the-last entry
     } lin;
+    // a dense linear-model objective's matrix (lbfgsx_objective_bind_dense, dense_topology.hip): R x F, row-major with a row
+    // stride of lda elements.  own: A is the context's compact copy of a host matrix (lda = F) and is freed with the rest;
+    // otherwise A is the caller's device array, used in place.  D outputs per row, L lanes per row in the row pass, chunks of C
+    // rows in the partial pass.  Freed with the other forms' list (graph_topology_free)
+    struct DenseTopo
+    {
+        int64_t R = 0, F = 0, lda = 0, chunks = 0;
+        int L = 0, C = 0, D = 0;
+        bool own = false;
+        const void* A = nullptr;                            // T[R*lda]
+        void *w = nullptr, *v = nullptr, *part = nullptr;   // T[R*D]: dphi/dz, T[R]: phi, T[chunks*n]: the chunk partials
+    } dense;
 
     // L-BFGS-B work set (allocated with LBFGSX_FLAG_BOUNDED) lives in lbfgsb part
     void* lb = nullptr;

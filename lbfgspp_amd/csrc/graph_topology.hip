@@ -128,6 +128,7 @@ void graph_topology_free(lbfgsx_ctx* c)
     c->graph_E = 0;
     c->mesh_K = c->mesh_D = 0;
     linear_topology_free(c);
+    dense_topology_free(c);
 }
 
 int graph_topology_build(lbfgsx_ctx* c, const int32_t* ei, const int32_t* ej, int64_t E, int on_device)

@@ -19,7 +19,9 @@
 // product and an optional one per coordinate), is a wrapper around linear_kernels.cuh with the matrix of linear_topology.hip;
 // it has two more kernels, the row passes, in slots 4 and 5; so has the seventh, a MULTI-OUTPUT LINEAR-MODEL objective (D
 // outputs per row, x an F x D matrix), a wrapper around linear_multi_kernels.cuh over the same matrix and the same argument
-// struct, bound by the same call.  A handle carries its form; the four slots of the
+// struct, bound by the same call.  An eighth, a DENSE LINEAR-MODEL objective (the multi-output form's bodies over a dense
+// row-major matrix), is a wrapper around linear_dense_kernels.cuh with the matrix of dense_topology.hip; besides the row
+// passes it has the partial pass in slot 7.  A handle carries its form; the four slots of the
 // loaded-kernel table and everything that launches them are the same.  What the forms differ in -- names, kernel names, struct
 // members, the bodies' signatures, the K and D accepted, the cache key -- is one row each of kForms below; the generator, the
 // validation and the refusals are written once and read it.
@@ -78,7 +80,7 @@ struct FormDesc
     "    const T* part;\n    const int32_t* long_col;\n    const uint32_t* long_chunk;\n"           \
     "    int64_t R, nnz;\n    int32_t L, C, nlong, pad_;\n"
 const BodyDesc kNoBody = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-const FormDesc kForms[7] = {
+const FormDesc kForms[8] = {
     {"term objective", "", "ObjTerm", "#include \"lbfgs_kernels.cuh\"\n#include \"lbfgsb_kernels.cuh\"\n",
      {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial", nullptr, nullptr, "k_trial_post"}, "", kNoBody,
      {"    // one term: x[0..K) in, g[0..K) out, the term's value returned\n", TERM_SIGNATURE, "objective_body", "body", nullptr,
@@ -162,7 +164,19 @@ const FormDesc kForms[7] = {
      {"    // the term of row r: z[c] = the row's product with column c of the F x D matrix x in, its D partial derivatives dz out,\n"
       "    // its value returned\n",
       "T row(const T (&z)[D], T (&dz)[D], int64_t r) const", "row_body", "row body", nullptr, nullptr},
-     "", 1, 1, 1, 16, nullptr, "D = # is not supported: a row has D = 1 .. 16 outputs", true, true, "matrix", "_linear"}};
+     "", 1, 1, 1, 16, nullptr, "D = # is not supported: a row has D = 1 .. 16 outputs", true, true, "matrix", "_linear"},
+    {"dense linear-model objective", "_dense", "ObjDense", "#include \"linear_dense_kernels.cuh\"\n",
+     {"k_dense_eval", "k_dense_trial", "k_dense_b_eval", "k_dense_b_dg_maxstep_trial", "k_dense_rows", "k_dense_rows_trial", nullptr,
+      "k_dense_partials"},
+     // launch_args.hpp: DenseArgs
+     "    const T* A;\n    T* w;\n    T* v;\n    T* part;\n"
+     "    int64_t R, F, lda, chunks;\n    int32_t L, C, pad0_, pad1_;\n",
+     {"    // the term of coordinate i = j*D + c: x[0] = x[i] in, its derivative g[0] out, its value returned\n", POINT_SIGNATURE("coord"),
+      "coord_body", "coordinate body", POINT_ABSENT, "kCoord"},
+     {"    // the term of row r: z[c] = row r of the dense matrix times column c of the F x D matrix x in, its D partial derivatives\n"
+      "    // dz out, its value returned\n",
+      "T row(const T (&z)[D], T (&dz)[D], int64_t r) const", "row_body", "row body", nullptr, nullptr},
+     "", 1, 1, 1, 16, nullptr, "D = # is not supported: a row has D = 1 .. 16 outputs", true, true, "matrix"}};
 #undef LINEAR_MEMBERS
 #undef TERM_SIGNATURE
 #undef POINT_SIGNATURE
@@ -175,10 +189,12 @@ const char* const kKernelParams[lbfgsx::JIT_NSLOTS] = {
     "const S*, const S*, const S*, const S*, const S*, S, S*, S*, int64_t, OBJ, RedWs, S*, int",
     "const S*, OBJ",
     "const S*, const S*, S, OBJ",
-    "const S*, const S*, S, S*, S*, int64_t, OBJ, RedWs, S*, int, TrialPost<S>"};
-const int kEmitOrder[lbfgsx::JIT_NSLOTS] = {0, 1, 6, 2, 3, 4, 5};
+    "const S*, const S*, S, S*, S*, int64_t, OBJ, RedWs, S*, int, TrialPost<S>",
+    "OBJ"};
+const int kEmitOrder[lbfgsx::JIT_NSLOTS] = {0, 1, 6, 2, 3, 4, 5, 7};
 // does a form have the kernel of slot k: the four every form has, a linear-model objective's two row passes, a term
-// objective's post form of k_trial (a table row names exactly the slots of its form)
+// objective's post form of k_trial, a dense linear-model objective's partial pass (a table row names exactly the slots of its
+// form)
 inline bool has_kernel(int form, int k) { return k >= 0 && k < lbfgsx::JIT_NSLOTS && kForms[form].kernels[k] != nullptr; }
 
 // ---- hipRTC, loaded on first use (a process that never compiles an objective does not need it)
@@ -440,12 +456,12 @@ struct lbfgsx_objective_code
     int form = LBFGSX_FORM_TERM, dtype = LBFGSX_F64, K = 1, D = 1;
     std::vector<char> code;
     std::string lowered[lbfgsx::JIT_NSLOTS];
-    long long vgprs[lbfgsx::JIT_NSLOTS] = {0, 0, 0, 0, 0, 0, 0}, scratch[lbfgsx::JIT_NSLOTS] = {0, 0, 0, 0, 0, 0, 0};
+    long long vgprs[lbfgsx::JIT_NSLOTS] = {0, 0, 0, 0, 0, 0, 0, 0}, scratch[lbfgsx::JIT_NSLOTS] = {0, 0, 0, 0, 0, 0, 0, 0};
     double compile_ms = 0.0;
     struct Loaded
     {
         hipModule_t mod = nullptr;
-        hipFunction_t fn[lbfgsx::JIT_NSLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        hipFunction_t fn[lbfgsx::JIT_NSLOTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     };
     std::mutex mu;
     std::map<int, Loaded> loaded;  // per device
@@ -666,6 +682,10 @@ long long lbfgsx_objective_source_linear_multi(int dtype, int D, const char* coo
 {
     return objective_source(LBFGSX_FORM_LINEAR_MULTI, dtype, 1, row_body, out, len, coord_body, D);
 }
+long long lbfgsx_objective_source_dense(int dtype, int D, const char* coord_body, const char* row_body, char* out, size_t len)
+{
+    return objective_source(LBFGSX_FORM_DENSE, dtype, 1, row_body, out, len, coord_body, D);
+}
 
 int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
 {
@@ -698,6 +718,11 @@ int lbfgsx_objective_compile_linear_multi(lbfgsx_objective** out, int dtype, int
                                           char* log, size_t log_len)
 {
     return objective_compile(LBFGSX_FORM_LINEAR_MULTI, out, dtype, 1, row_body, log, log_len, coord_body, D);
+}
+int lbfgsx_objective_compile_dense(lbfgsx_objective** out, int dtype, int D, const char* coord_body, const char* row_body, char* log,
+                                   size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_DENSE, out, dtype, 1, row_body, log, log_len, coord_body, D);
 }
 
 void lbfgsx_objective_destroy(lbfgsx_objective* obj) { delete obj; }
@@ -779,7 +804,7 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
         c->term_np = 0;
         c->term_form = LBFGSX_FORM_TERM;
         c->term_rows = c->term_cols = 0;
-        if (c->graph_inc || c->lin.colptr)
+        if (c->graph_inc || c->lin.colptr || c->dense.w)
         {
             lbfgsx::DeviceGuard dev_guard_(c->device);
             (void) lbfgsx::stream_sync(c->stream);  // no launch still walks the list
@@ -832,7 +857,7 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
             c->term_fn[k] = it->second.fn[k];
     }
     if (code->form != LBFGSX_FORM_GRAPH && code->form != LBFGSX_FORM_MESH && !lbfgsx::form_is_linear(code->form) &&
-        (c->graph_inc || c->lin.colptr))
+        code->form != LBFGSX_FORM_DENSE && (c->graph_inc || c->lin.colptr || c->dense.w))
     {
         (void) lbfgsx::stream_sync(c->stream);  // no launch still walks the list
         lbfgsx::graph_topology_free(c);
@@ -1101,6 +1126,74 @@ int lbfgsx_objective_linear_topology(lbfgsx_ctx* c, int64_t info[8], uint32_t* c
     }
     lbfgsx::DeviceGuard dev_guard_(c->device);
     return lbfgsx::linear_topology_read(c, colptr, trow, tpos, long_col, long_chunk, chunk);
+}
+
+int lbfgsx_objective_bind_dense(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t R, const void* A, int64_t lda, int a_on_device,
+                                int lanes, const void* const p[4], const double cs[8], int* id)
+{
+    if (!c || !obj)
+        return LBFGSX_E_INVALID;
+    if (const int rc = bind_begin(c, obj, LBFGSX_FORM_DENSE))
+        return rc;
+    const int D = obj->code->D;
+    const int64_t lim = 2147483647, F = c->n / D;
+    std::string why;
+    if (R < 1)
+        why = "R = " + std::to_string(R) + ": a dense linear-model objective has at least one row (R >= 1)";
+    else if (!A)
+        why = "A is null: a dense linear-model objective has its R x F matrix (R = " + std::to_string(R) + ")";
+    else if (c->n % D != 0)
+        why = "n = " + std::to_string(c->n) + " is not a multiple of D = " + std::to_string(D) +
+              ": x holds the D weights of each feature";
+    else if (lda < F)
+        why = "lda = " + std::to_string(lda) + " is less than F = n / D = " + std::to_string(F) +
+              ": a row of the matrix holds its F values first";
+    else if (R > lim)
+        why = "R = " + std::to_string(R) + " exceeds 2^31 - 1 = " + std::to_string(lim);
+    else if (F > lim)
+        why = "F = " + std::to_string(F) + " exceeds 2^31 - 1 = " + std::to_string(lim);
+    else if (lanes < 0 || lanes > 64 || (lanes & (lanes - 1)) != 0)
+        why = "lanes = " + std::to_string(lanes) + ": the lanes that share a row are 0 (by the rule) or a power of two in 1..64";
+    if (!why.empty())
+    {
+        lbfgsx::set_error("dense linear-model objective: " + why);
+        return LBFGSX_E_INVALID;
+    }
+    {
+        lbfgsx::DeviceGuard dev_guard_(c->device);
+        const int rc = lbfgsx::dense_topology_build(c, R, D, A, lda, a_on_device, lanes);
+        if (rc)
+            return rc;
+    }
+    return bind_end(c, obj, p, cs, id);
+}
+
+int lbfgsx_objective_dense_info(lbfgsx_ctx* c, int64_t info[8])
+{
+    if (!c || !c->term || c->term_form != LBFGSX_FORM_DENSE || !c->dense.w)
+    {
+        lbfgsx::set_error("lbfgsx_objective_dense_info: no dense linear-model objective is bound to this context");
+        return LBFGSX_E_INVALID;
+    }
+    if (info)
+    {
+        const lbfgsx_ctx::DenseTopo& d = c->dense;
+        const int64_t v[8] = {d.R, d.F, d.D, d.L, d.C, d.chunks, d.lda, d.own ? 1 : 0};
+        for (int k = 0; k < 8; k++)
+            info[k] = v[k];
+    }
+    return LBFGSX_OK;
+}
+
+int lbfgsx_objective_dense_read(lbfgsx_ctx* c, void* w, void* v, void* part)
+{
+    if (!c || !c->term || c->term_form != LBFGSX_FORM_DENSE || !c->dense.w)
+    {
+        lbfgsx::set_error("lbfgsx_objective_dense_read: no dense linear-model objective is bound to this context");
+        return LBFGSX_E_INVALID;
+    }
+    lbfgsx::DeviceGuard dev_guard_(c->device);
+    return lbfgsx::dense_topology_read(c, w, v, part);
 }
 
 int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4])

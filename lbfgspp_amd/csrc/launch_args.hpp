@@ -96,7 +96,10 @@ enum { JIT_K_EVAL = 0, JIT_K_TRIAL = 1, JIT_K_B_EVAL = 2, JIT_K_B_DG_MAXSTEP_TRI
 enum { JIT_K_LIN_ROWS = 4, JIT_K_LIN_ROWS_TRIAL = 5 };
 // a term objective has one more, the post form of k_trial (lbfgs_kernels.cuh: k_trial_post); the forms with kernels of their own
 // (chain, grid, graph, mesh, linear) have none
-enum { JIT_K_TRIAL_POST = 6, JIT_NSLOTS = 7 };
+enum { JIT_K_TRIAL_POST = 6 };
+// a dense linear-model objective has its row passes in slots 4 and 5 and one more, the partial pass between them and the
+// column pass (linear_dense_kernels.cuh: k_dense_partials)
+enum { JIT_K_DENSE_PARTIALS = 7, JIT_NSLOTS = 8 };
 // the by-value kernel argument: layout of the generated struct ObjTerm (four data pointers, eight scalars of type T)
 template <class T>
 struct TermArgs
@@ -186,10 +189,31 @@ inline LinearArgs<T> linear_args(const lbfgsx_ctx* c, const TermArgs<T>& t)
             l.nlong,
             0};
 }
+// the by-value argument of a dense linear-model objective's kernels: layout of the generated struct ObjDense (TermArgs, then
+// the matrix -- the caller's device array or the context's copy of a host one --, the row pass's outputs and the chunk
+// partials: ctx.hpp DenseTopo, dense_topology.hip)
+template <class T>
+struct DenseArgs
+{
+    TermArgs<T> t;
+    const T* A;
+    T* w;
+    T* v;
+    T* part;
+    int64_t R, F, lda, chunks;
+    int32_t L, C, pad0_, pad1_;
+};
+template <class T>
+inline DenseArgs<T> dense_args(const lbfgsx_ctx* c, const TermArgs<T>& t)
+{
+    const lbfgsx_ctx::DenseTopo& d = c->dense;
+    return {t, static_cast<const T*>(d.A), static_cast<T*>(d.w), static_cast<T*>(d.v), static_cast<T*>(d.part), d.R, d.F, d.lda,
+            d.chunks, d.L, d.C, 0, 0};
+}
 // the two forms that bind a CSR matrix: a linear-model objective and a multi-output one
 inline bool form_is_linear(int form) { return form == LBFGSX_FORM_LINEAR || form == LBFGSX_FORM_LINEAR_MULTI; }
 // the objective argument of the bound handle's kernels, by its form: &term for a term or chain objective, &grid for a grid
-// one, &graph for a graph one, &mesh for a mesh one, &linear for a linear-model one of either form
+// one, &graph for a graph one, &mesh for a mesh one, &linear for a linear-model one of either form, &dense for a dense one
 template <class T>
 struct BoundArgs
 {
@@ -198,6 +222,7 @@ struct BoundArgs
     GraphArgs<T> graph;
     MeshArgs<T> mesh;
     LinearArgs<T> linear;
+    DenseArgs<T> dense;
     void* ptr;
     explicit BoundArgs(const lbfgsx_ctx* c)
         : term(term_args<T>(c)),
@@ -205,12 +230,14 @@ struct BoundArgs
           graph{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const GraphEntry*>(c->graph_inc), c->graph_E},
           mesh{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const uint32_t*>(c->graph_inc), c->graph_E,
                c->mesh_D ? c->n / c->mesh_D : 0},
-          linear(linear_args<T>(c, term))
+          linear(linear_args<T>(c, term)),
+          dense(dense_args<T>(c, term))
     {
         ptr = (c->term_form == LBFGSX_FORM_GRID)    ? static_cast<void*>(&grid)
               : (c->term_form == LBFGSX_FORM_GRAPH) ? static_cast<void*>(&graph)
               : (c->term_form == LBFGSX_FORM_MESH)  ? static_cast<void*>(&mesh)
               : form_is_linear(c->term_form)        ? static_cast<void*>(&linear)
+              : (c->term_form == LBFGSX_FORM_DENSE) ? static_cast<void*>(&dense)
                                                     : static_cast<void*>(&term);
     }
     BoundArgs(const BoundArgs&) = delete;
@@ -225,6 +252,10 @@ struct BoundArgs
 //   multi-output linear  the same with every gathered value of x, xp, d and w, w written and read and the chunk partials
 //           counted D times (F + 1 column offsets); offsets, indices and matrix values once: the D coordinates of a feature
 //           read the same entries again, which are cache hits and are not modelled
+//   dense linear  one evaluation (row pass, partial pass, column pass): A twice (2 R F values), the weights the row pass
+//           reads (n values per vector gathered), w written and read (R*D each), v written and read (R each), the chunk
+//           partials written and read (chunks*n each).  The row pass's re-reads of x by the rows of a block and the partial
+//           pass's re-reads of w by the threads of a chunk are served by the caches and are not modelled
 // A trial launch adds it at its call site; an evaluation adds only a linear-model objective's, in linear_pre_eval.
 template <class T>
 inline void objective_model_add(const lbfgsx_ctx* c, int vectors_gathered)
@@ -242,6 +273,11 @@ inline void objective_model_add(const lbfgsx_ctx* c, int vectors_gathered)
         const double R = double(c->lin.R), nnz = double(c->lin.nnz), D = c->lin.D ? c->lin.D : 1;
         model_add((R + 1) * 4 + (double(c->n) / D + 1) * 4 + 2 * nnz * 4 + 2 * nnz * esz + nnz * esz * (vg + 1) * D +
                   2 * R * esz * D + 2 * R * esz + 2 * double(c->lin.nchunks) * esz * D);
+    }
+    else if (c->term_form == LBFGSX_FORM_DENSE)
+    {
+        const double R = double(c->dense.R), F = double(c->dense.F), D = c->dense.D, n = double(c->n);
+        model_add(2 * R * F * esz + n * esz * vg + 2 * R * D * esz + 2 * R * esz + 2 * double(c->dense.chunks) * n * esz);
     }
 }
 // graph_topology.hip: the incidence list of the context (ctx.hpp: graph_off, graph_inc, graph_E).  build validates the
@@ -266,6 +302,13 @@ int linear_topology_read(lbfgsx_ctx* c, uint32_t* colptr, int32_t* trow, uint32_
                          uint32_t* chunk);
 void linear_topology_free(lbfgsx_ctx* c);
 int linear_long_launch(lbfgsx_ctx* c);
+// dense_topology.hip: the matrix of a dense linear-model objective (ctx.hpp: dense).  A host matrix is copied, compactly
+// (lda = F), into an array the context owns; a device matrix is used in place.  lanes: 0 = by the rule (the largest power of
+// two <= F, at most 64: linear_lanes_rule with nnz / R = F).  read: w (R*D), v (R), part (chunks*n), any of them null
+constexpr int kDenseChunk = 256;  // C: the consecutive rows whose products one partial sums
+int dense_topology_build(lbfgsx_ctx* c, int64_t R, int D, const void* A, int64_t lda, int on_device, int lanes);
+int dense_topology_read(lbfgsx_ctx* c, void* w, void* v, void* part);
+void dense_topology_free(lbfgsx_ctx* c);
 inline bool term_bound(const lbfgsx_ctx* c, int objective) { return objective == LBFGSX_OBJ_BOUND && c->term != nullptr; }
 // one launch of loaded kernel `which` of the bound objective on the context's stream, block of kBlock threads; params as
 // hipModuleLaunchKernel takes them (one pointer per kernel argument)
@@ -273,38 +316,63 @@ int jit_launch(lbfgsx_ctx* c, int which, int grid, void** params);
 
 // ---- a linear-model objective's launches ahead of its column pass, on the same stream with no host wait in between: the
 // row pass (k_lin_rows over x, or k_lin_rows_trial over xp + step*d), then the long-column launch if the matrix has a long
-// column.  Nothing for the other forms.
+// column.  A dense linear-model objective's: the row pass, then the partial pass.  Nothing for the other forms.
+inline int linear_rows_grid(int64_t R, int L)
+{
+    const int64_t rpb = kBlock / L, b = (R + rpb - 1) / rpb;
+    return int(b < 1 ? 1 : (b > kGridCap ? kGridCap : b));
+}
 inline int linear_rows_grid(const lbfgsx_ctx* c)
 {
-    const int64_t rpb = kBlock / c->lin.L, b = (c->lin.R + rpb - 1) / rpb;
-    return int(b < 1 ? 1 : (b > kGridCap ? kGridCap : b));
+    return c->term_form == LBFGSX_FORM_DENSE ? linear_rows_grid(c->dense.R, c->dense.L) : linear_rows_grid(c->lin.R, c->lin.L);
+}
+// the blocks of k_dense_partials: one per work item (kBlock / S chunks x S packs of W columns, S = the next power of two >=
+// the packs of a row, at most kBlock: linear_dense_kernels.cuh), which the kernel strides over past the cap
+constexpr int64_t kDensePartialGridCap = 1 << 20;
+inline int dense_partials_grid(const lbfgsx_ctx* c)
+{
+    const int64_t W = 16 / c->esz, packs = (c->dense.F + W - 1) / W;
+    int64_t S = 1;
+    while (S < kBlock && S < packs)
+        S *= 2;
+    const int64_t cpb = kBlock / S, items = ((c->dense.chunks + cpb - 1) / cpb) * ((packs + S - 1) / S);
+    return int(items > kDensePartialGridCap ? kDensePartialGridCap : items);
 }
 // the column pass strides over v[R] as well as over the n coordinates: its grid covers the longer of the two
 inline int linear_col_grid(const lbfgsx_ctx* c, int grid)
 {
-    if (!form_is_linear(c->term_form))
+    if (!form_is_linear(c->term_form) && c->term_form != LBFGSX_FORM_DENSE)
         return grid;
-    const int gr = c->grid_for(c->lin.R);
+    const int gr = c->grid_for(c->term_form == LBFGSX_FORM_DENSE ? c->dense.R : c->lin.R);
     return gr > grid ? gr : grid;
+}
+// what follows a row pass ahead of the column pass
+template <class T>
+inline int linear_mid_launch(lbfgsx_ctx* c, BoundArgs<T>& obj)
+{
+    if (c->term_form != LBFGSX_FORM_DENSE)
+        return linear_long_launch(c);
+    void* params[] = {obj.ptr};
+    return jit_launch(c, JIT_K_DENSE_PARTIALS, dense_partials_grid(c), params);
 }
 template <class T>
 inline int linear_pre_eval(lbfgsx_ctx* c, BoundArgs<T>& obj, const T* x)
 {
-    if (!form_is_linear(c->term_form))
+    if (!form_is_linear(c->term_form) && c->term_form != LBFGSX_FORM_DENSE)
         return LBFGSX_OK;
     objective_model_add<T>(c, 1);
     void* params[] = {&x, obj.ptr};
     const int rc = jit_launch(c, JIT_K_LIN_ROWS, linear_rows_grid(c), params);
-    return rc ? rc : linear_long_launch(c);
+    return rc ? rc : linear_mid_launch<T>(c, obj);
 }
 template <class T>
 inline int linear_pre_trial(lbfgsx_ctx* c, BoundArgs<T>& obj, const T* xp, const T* d, T step)
 {
-    if (!form_is_linear(c->term_form))
+    if (!form_is_linear(c->term_form) && c->term_form != LBFGSX_FORM_DENSE)
         return LBFGSX_OK;
     void* params[] = {&xp, &d, &step, obj.ptr};
     const int rc = jit_launch(c, JIT_K_LIN_ROWS_TRIAL, linear_rows_grid(c), params);
-    return rc ? rc : linear_long_launch(c);
+    return rc ? rc : linear_mid_launch<T>(c, obj);
 }
 
 }  // namespace lbfgsx

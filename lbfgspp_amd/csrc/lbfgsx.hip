@@ -475,6 +475,7 @@ void lbfgsx_destroy(lbfgsx_ctx* c)
     (void) hipFree(c->graph_off);
     (void) hipFree(c->graph_inc);
     lbfgsx::linear_topology_free(c);
+    lbfgsx::dense_topology_free(c);
     (void) hipFree(c->S);
     (void) hipFree(c->Y);
     (void) hipFree(c->sc);

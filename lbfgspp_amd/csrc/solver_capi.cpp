@@ -48,6 +48,9 @@ struct lbfgsx_solver
         const int32_t *rowptr = nullptr, *col = nullptr;
         const void* val = nullptr;
         int lanes = 0;
+        // a dense linear-model objective's matrix in place of all of the above (A null: not one): R rows, row stride lda
+        const void* A = nullptr;
+        int64_t lda = 0;
     };
     // rows, cols: the shape of a grid objective, 0 for the other forms; gr: null for every form but a graph objective
     virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const GraphSpec* gr,
@@ -229,13 +232,17 @@ struct LbfgsImpl : lbfgsx_solver
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
         LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
-        if (gr && gr->rowptr)
+        DenseLinearObjective<Scalar> densed(obj);       // binds with the dense matrix when there is one
+        if (gr && gr->A)
+            densed.matrix(gr->R, static_cast<const Scalar*>(gr->A), gr->lda, gr->on_device != 0, gr->lanes);
+        else if (gr && gr->rowptr)
             lined.matrix(gr->R, gr->nnz, gr->rowptr, gr->col, static_cast<const Scalar*>(gr->val), gr->on_device != 0, gr->lanes);
         else if (gr && gr->elems)
             meshed.elements(gr->E, gr->elems, gr->on_device != 0);
         else if (gr)
             graphed.edges(gr->E, gr->ei, gr->ej, gr->on_device != 0);
-        TermObjective<Scalar>& f = (gr && gr->rowptr)  ? static_cast<TermObjective<Scalar>&>(lined)
+        TermObjective<Scalar>& f = (gr && gr->A)       ? static_cast<TermObjective<Scalar>&>(densed)
+                                   : (gr && gr->rowptr) ? static_cast<TermObjective<Scalar>&>(lined)
                                    : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
                                    : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
                                                        : shaped;
@@ -350,13 +357,17 @@ struct LbfgsbImpl : lbfgsx_solver
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
         LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
-        if (gr && gr->rowptr)
+        DenseLinearObjective<Scalar> densed(obj);       // binds with the dense matrix when there is one
+        if (gr && gr->A)
+            densed.matrix(gr->R, static_cast<const Scalar*>(gr->A), gr->lda, gr->on_device != 0, gr->lanes);
+        else if (gr && gr->rowptr)
             lined.matrix(gr->R, gr->nnz, gr->rowptr, gr->col, static_cast<const Scalar*>(gr->val), gr->on_device != 0, gr->lanes);
         else if (gr && gr->elems)
             meshed.elements(gr->E, gr->elems, gr->on_device != 0);
         else if (gr)
             graphed.edges(gr->E, gr->ei, gr->ej, gr->on_device != 0);
-        TermObjective<Scalar>& f = (gr && gr->rowptr)  ? static_cast<TermObjective<Scalar>&>(lined)
+        TermObjective<Scalar>& f = (gr && gr->A)       ? static_cast<TermObjective<Scalar>&>(densed)
+                                   : (gr && gr->rowptr) ? static_cast<TermObjective<Scalar>&>(lined)
                                    : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
                                    : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
                                                        : shaped;
@@ -949,6 +960,8 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_LINEAR_MULTI)
             throw std::invalid_argument("a multi-output linear-model objective is minimised with its matrix: "
                                         "lbfgsx_solver_minimize_linear");
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_DENSE)
+            throw std::invalid_argument("a dense linear-model objective is minimised with its matrix: lbfgsx_solver_minimize_dense");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_CHAIN)
         {
             if (n < K)
@@ -1101,6 +1114,48 @@ int lbfgsx_solver_minimize_linear(lbfgsx_solver* s, const lbfgsx_objective* obj,
     lbfgsx_solver::GraphSpec gr;
     gr.E = 0, gr.ei = gr.ej = nullptr, gr.on_device = matrix_on_device, gr.counts = counts, gr.elems = nullptr;
     gr.R = R, gr.nnz = nnz, gr.rowptr = rowptr, gr.col = col, gr.val = val, gr.lanes = lanes;
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+}
+
+int lbfgsx_solver_minimize_dense(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, const void* A, int64_t lda,
+                                 int a_on_device, int lanes, const void* const p[4], int host_mask, const int64_t counts[4],
+                                 const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
+                                 lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    const int bad = guarded(out, [&]() {
+        if (!s || !obj || n <= 0)
+            throw std::invalid_argument("lbfgsx_solver_minimize_dense: invalid argument");
+        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_DENSE)
+            throw std::invalid_argument("lbfgsx_solver_minimize_dense: the handle is not a dense linear-model objective "
+                                        "(lbfgsx_objective_compile_dense)");
+        const int D = lbfgsx_objective_dim(obj);
+        if (n % D != 0)
+            throw std::invalid_argument("dense linear-model objective: n = " + std::to_string(n) + " is not a multiple of D = " +
+                                        std::to_string(D) + ": x holds the D weights of each feature");
+        if (lbfgsx_objective_dtype(obj) != s->dtype)
+            throw std::invalid_argument("lbfgsx_solver_minimize_dense: the objective was compiled for the other dtype");
+        if (R < 1)
+            throw std::invalid_argument("dense linear-model objective: R = " + std::to_string(R) +
+                                        ": a dense linear-model objective has at least one row (R >= 1)");
+        if (!A)
+            throw std::invalid_argument("dense linear-model objective: A is null: a dense linear-model objective has its R x F "
+                                        "matrix (R = " + std::to_string(R) + ")");
+        if (lda < n / D)
+            throw std::invalid_argument("dense linear-model objective: lda = " + std::to_string(lda) + " is less than F = n / D = " +
+                                        std::to_string(n / D) + ": a row of the matrix holds its F values first");
+    });
+    if (bad)
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_dense: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    lbfgsx_solver::GraphSpec gr;
+    gr.E = 0, gr.ei = gr.ej = nullptr, gr.on_device = a_on_device, gr.counts = counts, gr.elems = nullptr;
+    gr.R = R, gr.A = A, gr.lda = lda, gr.lanes = lanes;
     return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 }

@@ -11,7 +11,8 @@ std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device ob
 `GraphObjective(edge_body, edges)` for edge terms over an index list,
 `MeshObjective(elem_body, elements, dim)` for K-node elements with vector unknowns, or
 `LinearObjective(row_body, (rowptr, col, val), n)` for a linear model over a sparse matrix, or
-`MultiLinearObjective(row_body, (rowptr, col, val), features, outputs)` for one with several outputs per row)
+`MultiLinearObjective(row_body, (rowptr, col, val), features, outputs)` for one with several outputs per row, or
+`DenseLinearObjective(row_body, matrix, outputs)` for one over a dense matrix)
 or the caller's own callable, `DeviceObjective(fn)`: fn(x, grad) -> float on torch
 tensors that alias the library's device vectors.  All O(n) work of the solver runs in the HIP library, Python only passes
 pointers.  There is no CPU fallback: without the built extension or a GPU these calls raise.
@@ -548,6 +549,100 @@ class MultiLinearObjective(LinearObjective):
         return (n, self.F, self.R, self.R * self.D)
 
 
+class DenseLinearObjective(TermObjective):
+    """The multi-output linear model over a DENSE matrix: x holds an F x D weight matrix, feature-major (x[j*D + c],
+    n = F * outputs), A is a dense R x F matrix, Z = A X, and
+    f(x) = sum over coordinates i of psi(x[i]; i) + sum over rows r of phi(Z[r, 0..D); r) -- logistic, softmax, Poisson and
+    least-squares regression on tabular features, non-negative least squares under LBFGSBSolver (include/lbfgsx.h, "dense
+    linear-model objectives").  The bodies are a MultiLinearObjective's: row_body sees T, constexpr int D, const T z[D],
+    T dz[D] (to fill), int64_t r, p0..p3 and c[8] and returns phi (outputs = 1: z[0] and dz[0]); coord_body (optional) sees
+    const T x[1], T g[1], int64_t i.
+
+        logit = DenseLinearObjective("const T m = p0[r] * z[0]; const T e = exp(T(0) - m);"
+                                     "dz[0] = T(0) - p0[r] * (e / (T(1) + e)); return log(T(1) + e);",
+                                     A, data=(labels,), scalars=(1e-3,),
+                                     coord_body="g[0] = c[0] * x[0]; return T(0.5) * (c[0] * (x[0] * x[0]));")
+
+    matrix: a 2-D numpy array (converted to the solver's dtype and copied to the device at every minimise), or a 2-D torch
+    tensor on the solver's device with unit column stride, of the solver's dtype, which is used IN PLACE with lda = its row
+    stride: it is not copied, and stays alive and unchanged while a minimise runs.  1 <= outputs <= 16.  lanes: the lanes that
+    share a row in the row pass, 0 = by the library's rule, otherwise a power of two <= 64.  Each data[k] has n, F, R or R * D
+    elements.  Otherwise a MultiLinearObjective's interface; usable wherever one is, refused where one is."""
+    _NAME = "DenseLinearObjective"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_dense", "lbfgsx_objective_source_dense"
+
+    def __init__(self, row_body, matrix, outputs=1, coord_body=None, data=(), scalars=(), lanes=0):
+        self.D = int(outputs)
+        if self.D < 1 or self.D > 16:
+            raise ValueError("DenseLinearObjective: D = %d is not supported: a row has D = 1 .. 16 outputs" % self.D)
+        if lanes not in (0, 1, 2, 4, 8, 16, 32, 64):
+            raise ValueError("DenseLinearObjective: lanes = %r: the lanes that share a row are 0 (by the rule) or a power of two "
+                             "in 1..64" % (lanes,))
+        self.lanes = int(lanes)
+        self.on_device = _is_torch(matrix) and matrix.is_cuda
+        if self.on_device:
+            torch = L.require_torch("DenseLinearObjective with a matrix on the device")
+            if matrix.dim() != 2:
+                raise ValueError("DenseLinearObjective: matrix on the device must be a 2-D tensor, not one of %d dimensions"
+                                 % matrix.dim())
+            if matrix.dtype not in (torch.float32, torch.float64):
+                raise ValueError("DenseLinearObjective: matrix on the device has dtype %s: it must be float32 or float64, the "
+                                 "solver's" % matrix.dtype)
+            if matrix.shape[0] >= 1 and matrix.shape[1] >= 1 and (
+                    (matrix.shape[1] > 1 and matrix.stride(1) != 1) or (matrix.shape[0] > 1 and matrix.stride(0) < matrix.shape[1])):
+                raise ValueError("DenseLinearObjective: matrix on the device has strides (%d, %d): it must be row-major with unit "
+                                 "column stride and a row stride >= its %d columns" % (matrix.stride(0), matrix.stride(1),
+                                                                                     matrix.shape[1]))
+            self.matrix = matrix
+            self.lda = int(matrix.stride(0)) if matrix.shape[0] > 1 else int(matrix.shape[1])
+        else:
+            a = matrix.detach().cpu().numpy() if _is_torch(matrix) else np.asarray(matrix)
+            if a.ndim != 2 or a.dtype.kind not in "fiu":
+                raise ValueError("DenseLinearObjective: matrix must be a 2-D array of numbers, not %s with %d dimensions"
+                                 % (a.dtype, a.ndim))
+            self.matrix = np.ascontiguousarray(a, np.float64 if a.dtype != np.float32 else np.float32)
+            self.lda = int(a.shape[1])
+        self.R, self.F = int(self.matrix.shape[0]), int(self.matrix.shape[1])
+        if self.R < 1 or self.F < 1:
+            raise ValueError("DenseLinearObjective: matrix has shape (%d, %d): a model has at least one row and one feature"
+                             % (self.R, self.F))
+        self.n = self.F * self.D
+        self.body, self.K = str(row_body), 1
+        self.coord_body = None if not coord_body else str(coord_body)
+        self._h = {}
+        self.set_data(*data)
+        self.set_scalars(*scalars)
+
+    def _form_args(self):
+        return (self.D, self.coord_body.encode() if self.coord_body else None)
+
+    def _check_n(self, n):
+        if n % self.D:
+            raise ValueError("DenseLinearObjective: n = %d is not a multiple of D = %d: x holds the D weights of each feature"
+                             % (n, self.D))
+        if n != self.n:
+            raise ValueError("DenseLinearObjective: the model has n = %d * %d = %d weights and x has %d elements"
+                             % (self.F, self.D, self.n, n))
+
+    def _data_sizes(self, n):
+        return (n, self.F, self.R, self.R * self.D)
+
+    def _matrix_args(self, solver):
+        """(A as an address, lda, on_device, what to keep alive) for a solver of the given dtype and device"""
+        if self.on_device:
+            torch = L.require_torch("DenseLinearObjective with a matrix on the device")
+            want = torch.float64 if solver.dtype == L.F64 else torch.float32
+            if self.matrix.dtype != want:
+                raise ValueError("DenseLinearObjective: matrix on the device has dtype %s and the solver %s: a device matrix is "
+                                 "used in place, not converted" % (self.matrix.dtype, want))
+            if self.matrix.device.index != solver.device:
+                raise ValueError("DenseLinearObjective: the matrix must be on cuda:%d" % solver.device)
+            torch.cuda.current_stream().synchronize()  # the matrix is complete when the library reads it
+            return self.matrix.data_ptr(), self.lda, 1, (self.matrix,)
+        a = np.ascontiguousarray(self.matrix, _NP[solver.dtype])
+        return a.ctypes.data, self.lda, 0, (a,)
+
+
 class TraceBuffer:
     """Per-evaluation record (fx and x[::stride]) for the parity tests."""
 
@@ -733,7 +828,12 @@ class _SolverBase:
             torch.cuda.current_stream().synchronize()  # the data arrays are complete when the library reads them
         tail = (C.byref(ptrs), mask, C.byref(cs), self._ptr(x), self._ptr(lb), self._ptr(ub), C.byref(trace.c) if trace else None,
                 C.byref(res))
-        if isinstance(f, LinearObjective):
+        if isinstance(f, DenseLinearObjective):
+            ap, lda, on_dev, keep_m = f._matrix_args(self)
+            rc = self._sol.lbfgsx_solver_minimize_dense(self._h, h, n, f.R, ap, lda, on_dev, f.lanes, tail[0], mask,
+                                                        C.byref(counts), *tail[2:])
+            del keep_m
+        elif isinstance(f, LinearObjective):
             rp, cp, vp, on_dev, keep_m = f._matrix_args(self)
             rc = self._sol.lbfgsx_solver_minimize_linear(self._h, h, n, f.R, f.nnz, rp, cp, vp, on_dev, f.lanes, tail[0], mask,
                                                          C.byref(counts), *tail[2:])
@@ -768,7 +868,8 @@ class _SolverBase:
         if not hasattr(f, "objective"):
             raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body), "
                             "GridObjective(body, shape), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim), "
-                            "LinearObjective(row_body, matrix, n), MultiLinearObjective(row_body, matrix, features, outputs) or DeviceObjective(fn)")
+                            "LinearObjective(row_body, matrix, n), MultiLinearObjective(row_body, matrix, features, outputs), "
+                            "DenseLinearObjective(row_body, matrix, outputs) or DeviceObjective(fn)")
         res = L.Result()
         a = None if f.a is None else np.ascontiguousarray(f.a, _NP[self.dtype])
         b = None if f.b is None else np.ascontiguousarray(f.b, _NP[self.dtype])
