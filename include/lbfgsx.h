@@ -383,6 +383,8 @@ int lbfgsx_objective_dim(const lbfgsx_objective* obj);
  * k_lin_b_dg_maxstep_trial: the arguments, tile order, reductions and completion word of the other forms' kernels) forms
  * the gradient per owned coordinate and adds v to f.  Its grid covers the longer of n and R.  A matrix with a long column
  * has a third launch between them, k_lin_long_cols (one block per chunk, precompiled in the library).  No float atomic.
+ * The row pass and the column walk are written once, for D outputs per row (lin_rows over an entry source, lin_coord); this
+ * form is their D = 1, and the multi-output and the dense form below use the same code.
  * lbfgsx_objective_compile_linear caches by (form, both bodies, dtype); the form is LBFGSX_FORM_LINEAR, lbfgsx_objective_K
  * returns 1.  The word asm in either body is refused; the compile log counts lines per body ("row_body", "coord_body").
  * lbfgsx_objective_info's maxima cover all six kernels.
@@ -430,11 +432,12 @@ int lbfgsx_objective_linear_topology(lbfgsx_ctx* c, int64_t info[8], uint32_t* c
  * contribution, +0 without any.  A column with more than C = 4096 entries is long, as in the scalar form: per chunk b and
  * output c the partial part[b*D + c] is formed by the scalar form's 256-thread rule over w[trow[q]*D + c], and the owner adds
  * a column's partials in ascending b.  f, roundings and the trial's gather of xp[i] + step*d[i]: the scalar form's.
- * Kernels (csrc/linear_multi_kernels.cuh): the row pass k_linm_rows / k_linm_rows_trial (L lanes per row, D accumulators per
- * lane, 16-byte loads of a feature's weight row when D*sizeof(T) is a multiple of 16, D cross-lane moves per halving, no LDS,
- * no atomic), the column pass k_linm_eval, k_linm_trial, k_linm_b_eval, k_linm_b_dg_maxstep_trial (a thread owns one 16-byte
- * pack of consecutive coordinates; coordinate i walks the list of feature i / D, so a pack may straddle two features), and
- * k_lin_long_cols_multi, one block per (chunk, output), precompiled, the third launch only when the matrix has a long column.
+ * Kernels (csrc/linear_multi_kernels.cuh; the bodies are the scalar form's, csrc/linear_kernels.cuh, with D from the
+ * generated struct): the row pass k_linm_rows / k_linm_rows_trial (L lanes per row, D accumulators per lane, 16-byte loads of
+ * a feature's weight row when D*sizeof(T) is a multiple of 16, D cross-lane moves per halving, no LDS, no atomic), the column
+ * pass k_linm_eval, k_linm_trial, k_linm_b_eval, k_linm_b_dg_maxstep_trial (a thread owns one 16-byte pack of consecutive
+ * coordinates; coordinate i walks the list of feature i / D, so a pack may straddle two features), and the scalar form's
+ * k_lin_long_cols with one block per (chunk, output), precompiled, the third launch only when the matrix has a long column.
  * lbfgsx_objective_compile_linear_multi caches by (form, both bodies, dtype, D); the form is LBFGSX_FORM_LINEAR_MULTI,
  * lbfgsx_objective_K returns 1 and lbfgsx_objective_dim D.  The handle is bound with lbfgsx_objective_bind_linear (and minimised
  * with lbfgsx_solver_minimize_linear), which accept a handle of either linear form; for this one they refuse n % D != 0 with
@@ -471,8 +474,9 @@ long long lbfgsx_objective_source_linear_multi(int dtype, int D, const char* coo
  *   f         the order-independent compensated sum of the other forms over all psi and phi values.
  *   trial     the weight used is xp[i] + step*d[i], the statement i's owner executes, never a read of the x the launch writes.
  * Kernels (csrc/linear_dense_kernels.cuh), three launches per evaluation on one stream, no host wait: the row pass
- * k_dense_rows / k_dense_rows_trial (kBlock / L rows per block step, the lanes of a row read consecutive elements, D
- * accumulators per lane, cross-lane halvings, no LDS, no atomic), the partial pass k_dense_partials (A read a second time,
+ * k_dense_rows / k_dense_rows_trial (the sparse forms' row pass with the dense row as its entry source: kBlock / L rows per
+ * block step, the lanes of a row read consecutive elements, D accumulators per lane, cross-lane halvings, no LDS, no atomic),
+ * the partial pass k_dense_partials (A read a second time,
  * column-wise without a strided access: a thread owns a 16-byte pack of consecutive columns and walks the C rows of a chunk
  * with W*D accumulators; small F packs several chunks into a block) and the column pass k_dense_eval, k_dense_trial,
  * k_dense_b_eval, k_dense_b_dg_maxstep_trial (a thread owns a 16-byte pack of coordinates and adds their partials).

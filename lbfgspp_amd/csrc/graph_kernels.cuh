@@ -116,37 +116,7 @@ struct GraphFamily
     }
 };
 
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_graph_eval(const T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                       T* __restrict__ out)
-{
-    own_eval<T, GraphFamily, OBJ, false>(x, g, nullptr, nullptr, n, obj, ws, out);
-}
-
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_graph_b_eval(const T* __restrict__ x, T* __restrict__ g, const T* __restrict__ lb,
-                                                         const T* __restrict__ ub, int64_t n, OBJ obj, RedWs ws,
-                                                         T* __restrict__ out)
-{
-    own_eval<T, GraphFamily, OBJ, true>(x, g, lb, ub, n, obj, ws, out);
-}
-
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_graph_trial(const T* __restrict__ xp, const T* __restrict__ d, T step,
-                                                        T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                        T* __restrict__ out, int rev)
-{
-    own_trial<T, GraphFamily, OBJ, false>(xp, nullptr, d, nullptr, nullptr, step, x, g, n, obj, ws, out, rev);
-}
-
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_graph_b_dg_maxstep_trial(const T* __restrict__ xp, const T* __restrict__ g0,
-                                                                     const T* __restrict__ d, const T* __restrict__ lb,
-                                                                     const T* __restrict__ ub, T step, T* __restrict__ x,
-                                                                     T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                                     T* __restrict__ out, int rev)
-{
-    own_trial<T, GraphFamily, OBJ, true>(xp, g0, d, lb, ub, step, x, g, n, obj, ws, out, rev);
-}
+// k_graph_eval, k_graph_trial, k_graph_b_eval, k_graph_b_dg_maxstep_trial
+LBFGSX_OWN_KERNELS(k_graph, GraphFamily)
 
 }  // namespace lbfgsx

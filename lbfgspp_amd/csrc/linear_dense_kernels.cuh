@@ -2,7 +2,8 @@
 //     f(x) = sum over coordinates i of psi(x[i]; i)  +  sum over rows r of phi(Z[r, 0..D); r),      Z = A X,
 // A dense, R x F, row-major with a row stride of lda >= F elements; x holds the F x D weight matrix X feature-major,
 // x[j*D + c], n = F*D; D = OBJ::D is a compile-time constant of the generated struct, 1 .. 16 (include/lbfgsx.h, "dense
-// linear-model objectives").  The bodies are the multi-output form's (linear_multi_kernels.cuh).
+// linear-model objectives").  The bodies are the multi-output form's (linear_multi_kernels.cuh), and the row pass is the
+// sparse forms' own (lin_rows, linear_kernels.cuh) over the dense row as its entry source (LinDense).
 //
 // An evaluation is three launches on one stream, no host wait in between:
 //   the ROW pass     k_dense_rows / k_dense_rows_trial   Z[r, :], then w[r*D + c] = dphi/dz_c and v[r] = phi
@@ -16,12 +17,10 @@
 // k_dense_partials holds no caller text; it is instantiated in the generated unit all the same, so that D stays a
 // compile-time constant without a precompiled copy per (T, D).
 //
-// Row sums.  The sparse forms' rule on the dense row: L lanes share a row (L a power of two <= 64, fixed at bind), lane l
-// takes columns l, l+L, .. in ascending order, s_l[c] = A[r,k]*x[k*D + c] for its first column and s_l[c] = s_l[c] + .. after
-// it, +0 without one; then s_l[c] = s_l[c] + s_{l+h}[c] for l < h, h = L/2 .. 1, by cross-lane moves: no LDS, no atomic.  The
-// lanes of a row read consecutive elements of it.  linm_group<T, D>() columns are in flight together, the multi-output form's
-// register reasoning for the 2*D values of the trial form.  Lane 0 runs the row body.  The same matrix given to the sparse
-// forms as CSR with every entry stored, and the same L, gives the same bits.
+// Row sums.  lin_rows on the dense row: L lanes share a row (L a power of two <= 64, fixed at bind), lane l takes columns
+// l, l+L, .. in ascending order, every column an entry (k, A[r,k]); the lanes of a row read consecutive elements of it.  The
+// statements being the sparse forms', the same matrix given to them as CSR with every entry stored, and the same L, gives
+// the same bits.
 //
 // Partials.  Rows are cut into chunks of C = kDenseChunk consecutive rows (the last one shorter).  A thread owns one 16-byte
 // pack of W consecutive columns and walks the rows of one chunk in ascending r with W*D accumulators, started from the first
@@ -31,8 +30,8 @@
 // with S the next power of two >= P, so a small F leaves few lanes idle.  A is read a second time here, never at a stride.
 //
 // Gradient.  A thread owns one 16-byte pack of consecutive coordinates (the frame's D = 1 ownership); coordinate i = j*D + c
-// takes psi's g[0] if there is a coordinate body, then part[b*n + i] in ascending b, started from the first contribution,
-// kLinGroup loads ahead of the adds.  Every coordinate has the same list, (0, chunks): the family's kRange.
+// takes psi's g[0] if there is a coordinate body (lin_coord_start, as in the sparse forms), then part[b*n + i] in ascending b,
+// started from the first contribution, kLinGroup loads ahead of the adds.  Every coordinate has the same list, (0, chunks): the family's kRange.
 //
 // f.  As the sparse forms: psi's values by the owners, and every row's value from v[R] by the same launch.
 //
@@ -46,97 +45,44 @@ namespace lbfgsx {
 constexpr int kDenseAhead = 4;  // rows whose loads of A are in flight together in the partial pass
 
 // ---------------------------------------------------------------- the row pass
-// ld(j, xj) fills xj[0..D) with the weight row of feature j -- from memory in k_dense_rows, recomputed from xp and d in
-// k_dense_rows_trial
-template <class T, class OBJ, class LD>
-__device__ __forceinline__ void dense_rows(const OBJ& obj, LD ld)
+// the entry source of a dense matrix (lin_rows, linear_kernels.cuh): lane `lane` of a live row starts at column `lane` and
+// the row ends before F; entry k of the row is (k, A[r*lda + k]), read only if it is `in` the row
+template <class T>
+struct LinDense
 {
-    constexpr int D = OBJ::D, G = linm_group<T, D>();
-    const int L = obj.L;
-    const int rpb = kBlock / L;
-    const int lane = int(threadIdx.x) & (L - 1);
-    const int slot = int(threadIdx.x) / L;
-    const int64_t F = obj.F;
-    for (int64_t r0 = int64_t(blockIdx.x) * rpb; r0 < obj.R; r0 += int64_t(gridDim.x) * rpb)
+    typedef int64_t col_t;
+    const T* __restrict__ A;
+    const T* __restrict__ row;
+    int64_t F, lda;
+    template <class OBJ>
+    __device__ __forceinline__ explicit LinDense(const OBJ& obj) : A(obj.A), row(obj.A), F(obj.F), lda(obj.lda)
     {
-        const int64_t r = r0 + slot;
-        const bool live = r < obj.R;
-        const T* __restrict__ a = obj.A + (live ? r : 0) * obj.lda;
-        int64_t k = live ? lane : 0;
-        const int64_t k1 = live ? F : 0;
-        T s[D];
-#pragma unroll
-        for (int c = 0; c < D; c++)
-            s[c] = T(0);
-        bool has = false;
-        for (; k < k1; k += int64_t(G) * L)
-        {
-            T vj[G], xj[G][D];
-#pragma unroll
-            for (int j = 0; j < G; j++)
-            {
-                vj[j] = T(0);
-                if (k + int64_t(j) * L < k1)
-                    vj[j] = a[k + int64_t(j) * L];
-            }
-#pragma unroll
-            for (int j = 0; j < G; j++)
-                if (k + int64_t(j) * L < k1)
-                    ld(k + int64_t(j) * L, xj[j]);
-#pragma unroll
-            for (int j = 0; j < G; j++)
-                if (k + int64_t(j) * L < k1)
-                {
-#pragma unroll
-                    for (int c = 0; c < D; c++)
-                    {
-                        const T prod = vj[j] * xj[j][c];
-                        s[c] = has ? s[c] + prod : prod;
-                    }
-                    has = true;
-                }
-        }
-        // lanes l >= h compute values nobody reads; all lanes of the wavefront take part in every move
-        for (int h = L >> 1; h >= 1; h >>= 1)
-        {
-#pragma unroll
-            for (int c = 0; c < D; c++)
-                s[c] = s[c] + __shfl_down(s[c], unsigned(h), L);
-        }
-        if (live && lane == 0)
-        {
-            T dz[D];
-#pragma unroll
-            for (int c = 0; c < D; c++)
-                dz[c] = T(0);
-            const T value = obj.row(s, dz, r);
-#pragma unroll
-            for (int c = 0; c < D; c++)
-                obj.w[r * D + c] = dz[c];
-            obj.v[r] = value;
-        }
     }
-}
+    __device__ __forceinline__ void span(int64_t r, bool live, int lane, int64_t& k, int64_t& k1)
+    {
+        row = A + (live ? r : 0) * lda;
+        k = live ? lane : 0;
+        k1 = live ? F : 0;
+    }
+    __device__ __forceinline__ void entry(int64_t k, bool in, col_t& c, T& v) const
+    {
+        c = k;
+        v = T(0);
+        if (in)
+            v = row[k];
+    }
+};
 
 template <class T, class OBJ>
 __global__ void __launch_bounds__(kBlock) k_dense_rows(const T* __restrict__ x, OBJ obj)
 {
-    constexpr int D = OBJ::D;
-    dense_rows<T>(obj, [&](int64_t j, T(&xj)[D]) __attribute__((always_inline)) { linm_load<T, D>(x + j * D, xj); });
+    lin_rows<T, LinDense<T>>(obj, LinGather<T, OBJ::D>{x});
 }
 
 template <class T, class OBJ>
 __global__ void __launch_bounds__(kBlock) k_dense_rows_trial(const T* __restrict__ xp, const T* __restrict__ d, T step, OBJ obj)
 {
-    constexpr int D = OBJ::D;
-    dense_rows<T>(obj, [&](int64_t j, T(&xj)[D]) __attribute__((always_inline)) {
-        T a[D], b[D];
-        linm_load<T, D>(xp + j * D, a);
-        linm_load<T, D>(d + j * D, b);
-#pragma unroll
-        for (int c = 0; c < D; c++)
-            xj[c] = a[c] + step * b[c];
-    });
+    lin_rows<T, LinDense<T>>(obj, LinGatherTrial<T, OBJ::D>{xp, d, step});
 }
 
 // ---------------------------------------------------------------- the partial pass
@@ -243,16 +189,7 @@ __device__ __forceinline__ T dense_coord(const OBJ& obj, int64_t i, T xi, uint32
 {
     constexpr int G = kLinGroup;
     const int64_t n = obj.F * OBJ::D;
-    T gv = T(0);
-    bool has = false;
-    if (OBJ::kCoord)
-    {
-        const T tx[1] = {xi};
-        T tg[1];
-        fx.add(obj.coord(tx, tg, i));
-        gv = tg[0];
-        has = true;
-    }
+    LinSum<T> gv = lin_coord_start<T>(obj, i, xi, fx);
     const T* __restrict__ part = obj.part;
     for (int64_t q = lo; q < int64_t(hi); q += G)
     {
@@ -267,24 +204,15 @@ __device__ __forceinline__ T dense_coord(const OBJ& obj, int64_t i, T xi, uint32
 #pragma unroll
         for (int t = 0; t < G; t++)
             if (q + t < int64_t(hi))
-            {
-                gv = has ? gv + pj[t] : pj[t];
-                has = true;
-            }
+                gv.add(pj[t]);
     }
-    return gv;
+    return gv.value;
 }
 
-// the frame's family (own_frame.cuh): n coordinates that all walk the chunks (0, chunks), and every row's value as the extra pass
-struct DenseFamily
+// the frame's family (own_frame.cuh): n coordinates that all walk the chunks (0, chunks)
+struct DenseFamily : LinFamilyBase
 {
-    static constexpr int D = 1, U = kLinTrialU;
     static constexpr bool kRange = true;
-    template <class OBJ>
-    static __device__ __forceinline__ int64_t nodes(const OBJ&, int64_t n)
-    {
-        return n;
-    }
     template <class OBJ>
     static __device__ __forceinline__ void range(const OBJ& obj, int64_t, uint32_t& lo, uint32_t& hi)
     {
@@ -297,44 +225,9 @@ struct DenseFamily
     {
         gi[0] = dense_coord<T>(obj, i, xi[0], lo, hi, fx);
     }
-    template <class T, class OBJ, class A>
-    static __device__ __forceinline__ void extra(const OBJ& obj, A& fx)
-    {
-        lin_row_values<T>(obj, fx);
-    }
 };
 
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_dense_eval(const T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                       T* __restrict__ out)
-{
-    own_eval<T, DenseFamily, OBJ, false>(x, g, nullptr, nullptr, n, obj, ws, out);
-}
-
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_dense_b_eval(const T* __restrict__ x, T* __restrict__ g, const T* __restrict__ lb,
-                                                         const T* __restrict__ ub, int64_t n, OBJ obj, RedWs ws,
-                                                         T* __restrict__ out)
-{
-    own_eval<T, DenseFamily, OBJ, true>(x, g, lb, ub, n, obj, ws, out);
-}
-
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_dense_trial(const T* __restrict__ xp, const T* __restrict__ d, T step,
-                                                        T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                        T* __restrict__ out, int rev)
-{
-    own_trial<T, DenseFamily, OBJ, false>(xp, nullptr, d, nullptr, nullptr, step, x, g, n, obj, ws, out, rev);
-}
-
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_dense_b_dg_maxstep_trial(const T* __restrict__ xp, const T* __restrict__ g0,
-                                                                     const T* __restrict__ d, const T* __restrict__ lb,
-                                                                     const T* __restrict__ ub, T step, T* __restrict__ x,
-                                                                     T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                                     T* __restrict__ out, int rev)
-{
-    own_trial<T, DenseFamily, OBJ, true>(xp, g0, d, lb, ub, step, x, g, n, obj, ws, out, rev);
-}
+// k_dense_eval, k_dense_trial, k_dense_b_eval, k_dense_b_dg_maxstep_trial
+LBFGSX_OWN_KERNELS(k_dense, DenseFamily)
 
 }  // namespace lbfgsx

@@ -1,6 +1,8 @@
 // lbfgspp_amd/csrc/linear_kernels.cuh -- the evaluation kernels for a LINEAR-MODEL objective
 //     f(x) = sum over coordinates j of psi(x[j]; j)  +  sum over rows r of phi(z_r; r),      z = A x,
-// A sparse, R x n, given in CSR (include/lbfgsx.h, "linear-model objectives").
+// A sparse, R x n, given in CSR (include/lbfgsx.h, "linear-model objectives"), and the row pass and the column walk that the
+// multi-output and the dense form (linear_multi_kernels.cuh, linear_dense_kernels.cuh) share with it: a row has D outputs,
+// D = OBJ::D where the generated struct has that member and 1 for the struct of this form, which has none (lin_outputs).
 //
 // An evaluation is two launches on one stream (three when the matrix has a long column, linear_topology.hip):
 //   the ROW pass   k_lin_rows / k_lin_rows_trial      z_r, then w[r] = phi'(z_r) and v[r] = phi(z_r)
@@ -11,97 +13,227 @@
 //     static constexpr bool kCoord;           T coord(const T (&x)[1], T (&g)[1], int64_t i) const;
 //     T row(T z, T& dz, int64_t r) const;     and the members of LinearArgs (launch_args.hpp).
 //
-// Row sum.  L lanes share one row (L a power of two <= 64, fixed at bind, so a group never leaves its wavefront).  Lane l
-// takes the row's entries k0+l, k0+l+L, .. in ascending order, s_l = val[k]*x[col[k]] for its first entry and
-// s_l = s_l + val[k]*x[col[k]] after it; a lane with no entry holds +0.  Then s_l = s_l + s_{l+h} for l < h, h = L/2 .. 1, by
-// cross-lane moves inside the group: no LDS allocation, no atomic, no reduction workspace.  z_r = s_0.  A block handles
-// kBlock / L rows per step and strides over the grid.  In k_lin_rows_trial the gathered value is xp[c] + step*d[c], the
-// statement c's owner executes in the column pass that follows: never a read of the x that pass writes.
+// Row sums (lin_rows, the one row pass of the three forms).  x holds D values per column c of the matrix, x[c*D ..].  L lanes
+// share one row (L a power of two <= 64, fixed at bind, so a group never leaves its wavefront).  Lane l takes the row's
+// entries k0+l, k0+l+L, .. in ascending order, s_l[o] = val[k]*x[col[k]*D + o] for its first entry and s_l[o] = s_l[o] + ..
+// after it; a lane with no entry holds +0.  Then s_l[o] = s_l[o] + s_{l+h}[o] for l < h, h = L/2 .. 1, by D cross-lane moves
+// per halving inside the group: no LDS allocation, no atomic, no reduction workspace.  z_r = s_0, and lane 0 runs the row body.
+// A block handles kBlock / L rows per step and strides over the grid.  Where a row's entries come from is the pass's SRC: CSR
+// here (LinCsr), the dense row in linear_dense_kernels.cuh.  A lane reads the D contiguous values of a column with 16-byte
+// loads when D*sizeof(T) is a multiple of 16 (every such group is then aligned).  linm_group<T, D>() entries are in flight
+// together: as many as keep the gathered values of the trial form (xp and d) within 256 bytes per lane, so D = 16 in f64 does
+// not spill; 4 at D = 1.  In the trial form the gathered value is xp[i] + step*d[i], the statement i's owner executes in the
+// column pass that follows: never a read of the x that pass writes.
 //
-// Gradient.  The thread that owns coordinate j writes grad[j]: psi's g[0] if there is a coordinate body, then tval[q]*w[trow[q]]
-// over the entries q in [colptr[j], colptr[j+1]) of the transposed list (ascending r, the caller's order within one r),
-// started from the first contribution (no leading 0 +); +0 if there is none.  A column with more than C entries is LONG: its
-// chunk partials were written by k_lin_long_cols (linear_topology.hip) and the owner adds them in ascending chunk index
-// instead of walking the entries.  A thread owns the W coordinates of a 16-byte pack; thread 0 of block 0 also owns the
-// coordinates past the last whole pack.  Entry loads are issued in groups of kLinGroup ahead of the w gathers, the gathers
-// ahead of the arithmetic.
+// Gradient (lin_coord, the one column walk of the two sparse forms).  A thread owns the W coordinates of a 16-byte pack;
+// thread 0 of block 0 also owns the coordinates past the last whole pack.  The owner of coordinate i = j*D + o writes grad[i]:
+// psi's g[0] if there is a coordinate body, then tval[q]*w[trow[q]*D + o] over the entries q in [colptr[j], colptr[j+1]) of
+// the transposed list (ascending r, the caller's order within one r), started from the first contribution (no leading 0 +);
+// +0 if there is none.  A column with more than C entries is LONG: its chunk partials part[b*D + o] were written by
+// k_lin_long_cols (linear_topology.hip) and the owner adds them in ascending chunk index b instead of walking the entries.
+// Entry loads are issued in groups of kLinGroup ahead of the w gathers, the gathers ahead of the arithmetic.
 //
 // f.  The owner adds psi's value; the same launch strides over v[R] in packs and adds every row's value to the same
 // order-independent accumulator (reduce.cuh).
 //
-// Every index read here was validated at bind: 0 <= col < n, 0 <= trow < R, list positions in [0, nnz).
+// Every index read here was validated at bind: 0 <= col < n / D, 0 <= trow < R, list positions in [0, nnz).
 #pragma once
 #include "own_frame.cuh"
 
 namespace lbfgsx {
 
-constexpr int kLinGroup = 4;   // entries whose loads are in flight together
+constexpr int kLinGroup = 4;   // entries whose loads are in flight together in the column walk
 constexpr int kLinTrialU = 2;  // the tile depth of the two trial column kernels
 
-// ---------------------------------------------------------------- the row pass
-// ld(c) = x[c] -- from memory in k_lin_rows, recomputed from xp and d in k_lin_rows_trial
-template <class T, class OBJ, class LD>
-__device__ __forceinline__ void lin_rows(const OBJ& obj, LD ld)
+// the outputs of a row: OBJ::D, or 1 for a struct without that member, whose row body takes scalars
+template <class OBJ, class = void>
+struct LinOutputs
 {
-    constexpr int G = kLinGroup;
-    const int L = obj.L;
-    const int rpb = kBlock / L;
-    const int lane = int(threadIdx.x) & (L - 1);
-    const int slot = int(threadIdx.x) / L;
-    const int32_t* __restrict__ rowptr = obj.rowptr;
-    const int32_t* __restrict__ col = obj.col;
-    const T* __restrict__ val = obj.val;
-    for (int64_t r0 = int64_t(blockIdx.x) * rpb; r0 < obj.R; r0 += int64_t(gridDim.x) * rpb)
+    static constexpr int value = 1;
+    static constexpr bool kScalarRow = true;
+};
+template <class OBJ>
+struct LinOutputs<OBJ, decltype(void(OBJ::D))>
+{
+    static constexpr int value = OBJ::D;
+    static constexpr bool kScalarRow = false;
+};
+template <class OBJ>
+constexpr int lin_outputs = LinOutputs<OBJ>::value;
+
+// entries whose loads are in flight together in the row pass
+template <class T, int D>
+__host__ __device__ constexpr int linm_group()
+{
+    return (2 * D * int(sizeof(T)) <= 64) ? 4 : (2 * D * int(sizeof(T)) <= 128) ? 2 : 1;
+}
+
+// ---------------------------------------------------------------- the row pass
+// the D values at p[0..D): 16-byte loads where every group of D is aligned
+template <class T, int D>
+__device__ __forceinline__ void linm_load(const T* __restrict__ p, T (&out)[D])
+{
+    constexpr int W = Vec16<T>::W;
+    if constexpr ((D * int(sizeof(T))) % 16 == 0)
     {
-        const int64_t r = r0 + slot;
-        const bool live = r < obj.R;
-        int64_t k = 0, k1 = 0;
+#pragma unroll
+        for (int j = 0; j < D / W; j++)
+        {
+            const Pack<T> pk = ldv(p, j);
+#pragma unroll
+            for (int k = 0; k < W; k++)
+                out[j * W + k] = pk.e[k];
+        }
+    }
+    else
+    {
+#pragma unroll
+        for (int c = 0; c < D; c++)
+            out[c] = p[c];
+    }
+}
+
+// what the row pass gathers for column j, ld(j, xj): the D values x[j*D ..] from memory ..
+template <class T, int D>
+struct LinGather
+{
+    const T* __restrict__ x;
+    __device__ __forceinline__ void operator()(int64_t j, T (&xj)[D]) const { linm_load<T, D>(x + j * D, xj); }
+};
+// .. and recomputed from xp and d in the trial form
+template <class T, int D>
+struct LinGatherTrial
+{
+    const T* __restrict__ xp;
+    const T* __restrict__ d;
+    T step;
+    __device__ __forceinline__ void operator()(int64_t j, T (&xj)[D]) const
+    {
+        T a[D], b[D];
+        linm_load<T, D>(xp + j * D, a);
+        linm_load<T, D>(d + j * D, b);
+#pragma unroll
+        for (int c = 0; c < D; c++)
+            xj[c] = a[c] + step * b[c];
+    }
+};
+
+// the entry source of a CSR matrix.  span: lane `lane` of row r starts at entry k and the row ends before k1, both 0 for a
+// row that is not `live` (r >= R).  entry: entry k of that row is (c, v) if it is `in` the row, and (0, +0) if not.  Nothing is
+// read for a row that is not live or an entry that is not in
+template <class T>
+struct LinCsr
+{
+    typedef int32_t col_t;
+    const int32_t* __restrict__ rowptr;
+    const int32_t* __restrict__ col;
+    const T* __restrict__ val;
+    template <class OBJ>
+    __device__ __forceinline__ explicit LinCsr(const OBJ& obj) : rowptr(obj.rowptr), col(obj.col), val(obj.val)
+    {
+    }
+    __device__ __forceinline__ void span(int64_t r, bool live, int lane, int64_t& k, int64_t& k1)
+    {
+        k = k1 = 0;
         if (live)
         {
             k = int64_t(rowptr[r]) + lane;
             k1 = rowptr[r + 1];
         }
-        T s = T(0);
+    }
+    __device__ __forceinline__ void entry(int64_t k, bool in, col_t& c, T& v) const
+    {
+        c = 0;
+        v = T(0);
+        if (in)
+        {
+            c = col[k];
+            v = val[k];
+        }
+    }
+};
+
+// the row body on arrays, whichever signature the generated struct has
+template <class T, class OBJ, int D>
+__device__ __forceinline__ T lin_row_body(const OBJ& obj, const T (&z)[D], T (&dz)[D], int64_t r)
+{
+    if constexpr (LinOutputs<OBJ>::kScalarRow)
+        return obj.row(z[0], dz[0], r);
+    else
+        return obj.row(z, dz, r);
+}
+
+// every row's D sums, its body, w and v.  SRC: where a row's entries come from; ld(j, xj) fills xj[0..D) with the D values
+// of column j (LinGather, LinGatherTrial)
+template <class T, class SRC, class OBJ, class LD>
+__device__ __forceinline__ void lin_rows(const OBJ& obj, LD ld)
+{
+    constexpr int D = lin_outputs<OBJ>, G = linm_group<T, D>();
+    const int L = obj.L;
+    const int rpb = kBlock / L;
+    const int lane = int(threadIdx.x) & (L - 1);
+    const int slot = int(threadIdx.x) / L;
+    SRC src(obj);
+    for (int64_t r0 = int64_t(blockIdx.x) * rpb; r0 < obj.R; r0 += int64_t(gridDim.x) * rpb)
+    {
+        const int64_t r = r0 + slot;
+        const bool live = r < obj.R;
+        int64_t k, k1;
+        src.span(r, live, lane, k, k1);
+        T s[D];
+#pragma unroll
+        for (int c = 0; c < D; c++)
+            s[c] = T(0);
         bool has = false;
         for (; k < k1; k += int64_t(G) * L)
         {
-            int32_t cj[G];
-            T vj[G], xj[G];
+            typename SRC::col_t cj[G];
+            T vj[G], xj[G][D];
+#pragma unroll
+            for (int j = 0; j < G; j++)
+                src.entry(k + int64_t(j) * L, k + int64_t(j) * L < k1, cj[j], vj[j]);
 #pragma unroll
             for (int j = 0; j < G; j++)
             {
-                cj[j] = 0;
-                vj[j] = T(0);
+                // D == 1 only: with the slot defined on both paths the compiler keeps the schedule the scalar form had before
+                // this pass served D outputs (f64, logistic row body: k_lin_rows 82 VGPRs and k_lin_rows_trial 83, 5 waves per
+                // SIMD; without the line 96 and 97, and the trial form drops to 4 waves).  At D > 1 the kernels come out the
+                // same without it (profiles/own_frame_kernel_resources.tsv)
+                if constexpr (D == 1)
+                    xj[j][0] = T(0);
                 if (k + int64_t(j) * L < k1)
-                {
-                    cj[j] = col[k + int64_t(j) * L];
-                    vj[j] = val[k + int64_t(j) * L];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < G; j++)
-            {
-                xj[j] = T(0);
-                if (k + int64_t(j) * L < k1)
-                    xj[j] = ld(int64_t(cj[j]));
+                    ld(int64_t(cj[j]), xj[j]);
             }
 #pragma unroll
             for (int j = 0; j < G; j++)
                 if (k + int64_t(j) * L < k1)
                 {
-                    const T prod = vj[j] * xj[j];
-                    s = has ? s + prod : prod;
+#pragma unroll
+                    for (int c = 0; c < D; c++)
+                    {
+                        const T prod = vj[j] * xj[j][c];
+                        s[c] = has ? s[c] + prod : prod;
+                    }
                     has = true;
                 }
         }
         // lanes l >= h compute values nobody reads; all lanes of the wavefront take part in every move
         for (int h = L >> 1; h >= 1; h >>= 1)
-            s = s + __shfl_down(s, unsigned(h), L);
+        {
+#pragma unroll
+            for (int c = 0; c < D; c++)
+                s[c] = s[c] + __shfl_down(s[c], unsigned(h), L);
+        }
         if (live && lane == 0)
         {
-            T dz = T(0);
-            const T value = obj.row(s, dz, r);
-            obj.w[r] = dz;
+            T dz[D];
+#pragma unroll
+            for (int c = 0; c < D; c++)
+                dz[c] = T(0);
+            const T value = lin_row_body<T>(obj, s, dz, r);
+#pragma unroll
+            for (int c = 0; c < D; c++)
+                obj.w[r * D + c] = dz[c];
             obj.v[r] = value;
         }
     }
@@ -110,31 +242,53 @@ __device__ __forceinline__ void lin_rows(const OBJ& obj, LD ld)
 template <class T, class OBJ>
 __global__ void __launch_bounds__(kBlock) k_lin_rows(const T* __restrict__ x, OBJ obj)
 {
-    lin_rows<T>(obj, [&](int64_t c) { return x[c]; });
+    lin_rows<T, LinCsr<T>>(obj, LinGather<T, lin_outputs<OBJ>>{x});
 }
 
 template <class T, class OBJ>
 __global__ void __launch_bounds__(kBlock) k_lin_rows_trial(const T* __restrict__ xp, const T* __restrict__ d, T step, OBJ obj)
 {
-    lin_rows<T>(obj, [&](int64_t c) { return xp[c] + step * d[c]; });
+    lin_rows<T, LinCsr<T>>(obj, LinGatherTrial<T, lin_outputs<OBJ>>{xp, d, step});
 }
 
 // ---------------------------------------------------------------- the column pass
-// coordinate j with value xj and transposed entries [lo, hi): its gradient, returned; psi's value goes to fx
-template <class T, class OBJ, class A>
-__device__ __forceinline__ T lin_coord(const OBJ& obj, int64_t j, T xj, uint32_t lo, uint32_t hi, A& fx)
+// a sum in a fixed order that starts from its first term (no leading 0 +); +0 without one
+template <class T>
+struct LinSum
 {
-    constexpr int G = kLinGroup;
-    T gv = T(0);
+    T value = T(0);
     bool has = false;
-    if (OBJ::kCoord)
+    __device__ __forceinline__ void add(T t)
     {
-        const T tx[1] = {xj};
-        T tg[1];
-        fx.add(obj.coord(tx, tg, j));
-        gv = tg[0];
+        value = has ? value + t : t;
         has = true;
     }
+};
+
+// how every form's coordinate i with value xi starts: psi's value to fx, its derivative as the first term of the gradient
+template <class T, class OBJ, class A>
+__device__ __forceinline__ LinSum<T> lin_coord_start(const OBJ& obj, int64_t i, T xi, A& fx)
+{
+    LinSum<T> gv;
+    if (OBJ::kCoord)
+    {
+        const T tx[1] = {xi};
+        T tg[1];
+        fx.add(obj.coord(tx, tg, i));
+        gv.add(tg[0]);
+    }
+    return gv;
+}
+
+// coordinate i = j*D + c with value xi and column j's transposed entries [lo, hi): its gradient, returned; psi's value goes
+// to fx
+template <class T, class OBJ, class A>
+__device__ __forceinline__ T lin_coord(const OBJ& obj, int64_t i, T xi, uint32_t lo, uint32_t hi, A& fx)
+{
+    constexpr int G = kLinGroup, D = lin_outputs<OBJ>;
+    const int64_t j = i / D;
+    const int c = int(i - j * D);
+    LinSum<T> gv = lin_coord_start<T>(obj, i, xi, fx);
     if (hi - lo > uint32_t(obj.C))
     {
         // a long column: its slot in the (ascending) table of long columns, then its chunk partials in ascending order
@@ -149,12 +303,8 @@ __device__ __forceinline__ T lin_coord(const OBJ& obj, int64_t j, T xj, uint32_t
         }
         const T* __restrict__ part = obj.part;
         for (uint32_t q = obj.long_chunk[a]; q < obj.long_chunk[a + 1]; q++)
-        {
-            const T pq = part[q];
-            gv = has ? gv + pq : pq;
-            has = true;
-        }
-        return gv;
+            gv.add(part[int64_t(q) * D + c]);
+        return gv.value;
     }
     const int32_t* __restrict__ trow = obj.trow;
     const T* __restrict__ tval = obj.tval;
@@ -179,18 +329,14 @@ __device__ __forceinline__ T lin_coord(const OBJ& obj, int64_t j, T xj, uint32_t
         {
             wj[t] = T(0);
             if (q + t < int64_t(hi))
-                wj[t] = w[rj[t]];
+                wj[t] = w[int64_t(rj[t]) * D + c];
         }
 #pragma unroll
         for (int t = 0; t < G; t++)
             if (q + t < int64_t(hi))
-            {
-                const T prod = vj[t] * wj[t];
-                gv = has ? gv + prod : prod;
-                has = true;
-            }
+                gv.add(vj[t] * wj[t]);
     }
-    return gv;
+    return gv.value;
 }
 
 // every row's value, once: the launch strides over v[R] in packs; thread 0 of block 0 takes the rows past the last whole pack
@@ -212,25 +358,15 @@ __device__ __forceinline__ void lin_row_values(const OBJ& obj, A& fx)
             fx.add(v[r]);
 }
 
-// the frame's family (own_frame.cuh): n coordinates, the transposed list at colptr, and every row's value as the extra pass
-struct LinFamily
+// what the families of the three forms share (own_frame.cuh): n coordinates, the frame's D = 1 ownership of one 16-byte
+// pack of them, and every row's value as the extra pass
+struct LinFamilyBase
 {
     static constexpr int D = 1, U = kLinTrialU;
     template <class OBJ>
     static __device__ __forceinline__ int64_t nodes(const OBJ&, int64_t n)
     {
         return n;
-    }
-    template <class OBJ>
-    static __device__ __forceinline__ const uint32_t* off(const OBJ& obj)
-    {
-        return obj.colptr;
-    }
-    template <class T, class OBJ, class LD, class A>
-    static __device__ __forceinline__ void node(const OBJ& obj, int64_t j, const T (&xj)[1], uint32_t lo, uint32_t hi, LD, A& fx,
-                                                T (&gj)[1])
-    {
-        gj[0] = lin_coord<T>(obj, j, xj[0], lo, hi, fx);
     }
     template <class T, class OBJ, class A>
     static __device__ __forceinline__ void extra(const OBJ& obj, A& fx)
@@ -239,37 +375,35 @@ struct LinFamily
     }
 };
 
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_lin_eval(const T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                     T* __restrict__ out)
+// the family of the two sparse forms: the transposed list at colptr.  SHARED false: a coordinate is a column and colptr
+// holds the frame's offsets, n + 1 of them.  SHARED true: the D coordinates of a column walk one list and colptr has n / D + 1
+// entries, so the family gives (lo, hi) per coordinate (kRange)
+template <bool SHARED>
+struct LinFamily : LinFamilyBase
 {
-    own_eval<T, LinFamily, OBJ, false>(x, g, nullptr, nullptr, n, obj, ws, out);
-}
+    static constexpr bool kRange = SHARED;
+    template <class OBJ>
+    static __device__ __forceinline__ const uint32_t* off(const OBJ& obj)
+    {
+        return obj.colptr;
+    }
+    template <class OBJ>
+    static __device__ __forceinline__ void range(const OBJ& obj, int64_t i, uint32_t& lo, uint32_t& hi)
+    {
+        const uint32_t* __restrict__ colptr = obj.colptr;
+        const int64_t j = i / lin_outputs<OBJ>;
+        lo = colptr[j];
+        hi = colptr[j + 1];
+    }
+    template <class T, class OBJ, class LD, class A>
+    static __device__ __forceinline__ void node(const OBJ& obj, int64_t i, const T (&xi)[1], uint32_t lo, uint32_t hi, LD, A& fx,
+                                                T (&gi)[1])
+    {
+        gi[0] = lin_coord<T>(obj, i, xi[0], lo, hi, fx);
+    }
+};
 
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_lin_b_eval(const T* __restrict__ x, T* __restrict__ g, const T* __restrict__ lb,
-                                                       const T* __restrict__ ub, int64_t n, OBJ obj, RedWs ws,
-                                                       T* __restrict__ out)
-{
-    own_eval<T, LinFamily, OBJ, true>(x, g, lb, ub, n, obj, ws, out);
-}
-
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_lin_trial(const T* __restrict__ xp, const T* __restrict__ d, T step,
-                                                      T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                      T* __restrict__ out, int rev)
-{
-    own_trial<T, LinFamily, OBJ, false>(xp, nullptr, d, nullptr, nullptr, step, x, g, n, obj, ws, out, rev);
-}
-
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_lin_b_dg_maxstep_trial(const T* __restrict__ xp, const T* __restrict__ g0,
-                                                                   const T* __restrict__ d, const T* __restrict__ lb,
-                                                                   const T* __restrict__ ub, T step, T* __restrict__ x,
-                                                                   T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                                   T* __restrict__ out, int rev)
-{
-    own_trial<T, LinFamily, OBJ, true>(xp, g0, d, lb, ub, step, x, g, n, obj, ws, out, rev);
-}
+// k_lin_eval, k_lin_trial, k_lin_b_eval, k_lin_b_dg_maxstep_trial
+LBFGSX_OWN_KERNELS(k_lin, LinFamily<false>)
 
 }  // namespace lbfgsx

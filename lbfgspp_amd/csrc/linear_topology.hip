@@ -1,7 +1,7 @@
 // lbfgspp_amd/csrc/linear_topology.hip -- the matrix of a linear-model objective, prepared on the device at bind
 // (include/lbfgsx.h, "linear-model objectives"; walked by linear_kernels.cuh), and the one kernel of the form that holds no
 // caller text, k_lin_long_cols.  A multi-output objective (linear_multi_kernels.cuh) has the same build over the F = n / D
-// columns of its matrix (n below is then F), w of R*D elements, D partials per chunk and k_lin_long_cols_multi.
+// columns of its matrix (n below is then F), w of R*D elements and D partials per chunk; k_lin_long_cols takes D at run time.
 //
 //   1. the caller's rowptr[R+1], col[nnz], val[nnz] (host or device) are copied into arrays the context owns;
 //   2. k_lin_validate, the only launch of a refused bind, reduces the count of offending positions and the smallest one:
@@ -140,41 +140,14 @@ __global__ void __launch_bounds__(kBlock) k_lin_find_long(const uint32_t* __rest
     }
 }
 
-// One block per chunk of a long column: thread t sums the products of the chunk's entries t, t + kBlock, .. in ascending
-// order, started from its first (+0 if it has none); then s_t = s_t + s_{t+h} for t < h, h = kBlock/2 .. 1.  part[b] is
-// thread 0's value.  Every q lies in [0, nnz) and every trow[q] in [0, R) by construction of the list.
+// One block per (chunk b of a long column, output c), blockIdx.x = b*D + c (the scalar form has D = 1): thread t sums the
+// products tval[q]*w[trow[q]*D + c] of the chunk's entries t, t + kBlock, .. in ascending order, started from its first (+0
+// if it has none); then s_t = s_t + s_{t+h} for t < h, h = kBlock/2 .. 1.  part[b*D + c] is thread 0's value.  Every q lies in
+// [0, nnz) and every trow[q] in [0, R) by construction of the list.
 template <class T>
 __global__ void __launch_bounds__(kBlock) k_lin_long_cols(const uint32_t* __restrict__ chunk, const int32_t* __restrict__ trow,
                                                           const T* __restrict__ tval, const T* __restrict__ w,
-                                                          T* __restrict__ part)
-{
-    __shared__ T sh[kBlock];
-    const uint32_t beg = chunk[2 * blockIdx.x], end = chunk[2 * blockIdx.x + 1];
-    T s = T(0);
-    bool has = false;
-    for (int64_t q = int64_t(beg) + threadIdx.x; q < int64_t(end); q += kBlock)
-    {
-        const T prod = tval[q] * w[trow[q]];
-        s = has ? s + prod : prod;
-        has = true;
-    }
-    sh[threadIdx.x] = s;
-    for (int h = kBlock / 2; h >= 1; h >>= 1)
-    {
-        __syncthreads();
-        if (int(threadIdx.x) < h)
-            sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + h];
-    }
-    if (threadIdx.x == 0)
-        part[blockIdx.x] = sh[0];
-}
-
-// The same per output c of a multi-output objective: one block per (chunk b, output c), blockIdx.x = b*D + c, over
-// w[trow[q]*D + c], into part[b*D + c].
-template <class T>
-__global__ void __launch_bounds__(kBlock) k_lin_long_cols_multi(const uint32_t* __restrict__ chunk,
-                                                                const int32_t* __restrict__ trow, const T* __restrict__ tval,
-                                                                const T* __restrict__ w, T* __restrict__ part, int D)
+                                                          T* __restrict__ part, int D)
 {
     __shared__ T sh[kBlock];
     const unsigned b = blockIdx.x / unsigned(D), c = blockIdx.x % unsigned(D);
@@ -428,23 +401,14 @@ int linear_long_launch(lbfgsx_ctx* c)
         return LBFGSX_OK;
     const uint32_t* chunk = static_cast<const uint32_t*>(l.chunk);
     const int32_t* trow = static_cast<const int32_t*>(l.trow);
-    if (l.D)
-    {
-        const unsigned blocks = unsigned(l.nchunks) * unsigned(l.D);
-        if (c->dtype == LBFGSX_F64)
-            LBFGSX_LAUNCH((k_lin_long_cols_multi<double>), dim3(blocks), dim3(kBlock), 0, c->stream, chunk, trow,
-                          static_cast<const double*>(l.tval), static_cast<const double*>(l.w), static_cast<double*>(l.part), l.D);
-        else
-            LBFGSX_LAUNCH((k_lin_long_cols_multi<float>), dim3(blocks), dim3(kBlock), 0, c->stream, chunk, trow,
-                          static_cast<const float*>(l.tval), static_cast<const float*>(l.w), static_cast<float*>(l.part), l.D);
-        return LBFGSX_OK;
-    }
+    const int D = l.D ? l.D : 1;  // the scalar form binds with D = 0
+    const unsigned blocks = unsigned(l.nchunks) * unsigned(D);
     if (c->dtype == LBFGSX_F64)
-        LBFGSX_LAUNCH((k_lin_long_cols<double>), dim3(unsigned(l.nchunks)), dim3(kBlock), 0, c->stream, chunk, trow,
-                      static_cast<const double*>(l.tval), static_cast<const double*>(l.w), static_cast<double*>(l.part));
+        LBFGSX_LAUNCH((k_lin_long_cols<double>), dim3(blocks), dim3(kBlock), 0, c->stream, chunk, trow,
+                      static_cast<const double*>(l.tval), static_cast<const double*>(l.w), static_cast<double*>(l.part), D);
     else
-        LBFGSX_LAUNCH((k_lin_long_cols<float>), dim3(unsigned(l.nchunks)), dim3(kBlock), 0, c->stream, chunk, trow,
-                      static_cast<const float*>(l.tval), static_cast<const float*>(l.w), static_cast<float*>(l.part));
+        LBFGSX_LAUNCH((k_lin_long_cols<float>), dim3(blocks), dim3(kBlock), 0, c->stream, chunk, trow,
+                      static_cast<const float*>(l.tval), static_cast<const float*>(l.w), static_cast<float*>(l.part), D);
     return LBFGSX_OK;
 }
 

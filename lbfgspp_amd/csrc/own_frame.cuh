@@ -1,7 +1,7 @@
 // lbfgspp_amd/csrc/own_frame.cuh -- the frame of the owner-computes gather kernels: the four evaluation kernels of a GRAPH,
-// a MESH and a LINEAR-MODEL objective (graph_kernels.cuh, mesh_kernels.cuh, the column pass of linear_kernels.cuh and of
-// linear_multi_kernels.cuh) are
-// own_eval and own_trial, bounded or not, around the family's walk of one node's list.
+// a MESH and a LINEAR-MODEL objective (graph_kernels.cuh, mesh_kernels.cuh, the column pass of linear_kernels.cuh,
+// linear_multi_kernels.cuh and linear_dense_kernels.cuh) are own_eval and own_trial, bounded or not, around the family's walk
+// of one node's list.  LBFGSX_OWN_KERNELS, at the end of this file, defines a family's four kernels.
 //
 // Ownership.  x holds D unknowns per node, node-major.  A thread owns W = 16 / sizeof(T) consecutive nodes: exactly D whole
 // 16-byte packs of x from pack vi*D; it loads the W + 1 offsets of its nodes' lists, walks each list and writes the nodes'
@@ -15,7 +15,8 @@
 //     const uint32_t* off(const OBJ&)                           the offsets of the nodes' lists, nodes + 1 of them
 //     or  static constexpr bool kRange = true;  void range(obj, v, lo, hi)   a family whose nodes share lists (the multi-output
 //                                                               linear model: D coordinates walk one feature's list): node
-//                                                               v's entries [lo, hi), in place of off[v] and off[v + 1]
+//                                                               v's entries [lo, hi), in place of off[v] and off[v + 1];
+//                                                               kRange = false is the same as no kRange
 //     void node<T>(obj, v, xv[D], lo, hi, ld, fx, gv[D])        node v with values xv and entries [lo, hi): its D partial
 //                                                               derivatives to gv, what it owns of f to fx; ld(i) = x[i]
 //     void extra<T>(obj, fx)                                    what else the launch adds to f, after the tail
@@ -303,5 +304,38 @@ __device__ __forceinline__ void own_trial(const T* __restrict__ xp, const T* __r
         }
     }
 }
+
+// ---------------------------------------------------------------- the four kernels of a family
+// PREFIX_eval, PREFIX_trial, PREFIX_b_eval and PREFIX_b_dg_maxstep_trial for the family FAMILY, with the parameter lists of
+// k_eval, k_trial, k_b_eval and k_b_dg_maxstep_trial (OBJ after n): launch_args.hpp serves all the families
+#define LBFGSX_OWN_KERNELS(PREFIX, FAMILY)                                                                                     \
+    template <class T, class OBJ>                                                                                              \
+    __global__ void __launch_bounds__(kBlock)                                                                                  \
+        PREFIX##_eval(const T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws, T* __restrict__ out)           \
+    {                                                                                                                          \
+        own_eval<T, FAMILY, OBJ, false>(x, g, nullptr, nullptr, n, obj, ws, out);                                              \
+    }                                                                                                                          \
+    template <class T, class OBJ>                                                                                              \
+    __global__ void __launch_bounds__(kBlock)                                                                                  \
+        PREFIX##_b_eval(const T* __restrict__ x, T* __restrict__ g, const T* __restrict__ lb, const T* __restrict__ ub,        \
+                        int64_t n, OBJ obj, RedWs ws, T* __restrict__ out)                                                     \
+    {                                                                                                                          \
+        own_eval<T, FAMILY, OBJ, true>(x, g, lb, ub, n, obj, ws, out);                                                         \
+    }                                                                                                                          \
+    template <class T, class OBJ>                                                                                              \
+    __global__ void __launch_bounds__(kBlock)                                                                                  \
+        PREFIX##_trial(const T* __restrict__ xp, const T* __restrict__ d, T step, T* __restrict__ x, T* __restrict__ g,        \
+                       int64_t n, OBJ obj, RedWs ws, T* __restrict__ out, int rev)                                             \
+    {                                                                                                                          \
+        own_trial<T, FAMILY, OBJ, false>(xp, nullptr, d, nullptr, nullptr, step, x, g, n, obj, ws, out, rev);                  \
+    }                                                                                                                          \
+    template <class T, class OBJ>                                                                                              \
+    __global__ void __launch_bounds__(kBlock)                                                                                  \
+        PREFIX##_b_dg_maxstep_trial(const T* __restrict__ xp, const T* __restrict__ g0, const T* __restrict__ d,               \
+                                    const T* __restrict__ lb, const T* __restrict__ ub, T step, T* __restrict__ x,             \
+                                    T* __restrict__ g, int64_t n, OBJ obj, RedWs ws, T* __restrict__ out, int rev)             \
+    {                                                                                                                          \
+        own_trial<T, FAMILY, OBJ, true>(xp, g0, d, lb, ub, step, x, g, n, obj, ws, out, rev);                                  \
+    }
 
 }  // namespace lbfgsx

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""Registers, scratch and occupancy of the graph, mesh and linear-model kernels in two trees, side by side
-(profiles/own_frame_kernel_resources.tsv).  No GPU is needed: the generated sources are compiled for gfx950 here.
+"""Registers, scratch and occupancy of the graph, mesh and linear-model (sparse, multi-output, dense) kernels in two trees,
+side by side (profiles/own_frame_kernel_resources.tsv).  No GPU is needed: the generated sources are compiled for gfx950 here.
 
 Each tree (a built checkout: the parent commit's and this one) is asked, in a process of its own, for the generated
 translation unit -- source() -- of
     graph    ASYM_EDGE with and without NODE                                   (tests/graph_ref.py)
     mesh     every (K, D) with the bodies tests/test_mesh_objective_cpu.py compiles (tests/mesh_ref.py)
     linear   LOGISTIC with and without RIDGE                                   (tests/linear_ref.py)
+    multi    MHINGE at D = 1, 3, 10, 16 with and without RIDGE                 (tests/multilinear_ref.py)
+    dense    the same bodies and D over a dense matrix
 at f64 and f32.  Each is compiled against its own tree's lbfgspp_amd/csrc with the library's flags,
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off --cuda-device-only -S -Rpass-analysis=kernel-resource-usage
 and the compiler's remarks give VGPRs, scratch bytes per lane and occupancy (waves per SIMD) per kernel.
@@ -40,6 +42,7 @@ def emit_sources(tree):
     import linear_ref as LR
     import lbfgspp_amd as A
     import mesh_ref as MR
+    import multilinear_ref as ML
     out = {}
     one_edge = (np.array([0]), np.array([1]))
     one_entry = (np.array([0, 1], np.int32), np.array([0], np.int32), np.array([1.0]))
@@ -55,6 +58,12 @@ def emit_sources(tree):
                     out["mesh/K%dD%d/%s/%s" % (K, D, name, dname)] = A.MeshObjective(elem, MR.strip(K, K), D, node_body=node).source(dtype)
         for name, coord in (("logistic+ridge", LR.RIDGE), ("logistic", None)):
             out["linear/%s/%s" % (name, dname)] = A.LinearObjective(LR.LOGISTIC, one_entry, 1, coord_body=coord).source(dtype)
+        for D in (1, 3, 10, 16):
+            for name, coord in (("mhinge+ridge", ML.RIDGE), ("mhinge", None)):
+                out["multi/D%d/%s/%s" % (D, name, dname)] = A.MultiLinearObjective(ML.MHINGE, one_entry, 1, D,
+                                                                                  coord_body=coord).source(dtype)
+                out["dense/D%d/%s/%s" % (D, name, dname)] = A.DenseLinearObjective(ML.MHINGE, np.ones((1, 1)), D,
+                                                                                  coord_body=coord).source(dtype)
     return out
 
 
