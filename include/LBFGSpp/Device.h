@@ -131,12 +131,15 @@ public:
     explicit TermObjective(const lbfgsx_objective* compiled) : m_h(const_cast<lbfgsx_objective*>(compiled)) {}
 
 protected:
-    // node: a GraphObjective's or MeshObjective's node body (empty: none); D: a MeshObjective's unknowns per node
-    TermObjective(int form, int K, const std::string& body, const char* who, const std::string& node = std::string(), int D = 1)
+    // node: a GraphObjective's or MeshObjective's node body (empty: none); D: a MeshObjective's unknowns per node; edge: a
+    // GraphLinearObjective's edge body
+    TermObjective(int form, int K, const std::string& body, const char* who, const std::string& node = std::string(), int D = 1,
+                  const std::string& edge = std::string())
     {
         std::vector<char> log(16384, '\0');
         const int dt = detail::dtype_of<Scalar>::value;
-        const int rc = (form == LBFGSX_FORM_DENSE) ? lbfgsx_objective_compile_dense(&m_h, dt, D, node.c_str(), body.c_str(), log.data(), log.size())
+        const int rc = (form == LBFGSX_FORM_LINEAR_GRAPH) ? lbfgsx_objective_compile_linear_graph(&m_h, dt, node.c_str(), edge.c_str(), body.c_str(), log.data(), log.size())
+                       : (form == LBFGSX_FORM_DENSE) ? lbfgsx_objective_compile_dense(&m_h, dt, D, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_LINEAR_MULTI) ? lbfgsx_objective_compile_linear_multi(&m_h, dt, D, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_LINEAR)  ? lbfgsx_objective_compile_linear(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_MESH)  ? lbfgsx_objective_compile_mesh(&m_h, dt, K, D, node.c_str(), body.c_str(), log.data(), log.size())
@@ -247,6 +250,9 @@ public:
         }
         if (m_dense)
             detail::check(lbfgsx_objective_bind_dense(c, m_h, m_R, m_A, m_lda, m_matrix_dev ? 1 : 0, m_lanes, p, m_c, &id));
+        else if ((m_rowptr || m_R || m_nnz) && (m_E || m_ei || m_ej))
+            detail::check(lbfgsx_objective_bind_linear_graph(c, m_h, m_R, m_nnz, m_rowptr, m_col, m_val, m_matrix_dev ? 1 : 0, m_lanes,
+                                                             m_E, m_ei, m_ej, m_edges_dev ? 1 : 0, p, m_c, &id));
         else if (m_rowptr || m_R || m_nnz)
             detail::check(lbfgsx_objective_bind_linear(c, m_h, m_R, m_nnz, m_rowptr, m_col, m_val, m_matrix_dev ? 1 : 0, m_lanes, p,
                                                        m_c, &id));
@@ -379,6 +385,39 @@ public:
     }
 };
 
+// A linear model with a coupling term over a graph on its weights: f(x) = sum over coordinates j of psi(x[j]; j) + sum over the
+// E edges of rho(x[ei[e]], x[ej[e]]; e) + sum over the R rows of phi(z_r; r), z = A x (include/lbfgsx.h, "graph-regularised
+// linear-model objectives") -- reconstruction with a smoothness prior under bounds, regression with a GMRF prior, Laplacian-
+// regularised least squares.  The row and coordinate bodies are a LinearObjective's, the edge body a GraphObjective's; the three
+// share p0..p3 and c[8], so a data array has n, E or R elements.
+//     GraphLinearObjective<double> f("const T u = z - p0[r]; dz = u; return T(0.5) * (u * u);",
+//                                    "const T d = x[0] - x[1]; const T w = c[0] * d; g[0] = w; g[1] = T(0) - w; return T(0.5) * (w * d);");
+//     f.matrix(R, nnz, rowptr, col, val).edges(E, ei, ej).host_data(0, b, R).scalars({lambda});      solver.minimize(f, x, fx, lb, ub);
+// matrix() is a LinearObjective's and edges() a GraphObjective's, with their validation at every minimize().  Accepted wherever
+// a LinearObjective is, refused where it is.
+template <typename Scalar>
+class GraphLinearObjective : public TermObjective<Scalar>
+{
+public:
+    GraphLinearObjective(const std::string& row_body, const std::string& edge_body, const std::string& coord_body = std::string())
+        : TermObjective<Scalar>(LBFGSX_FORM_LINEAR_GRAPH, 1, row_body, "GraphLinearObjective: ", coord_body, 1, edge_body)
+    {
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile_linear_graph); it stays the caller's
+    explicit GraphLinearObjective(const lbfgsx_objective* compiled) : TermObjective<Scalar>(compiled) {}
+    GraphLinearObjective& matrix(std::int64_t R, std::int64_t nnz, const std::int32_t* rowptr, const std::int32_t* col,
+                                 const Scalar* val, bool on_device = false, int lanes = 0)
+    {
+        this->set_matrix(R, nnz, rowptr, col, val, on_device, lanes);
+        return *this;
+    }
+    GraphLinearObjective& edges(std::int64_t E, const std::int32_t* ei, const std::int32_t* ej, bool on_device = false)
+    {
+        this->set_edges(E, ei, ej, on_device);
+        return *this;
+    }
+};
+
 // A linear model with D outputs per sample: x holds an F x D weight matrix, feature-major (x[j*D + c], n = F*D), A is a sparse
 // R x F CSR matrix, Z = A X and f(x) = sum over coordinates i of psi(x[i]; i) + sum over rows r of phi(Z[r, 0..D); r)
 // (include/lbfgsx.h, "multi-output linear-model objectives"): softmax regression, multi-class SVMs, multi-target least
@@ -436,7 +475,7 @@ public:
 
 namespace detail {
 // the objectives compiled at run time into the fused kernels: a TermObjective, a ChainObjective, a GridObjective, a
-// GraphObjective, a MeshObjective, a LinearObjective, a MultiLinearObjective or a DenseLinearObjective
+// GraphObjective, a MeshObjective, a LinearObjective, a GraphLinearObjective, a MultiLinearObjective or a DenseLinearObjective
 template <typename Scalar, typename Foo>
 struct is_compiled_objective
 {
@@ -445,6 +484,7 @@ struct is_compiled_objective
                                   std::is_same<F, GridObjective<Scalar> >::value || std::is_same<F, GraphObjective<Scalar> >::value ||
                                   std::is_same<F, MeshObjective<Scalar> >::value || std::is_same<F, LinearObjective<Scalar> >::value ||
                                   std::is_same<F, MultiLinearObjective<Scalar> >::value ||
+                                  std::is_same<F, GraphLinearObjective<Scalar> >::value ||
                                   std::is_same<F, DenseLinearObjective<Scalar> >::value;
 };
 }  // namespace detail

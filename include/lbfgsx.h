@@ -216,7 +216,7 @@ int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4]);
  * with n < K is refused (any n >= K is accepted: n need not be a multiple of anything).  The compile log, the refusal of
  * asm and the line numbers are those of lbfgsx_objective_compile. */
 enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2, LBFGSX_FORM_GRAPH = 3, LBFGSX_FORM_MESH = 4, LBFGSX_FORM_LINEAR = 5,
-       LBFGSX_FORM_LINEAR_MULTI = 6, LBFGSX_FORM_DENSE = 7 };
+       LBFGSX_FORM_LINEAR_MULTI = 6, LBFGSX_FORM_DENSE = 7, LBFGSX_FORM_LINEAR_GRAPH = 8 };
 int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len);
 long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char* out, size_t len);
 int lbfgsx_objective_form(const lbfgsx_objective* obj);
@@ -507,6 +507,59 @@ int lbfgsx_objective_bind_dense(lbfgsx_ctx* c, const lbfgsx_objective* obj, int6
                                 int lanes, const void* const p[4], const double cs[8], int* id);
 int lbfgsx_objective_dense_info(lbfgsx_ctx* c, int64_t info[8]);
 int lbfgsx_objective_dense_read(lbfgsx_ctx* c, void* w, void* v, void* part);
+/* ---- graph-regularised linear-model objectives: edge terms in the linear column pass ------------------------------------------
+ * The scalar linear-model form with a coupling term over a graph on its coordinates: x has n coordinates, A is a sparse R x n
+ * CSR matrix, the E edges are (ei[e], ej[e]) with 0 <= ei[e], ej[e] < n, ei[e] != ej[e], and
+ *     f(x) = sum over coordinates j of psi(x[j]; j)  +  sum over edges e of rho(x[ei[e]], x[ej[e]]; e)
+ *            +  sum over rows r of phi(z_r; r),      z = A x
+ * -- tomographic and deblurring reconstruction with a smoothness or smoothed-TV prior under non-negativity (L-BFGS-B),
+ * Poisson or logistic regression with a GMRF / ICAR prior on a latent field, Laplacian-regularised least squares, fused and
+ * graph-trend regression with a Huber penalty on differences, network-coupled GLMs.  Three bodies of HIP/C++ text:
+ *   row_body   a linear-model objective's: T, const T z, T& dz, int64_t r, p0..p3, c[8]; returns phi(z);
+ *   edge_body  a graph objective's: T, const T x[2] (x at ei[e] and at ej[e]), T g[2], int64_t e, i, j, p0..p3, c[8]; returns rho;
+ *   coord_body (NULL or empty: none) T, const T x[1], T g[1], int64_t i, p0..p3, c[8]; returns psi.
+ * The three bodies share the four data arrays and the eight scalars: a data array has n, E or R elements, as the body that
+ * indexes it needs (lbfgsx_objective_upload_count).
+ * Semantics (tests/graph_linear_ref.py is the bit-exact numpy restatement):
+ *   z_r, w[r], v[r], L, long columns, chunks and C = 4096 are exactly the linear-model form's;
+ *   grad[j] in this order, started from the first contribution (no leading 0 +; +0 if there is none): psi's g[0] if there is
+ *           a coordinate body; g_e[side] of j's incidence entries in ascending e (the graph form's rule: an edge is evaluated
+ *           from both ends on identical inputs, so both evaluations have the same bits); the matrix contributions exactly as
+ *           the linear-model form adds them, tval[q]*w[trow[q]] in ascending q or a long column's chunk partials in ascending b;
+ *   f       the order-independent (compensated) sum over every psi value, every edge value (added by the owner of end 0) and
+ *           every v[r];
+ *   in the trial kernels every gathered value, an edge's other end or a row's x[col], is xp[u] + step*d[u], never a read of
+ *   the x the launch writes; one rounding per source operation, no contraction.
+ * An evaluation is the linear-model form's launches (csrc/linear_graph_kernels.cuh): the row pass k_lin_rows /
+ * k_lin_rows_trial instantiated for this form's struct, k_lin_long_cols when the matrix has a long column, then the column
+ * pass k_ling_eval, k_ling_trial, k_ling_b_eval or k_ling_b_dg_maxstep_trial, whose node runs the coordinate term, then the
+ * node's edges (graph_walk), then its column (the rest of lin_coord) into one running sum: x, xp, d, g, lb and ub are streamed once
+ * for both terms.  2 launches per evaluation, 3 with a long column.  No LDS, no float atomic.
+ * lbfgsx_objective_compile_linear_graph caches by (form, three bodies, dtype); the form is LBFGSX_FORM_LINEAR_GRAPH,
+ * lbfgsx_objective_K returns 1.  The word asm in any body is refused; the compile log counts lines per body ("coord_body",
+ * "edge_body", "row_body").  lbfgsx_objective_info's maxima cover all six kernels.
+ * lbfgsx_objective_bind_linear_graph builds both lists on the device: the incidence list of lbfgsx_objective_bind_graph
+ * (5 launches), then the transposed matrix of lbfgsx_objective_bind_linear (6 launches) beside it.  Each build validates its
+ * indices in its first launch; an offender in either list returns LBFGSX_E_INVALID with the first offending edge or
+ * position named, as those two calls name it, and leaves no objective bound and no list on the context (an offending edge: 1
+ * launch; an offending matrix: the 5 of the edges and 1).  Also refused, the values named: a handle of another form, E < 1,
+ * R < 1, nnz < 1, E, R, nnz or n above 2^31 - 1, lanes not 0 or a power of two <= 64.  The other bind calls refuse the handle
+ * as they refuse every form that is not theirs: lbfgsx_objective_bind with "a graph-regularised linear-model objective is bound
+ * with its matrix and edges: lbfgsx_objective_bind_linear_graph"; lbfgsx_objective_bind_linear, _bind_graph, _bind_mesh, _bind_grid
+ * and _bind_dense with "<the call>: the handle is a graph-regularised linear-model objective, not a <that call's form>".
+ * lbfgsx_objective_topology and lbfgsx_objective_linear_topology both read back from a context bound this way.
+ * Byte model of one evaluation: the linear-model form's plus the graph form's list terms (n+1 offsets, 2E entries of 8
+ * bytes, 2E gathered values, of x or of xp and d).
+ * Not built: D > 1 outputs per row, the dense matrix, mesh elements in place of edges, the lock-step batch, a bench.py leg.
+ * Registers, measurements: DESIGN.md section 1. */
+int lbfgsx_objective_compile_linear_graph(lbfgsx_objective** out, int dtype, const char* coord_body, const char* edge_body,
+                                          const char* row_body, char* log, size_t log_len);
+long long lbfgsx_objective_source_linear_graph(int dtype, const char* coord_body, const char* edge_body, const char* row_body,
+                                               char* out, size_t len);
+int lbfgsx_objective_bind_linear_graph(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t R, int64_t nnz, const int32_t* rowptr,
+                                       const int32_t* col, const void* val, int matrix_on_device, int lanes, int64_t E,
+                                       const int32_t* ei, const int32_t* ej, int edges_on_device, const void* const p[4],
+                                       const double cs[8], int* id);
 /* Every entry point of this ABI makes the context's device current for its own duration and restores the caller's
  * afterwards.  Code that launches its OWN kernels on the context's vectors (a device functor, lbfgsx_vec) must run with
  * that device current too: lbfgsx_device tells which one it is, lbfgsx_device_push makes it current for the calling

@@ -172,6 +172,16 @@ int lbfgsx_solver_minimize_dense(lbfgsx_solver* s, const lbfgsx_objective* obj, 
                                  int a_on_device, int lanes, const void* const p[4], int host_mask, const int64_t counts[4],
                                  const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
                                  lbfgsx_result* out);
+/* The same for a graph-regularised linear-model objective (lbfgsx_objective_compile_linear_graph, include/lbfgsx.h
+ * "graph-regularised linear-model objectives"): the matrix as for lbfgsx_solver_minimize_linear, the E edges as for
+ * lbfgsx_solver_minimize_graph, each host arrays or device arrays by its own flag; a data array has n, E or R elements.  A
+ * handle of another form, E < 1, R < 1 and nnz < 1 are refused with LBFGSX_E_INVALID before a device is needed, as are the
+ * edges and matrices lbfgsx_objective_bind_linear_graph refuses; every other minimise entry refuses the handle. */
+int lbfgsx_solver_minimize_linear_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, int64_t nnz,
+                                        const int32_t* rowptr, const int32_t* col, const void* val, int matrix_on_device,
+                                        int lanes, int64_t E, const int32_t* ei, const int32_t* ej, int edges_on_device,
+                                        const void* const p[4], int host_mask, const int64_t counts[4], const double c[8],
+                                        void* x, const void* lb, const void* ub, lbfgsx_trace* trace, lbfgsx_result* out);
 int lbfgsx_solver_minimize_mesh(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t E, const int32_t* elems,
                                 int elems_on_device, const void* const p[4], int host_mask, const int64_t counts[4],
                                 const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,

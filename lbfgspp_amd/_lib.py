@@ -236,6 +236,14 @@ def load():
     sig(core, "lbfgsx_objective_linear_topology", i32, vp, C.POINTER(i64 * 8), u32p, i32p, u32p, i32p, u32p, u32p)
     sig(sol, "lbfgsx_solver_minimize_linear", i32, vp, vp, i64, i64, i64, vp, vp, vp, i32, i32, C.POINTER(vp * 4), i32,
         C.POINTER(i64 * 4), C.POINTER(dbl * 8), vp, vp, vp, C.POINTER(Trace), C.POINTER(Result))
+    # graph-regularised linear-model objectives: three bodies; the CSR matrix and the edges travel with the binding
+    sig(core, "lbfgsx_objective_compile_linear_graph", i32, C.POINTER(vp), i32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+        C.c_size_t)
+    sig(core, "lbfgsx_objective_source_linear_graph", C.c_longlong, i32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_bind_linear_graph", i32, vp, vp, i64, i64, vp, vp, vp, i32, i32, i64, vp, vp, i32,
+        C.POINTER(vp * 4), C.POINTER(dbl * 8), C.POINTER(i32))
+    sig(sol, "lbfgsx_solver_minimize_linear_graph", i32, vp, vp, i64, i64, i64, vp, vp, vp, i32, i32, i64, vp, vp, i32,
+        C.POINTER(vp * 4), i32, C.POINTER(i64 * 4), C.POINTER(dbl * 8), vp, vp, vp, C.POINTER(Trace), C.POINTER(Result))
     # dense linear-model objectives: the multi-output form's bodies; the dense matrix travels with the binding
     sig(core, "lbfgsx_objective_compile_dense", i32, C.POINTER(vp), i32, i32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t)
     sig(core, "lbfgsx_objective_source_dense", C.c_longlong, i32, i32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t)

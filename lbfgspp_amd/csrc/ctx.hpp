@@ -281,7 +281,8 @@ struct lbfgsx_ctx
     int mesh_K = 0, mesh_D = 0;
     // a linear-model objective's matrix (lbfgsx_objective_bind_linear, linear_topology.hip): the context's own copy of the
     // caller's CSR arrays, the transposed list built from them at every bind, the row pass's two output vectors and the
-    // chunk table of the long columns.  Freed with the other forms' list (graph_topology_free).  A multi-output linear-model
+    // chunk table of the long columns.  Freed with the other forms' list (graph_topology_free); a graph-regularised linear-model
+    // objective (lbfgsx_objective_bind_linear_graph) holds this matrix AND the incidence list above.  A multi-output linear-model
     // objective's matrix lives here too: D > 0 is its outputs per row, the matrix then has n / D columns, w holds R*D
     // elements and part nchunks*D (0: the scalar form, where the comments below hold as written)
     struct LinearTopo

@@ -35,22 +35,13 @@ namespace lbfgsx {
 constexpr int kGraphGroup = 4;   // entries whose loads are in flight together
 constexpr int kGraphTrialU = 2;  // the tile depth of the two trial kernels
 
-// node v with value xv and entries [lo, hi): its gradient, returned; its node value and the values of the edges it is end 0
-// of go to fx.  ld(u) = x[u] -- from memory in the evaluation kernels, recomputed from xp and d in the trial kernels
+// the walk of node v with value xv over its entries [lo, hi): g_e[side] of each added to gv, which holds what precedes them in
+// the node's sum; the values of the edges v is end 0 of go to fx.  ld(u) = x[u] -- from memory in the evaluation kernels,
+// recomputed from xp and d in the trial kernels
 template <class T, class OBJ, class LD, class A>
-__device__ __forceinline__ T graph_node(const OBJ& obj, int64_t v, T xv, uint32_t lo, uint32_t hi, LD ld, A& fx)
+__device__ __forceinline__ void graph_walk(const OBJ& obj, int64_t v, T xv, uint32_t lo, uint32_t hi, LD ld, A& fx, LinSum<T>& gv)
 {
     constexpr int G = kGraphGroup;
-    T gv = T(0);
-    bool has = false;
-    if (OBJ::kNode)
-    {
-        const T tx[1] = {xv};
-        T tg[1];
-        fx.add(obj.node(tx, tg, v));
-        gv = tg[0];
-        has = true;
-    }
     const GraphEntry* __restrict__ inc = obj.inc;
     for (int64_t q = lo; q < int64_t(hi); q += G)
     {
@@ -80,14 +71,28 @@ __device__ __forceinline__ T graph_node(const OBJ& obj, int64_t v, T xv, uint32_
                 const T tx[2] = {far ? xo[j] : xv, far ? xv : xo[j]};
                 T tg[2];
                 const T val = obj.edge(tx, tg, int64_t(en[j].es >> 1), far ? u : v, far ? v : u);
-                const T mine = far ? tg[1] : tg[0];
-                gv = has ? gv + mine : mine;
-                has = true;
+                gv.add(far ? tg[1] : tg[0]);
                 if (!far)
                     fx.add(val);
             }
     }
-    return gv;
+}
+
+// node v with value xv and entries [lo, hi): its gradient, returned; its node value and the values of the edges it is end 0
+// of go to fx
+template <class T, class OBJ, class LD, class A>
+__device__ __forceinline__ T graph_node(const OBJ& obj, int64_t v, T xv, uint32_t lo, uint32_t hi, LD ld, A& fx)
+{
+    LinSum<T> gv;
+    if (OBJ::kNode)
+    {
+        const T tx[1] = {xv};
+        T tg[1];
+        fx.add(obj.node(tx, tg, v));
+        gv.add(tg[0]);
+    }
+    graph_walk<T>(obj, v, xv, lo, hi, ld, fx, gv);
+    return gv.value;
 }
 
 // the frame's family (own_frame.cuh): n nodes of one unknown, the list at off, no extra pass

@@ -21,7 +21,9 @@
 // outputs per row, x an F x D matrix), a wrapper around linear_multi_kernels.cuh over the same matrix and the same argument
 // struct, bound by the same call.  An eighth, a DENSE LINEAR-MODEL objective (the multi-output form's bodies over a dense
 // row-major matrix), is a wrapper around linear_dense_kernels.cuh with the matrix of dense_topology.hip; besides the row
-// passes it has the partial pass in slot 7.  A handle carries its form; the four slots of the
+// passes it has the partial pass in slot 7.  A ninth, a GRAPH-REGULARISED LINEAR-MODEL objective (the sixth form with an edge term
+// over an index list on its coordinates: three bodies), is a wrapper around linear_graph_kernels.cuh with both the matrix and
+// the incidence list; its row passes are the sixth form's.  A handle carries its form; the four slots of the
 // loaded-kernel table and everything that launches them are the same.  What the forms differ in -- names, kernel names, struct
 // members, the bodies' signatures, the K and D accepted, the cache key -- is one row each of kForms below; the generator, the
 // validation and the refusals are written once and read it.
@@ -68,6 +70,7 @@ struct FormDesc
     bool key_second, key_d;                   // do the second body and D enter the cache key
     const char* bound_with;                   // what lbfgsx_objective_bind says the form is bound with; null: it binds it
     const char* bind_suffix;                  // of the call that binds it, where that is another form's; null: suffix
+    BodyDesc third;                           // a form of three bodies: the required one between the two (no signature: none)
 };
 #define TERM_SIGNATURE "T term(const T (&x)[K], T (&g)[K], int64_t i) const"
 #define POINT_SIGNATURE(name) "T " name "(const T (&x)[1], T (&g)[1], int64_t i) const"
@@ -80,7 +83,7 @@ struct FormDesc
     "    const T* part;\n    const int32_t* long_col;\n    const uint32_t* long_chunk;\n"           \
     "    int64_t R, nnz;\n    int32_t L, C, nlong, pad_;\n"
 const BodyDesc kNoBody = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-const FormDesc kForms[8] = {
+const FormDesc kForms[9] = {
     {"term objective", "", "ObjTerm", "#include \"lbfgs_kernels.cuh\"\n#include \"lbfgsb_kernels.cuh\"\n",
      {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial", nullptr, nullptr, "k_trial_post"}, "", kNoBody,
      {"    // one term: x[0..K) in, g[0..K) out, the term's value returned\n", TERM_SIGNATURE, "objective_body", "body", nullptr,
@@ -176,7 +179,18 @@ const FormDesc kForms[8] = {
      {"    // the term of row r: z[c] = row r of the dense matrix times column c of the F x D matrix x in, its D partial derivatives\n"
       "    // dz out, its value returned\n",
       "T row(const T (&z)[D], T (&dz)[D], int64_t r) const", "row_body", "row body", nullptr, nullptr},
-     "", 1, 1, 1, 16, nullptr, "D = # is not supported: a row has D = 1 .. 16 outputs", true, true, "matrix"}};
+     "", 1, 1, 1, 16, nullptr, "D = # is not supported: a row has D = 1 .. 16 outputs", true, true, "matrix"},
+    {"graph-regularised linear-model objective", "_linear_graph", "ObjLinearGraph", "#include \"linear_graph_kernels.cuh\"\n",
+     {"k_ling_eval", "k_ling_trial", "k_ling_b_eval", "k_ling_b_dg_maxstep_trial", "k_lin_rows", "k_lin_rows_trial"},
+     // launch_args.hpp: LinearGraphArgs
+     LINEAR_MEMBERS "    const uint32_t* off;\n    const GraphEntry* inc;\n    int64_t E;\n",
+     {"    // the term of coordinate i: x[0] = x[i] in, its derivative g[0] out, its value returned\n", POINT_SIGNATURE("coord"),
+      "coord_body", "coordinate body", POINT_ABSENT, "kCoord"},
+     {"    // the term of row r: z = the row's product with x in, its derivative dz out, its value returned\n",
+      "T row(const T z, T& dz, int64_t r) const", "row_body", "row body", nullptr, nullptr},
+     "", 1, 1, 1, 1, nullptr, nullptr, true, false, "matrix and edges", nullptr,
+     {"    // the term of edge e = (i, j): x = {x[i], x[j]} in, its two partial derivatives g out, its value returned\n",
+      "T edge(const T (&x)[2], T (&g)[2], int64_t e, int64_t i, int64_t j) const", "edge_body", "edge body", nullptr, nullptr}}};
 #undef LINEAR_MEMBERS
 #undef TERM_SIGNATURE
 #undef POINT_SIGNATURE
@@ -281,8 +295,8 @@ void emit_body(std::string& s, const BodyDesc& b, const char* text)
 
 // the struct the form's kernel header asks for (the leading members are TermArgs', launch_args.hpp), and the explicit
 // instantiations of its kernels.  second: a graph, mesh or linear-model objective's optional body (null or empty: none); D: a
-// mesh objective's unknowns per node, 1 for the other forms
-std::string generate(int form, int dtype, int K, const char* body, const char* second, int D)
+// mesh objective's unknowns per node, 1 for the other forms; third: the edge body of a form of three bodies
+std::string generate(int form, int dtype, int K, const char* body, const char* second, int D, const char* third = nullptr)
 {
     const FormDesc& f = kForms[form];
     std::string s;
@@ -301,6 +315,8 @@ std::string generate(int form, int dtype, int K, const char* body, const char* s
     s += f.members;
     if (f.second.signature)
         emit_body(s, f.second, second);
+    if (f.third.signature)
+        emit_body(s, f.third, third);
     emit_body(s, f.body, body);
     s += f.rest;
     s += "};\n";
@@ -324,7 +340,8 @@ std::string refusal(const char* rule, int value)
     return k == std::string::npos ? s : s.replace(k, 1, std::to_string(value));
 }
 
-bool valid_request(int form, int dtype, int K, const char* body, const char* second, int D, std::string& why)
+bool valid_request(int form, int dtype, int K, const char* body, const char* second, int D, std::string& why,
+                   const char* third = nullptr)
 {
     const FormDesc& f = kForms[form];
     const std::string name = std::string(f.name) + ": ";
@@ -335,8 +352,12 @@ bool valid_request(int form, int dtype, int K, const char* body, const char* sec
         why = name + refusal(f.k_refusal, K);
     else if (f.d_refusal && (D < f.d_lo || D > f.d_hi))
         why = name + refusal(f.d_refusal, D);
+    else if (f.third.signature && (!third || !*third))
+        why = name + "empty " + f.third.noun;
     else if (!body || !*body)
         why = name + "empty " + f.body.noun;
+    else if (f.third.signature && std::strstr(third, "asm"))
+        why = name + "the " + f.third.noun + no_asm;
     else if (std::strstr(body, "asm"))
         why = name + "the " + f.body.noun + no_asm;
     else if (f.second.signature && second && std::strstr(second, "asm"))
@@ -476,7 +497,7 @@ std::map<std::string, std::unique_ptr<lbfgsx_objective_code> >& cache()
     return m;
 }
 
-int compile_code(int form, int dtype, int K, int D, const char* body, const char* node,
+int compile_code(int form, int dtype, int K, int D, const char* body, const char* node, const char* third,
                  std::unique_ptr<lbfgsx_objective_code>& out, std::string& log)
 {
     const Rtc& r = rtc();
@@ -485,7 +506,7 @@ int compile_code(int form, int dtype, int K, int D, const char* body, const char
         log = r.error;
         return LBFGSX_E_RUNTIME;
     }
-    const std::string src = generate(form, dtype, K, body, node, D);
+    const std::string src = generate(form, dtype, K, body, node, D, third);
     // the kernel headers ask for <hip/hip_runtime.h>; hipRTC has the runtime's declarations built in, so the name resolves
     // to an empty header instead of depending on where ROCm's headers are installed
     const char* hsrc[] = {"\n"};
@@ -591,22 +612,22 @@ int jit_launch(lbfgsx_ctx* c, int which, int grid, void** params)
 namespace {
 
 long long objective_source(int form, int dtype, int K, const char* body, char* out, size_t len, const char* node = nullptr,
-                           int D = 1)
+                           int D = 1, const char* third = nullptr)
 {
     std::string why;
-    if (!valid_request(form, dtype, K, body, node, D, why))
+    if (!valid_request(form, dtype, K, body, node, D, why, third))
     {
         lbfgsx::set_error(why);
         return LBFGSX_E_INVALID;
     }
-    const std::string s = generate(form, dtype, K, body, node, D);
+    const std::string s = generate(form, dtype, K, body, node, D, third);
     if (out && len > 0)
         std::snprintf(out, len, "%s", s.c_str());
     return (long long) s.size() + 1;
 }
 
 int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len,
-                      const char* node = nullptr, int D = 1)
+                      const char* node = nullptr, int D = 1, const char* third = nullptr)
 {
     if (log && log_len > 0)
         log[0] = '\0';
@@ -614,7 +635,7 @@ int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const 
         return LBFGSX_E_INVALID;
     *out = nullptr;
     std::string why;
-    if (!valid_request(form, dtype, K, body, node, D, why))
+    if (!valid_request(form, dtype, K, body, node, D, why, third))
     {
         lbfgsx::set_error(why);
         put_log(log, log_len, why);
@@ -623,6 +644,8 @@ int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const 
     std::string key = std::to_string(form) + "/" + std::to_string(dtype) + "/" + std::to_string(K) + "/" + body;
     if (kForms[form].key_second)
         key += std::string("\x1f") + (node ? node : "");  // both bodies
+    if (kForms[form].third.signature)
+        key += std::string("\x1f") + third;  // all three
     if (kForms[form].key_d)
         key += "\x1f" + std::to_string(D);
     std::lock_guard<std::mutex> lock(g_cache_mu);
@@ -632,7 +655,7 @@ int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const 
     {
         std::unique_ptr<lbfgsx_objective_code> code;
         std::string text;
-        const int rc = compile_code(form, dtype, K, D, body, node, code, text);
+        const int rc = compile_code(form, dtype, K, D, body, node, third, code, text);
         if (rc)
         {
             lbfgsx::set_error(std::string(kForms[form].name) + ": compilation failed\n" + text);
@@ -686,6 +709,11 @@ long long lbfgsx_objective_source_dense(int dtype, int D, const char* coord_body
 {
     return objective_source(LBFGSX_FORM_DENSE, dtype, 1, row_body, out, len, coord_body, D);
 }
+long long lbfgsx_objective_source_linear_graph(int dtype, const char* coord_body, const char* edge_body, const char* row_body,
+                                               char* out, size_t len)
+{
+    return objective_source(LBFGSX_FORM_LINEAR_GRAPH, dtype, 1, row_body, out, len, coord_body, 1, edge_body);
+}
 
 int lbfgsx_objective_compile(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len)
 {
@@ -723,6 +751,11 @@ int lbfgsx_objective_compile_dense(lbfgsx_objective** out, int dtype, int D, con
                                    size_t log_len)
 {
     return objective_compile(LBFGSX_FORM_DENSE, out, dtype, 1, row_body, log, log_len, coord_body, D);
+}
+int lbfgsx_objective_compile_linear_graph(lbfgsx_objective** out, int dtype, const char* coord_body, const char* edge_body,
+                                          const char* row_body, char* log, size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_LINEAR_GRAPH, out, dtype, 1, row_body, log, log_len, coord_body, 1, edge_body);
 }
 
 void lbfgsx_objective_destroy(lbfgsx_objective* obj) { delete obj; }
@@ -857,7 +890,8 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
             c->term_fn[k] = it->second.fn[k];
     }
     if (code->form != LBFGSX_FORM_GRAPH && code->form != LBFGSX_FORM_MESH && !lbfgsx::form_is_linear(code->form) &&
-        code->form != LBFGSX_FORM_DENSE && (c->graph_inc || c->lin.colptr || c->dense.w))
+        code->form != LBFGSX_FORM_DENSE && code->form != LBFGSX_FORM_LINEAR_GRAPH &&
+        (c->graph_inc || c->lin.colptr || c->dense.w))
     {
         (void) lbfgsx::stream_sync(c->stream);  // no launch still walks the list
         lbfgsx::graph_topology_free(c);
@@ -1011,7 +1045,7 @@ int lbfgsx_objective_bind_graph(lbfgsx_ctx* c, const lbfgsx_objective* obj, int6
 
 int lbfgsx_objective_topology(lbfgsx_ctx* c, int64_t* E, uint32_t* off, int32_t* other, uint32_t* edge_side)
 {
-    if (!c || !c->term || c->term_form != LBFGSX_FORM_GRAPH || !c->graph_inc)
+    if (!c || !c->term || (c->term_form != LBFGSX_FORM_GRAPH && c->term_form != LBFGSX_FORM_LINEAR_GRAPH) || !c->graph_inc)
     {
         lbfgsx::set_error("lbfgsx_objective_topology: no graph objective is bound to this context");
         return LBFGSX_E_INVALID;
@@ -1113,7 +1147,7 @@ int lbfgsx_objective_bind_linear(lbfgsx_ctx* c, const lbfgsx_objective* obj, int
 int lbfgsx_objective_linear_topology(lbfgsx_ctx* c, int64_t info[8], uint32_t* colptr, int32_t* trow, uint32_t* tpos,
                                      int32_t* long_col, uint32_t* long_chunk, uint32_t* chunk)
 {
-    if (!c || !c->term || !lbfgsx::form_is_linear(c->term_form) || !c->lin.colptr)
+    if (!c || !c->term || !lbfgsx::form_has_csr(c->term_form) || !c->lin.colptr)
     {
         lbfgsx::set_error("lbfgsx_objective_linear_topology: no linear-model objective is bound to this context");
         return LBFGSX_E_INVALID;
@@ -1126,6 +1160,55 @@ int lbfgsx_objective_linear_topology(lbfgsx_ctx* c, int64_t info[8], uint32_t* c
     }
     lbfgsx::DeviceGuard dev_guard_(c->device);
     return lbfgsx::linear_topology_read(c, colptr, trow, tpos, long_col, long_chunk, chunk);
+}
+
+int lbfgsx_objective_bind_linear_graph(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t R, int64_t nnz, const int32_t* rowptr,
+                                       const int32_t* col, const void* val, int matrix_on_device, int lanes, int64_t E,
+                                       const int32_t* ei, const int32_t* ej, int edges_on_device, const void* const p[4],
+                                       const double cs[8], int* id)
+{
+    if (!c || !obj)
+        return LBFGSX_E_INVALID;
+    if (const int rc = bind_begin(c, obj, LBFGSX_FORM_LINEAR_GRAPH))
+        return rc;
+    const int64_t lim = 2147483647;
+    std::string why;
+    if (E < 1 || !ei || !ej)
+        why = "E = " + std::to_string(E) + ": a graph-regularised linear-model objective has at least one edge (E >= 1) and both index arrays";
+    else if (E > lim)
+        why = "E = " + std::to_string(E) + " exceeds 2^31 - 1 = " + std::to_string(lim) +
+              ": an incidence entry holds (e << 1) | side in 32 bits";
+    else if (R < 1 || nnz < 1 || !rowptr || !col || !val)
+        why = "R = " + std::to_string(R) + ", nnz = " + std::to_string(nnz) +
+              ": a linear-model objective has at least one row and one entry (R >= 1, nnz >= 1) and its three CSR arrays";
+    else if (R > lim)
+        why = "R = " + std::to_string(R) + " exceeds 2^31 - 1 = " + std::to_string(lim) + ": row indices are int32";
+    else if (nnz > lim)
+        why = "nnz = " + std::to_string(nnz) + " exceeds 2^31 - 1 = " + std::to_string(lim) + ": row offsets are int32";
+    else if (c->n > lim)
+        why = "n = " + std::to_string(c->n) + " exceeds 2^31 - 1 = " + std::to_string(lim) + ": column and node indices are int32";
+    else if (lanes < 0 || lanes > 64 || (lanes & (lanes - 1)) != 0)
+        why = "lanes = " + std::to_string(lanes) + ": the lanes that share a row are 0 (by the rule) or a power of two in 1..64";
+    if (!why.empty())
+    {
+        lbfgsx::set_error(std::string(kForms[LBFGSX_FORM_LINEAR_GRAPH].name) + ": " + why);
+        return LBFGSX_E_INVALID;
+    }
+    {
+        // the edges first, then the matrix beside them: either build validates its indices before anything else and leaves the
+        // context without a list when one offends
+        lbfgsx::DeviceGuard dev_guard_(c->device);
+        int rc = lbfgsx::graph_topology_build(c, ei, ej, E, edges_on_device);
+        if (rc)
+            return rc;
+        rc = lbfgsx::linear_topology_build(c, R, nnz, rowptr, col, val, matrix_on_device, lanes, 0, true);
+        if (rc)
+        {
+            lbfgsx::graph_topology_free(c);
+            return rc;
+        }
+    }
+    return bind_end(c, obj, p, cs, id);
 }
 
 int lbfgsx_objective_bind_dense(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t R, const void* A, int64_t lda, int a_on_device,

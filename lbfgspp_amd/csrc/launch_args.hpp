@@ -210,10 +210,23 @@ inline DenseArgs<T> dense_args(const lbfgsx_ctx* c, const TermArgs<T>& t)
     return {t, static_cast<const T*>(d.A), static_cast<T*>(d.w), static_cast<T*>(d.v), static_cast<T*>(d.part), d.R, d.F, d.lda,
             d.chunks, d.L, d.C, 0, 0};
 }
-// the two forms that bind a CSR matrix: a linear-model objective and a multi-output one
+// the by-value argument of a graph-regularised linear-model objective's kernels: layout of the generated struct
+// ObjLinearGraph (LinearArgs, then the context's incidence list as in GraphArgs)
+template <class T>
+struct LinearGraphArgs
+{
+    LinearArgs<T> l;
+    const uint32_t* off;
+    const GraphEntry* inc;
+    int64_t E;
+};
+// the two forms that lbfgsx_objective_bind_linear binds: a linear-model objective and a multi-output one
 inline bool form_is_linear(int form) { return form == LBFGSX_FORM_LINEAR || form == LBFGSX_FORM_LINEAR_MULTI; }
+// the forms whose evaluation is a row pass over a CSR matrix and a column walk: those two and the graph-regularised one
+inline bool form_has_csr(int form) { return form_is_linear(form) || form == LBFGSX_FORM_LINEAR_GRAPH; }
 // the objective argument of the bound handle's kernels, by its form: &term for a term or chain objective, &grid for a grid
-// one, &graph for a graph one, &mesh for a mesh one, &linear for a linear-model one of either form, &dense for a dense one
+// one, &graph for a graph one, &mesh for a mesh one, &linear for a linear-model one of either form, &dense for a dense one,
+// &linear_graph for a graph-regularised linear-model one
 template <class T>
 struct BoundArgs
 {
@@ -223,6 +236,7 @@ struct BoundArgs
     MeshArgs<T> mesh;
     LinearArgs<T> linear;
     DenseArgs<T> dense;
+    LinearGraphArgs<T> linear_graph;
     void* ptr;
     explicit BoundArgs(const lbfgsx_ctx* c)
         : term(term_args<T>(c)),
@@ -231,13 +245,15 @@ struct BoundArgs
           mesh{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const uint32_t*>(c->graph_inc), c->graph_E,
                c->mesh_D ? c->n / c->mesh_D : 0},
           linear(linear_args<T>(c, term)),
-          dense(dense_args<T>(c, term))
+          dense(dense_args<T>(c, term)),
+          linear_graph{linear, static_cast<const uint32_t*>(c->graph_off), static_cast<const GraphEntry*>(c->graph_inc), c->graph_E}
     {
         ptr = (c->term_form == LBFGSX_FORM_GRID)    ? static_cast<void*>(&grid)
               : (c->term_form == LBFGSX_FORM_GRAPH) ? static_cast<void*>(&graph)
               : (c->term_form == LBFGSX_FORM_MESH)  ? static_cast<void*>(&mesh)
               : form_is_linear(c->term_form)        ? static_cast<void*>(&linear)
               : (c->term_form == LBFGSX_FORM_DENSE) ? static_cast<void*>(&dense)
+              : (c->term_form == LBFGSX_FORM_LINEAR_GRAPH) ? static_cast<void*>(&linear_graph)
                                                     : static_cast<void*>(&term);
     }
     BoundArgs(const BoundArgs&) = delete;
@@ -256,19 +272,21 @@ struct BoundArgs
 //           reads (n values per vector gathered), w written and read (R*D each), v written and read (R each), the chunk
 //           partials written and read (chunks*n each).  The row pass's re-reads of x by the rows of a block and the partial
 //           pass's re-reads of w by the threads of a chunk are served by the caches and are not modelled
+//   graph-regularised linear  the linear form's terms plus the graph form's list terms (its offsets, entries and gathered other
+//           ends): the column pass walks both lists
 // A trial launch adds it at its call site; an evaluation adds only a linear-model objective's, in linear_pre_eval.
 template <class T>
 inline void objective_model_add(const lbfgsx_ctx* c, int vectors_gathered)
 {
     const double esz = sizeof(T), vg = vectors_gathered;
-    if (c->term_form == LBFGSX_FORM_GRAPH)
+    if (c->term_form == LBFGSX_FORM_GRAPH || c->term_form == LBFGSX_FORM_LINEAR_GRAPH)
         model_add(double(c->n + 1) * 4 + double(2 * c->graph_E) * 8 + double(2 * c->graph_E) * esz * vg);
-    else if (c->term_form == LBFGSX_FORM_MESH)
+    if (c->term_form == LBFGSX_FORM_MESH)
     {
         const double K = c->mesh_K, D = c->mesh_D, KE = K * double(c->graph_E);
         model_add(double(c->n / c->mesh_D + 1) * 4 + KE * 4 * K + KE * (K - 1) * D * esz * vg);
     }
-    else if (form_is_linear(c->term_form))
+    else if (form_has_csr(c->term_form))
     {
         const double R = double(c->lin.R), nnz = double(c->lin.nnz), D = c->lin.D ? c->lin.D : 1;
         model_add((R + 1) * 4 + (double(c->n) / D + 1) * 4 + 2 * nnz * 4 + 2 * nnz * esz + nnz * esz * (vg + 1) * D +
@@ -293,11 +311,12 @@ int mesh_topology_read(lbfgsx_ctx* c, uint32_t* off, uint32_t* words);
 // first and leaves the context without a matrix when one offends (LBFGSX_E_INVALID, the position named); lanes: 0 = by the
 // rule (linear_lanes_rule), otherwise the lanes per row.  long_launch: the launch between the two passes, none when the
 // matrix has no long column.  D: the outputs per row of a multi-output objective (the matrix then has n / D columns), 0 for
-// the scalar form
+// the scalar form.  beside_graph: the incidence list the context holds stays (lbfgsx_objective_bind_linear_graph builds it first);
+// otherwise every other form's list is freed first
 constexpr int kLinearChunk = 4096;  // C: a column with more entries is long and is summed in chunks of C by k_lin_long_cols
 int linear_lanes_rule(int64_t R, int64_t nnz);
 int linear_topology_build(lbfgsx_ctx* c, int64_t R, int64_t nnz, const int32_t* rowptr, const int32_t* col, const void* val,
-                          int on_device, int lanes, int D = 0);
+                          int on_device, int lanes, int D = 0, bool beside_graph = false);
 int linear_topology_read(lbfgsx_ctx* c, uint32_t* colptr, int32_t* trow, uint32_t* tpos, int32_t* long_col, uint32_t* long_chunk,
                          uint32_t* chunk);
 void linear_topology_free(lbfgsx_ctx* c);
@@ -341,7 +360,7 @@ inline int dense_partials_grid(const lbfgsx_ctx* c)
 // the column pass strides over v[R] as well as over the n coordinates: its grid covers the longer of the two
 inline int linear_col_grid(const lbfgsx_ctx* c, int grid)
 {
-    if (!form_is_linear(c->term_form) && c->term_form != LBFGSX_FORM_DENSE)
+    if (!form_has_csr(c->term_form) && c->term_form != LBFGSX_FORM_DENSE)
         return grid;
     const int gr = c->grid_for(c->term_form == LBFGSX_FORM_DENSE ? c->dense.R : c->lin.R);
     return gr > grid ? gr : grid;
@@ -358,7 +377,7 @@ inline int linear_mid_launch(lbfgsx_ctx* c, BoundArgs<T>& obj)
 template <class T>
 inline int linear_pre_eval(lbfgsx_ctx* c, BoundArgs<T>& obj, const T* x)
 {
-    if (!form_is_linear(c->term_form) && c->term_form != LBFGSX_FORM_DENSE)
+    if (!form_has_csr(c->term_form) && c->term_form != LBFGSX_FORM_DENSE)
         return LBFGSX_OK;
     objective_model_add<T>(c, 1);
     void* params[] = {&x, obj.ptr};
@@ -368,7 +387,7 @@ inline int linear_pre_eval(lbfgsx_ctx* c, BoundArgs<T>& obj, const T* x)
 template <class T>
 inline int linear_pre_trial(lbfgsx_ctx* c, BoundArgs<T>& obj, const T* xp, const T* d, T step)
 {
-    if (!form_is_linear(c->term_form) && c->term_form != LBFGSX_FORM_DENSE)
+    if (!form_has_csr(c->term_form) && c->term_form != LBFGSX_FORM_DENSE)
         return LBFGSX_OK;
     void* params[] = {&xp, &d, &step, obj.ptr};
     const int rc = jit_launch(c, JIT_K_LIN_ROWS_TRIAL, linear_rows_grid(c), params);

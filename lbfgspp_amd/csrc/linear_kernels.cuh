@@ -252,19 +252,6 @@ __global__ void __launch_bounds__(kBlock) k_lin_rows_trial(const T* __restrict__
 }
 
 // ---------------------------------------------------------------- the column pass
-// a sum in a fixed order that starts from its first term (no leading 0 +); +0 without one
-template <class T>
-struct LinSum
-{
-    T value = T(0);
-    bool has = false;
-    __device__ __forceinline__ void add(T t)
-    {
-        value = has ? value + t : t;
-        has = true;
-    }
-};
-
 // how every form's coordinate i with value xi starts: psi's value to fx, its derivative as the first term of the gradient
 template <class T, class OBJ, class A>
 __device__ __forceinline__ LinSum<T> lin_coord_start(const OBJ& obj, int64_t i, T xi, A& fx)
@@ -280,15 +267,26 @@ __device__ __forceinline__ LinSum<T> lin_coord_start(const OBJ& obj, int64_t i, 
     return gv;
 }
 
+// what the sparse forms put between psi's term and the column's contributions: nothing
+struct LinNoMid
+{
+    template <class S>
+    __device__ __forceinline__ void operator()(S&) const
+    {
+    }
+};
+
 // coordinate i = j*D + c with value xi and column j's transposed entries [lo, hi): its gradient, returned; psi's value goes
-// to fx
-template <class T, class OBJ, class A>
-__device__ __forceinline__ T lin_coord(const OBJ& obj, int64_t i, T xi, uint32_t lo, uint32_t hi, A& fx)
+// to fx.  The gradient is one running sum: psi's derivative, then whatever mid(gv) adds to it (the graph-regularised form's edge
+// terms, linear_graph_kernels.cuh), then the column's contributions
+template <class T, class OBJ, class A, class MID = LinNoMid>
+__device__ __forceinline__ T lin_coord(const OBJ& obj, int64_t i, T xi, uint32_t lo, uint32_t hi, A& fx, MID mid = MID())
 {
     constexpr int G = kLinGroup, D = lin_outputs<OBJ>;
     const int64_t j = i / D;
     const int c = int(i - j * D);
     LinSum<T> gv = lin_coord_start<T>(obj, i, xi, fx);
+    mid(gv);
     if (hi - lo > uint32_t(obj.C))
     {
         // a long column: its slot in the (ascending) table of long columns, then its chunk partials in ascending order

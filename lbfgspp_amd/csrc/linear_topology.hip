@@ -358,10 +358,11 @@ void linear_topology_free(lbfgsx_ctx* c)
 }
 
 int linear_topology_build(lbfgsx_ctx* c, int64_t R, int64_t nnz, const int32_t* rowptr, const int32_t* col, const void* val,
-                          int on_device, int lanes, int D)
+                          int on_device, int lanes, int D, bool beside_graph)
 {
     LBFGSX_HIP(stream_sync(c->stream));  // no launch of an earlier binding still walks the list this call frees
-    graph_topology_free(c);
+    if (!beside_graph)
+        graph_topology_free(c);
     const int rc = build(c, R, nnz, rowptr, col, val, on_device, lanes, D);
     if (rc)
     {

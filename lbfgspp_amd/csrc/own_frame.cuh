@@ -1,7 +1,8 @@
 // lbfgspp_amd/csrc/own_frame.cuh -- the frame of the owner-computes gather kernels: the four evaluation kernels of a GRAPH,
 // a MESH and a LINEAR-MODEL objective (graph_kernels.cuh, mesh_kernels.cuh, the column pass of linear_kernels.cuh,
-// linear_multi_kernels.cuh and linear_dense_kernels.cuh) are own_eval and own_trial, bounded or not, around the family's walk
-// of one node's list.  LBFGSX_OWN_KERNELS, at the end of this file, defines a family's four kernels.
+// linear_multi_kernels.cuh, linear_dense_kernels.cuh and linear_graph_kernels.cuh) are own_eval and own_trial, bounded or
+// not, around the family's walk of one node's list.  LBFGSX_OWN_KERNELS, at the end of this file, defines a family's four
+// kernels.
 //
 // Ownership.  x holds D unknowns per node, node-major.  A thread owns W = 16 / sizeof(T) consecutive nodes: exactly D whole
 // 16-byte packs of x from pack vi*D; it loads the W + 1 offsets of its nodes' lists, walks each list and writes the nodes'
@@ -25,6 +26,20 @@
 #include "lbfgsb_kernels.cuh"
 
 namespace lbfgsx {
+
+// a sum in a fixed order that starts from its first term (no leading 0 +); +0 without one: what a node's walk accumulates
+// its partial derivative in, whichever family's lists it walks
+template <class T>
+struct LinSum
+{
+    T value = T(0);
+    bool has = false;
+    __device__ __forceinline__ void add(T t)
+    {
+        value = has ? value + t : t;
+        has = true;
+    }
+};
 
 // does family F give a node's (lo, hi) itself (F::kRange); the default is the load from F::off
 template <class F, class = void>

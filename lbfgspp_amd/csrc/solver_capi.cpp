@@ -48,6 +48,9 @@ struct lbfgsx_solver
         const int32_t *rowptr = nullptr, *col = nullptr;
         const void* val = nullptr;
         int lanes = 0;
+        // a graph-regularised linear-model objective has both: the matrix above and the edges ei, ej, which are device arrays
+        // when edges_dev says so (on_device then speaks of the matrix alone)
+        int edges_dev = 0;
         // a dense linear-model objective's matrix in place of all of the above (A null: not one): R rows, row stride lda
         const void* A = nullptr;
         int64_t lda = 0;
@@ -233,8 +236,13 @@ struct LbfgsImpl : lbfgsx_solver
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
         LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
         DenseLinearObjective<Scalar> densed(obj);       // binds with the dense matrix when there is one
+        GraphLinearObjective<Scalar> coupled(obj);      // binds with the matrix and the edges when there are both
+        const bool both = gr && gr->rowptr && gr->ei;
         if (gr && gr->A)
             densed.matrix(gr->R, static_cast<const Scalar*>(gr->A), gr->lda, gr->on_device != 0, gr->lanes);
+        else if (both)
+            coupled.matrix(gr->R, gr->nnz, gr->rowptr, gr->col, static_cast<const Scalar*>(gr->val), gr->on_device != 0, gr->lanes)
+                .edges(gr->E, gr->ei, gr->ej, gr->edges_dev != 0);
         else if (gr && gr->rowptr)
             lined.matrix(gr->R, gr->nnz, gr->rowptr, gr->col, static_cast<const Scalar*>(gr->val), gr->on_device != 0, gr->lanes);
         else if (gr && gr->elems)
@@ -242,6 +250,7 @@ struct LbfgsImpl : lbfgsx_solver
         else if (gr)
             graphed.edges(gr->E, gr->ei, gr->ej, gr->on_device != 0);
         TermObjective<Scalar>& f = (gr && gr->A)       ? static_cast<TermObjective<Scalar>&>(densed)
+                                   : both              ? static_cast<TermObjective<Scalar>&>(coupled)
                                    : (gr && gr->rowptr) ? static_cast<TermObjective<Scalar>&>(lined)
                                    : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
                                    : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
@@ -358,8 +367,13 @@ struct LbfgsbImpl : lbfgsx_solver
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
         LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
         DenseLinearObjective<Scalar> densed(obj);       // binds with the dense matrix when there is one
+        GraphLinearObjective<Scalar> coupled(obj);      // binds with the matrix and the edges when there are both
+        const bool both = gr && gr->rowptr && gr->ei;
         if (gr && gr->A)
             densed.matrix(gr->R, static_cast<const Scalar*>(gr->A), gr->lda, gr->on_device != 0, gr->lanes);
+        else if (both)
+            coupled.matrix(gr->R, gr->nnz, gr->rowptr, gr->col, static_cast<const Scalar*>(gr->val), gr->on_device != 0, gr->lanes)
+                .edges(gr->E, gr->ei, gr->ej, gr->edges_dev != 0);
         else if (gr && gr->rowptr)
             lined.matrix(gr->R, gr->nnz, gr->rowptr, gr->col, static_cast<const Scalar*>(gr->val), gr->on_device != 0, gr->lanes);
         else if (gr && gr->elems)
@@ -367,6 +381,7 @@ struct LbfgsbImpl : lbfgsx_solver
         else if (gr)
             graphed.edges(gr->E, gr->ei, gr->ej, gr->on_device != 0);
         TermObjective<Scalar>& f = (gr && gr->A)       ? static_cast<TermObjective<Scalar>&>(densed)
+                                   : both              ? static_cast<TermObjective<Scalar>&>(coupled)
                                    : (gr && gr->rowptr) ? static_cast<TermObjective<Scalar>&>(lined)
                                    : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
                                    : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
@@ -962,6 +977,9 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
                                         "lbfgsx_solver_minimize_linear");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_DENSE)
             throw std::invalid_argument("a dense linear-model objective is minimised with its matrix: lbfgsx_solver_minimize_dense");
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_LINEAR_GRAPH)
+            throw std::invalid_argument("a graph-regularised linear-model objective is minimised with its matrix and edges: "
+                                        "lbfgsx_solver_minimize_linear_graph");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_CHAIN)
         {
             if (n < K)
@@ -1114,6 +1132,44 @@ int lbfgsx_solver_minimize_linear(lbfgsx_solver* s, const lbfgsx_objective* obj,
     lbfgsx_solver::GraphSpec gr;
     gr.E = 0, gr.ei = gr.ej = nullptr, gr.on_device = matrix_on_device, gr.counts = counts, gr.elems = nullptr;
     gr.R = R, gr.nnz = nnz, gr.rowptr = rowptr, gr.col = col, gr.val = val, gr.lanes = lanes;
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+}
+
+int lbfgsx_solver_minimize_linear_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, int64_t nnz,
+                                        const int32_t* rowptr, const int32_t* col, const void* val, int matrix_on_device,
+                                        int lanes, int64_t E, const int32_t* ei, const int32_t* ej, int edges_on_device,
+                                        const void* const p[4], int host_mask, const int64_t counts[4], const double c[8],
+                                        void* x, const void* lb, const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    const int bad = guarded(out, [&]() {
+        if (!s || !obj || n <= 0)
+            throw std::invalid_argument("lbfgsx_solver_minimize_linear_graph: invalid argument");
+        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_LINEAR_GRAPH)
+            throw std::invalid_argument("lbfgsx_solver_minimize_linear_graph: the handle is not a graph-regularised linear-model "
+                                        "objective (lbfgsx_objective_compile_linear_graph)");
+        if (lbfgsx_objective_dtype(obj) != s->dtype)
+            throw std::invalid_argument("lbfgsx_solver_minimize_linear_graph: the objective was compiled for the other dtype");
+        if (E < 1 || !ei || !ej)
+            throw std::invalid_argument("graph-regularised linear-model objective: E = " + std::to_string(E) +
+                                        ": a graph-regularised linear-model objective has at least one edge (E >= 1) and both "
+                                        "index arrays");
+        if (R < 1 || nnz < 1 || !rowptr || !col || !val)
+            throw std::invalid_argument("graph-regularised linear-model objective: R = " + std::to_string(R) + ", nnz = " +
+                                        std::to_string(nnz) + ": a linear-model objective has at least one row and one entry "
+                                        "(R >= 1, nnz >= 1) and its three CSR arrays");
+    });
+    if (bad)
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_linear_graph: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    lbfgsx_solver::GraphSpec gr;
+    gr.E = E, gr.ei = ei, gr.ej = ej, gr.on_device = matrix_on_device, gr.counts = counts, gr.elems = nullptr;
+    gr.R = R, gr.nnz = nnz, gr.rowptr = rowptr, gr.col = col, gr.val = val, gr.lanes = lanes, gr.edges_dev = edges_on_device;
     return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 

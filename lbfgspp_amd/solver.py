@@ -11,6 +11,7 @@ std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device ob
 `GraphObjective(edge_body, edges)` for edge terms over an index list,
 `MeshObjective(elem_body, elements, dim)` for K-node elements with vector unknowns, or
 `LinearObjective(row_body, (rowptr, col, val), n)` for a linear model over a sparse matrix, or
+`GraphLinearObjective(row_body, (rowptr, col, val), (ei, ej), edge_body, n)` for one with an edge term over a graph on its weights, or
 `MultiLinearObjective(row_body, (rowptr, col, val), features, outputs)` for one with several outputs per row, or
 `DenseLinearObjective(row_body, matrix, outputs)` for one over a dense matrix)
 or the caller's own callable, `DeviceObjective(fn)`: fn(x, grad) -> float on torch
@@ -506,6 +507,51 @@ class LinearObjective(TermObjective):
         return self.rowptr.ctypes.data, self.col.ctypes.data, val.ctypes.data, 0, (val,)
 
 
+class GraphLinearObjective(LinearObjective):
+    """A linear model with a coupling term over a graph on its weights: x are the n weights, A is a sparse R x n CSR matrix,
+    the E edges are (ei[e], ej[e]), and
+    f(x) = sum over coordinates j of psi(x[j]; j) + sum over edges e of rho(x[ei[e]], x[ej[e]]; e) + sum over rows r of
+    phi(z_r; r) with z = A x -- tomographic and deblurring reconstruction with a smoothness or smoothed-TV prior under
+    non-negativity (LBFGSBSolver), Poisson or logistic regression with a GMRF / ICAR prior on a latent field, Laplacian-
+    regularised least squares, fused and graph-trend regression (include/lbfgsx.h, "graph-regularised linear-model
+    objectives").  row_body and coord_body are a LinearObjective's, edge_body is a GraphObjective's (T, const T x[2], T g[2],
+    int64_t e, i, j); the three share p0..p3 and c[8].  grad[j] is the coordinate term's g[0], then the g_e[side] of the edges
+    incident to j in ascending e, then val * phi'(z_r) over the entries of column j in ascending r.
+
+        smooth = GraphLinearObjective("const T u = z - p0[r]; dz = u; return T(0.5) * (u * u);", (rowptr, col, val), (ei, ej),
+                                      "const T d = x[0] - x[1]; const T w = c[0] * d; g[0] = w; g[1] = T(0) - w;"
+                                      "return T(0.5) * (w * d);", n=n, data=(b,), scalars=(lam,))
+
+    matrix as for a LinearObjective, edges as for a GraphObjective (E >= 1, so n >= 2); both are copied, validated and turned
+    into the transposed matrix and the incidence list on the device at every minimise.  Each data[k] has n, E or R elements.
+    Otherwise a LinearObjective's interface; usable wherever one is, refused where one is."""
+    _NAME = "GraphLinearObjective"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_linear_graph", "lbfgsx_objective_source_linear_graph"
+
+    def __init__(self, row_body, matrix, edges, edge_body, n, coord_body=None, lanes=0, data=(), scalars=()):
+        try:
+            ei, ej = edges
+        except (TypeError, ValueError):
+            raise ValueError("GraphLinearObjective: edges must be a pair (ei, ej) of integer arrays") from None
+        # the matrix and the index arrays are checked as the two parent forms check them, in their words
+        self.ei, self.ej = GraphObjective._indices(ei, "ei"), GraphObjective._indices(ej, "ej")
+        super().__init__(row_body, matrix, n, coord_body, data, scalars, lanes)
+        if self.ei.size != self.ej.size:
+            raise ValueError("GraphLinearObjective: ei has %d elements and ej has %d: one pair per edge" % (self.ei.size, self.ej.size))
+        if self.ei.size < 1:
+            raise ValueError("GraphLinearObjective: E = 0: a graph-regularised linear model has at least one edge")
+        self.E = int(self.ei.size)
+        if self.n < 2:
+            raise ValueError("GraphLinearObjective: n = %d: an edge joins two different coordinates (n >= 2)" % self.n)
+        self.edge_body = str(edge_body)
+
+    def _form_args(self):
+        return (self.coord_body.encode() if self.coord_body else None, self.edge_body.encode())
+
+    def _data_sizes(self, n):
+        return (n, self.E, self.R)
+
+
 class MultiLinearObjective(LinearObjective):
     """A linear model with D = outputs values per sample: x holds an F x D weight matrix, feature-major (x[j*D + c],
     n = features * outputs), A is a sparse R x F CSR matrix, Z = A X, and
@@ -828,7 +874,13 @@ class _SolverBase:
             torch.cuda.current_stream().synchronize()  # the data arrays are complete when the library reads them
         tail = (C.byref(ptrs), mask, C.byref(cs), self._ptr(x), self._ptr(lb), self._ptr(ub), C.byref(trace.c) if trace else None,
                 C.byref(res))
-        if isinstance(f, DenseLinearObjective):
+        if isinstance(f, GraphLinearObjective):
+            rp, cp, vp, on_dev, keep_m = f._matrix_args(self)
+            rc = self._sol.lbfgsx_solver_minimize_linear_graph(self._h, h, n, f.R, f.nnz, rp, cp, vp, on_dev, f.lanes, f.E,
+                                                               f.ei.ctypes.data, f.ej.ctypes.data, 0, tail[0], mask,
+                                                               C.byref(counts), *tail[2:])
+            del keep_m
+        elif isinstance(f, DenseLinearObjective):
             ap, lda, on_dev, keep_m = f._matrix_args(self)
             rc = self._sol.lbfgsx_solver_minimize_dense(self._h, h, n, f.R, ap, lda, on_dev, f.lanes, tail[0], mask,
                                                         C.byref(counts), *tail[2:])
@@ -868,7 +920,8 @@ class _SolverBase:
         if not hasattr(f, "objective"):
             raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body), "
                             "GridObjective(body, shape), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim), "
-                            "LinearObjective(row_body, matrix, n), MultiLinearObjective(row_body, matrix, features, outputs), "
+                            "LinearObjective(row_body, matrix, n), GraphLinearObjective(row_body, matrix, edges, edge_body, n), "
+                            "MultiLinearObjective(row_body, matrix, features, outputs), "
                             "DenseLinearObjective(row_body, matrix, outputs) or DeviceObjective(fn)")
         res = L.Result()
         a = None if f.a is None else np.ascontiguousarray(f.a, _NP[self.dtype])
