@@ -4,8 +4,10 @@
 //
 // k_grid_eval, k_grid_trial, k_grid_b_eval and k_grid_b_dg_maxstep_trial take the arguments of k_eval, k_trial, k_b_eval and
 // k_b_dg_maxstep_trial and are launched with their grids: the same outputs, tile order, reductions and completion signal;
-// launch_args.hpp serves all three families.  They are compiled at run time only (jit_objective.hip): OBJ is the struct
-// generated around the caller's text for one cell,
+// launch_args.hpp serves all three families.  They are halo_eval and halo_trial (halo_frame.cuh) around GridFamily, at the
+// end of this file: the frame holds the loops, the bounds, the sums and the tail's order; this file holds what a grid loads,
+// its three windows, the cells of a pack and the position carried along the loop.  They are compiled at run time only
+// (jit_objective.hip): OBJ is the struct generated around the caller's text for one cell,
 //     int64_t rows, cols;   T term(const T (&x)[4], T (&g)[4], int64_t i, int64_t row, int64_t col) const;
 //
 // Ownership.  The thread that owns coordinate j = r*cols + c writes grad[j] and adds the value of the cell whose origin is j
@@ -229,59 +231,6 @@ __device__ __forceinline__ T grid_tail(const OBJ& obj, int64_t j, LD ld, A& fx)
     return gi;
 }
 
-// ---------------------------------------------------------------- k_eval's counterpart
-// out[0] = f(x), out[1] = g.g, out[2] = x.x
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_grid_eval(const T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                      T* __restrict__ out)
-{
-    typedef typename AccOf<T>::type A;
-    constexpr int W = Vec16<T>::W;
-    A acc[3];
-    const int64_t cols = obj.cols;
-    const bool aligned = cols % W == 0;
-    const int64_t nv = n / W;
-    const int64_t stride = int64_t(gridDim.x) * kBlock;
-    const int lane = threadIdx.x & 63;
-    const GridPos step = grid_pos(stride * W, cols);
-    GridPos pos = grid_pos((int64_t(blockIdx.x) * kBlock + threadIdx.x) * W, cols);
-    for (int64_t v0 = int64_t(blockIdx.x) * kBlock + (threadIdx.x - lane); v0 < nv; v0 += stride)
-    {
-        const int64_t vi = v0 + lane;
-        GridLoads<T> xv;
-        T up[W + 2], mid[W + 2], dn[W + 2];
-        grid_load(x, vi, nv, n, cols, aligned, xv);
-        grid_windows(xv, vi, nv, n, cols, [&](int64_t e) { return x[e]; }, up, mid, dn);
-        if (vi < nv)
-        {
-            Pack<T> pg;
-            grid_pack(obj, vi, pos, up, mid, dn, pg, acc[0]);
-            stv(g, vi, pg);
-#pragma unroll
-            for (int k = 0; k < W; k++)
-            {
-                acc[1].add_prod(pg.e[k], pg.e[k]);
-                acc[2].add_prod(xv.p[1].e[k], xv.p[1].e[k]);
-            }
-        }
-        grid_advance(pos, step, cols);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int64_t i = nv * W; i < n; i++)
-        {
-            const T gi = grid_tail<T>(obj, i, [&](int64_t k) { return x[k]; }, acc[0]);
-            g[i] = gi;
-            acc[1].add_prod(gi, gi);
-            acc[2].add_prod(x[i], x[i]);
-        }
-    if (grid_reduce<3>(acc, ws) && threadIdx.x == 0)
-    {
-        out[0] = T(acc[0].value());
-        out[1] = T(acc[1].value());
-        out[2] = T(acc[2].value());
-    }
-}
-
 // the tile depth of the two trial kernels: a tile loads three rows of xp and of d (the chain kernels' 4 with one row)
 constexpr int kGridTrialU = 2;
 
@@ -300,250 +249,49 @@ __device__ __forceinline__ void grid_axpy(const GridLoads<T>& xp, const GridLoad
     }
 }
 
-// ---------------------------------------------------------------- k_trial's counterpart
-// x = xp + step*d ; g = grad f(x) ; out[0] = f(x), out[1] = g.d
+// the frame's family (halo_frame.cuh): three rows of halo 1, and the (row, col) of a pack carried along the loop
 template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_grid_trial(const T* __restrict__ xp, const T* __restrict__ d, T step,
-                                                       T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                       T* __restrict__ out, int rev)
+struct GridFamily
 {
-    typedef typename AccOf<T>::type A;
-    constexpr int W = Vec16<T>::W;
-    constexpr int U = kGridTrialU;
-    A acc[2];
-    const int64_t cols = obj.cols;
-    const bool aligned = cols % W == 0;
-    const int64_t nv = n / W;
-    const int64_t tile = int64_t(kBlock) * U;
-    const int64_t top = ((nv + tile - 1) / tile - 1) * tile;
-    const GridPos ustep = grid_pos(int64_t(kBlock) * W, cols);
-    const GridPos tstep = grid_pos(int64_t(gridDim.x) * tile * W, cols);
-    const int64_t first = int64_t(blockIdx.x) * tile;
-    GridPos pos0 = {0, 0};
-    if (first < nv)
-        pos0 = grid_pos(((rev ? top - first : first) + threadIdx.x) * W, cols);
-    for (int64_t t0 = first; t0 < nv; t0 += int64_t(gridDim.x) * tile)  // the block's: all lanes stay in
-    {
-        const int64_t base = (rev ? top - t0 : t0) + threadIdx.x;
-        GridLoads<T> lxp[U], ld_[U];
-#pragma unroll
-        for (int u = 0; u < U; u++)
-        {
-            grid_load(xp, base + u * kBlock, nv, n, cols, aligned, lxp[u]);
-            grid_load(d, base + u * kBlock, nv, n, cols, aligned, ld_[u]);
-        }
-        GridPos pos = pos0;
-#pragma unroll
-        for (int u = 0; u < U; u++)
-        {
-            const int64_t vi = base + u * kBlock;
-            GridLoads<T> xv;
-            T up[W + 2], mid[W + 2], dn[W + 2];
-            grid_axpy(lxp[u], ld_[u], step, xv);
-            grid_windows(xv, vi, nv, n, cols, [&](int64_t e) { return xp[e] + step * d[e]; }, up, mid, dn);
-            if (vi < nv)
-            {
-                Pack<T> pg;
-                grid_pack(obj, vi, pos, up, mid, dn, pg, acc[0]);
-                stv(x, vi, xv.p[1]);
-                stv(g, vi, pg);
-#pragma unroll
-                for (int k = 0; k < W; k++)
-                    acc[1].add_prod(pg.e[k], ld_[u].p[1].e[k]);
-            }
-            grid_advance(pos, ustep, cols);
-        }
-        if (rev)
-            grid_retreat(pos0, tstep, cols);
-        else
-            grid_advance(pos0, tstep, cols);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int64_t i = nv * W; i < n; i++)
-        {
-            x[i] = xp[i] + step * d[i];
-            const T gi = grid_tail<T>(obj, i, [&](int64_t k) { return xp[k] + step * d[k]; }, acc[0]);
-            g[i] = gi;
-            acc[1].add_prod(gi, d[i]);
-        }
-    if (grid_reduce<2>(acc, ws) && threadIdx.x == 0)
-    {
-        out[0] = T(acc[0].value());
-        out[1] = T(acc[1].value());
-        ws_signal(ws);
-    }
-}
+    static constexpr int W = Vec16<T>::W;
+    static constexpr int U = kGridTrialU;
+    typedef GridLoads<T> Loads;
+    typedef GridPos Pos;
+    __device__ __forceinline__ static Pos pos(const OBJ& obj, int64_t flat) { return grid_pos(flat, obj.cols); }
+    __device__ __forceinline__ static void advance(const OBJ& obj, Pos& p, const Pos& step) { grid_advance(p, step, obj.cols); }
+    __device__ __forceinline__ static void retreat(const OBJ& obj, Pos& p, const Pos& step) { grid_retreat(p, step, obj.cols); }
 
-// ---------------------------------------------------------------- k_b_eval's counterpart
-// out[0] = f(x), out[1] = x.x, out[2] = ||P(x-g)-x||_inf
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_grid_b_eval(const T* __restrict__ x, T* __restrict__ g, const T* __restrict__ lb,
-                                                        const T* __restrict__ ub, int64_t n, OBJ obj, RedWs ws,
-                                                        T* __restrict__ out)
-{
-    typedef typename AccOf<T>::type A;
-    constexpr int W = Vec16<T>::W;
-    A acc[2];
-    double pg = 0.0;
-    const int64_t cols = obj.cols;
-    const bool aligned = cols % W == 0;
-    const int64_t nv = n / W;
-    const int64_t stride = int64_t(gridDim.x) * kBlock;
-    const int lane = threadIdx.x & 63;
-    const GridPos step = grid_pos(stride * W, cols);
-    GridPos pos = grid_pos((int64_t(blockIdx.x) * kBlock + threadIdx.x) * W, cols);
-    for (int64_t v0 = int64_t(blockIdx.x) * kBlock + (threadIdx.x - lane); v0 < nv; v0 += stride)
+    __device__ __forceinline__ static void load(const T* __restrict__ v, int64_t vi, int64_t nv, int64_t n, const OBJ& obj,
+                                                Loads& o)
     {
-        const int64_t vi = v0 + lane;
-        GridLoads<T> xv;
-        Pack<T> pl, pu;
+        grid_load(v, vi, nv, n, obj.cols, obj.cols % W == 0, o);
+    }
+    __device__ __forceinline__ static void axpy(const Loads& xp, const Loads& d, T step, Loads& x)
+    {
+        grid_axpy(xp, d, step, x);
+    }
+    __device__ __forceinline__ static const Pack<T>& own(const Loads& l) { return l.p[1]; }
+    template <class LD, class BODY>
+    __device__ __forceinline__ static void gather(const Loads& xv, int64_t vi, int64_t nv, int64_t n, const OBJ& obj, LD ld,
+                                                  BODY body)
+    {
         T up[W + 2], mid[W + 2], dn[W + 2];
-        grid_load(x, vi, nv, n, cols, aligned, xv);
-        if (vi < nv)
-        {
-            pl = ldv(lb, vi);
-            pu = ldv(ub, vi);
-        }
-        grid_windows(xv, vi, nv, n, cols, [&](int64_t e) { return x[e]; }, up, mid, dn);
-        if (vi < nv)
-        {
-            Pack<T> pgv;
-            grid_pack(obj, vi, pos, up, mid, dn, pgv, acc[0]);
-            stv(g, vi, pgv);
-#pragma unroll
-            for (int k = 0; k < W; k++)
-            {
-                acc[1].add_prod(xv.p[1].e[k], xv.p[1].e[k]);
-                pg = fmax(pg, double(projg_term(xv.p[1].e[k], pgv.e[k], pl.e[k], pu.e[k])));
-            }
-        }
-        grid_advance(pos, step, cols);
+        grid_windows(xv, vi, nv, n, obj.cols, ld, up, mid, dn);
+        body(up, mid, dn);
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int64_t i = nv * W; i < n; i++)
-        {
-            const T gi = grid_tail<T>(obj, i, [&](int64_t k) { return x[k]; }, acc[0]);
-            g[i] = gi;
-            acc[1].add_prod(x[i], x[i]);
-            pg = fmax(pg, double(projg_term(x[i], gi, lb[i], ub[i])));
-        }
-    ext_publish<false>(pg, ws, 4);
-    if (grid_reduce<2>(acc, ws))
+    template <class A>
+    __device__ __forceinline__ static void pack(const OBJ& obj, int64_t vi, int64_t, const Pos& pos, Pack<T>& g, A& fx,
+                                                const T (&up)[W + 2], const T (&mid)[W + 2], const T (&dn)[W + 2])
     {
-        const double pgmax = ext_collect<false>(ws, 4);
-        if (threadIdx.x == 0)
-        {
-            out[0] = T(acc[0].value());
-            out[1] = T(acc[1].value());
-            out[2] = T(pgmax);
-        }
+        grid_pack(obj, vi, pos, up, mid, dn, g, fx);
     }
-}
+    template <class LD, class A>
+    __device__ __forceinline__ static T tail(const OBJ& obj, int64_t i, int64_t, LD ld, A& fx)
+    {
+        return grid_tail<T>(obj, i, ld, fx);
+    }
+};
 
-// ---------------------------------------------------------------- k_b_dg_maxstep_trial's counterpart
-// out[0] = g0.d, out[1] = step_max, out[2] = f(x), out[3] = grad(x).d at x = xp + step*d
-template <class T, class OBJ>
-__global__ void __launch_bounds__(kBlock) k_grid_b_dg_maxstep_trial(const T* __restrict__ xp, const T* __restrict__ g0,
-                                                                    const T* __restrict__ d, const T* __restrict__ lb,
-                                                                    const T* __restrict__ ub, T step, T* __restrict__ x,
-                                                                    T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
-                                                                    T* __restrict__ out, int rev)
-{
-    typedef typename AccOf<T>::type A;
-    constexpr int W = Vec16<T>::W;
-    constexpr int U = kGridTrialU;
-    A acc[3];  // f's sum, grad(x).d, g0.d
-    double smin = __longlong_as_double(0x7FF0000000000000ll);
-    auto feas = [&](T xi, T di, T lo, T up) __attribute__((always_inline)) {
-        if (di > T(0))
-            smin = fmin(smin, double((up - xi) / di) + 0.0);
-        else if (di < T(0))
-            smin = fmin(smin, double((lo - xi) / di) + 0.0);
-    };
-    const int64_t cols = obj.cols;
-    const bool aligned = cols % W == 0;
-    const int64_t nv = n / W;
-    const int64_t tile = int64_t(kBlock) * U;
-    const int64_t top = ((nv + tile - 1) / tile - 1) * tile;
-    const GridPos ustep = grid_pos(int64_t(kBlock) * W, cols);
-    const GridPos tstep = grid_pos(int64_t(gridDim.x) * tile * W, cols);
-    const int64_t first = int64_t(blockIdx.x) * tile;
-    GridPos pos0 = {0, 0};
-    if (first < nv)
-        pos0 = grid_pos(((rev ? top - first : first) + threadIdx.x) * W, cols);
-    for (int64_t t0 = first; t0 < nv; t0 += int64_t(gridDim.x) * tile)
-    {
-        const int64_t base = (rev ? top - t0 : t0) + threadIdx.x;
-        GridLoads<T> lxp[U], ld_[U];
-        Pack<T> pg0[U], plo[U], pup[U];
-#pragma unroll
-        for (int u = 0; u < U; u++)
-        {
-            const int64_t vi = base + u * kBlock;
-            grid_load(xp, vi, nv, n, cols, aligned, lxp[u]);
-            grid_load(d, vi, nv, n, cols, aligned, ld_[u]);
-            if (vi < nv)
-            {
-                pg0[u] = ldv<T>(g0, vi);
-                plo[u] = ldv<T>(lb, vi);
-                pup[u] = ldv<T>(ub, vi);
-            }
-        }
-        GridPos pos = pos0;
-#pragma unroll
-        for (int u = 0; u < U; u++)
-        {
-            const int64_t vi = base + u * kBlock;
-            GridLoads<T> xv;
-            T up[W + 2], mid[W + 2], dn[W + 2];
-            grid_axpy(lxp[u], ld_[u], step, xv);
-            grid_windows(xv, vi, nv, n, cols, [&](int64_t e) { return xp[e] + step * d[e]; }, up, mid, dn);
-            if (vi < nv)
-            {
-                Pack<T> pg;
-#pragma unroll
-                for (int k = 0; k < W; k++)
-                {
-                    acc[2].add_prod(pg0[u].e[k], ld_[u].p[1].e[k]);
-                    feas(lxp[u].p[1].e[k], ld_[u].p[1].e[k], plo[u].e[k], pup[u].e[k]);
-                }
-                grid_pack(obj, vi, pos, up, mid, dn, pg, acc[0]);
-                stv<T>(x, vi, xv.p[1]);
-                stv<T>(g, vi, pg);
-#pragma unroll
-                for (int k = 0; k < W; k++)
-                    acc[1].add_prod(pg.e[k], ld_[u].p[1].e[k]);
-            }
-            grid_advance(pos, ustep, cols);
-        }
-        if (rev)
-            grid_retreat(pos0, tstep, cols);
-        else
-            grid_advance(pos0, tstep, cols);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int64_t i = nv * W; i < n; i++)
-        {
-            acc[2].add_prod(g0[i], d[i]);
-            feas(xp[i], d[i], lb[i], ub[i]);
-            x[i] = xp[i] + step * d[i];
-            const T gi = grid_tail<T>(obj, i, [&](int64_t k) { return xp[k] + step * d[k]; }, acc[0]);
-            g[i] = gi;
-            acc[1].add_prod(gi, d[i]);
-        }
-    ext_publish<true>(smin, ws, 6);
-    if (grid_reduce<3>(acc, ws))
-    {
-        const double smin_all = ext_collect<true>(ws, 6);
-        if (threadIdx.x == 0)
-        {
-            out[0] = T(acc[2].value());
-            out[1] = T(smin_all);
-            out[2] = T(acc[0].value());
-            out[3] = T(acc[1].value());
-            ws_signal(ws);
-        }
-    }
-}
+LBFGSX_FRAME_KERNELS(k_grid, halo_eval, halo_trial, GridFamily<T, OBJ>)
 
 }  // namespace lbfgsx

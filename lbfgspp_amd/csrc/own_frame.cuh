@@ -24,6 +24,7 @@
 #pragma once
 #include "lbfgs_kernels.cuh"
 #include "lbfgsb_kernels.cuh"
+#include "frame_kernels.cuh"
 
 namespace lbfgsx {
 
@@ -321,36 +322,7 @@ __device__ __forceinline__ void own_trial(const T* __restrict__ xp, const T* __r
 }
 
 // ---------------------------------------------------------------- the four kernels of a family
-// PREFIX_eval, PREFIX_trial, PREFIX_b_eval and PREFIX_b_dg_maxstep_trial for the family FAMILY, with the parameter lists of
-// k_eval, k_trial, k_b_eval and k_b_dg_maxstep_trial (OBJ after n): launch_args.hpp serves all the families
-#define LBFGSX_OWN_KERNELS(PREFIX, FAMILY)                                                                                     \
-    template <class T, class OBJ>                                                                                              \
-    __global__ void __launch_bounds__(kBlock)                                                                                  \
-        PREFIX##_eval(const T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj, RedWs ws, T* __restrict__ out)           \
-    {                                                                                                                          \
-        own_eval<T, FAMILY, OBJ, false>(x, g, nullptr, nullptr, n, obj, ws, out);                                              \
-    }                                                                                                                          \
-    template <class T, class OBJ>                                                                                              \
-    __global__ void __launch_bounds__(kBlock)                                                                                  \
-        PREFIX##_b_eval(const T* __restrict__ x, T* __restrict__ g, const T* __restrict__ lb, const T* __restrict__ ub,        \
-                        int64_t n, OBJ obj, RedWs ws, T* __restrict__ out)                                                     \
-    {                                                                                                                          \
-        own_eval<T, FAMILY, OBJ, true>(x, g, lb, ub, n, obj, ws, out);                                                         \
-    }                                                                                                                          \
-    template <class T, class OBJ>                                                                                              \
-    __global__ void __launch_bounds__(kBlock)                                                                                  \
-        PREFIX##_trial(const T* __restrict__ xp, const T* __restrict__ d, T step, T* __restrict__ x, T* __restrict__ g,        \
-                       int64_t n, OBJ obj, RedWs ws, T* __restrict__ out, int rev)                                             \
-    {                                                                                                                          \
-        own_trial<T, FAMILY, OBJ, false>(xp, nullptr, d, nullptr, nullptr, step, x, g, n, obj, ws, out, rev);                  \
-    }                                                                                                                          \
-    template <class T, class OBJ>                                                                                              \
-    __global__ void __launch_bounds__(kBlock)                                                                                  \
-        PREFIX##_b_dg_maxstep_trial(const T* __restrict__ xp, const T* __restrict__ g0, const T* __restrict__ d,               \
-                                    const T* __restrict__ lb, const T* __restrict__ ub, T step, T* __restrict__ x,             \
-                                    T* __restrict__ g, int64_t n, OBJ obj, RedWs ws, T* __restrict__ out, int rev)             \
-    {                                                                                                                          \
-        own_trial<T, FAMILY, OBJ, true>(xp, g0, d, lb, ub, step, x, g, n, obj, ws, out, rev);                                  \
-    }
+// PREFIX_eval, PREFIX_trial, PREFIX_b_eval and PREFIX_b_dg_maxstep_trial for the family FAMILY (frame_kernels.cuh)
+#define LBFGSX_OWN_KERNELS(PREFIX, FAMILY) LBFGSX_FRAME_KERNELS(PREFIX, own_eval, own_trial, FAMILY)
 
 }  // namespace lbfgsx

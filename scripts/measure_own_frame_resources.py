@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""Registers, scratch and occupancy of the graph, mesh and linear-model (sparse, multi-output, dense) kernels in two trees,
-side by side (profiles/own_frame_kernel_resources.tsv).  No GPU is needed: the generated sources are compiled for gfx950 here.
+"""Registers, scratch and occupancy of the kernels on the two kernel frames -- own_frame.cuh: graph, mesh and linear-model
+(sparse, multi-output, dense); halo_frame.cuh: chain and grid -- in two trees, side by side
+(profiles/own_frame_kernel_resources.tsv).  No GPU is needed: the generated sources are compiled for gfx950 here.
 
 Each tree (a built checkout: the parent commit's and this one) is asked, in a process of its own, for the generated
 translation unit -- source() -- of
+    chain    ASYM2, ASYM3, CHAINED_ROSEN, SECOND_DIFF at their K                 (tests/chain_ref.py)
+    grid     ASYM4, ALLENCAHN                                                  (tests/grid_ref.py)
     graph    ASYM_EDGE with and without NODE                                   (tests/graph_ref.py)
     mesh     every (K, D) with the bodies tests/test_mesh_objective_cpu.py compiles (tests/mesh_ref.py)
     linear   LOGISTIC with and without RIDGE                                   (tests/linear_ref.py)
@@ -38,7 +41,9 @@ def emit_sources(tree):
         sys.path.insert(0, p)
     import numpy as np
 
+    import chain_ref as CR
     import graph_ref as GR
+    import grid_ref as GD
     import linear_ref as LR
     import lbfgspp_amd as A
     import mesh_ref as MR
@@ -47,6 +52,11 @@ def emit_sources(tree):
     one_edge = (np.array([0]), np.array([1]))
     one_entry = (np.array([0, 1], np.int32), np.array([0], np.int32), np.array([1.0]))
     for dname, dtype in (("f64", np.float64), ("f32", np.float32)):
+        for name, body, K in (("asym2", CR.ASYM2, 2), ("asym3", CR.ASYM3, 3), ("chained_rosen", CR.CHAINED_ROSEN, 2),
+                              ("second_diff", CR.SECOND_DIFF, 3)):
+            out["chain/K%d/%s/%s" % (K, name, dname)] = A.ChainObjective(body, K=K).source(dtype)
+        for name, body in (("asym4", GD.ASYM4), ("allencahn", GD.ALLENCAHN)):
+            out["grid/%s/%s" % (name, dname)] = A.GridObjective(body, shape=(2, 2)).source(dtype)
         for name, node in (("asym+node", GR.NODE), ("asym", None)):
             out["graph/%s/%s" % (name, dname)] = A.GraphObjective(GR.ASYM_EDGE, edges=one_edge, node_body=node).source(dtype)
         for K in (2, 3, 4):
@@ -117,8 +127,9 @@ def main():
         res = list(ex.map(resources, jobs))
     bad = []
     with open(args.out, "w") as f:
-        f.write("# VGPRs, scratch bytes per lane and occupancy (waves per SIMD) of every graph, mesh and linear-model kernel, from the\n"
-                "# compiler's kernel-resource-usage remarks: the parent commit and the kernels on own_frame.cuh, side by side\n"
+        f.write("# VGPRs, scratch bytes per lane and occupancy (waves per SIMD) of every chain, grid, graph, mesh and linear-model\n"
+                "# kernel, from the compiler's kernel-resource-usage remarks: the parent commit and this tree's kernels on\n"
+                "# own_frame.cuh and halo_frame.cuh, side by side\n"
                 "# (scripts/measure_own_frame_resources.py; case = form/bodies/dtype)\n")
         f.write("case\tkernel\tvgpr_parent\tvgpr_head\tscratch_parent\tscratch_head\toccupancy_parent\toccupancy_head\tsame_source\n")
         for i, c in enumerate(cases):

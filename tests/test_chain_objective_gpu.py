@@ -28,6 +28,7 @@ BODY = {2: CR.ASYM2, 3: CR.ASYM3}
 TERMS = {2: CR.asym2_terms, 3: CR.asym3_terms}
 # the capped grid is 1024 blocks and a tile of the trial kernels 1024 packs: past 1024 tiles every block walks its stride twice
 WRAP_F64 = 1024 * 1024 * 2 + 2 * 1024 * 2 + 3
+WRAP_F32 = 1024 * 1024 * 4 + 2 * 1024 * 4 + 3  # the same with W = 4: two tiles past the wrap and a tail
 
 
 @pytest.fixture(scope="module")
@@ -43,8 +44,10 @@ def _shapes():
     for dtype in (O.F64, O.F32):
         for K in (2, 3):
             ns = [K, K + 1, 5, 127, 128, 129, 255, 256, 257, 511, 513, 1025, 2049, 4099, 3 * 4096 + 5]
-            if dtype == O.F64 and K == 2:
+            if dtype == O.F64:
                 ns.append(WRAP_F64)
+            elif K == 2:
+                ns.append(WRAP_F32)
             for n in ns:
                 ps.append(pytest.param(dtype, K, n, id="%s-K%d-%d" % ("f64" if dtype == O.F64 else "f32", K, n)))
     return ps

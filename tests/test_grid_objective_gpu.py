@@ -29,6 +29,9 @@ TRIAL_U = 2                  # grid_kernels.cuh: kGridTrialU, the tile depth of 
 # the capped grid is 1024 blocks and a tile of the trial kernels 512 packs: from 2 * 1024 tiles on every block walks its stride
 # twice (the evaluation kernels, whose step is a block's 256 packs, four times); cols even: the aligned path
 WRAP_F64 = (1025, 2052)
+# f32: a tile of the trial kernels is 2048 coordinates, so 2052 tiles again; and one column more: the unaligned path, where the
+# position carried from tile to tile is advanced and retreated by a step with a column part
+WRAP_F32 = ((1025, 4100), (1025, 4101))
 
 
 def _shape_list(dtype):
@@ -40,8 +43,7 @@ def _shape_list(dtype):
     shapes += [(3, cols) for cols in (256 * W - W, 256 * W + W, 256 * W + 1)]             # a block's span
     shapes += [(3, cols) for cols in (TRIAL_U * 256 * W - W, TRIAL_U * 256 * W + W)]      # a trial tile's span
     shapes += [(4099, 2), (4099, 3), (3, 43)]                                              # tall and thin; a flat tail
-    if dtype == O.F64:
-        shapes.append(WRAP_F64)
+    shapes += [WRAP_F64] if dtype == O.F64 else list(WRAP_F32)
     return shapes
 
 
