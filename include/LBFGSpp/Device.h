@@ -104,6 +104,8 @@ class TermObjective
     const Scalar* m_host[4] = {nullptr, nullptr, nullptr, nullptr};
     double m_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::int64_t m_rows = 0, m_cols = 0;  // a GridObjective's shape; 0: the handle is bound without one
+    std::int64_t m_slabs = 0;             // a VolumeObjective's slabs, with the two above
+    bool m_volume = false;
     std::int64_t m_E = 0;                 // a GraphObjective's edges; 0: the handle is bound without any
     const std::int32_t *m_ei = nullptr, *m_ej = nullptr;
     bool m_edges_dev = false;
@@ -144,6 +146,7 @@ protected:
                        : (form == LBFGSX_FORM_LINEAR)  ? lbfgsx_objective_compile_linear(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_MESH)  ? lbfgsx_objective_compile_mesh(&m_h, dt, K, D, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRAPH) ? lbfgsx_objective_compile_graph(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
+                       : (form == LBFGSX_FORM_VOLUME) ? lbfgsx_objective_compile_volume(&m_h, dt, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRID)  ? lbfgsx_objective_compile_grid(&m_h, dt, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_CHAIN) ? lbfgsx_objective_compile_chain(&m_h, dt, K, body.c_str(), log.data(), log.size())
                                                      : lbfgsx_objective_compile(&m_h, dt, K, body.c_str(), log.data(), log.size());
@@ -155,6 +158,13 @@ protected:
     }
     void set_shape(std::int64_t rows, std::int64_t cols)
     {
+        m_rows = rows;
+        m_cols = cols;
+    }
+    void set_shape3(std::int64_t slabs, std::int64_t rows, std::int64_t cols)
+    {
+        m_volume = true;
+        m_slabs = slabs;
         m_rows = rows;
         m_cols = cols;
     }
@@ -260,6 +270,8 @@ public:
             detail::check(lbfgsx_objective_bind_mesh(c, m_h, m_E, m_elems, m_edges_dev ? 1 : 0, p, m_c, &id));
         else if (m_E || m_ei || m_ej)
             detail::check(lbfgsx_objective_bind_graph(c, m_h, m_E, m_ei, m_ej, m_edges_dev ? 1 : 0, p, m_c, &id));
+        else if (m_volume)
+            detail::check(lbfgsx_objective_bind_volume(c, m_h, m_slabs, m_rows, m_cols, p, m_c, &id));
         else if (m_rows || m_cols)
             detail::check(lbfgsx_objective_bind_grid(c, m_h, m_rows, m_cols, p, m_c, &id));
         else
@@ -301,6 +313,32 @@ public:
     GridObjective(const lbfgsx_objective* compiled, std::int64_t rows, std::int64_t cols) : TermObjective<Scalar>(compiled)
     {
         this->set_shape(rows, cols);
+    }
+};
+
+// An objective on a slab-major slabs x rows x cols array, x of slabs*rows*cols elements: f(x) = the sum over the
+// (slabs-1)(rows-1)(cols-1) cells of phi(x[8]; s, r, c), x[4*ds + 2*dr + dc] = x[s+ds, r+dr, c+dc] (include/lbfgsx.h, "volume
+// objectives").  The body is the text of one cell: it sees T, const T x[8], T g[8], int64_t i (= (slab*rows + row)*cols + col),
+// slab, row, col, slabs, rows, cols, p0..p3 and c[8].
+//     VolumeObjective<double> f(slabs, rows, cols, "const T a = x[1] - x[0]; const T b = x[2] - x[0]; const T e = x[4] - x[0];"
+//         "for (int k = 0; k < 8; k++) g[k] = T(0); g[1] = a; g[2] = b; g[4] = e; g[0] = (-a - b) - e;"
+//         "return T(0.5) * ((a * a + b * b) + e * e);");
+// data, scalars and binding are a TermObjective's.  Accepted by LBFGSSolver::minimize and LBFGSBSolver::minimize wherever a
+// GridObjective is, refused where it is; an extent < 2 or x.size() != slabs*rows*cols throws std::invalid_argument.
+template <typename Scalar>
+class VolumeObjective : public TermObjective<Scalar>
+{
+public:
+    VolumeObjective(std::int64_t slabs, std::int64_t rows, std::int64_t cols, const std::string& body)
+        : TermObjective<Scalar>(LBFGSX_FORM_VOLUME, 8, body, "VolumeObjective: ")
+    {
+        this->set_shape3(slabs, rows, cols);
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile_volume); it stays the caller's
+    VolumeObjective(const lbfgsx_objective* compiled, std::int64_t slabs, std::int64_t rows, std::int64_t cols)
+        : TermObjective<Scalar>(compiled)
+    {
+        this->set_shape3(slabs, rows, cols);
     }
 };
 
@@ -475,13 +513,14 @@ public:
 
 namespace detail {
 // the objectives compiled at run time into the fused kernels: a TermObjective, a ChainObjective, a GridObjective, a
-// GraphObjective, a MeshObjective, a LinearObjective, a GraphLinearObjective, a MultiLinearObjective or a DenseLinearObjective
+// VolumeObjective, a GraphObjective, a MeshObjective, a LinearObjective, a GraphLinearObjective, a MultiLinearObjective or a DenseLinearObjective
 template <typename Scalar, typename Foo>
 struct is_compiled_objective
 {
     typedef typename std::decay<Foo>::type F;
     static constexpr bool value = std::is_same<F, TermObjective<Scalar> >::value || std::is_same<F, ChainObjective<Scalar> >::value ||
                                   std::is_same<F, GridObjective<Scalar> >::value || std::is_same<F, GraphObjective<Scalar> >::value ||
+                                  std::is_same<F, VolumeObjective<Scalar> >::value ||
                                   std::is_same<F, MeshObjective<Scalar> >::value || std::is_same<F, LinearObjective<Scalar> >::value ||
                                   std::is_same<F, MultiLinearObjective<Scalar> >::value ||
                                   std::is_same<F, GraphLinearObjective<Scalar> >::value ||
@@ -536,7 +575,8 @@ namespace detail {
 
 // Uniform view of the four kinds of objective `Foo` the solvers accept:
 //   BuiltinObjective<Scalar>                              -> fused device kernels
-//   TermObjective<Scalar>, ChainObjective<Scalar>, GridObjective<Scalar>, GraphObjective<Scalar>, MeshObjective<Scalar>
+//   TermObjective<Scalar>, ChainObjective<Scalar>, GridObjective<Scalar>, VolumeObjective<Scalar>, GraphObjective<Scalar>,
+//   MeshObjective<Scalar>
 //                                                         -> the same kernels, compiled at run time
 //   Scalar f(const DeviceVector<Scalar>& x, DeviceVector<Scalar>& grad)   -> user device functor
 //   Scalar f(const Vec& x, Vec& grad) with host vectors   -> staged through host memory (compatibility)

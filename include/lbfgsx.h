@@ -216,7 +216,7 @@ int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4]);
  * with n < K is refused (any n >= K is accepted: n need not be a multiple of anything).  The compile log, the refusal of
  * asm and the line numbers are those of lbfgsx_objective_compile. */
 enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2, LBFGSX_FORM_GRAPH = 3, LBFGSX_FORM_MESH = 4, LBFGSX_FORM_LINEAR = 5,
-       LBFGSX_FORM_LINEAR_MULTI = 6, LBFGSX_FORM_DENSE = 7, LBFGSX_FORM_LINEAR_GRAPH = 8 };
+       LBFGSX_FORM_LINEAR_MULTI = 6, LBFGSX_FORM_DENSE = 7, LBFGSX_FORM_LINEAR_GRAPH = 8, LBFGSX_FORM_VOLUME = 9 };
 int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len);
 long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char* out, size_t len);
 int lbfgsx_objective_form(const lbfgsx_objective* obj);
@@ -251,6 +251,44 @@ long long lbfgsx_objective_source_grid(int dtype, const char* body, char* out, s
 int lbfgsx_objective_bind_grid(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
                                const double cs[8], int* id);
 int lbfgsx_objective_shape(const lbfgsx_ctx* c, int64_t* rows, int64_t* cols);
+/* ---- volume objectives: 2x2x2-cell terms on a slab-major 3-D array --------------------------------------------------------
+ * x is a slab-major slabs x rows x cols array, n = slabs*rows*cols, all three extents >= 2; node (s, r, c) has flat index
+ * (s*rows + r)*cols + c, and
+ *     f(x) = sum over cells (s, r, c), 0 <= s < slabs-1, 0 <= r < rows-1, 0 <= c < cols-1, of phi(x[8]; s, r, c),
+ *     x[4*ds + 2*dr + dc] = x[s+ds, r+dr, c+dc]              (slots 0..3 are the grid form's, on slab s)
+ * -- volumetric denoising and deblurring, 3-D phase-field and Allen-Cahn energies, tomographic volumes, minimal-surface and
+ * obstacle problems in 3-D.  `body` is the text of ONE CELL: it sees T, const T x[8] in the order above, T g[8] (the cell's
+ * eight partial derivatives, to fill), int64_t i (the flat index of x[0]), int64_t slab, row, col, slabs, rows, cols, p0..p3
+ * and c[8], and returns the cell's value.  It may read p0 at the eight corners, p0[i + dc + dr*cols + ds*rows*cols]: a cell
+ * that does not exist is never evaluated, and no index outside [0, n) is loaded.  A per-node term is written inside the
+ * body as for a grid: node (slab, row, col) goes to the cell that starts there, and the last layer of cells in each direction
+ * picks up the nodes no cell starts at -- corner (ds, dr, dc) of a cell is added by it iff
+ *     (ds == 0 || slab + 2 == slabs) && (dr == 0 || row + 2 == rows) && (dc == 0 || col + 2 == cols),
+ *     e.g.  v += node(x[0], i);   if (col + 2 == cols) v += node(x[1], i + 1);
+ *           if (slab + 2 == slabs && row + 2 == rows) v += node(x[6], i + (rows + 1)*cols);   ...
+ * with the matching additions to g[0..7]: every node is then counted exactly once.
+ * Semantics (a numpy restatement with one operation per source operation is bit-exact):
+ *   grad[s,r,c] = g[7] of cell (s-1, r-1, c-1) + g[6] of (s-1, r-1, c) + g[5] of (s-1, r, c-1) + g[4] of (s-1, r, c) +
+ *                 g[3] of (s, r-1, c-1) + g[2] of (s, r-1, c) + g[1] of (s, r, c-1) + g[0] of (s, r, c): the cells that exist,
+ *                 in this order (ascending flat index of the cell's origin), started from the first (no leading 0 +);
+ *   f           = the order-independent (compensated) sum of the cells' values, each added once, by the thread that owns the
+ *                 cell's origin;
+ *   one rounding per source operation, no contraction, no floating-point atomic.
+ * lbfgsx_objective_compile_volume wraps the body for the four kernels of csrc/volume_kernels.cuh -- the counterparts of
+ * k_eval, k_trial, k_b_eval and k_b_dg_maxstep_trial with the same arguments, grids and reductions; the eight packs a row
+ * or a slab away from a thread's pack are re-read through the caches, and the form adds nothing to the byte model -- and
+ * caches by (form, body, K, dtype) with K = 8: the same text as a grid and as a volume objective are two entries, and the
+ * shape is not part of the key.  The handle's form is LBFGSX_FORM_VOLUME.  lbfgsx_objective_bind_volume binds it with the
+ * shape; it refuses (LBFGSX_E_INVALID, the values named) a handle of another form, an extent < 2, and a product that is not
+ * n or overflows.  lbfgsx_objective_bind and lbfgsx_objective_bind_grid refuse a volume handle.  lbfgsx_objective_shape3
+ * reads the bound shape back (lbfgsx_objective_shape speaks of grid objectives only).  lbfgsx_objective_info,
+ * lbfgsx_objective_upload and the four evaluation entry points take it like a term objective's; the compile log, the refusal
+ * of asm and the line numbers are those of lbfgsx_objective_compile. */
+int lbfgsx_objective_compile_volume(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len);
+long long lbfgsx_objective_source_volume(int dtype, const char* body, char* out, size_t len);
+int lbfgsx_objective_bind_volume(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
+                                 const void* const p[4], const double cs[8], int* id);
+int lbfgsx_objective_shape3(const lbfgsx_ctx* c, int64_t* slabs, int64_t* rows, int64_t* cols);
 /* ---- graph objectives: edge terms over an index list ---------------------------------------------------------------------
  * x has n coordinates, the NODES; the caller gives E edges as two int32 arrays ei[E], ej[E], and
  *     f(x) = sum over nodes v of psi(x[v]; v)  +  sum over edges e of phi(x[ei[e]], x[ej[e]]; e)

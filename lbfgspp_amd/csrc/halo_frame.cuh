@@ -1,6 +1,6 @@
-// lbfgspp_amd/csrc/halo_frame.cuh -- the frame of the halo kernels: the four evaluation kernels of a CHAIN and of a GRID
-// objective (chain_kernels.cuh, grid_kernels.cuh) are halo_eval and halo_trial, bounded or not, around the family's loads,
-// windows and terms.  Their parameter lists, BOUNDED conventions, outputs, tile order, reductions and completion signal are
+// lbfgspp_amd/csrc/halo_frame.cuh -- the frame of the halo kernels: the four evaluation kernels of a CHAIN, of a GRID and of
+// a VOLUME objective (chain_kernels.cuh, grid_kernels.cuh, volume_kernels.cuh) are halo_eval and halo_trial, bounded or not,
+// around the family's loads, windows and terms.  Their parameter lists, BOUNDED conventions, outputs, tile order, reductions and completion signal are
 // those of own_eval / own_trial (own_frame.cuh), that is of k_eval, k_trial, k_b_eval and k_b_dg_maxstep_trial.
 //
 // Ownership.  A thread owns the W = 16 / sizeof(T) coordinates of a 16-byte pack: it writes their grad (and x in the trial
@@ -24,7 +24,8 @@
 //                                                          never a read of the x the launch writes), for 0 <= i < n only
 //     struct Pos;  Pos pos(obj, flat);  void advance(obj, Pos&, step);  void retreat(obj, Pos&, step)
 //                                                          what a family carries along the loop about a pack's position
-//                                                          (the grid's row and column; nothing for a chain)
+//                                                          (the grid's row and column, the volume's slab too; nothing for a
+//                                                          chain)
 //     void pack(obj, vi, n, pos, Pack<T>& g, A& fx, windows...)   pack vi: its W partial derivatives, the terms it owns to fx
 //     T tail(obj, i, n, ld, fx)                            coordinate i past the last whole pack: the same
 // The windows are the family's own arrays and reach pack through the frame's body, not as one object the frame holds: as one
@@ -178,8 +179,20 @@ __device__ __forceinline__ void halo_trial(const T* __restrict__ xp, const T* __
 #pragma unroll
                     for (int k = 0; k < W; k++)
                     {
-                        acc[NA - 1].add_prod(pg0[u].e[k], pd.e[k]);
-                        feas(pxp.e[k], pd.e[k], plo[u].e[k], pup[u].e[k]);
+                        if constexpr (U == 1)
+                        {
+                            // the bounds by value, read first: as operands of feas the two reads are sunk into the branches on
+                            // d's sign and, at this depth (k_volume_b_dg_maxstep_trial), lb's and ub's packs then live in 48
+                            // bytes of scratch.  The deeper tiles keep the statements they were measured with
+                            const T lo = plo[u].e[k], up = pup[u].e[k];
+                            acc[NA - 1].add_prod(pg0[u].e[k], pd.e[k]);
+                            feas(pxp.e[k], pd.e[k], lo, up);
+                        }
+                        else
+                        {
+                            acc[NA - 1].add_prod(pg0[u].e[k], pd.e[k]);
+                            feas(pxp.e[k], pd.e[k], plo[u].e[k], pup[u].e[k]);
+                        }
                     }
                 }
                 F::pack(obj, vi, n, pos, pg, acc[0], win...);

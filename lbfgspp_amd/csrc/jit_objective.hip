@@ -8,7 +8,7 @@
 // same kernel text, the same flags, the same sums.  The code object is loaded per device with hipModuleLoadData and the
 // kernels are launched with hipModuleLaunchKernel from the arguments launch_args.hpp works out for both forms.
 //
-// Four forms of objective share all of this (include/lbfgsx.h): a TERM objective (terms that do not overlap: the struct with
+// Ten forms of objective share all of this (include/lbfgsx.h): a TERM objective (terms that do not overlap: the struct with
 // pack / tail / finish above), a CHAIN objective (one term starting at every coordinate: a second generated wrapper that
 // includes chain_kernels.cuh and instantiates its four kernels, which take the arguments of the four above) and a GRID
 // objective (one term per 2x2 cell of a row-major grid: a third wrapper around grid_kernels.cuh, whose struct also carries
@@ -23,7 +23,9 @@
 // row-major matrix), is a wrapper around linear_dense_kernels.cuh with the matrix of dense_topology.hip; besides the row
 // passes it has the partial pass in slot 7.  A ninth, a GRAPH-REGULARISED LINEAR-MODEL objective (the sixth form with an edge term
 // over an index list on its coordinates: three bodies), is a wrapper around linear_graph_kernels.cuh with both the matrix and
-// the incidence list; its row passes are the sixth form's.  A handle carries its form; the four slots of the
+// the incidence list; its row passes are the sixth form's.  A tenth, a VOLUME objective (one term per 2x2x2 cell of a
+// slab-major 3-D array), is the grid form with one more extent: a wrapper around volume_kernels.cuh whose struct carries the
+// three extents.  A handle carries its form; the four slots of the
 // loaded-kernel table and everything that launches them are the same.  What the forms differ in -- names, kernel names, struct
 // members, the bodies' signatures, the K and D accepted, the cache key -- is one row each of kForms below; the generator, the
 // validation and the refusals are written once and read it.
@@ -83,7 +85,7 @@ struct FormDesc
     "    const T* part;\n    const int32_t* long_col;\n    const uint32_t* long_chunk;\n"           \
     "    int64_t R, nnz;\n    int32_t L, C, nlong, pad_;\n"
 const BodyDesc kNoBody = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-const FormDesc kForms[9] = {
+const FormDesc kForms[10] = {
     {"term objective", "", "ObjTerm", "#include \"lbfgs_kernels.cuh\"\n#include \"lbfgsb_kernels.cuh\"\n",
      {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial", nullptr, nullptr, "k_trial_post"}, "", kNoBody,
      {"    // one term: x[0..K) in, g[0..K) out, the term's value returned\n", TERM_SIGNATURE, "objective_body", "body", nullptr,
@@ -190,7 +192,14 @@ const FormDesc kForms[9] = {
       "T row(const T z, T& dz, int64_t r) const", "row_body", "row body", nullptr, nullptr},
      "", 1, 1, 1, 1, nullptr, nullptr, true, false, "matrix and edges", nullptr,
      {"    // the term of edge e = (i, j): x = {x[i], x[j]} in, its two partial derivatives g out, its value returned\n",
-      "T edge(const T (&x)[2], T (&g)[2], int64_t e, int64_t i, int64_t j) const", "edge_body", "edge body", nullptr, nullptr}}};
+      "T edge(const T (&x)[2], T (&g)[2], int64_t e, int64_t i, int64_t j) const", "edge_body", "edge body", nullptr, nullptr}},
+    {"volume objective", "_volume", "ObjVolume", "#include \"volume_kernels.cuh\"\n",
+     {"k_volume_eval", "k_volume_trial", "k_volume_b_eval", "k_volume_b_dg_maxstep_trial"}, "    int64_t slabs, rows, cols;\n", kNoBody,
+     {"    // the cell whose origin is node (slab, row, col), flat index i = (slab*rows + row)*cols + col:\n"
+      "    // x[4*ds + 2*dr + dc] = x[slab+ds, row+dr, col+dc] in, its eight partial derivatives g out, its value returned\n",
+      "T term(const T (&x)[8], T (&g)[8], int64_t i, int64_t slab, int64_t row, int64_t col) const", "objective_body", "body",
+      nullptr, nullptr},
+     "", 8, 8, 1, 1, "a cell reads K = 8 coordinates", nullptr, false, false, "shape"}};
 #undef LINEAR_MEMBERS
 #undef TERM_SIGNATURE
 #undef POINT_SIGNATURE
@@ -688,6 +697,10 @@ long long lbfgsx_objective_source_grid(int dtype, const char* body, char* out, s
 {
     return objective_source(LBFGSX_FORM_GRID, dtype, 4, body, out, len);
 }
+long long lbfgsx_objective_source_volume(int dtype, const char* body, char* out, size_t len)
+{
+    return objective_source(LBFGSX_FORM_VOLUME, dtype, 8, body, out, len);
+}
 long long lbfgsx_objective_source_graph(int dtype, const char* node_body, const char* edge_body, char* out, size_t len)
 {
     return objective_source(LBFGSX_FORM_GRAPH, dtype, 2, edge_body, out, len, node_body);
@@ -726,6 +739,10 @@ int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, con
 int lbfgsx_objective_compile_grid(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len)
 {
     return objective_compile(LBFGSX_FORM_GRID, out, dtype, 4, body, log, log_len);
+}
+int lbfgsx_objective_compile_volume(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_VOLUME, out, dtype, 8, body, log, log_len);
 }
 int lbfgsx_objective_compile_graph(lbfgsx_objective** out, int dtype, const char* node_body, const char* edge_body, char* log,
                                    size_t log_len)
@@ -825,9 +842,10 @@ int lbfgsx_objective_upload(lbfgsx_ctx* c, int slot, const void* host, void** de
 
 namespace {
 
-// lbfgsx_objective_bind and lbfgsx_objective_bind_grid: rows = cols = 0 for a handle without a shape
+// lbfgsx_objective_bind, lbfgsx_objective_bind_grid and lbfgsx_objective_bind_volume: rows = cols = 0 for a handle without a
+// shape, slabs = 0 for every form but a volume objective
 int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
-                   const double cs[8], int* id)
+                   const double cs[8], int* id, int64_t slabs = 0)
 {
     c->st_valid = false;
     c->spec_valid = false;
@@ -836,7 +854,7 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
         c->term = nullptr;
         c->term_np = 0;
         c->term_form = LBFGSX_FORM_TERM;
-        c->term_rows = c->term_cols = 0;
+        c->term_slabs = c->term_rows = c->term_cols = 0;
         if (c->graph_inc || c->lin.colptr || c->dense.w)
         {
             lbfgsx::DeviceGuard dev_guard_(c->device);
@@ -898,6 +916,7 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
     }
     c->term = &code->self;
     c->term_form = code->form;
+    c->term_slabs = slabs;
     c->term_rows = rows;
     c->term_cols = cols;
     c->term_np = 0;
@@ -1002,6 +1021,46 @@ int lbfgsx_objective_shape(const lbfgsx_ctx* c, int64_t* rows, int64_t* cols)
         lbfgsx::set_error("lbfgsx_objective_shape: no grid objective is bound to this context");
         return LBFGSX_E_INVALID;
     }
+    if (rows)
+        *rows = c->term_rows;
+    if (cols)
+        *cols = c->term_cols;
+    return LBFGSX_OK;
+}
+
+int lbfgsx_objective_bind_volume(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
+                                 const void* const p[4], const double cs[8], int* id)
+{
+    if (!c || !obj)
+        return LBFGSX_E_INVALID;
+    if (!handle_is(obj, LBFGSX_FORM_VOLUME))
+        return LBFGSX_E_INVALID;
+    const std::string shape = "slabs = " + std::to_string(slabs) + ", rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
+    long long prod = 0;
+    if (slabs < 2 || rows < 2 || cols < 2)
+    {
+        lbfgsx::set_error("volume objective: " + shape +
+                          ": a volume has at least 2 slabs, 2 rows and 2 columns (slabs >= 2, rows >= 2, cols >= 2)");
+        return LBFGSX_E_INVALID;
+    }
+    if (__builtin_mul_overflow((long long) rows, (long long) cols, &prod) || __builtin_mul_overflow(prod, (long long) slabs, &prod) ||
+        prod != (long long) c->n)
+    {
+        lbfgsx::set_error("volume objective: " + shape + " does not multiply to n = " + std::to_string(c->n));
+        return LBFGSX_E_INVALID;
+    }
+    return objective_bind(c, obj, rows, cols, p, cs, id, slabs);
+}
+
+int lbfgsx_objective_shape3(const lbfgsx_ctx* c, int64_t* slabs, int64_t* rows, int64_t* cols)
+{
+    if (!c || !c->term || c->term_form != LBFGSX_FORM_VOLUME)
+    {
+        lbfgsx::set_error("lbfgsx_objective_shape3: no volume objective is bound to this context");
+        return LBFGSX_E_INVALID;
+    }
+    if (slabs)
+        *slabs = c->term_slabs;
     if (rows)
         *rows = c->term_rows;
     if (cols)

@@ -124,6 +124,13 @@ struct GridArgs
     TermArgs<T> t;
     int64_t rows, cols;
 };
+// the by-value argument of a volume objective's kernels: layout of the generated struct ObjVolume (TermArgs, then the shape)
+template <class T>
+struct VolumeArgs
+{
+    TermArgs<T> t;
+    int64_t slabs, rows, cols;
+};
 // the by-value argument of a graph objective's kernels: layout of the generated struct ObjGraph (TermArgs, then the
 // context's incidence list: uint32 off[n+1], 8-byte entries inc[2E] (graph_entry.hpp), and E)
 struct GraphEntry;
@@ -225,13 +232,14 @@ inline bool form_is_linear(int form) { return form == LBFGSX_FORM_LINEAR || form
 // the forms whose evaluation is a row pass over a CSR matrix and a column walk: those two and the graph-regularised one
 inline bool form_has_csr(int form) { return form_is_linear(form) || form == LBFGSX_FORM_LINEAR_GRAPH; }
 // the objective argument of the bound handle's kernels, by its form: &term for a term or chain objective, &grid for a grid
-// one, &graph for a graph one, &mesh for a mesh one, &linear for a linear-model one of either form, &dense for a dense one,
+// one, &volume for a volume one, &graph for a graph one, &mesh for a mesh one, &linear for a linear-model one of either form, &dense for a dense one,
 // &linear_graph for a graph-regularised linear-model one
 template <class T>
 struct BoundArgs
 {
     TermArgs<T> term;
     GridArgs<T> grid;
+    VolumeArgs<T> volume;
     GraphArgs<T> graph;
     MeshArgs<T> mesh;
     LinearArgs<T> linear;
@@ -241,6 +249,7 @@ struct BoundArgs
     explicit BoundArgs(const lbfgsx_ctx* c)
         : term(term_args<T>(c)),
           grid{term, c->term_rows, c->term_cols},
+          volume{term, c->term_slabs, c->term_rows, c->term_cols},
           graph{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const GraphEntry*>(c->graph_inc), c->graph_E},
           mesh{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const uint32_t*>(c->graph_inc), c->graph_E,
                c->mesh_D ? c->n / c->mesh_D : 0},
@@ -249,6 +258,7 @@ struct BoundArgs
           linear_graph{linear, static_cast<const uint32_t*>(c->graph_off), static_cast<const GraphEntry*>(c->graph_inc), c->graph_E}
     {
         ptr = (c->term_form == LBFGSX_FORM_GRID)    ? static_cast<void*>(&grid)
+              : (c->term_form == LBFGSX_FORM_VOLUME) ? static_cast<void*>(&volume)
               : (c->term_form == LBFGSX_FORM_GRAPH) ? static_cast<void*>(&graph)
               : (c->term_form == LBFGSX_FORM_MESH)  ? static_cast<void*>(&mesh)
               : form_is_linear(c->term_form)        ? static_cast<void*>(&linear)
@@ -258,7 +268,7 @@ struct BoundArgs
     }
     BoundArgs(const BoundArgs&) = delete;
 };
-// what the bound objective's lists add to the byte model, by its form; nothing for a term, chain or grid objective.
+// what the bound objective's lists add to the byte model, by its form; nothing for a term, chain, grid or volume objective.
 // vectors_gathered: 1 in an evaluation, 2 in a trial, which gathers xp and d -- the values, not the sectors fetched for them.
 //   graph   one launch: the offsets, the 2E entries of 8 bytes, and every gathered value once
 //   mesh    one launch: (N+1)*4 bytes of offsets, K*E entries of 4K bytes, and (K-1)*D gathered values per entry

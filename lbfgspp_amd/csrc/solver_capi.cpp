@@ -55,8 +55,8 @@ struct lbfgsx_solver
         const void* A = nullptr;
         int64_t lda = 0;
     };
-    // rows, cols: the shape of a grid objective, 0 for the other forms; gr: null for every form but a graph objective
-    virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const GraphSpec* gr,
+    // rows, cols: the shape of a grid objective, with slabs of a volume objective, 0 for the other forms; gr: null for every form but a graph objective
+    virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t slabs, int64_t rows, int64_t cols, const GraphSpec* gr,
                               const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
                               lbfgsx_trace* tr, lbfgsx_result* out) = 0;
 };
@@ -227,11 +227,12 @@ struct LbfgsImpl : lbfgsx_solver
             throw;
         }
     }
-    void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const GraphSpec* gr,
+    void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t slabs, int64_t rows, int64_t cols, const GraphSpec* gr,
                       const void* const p[4], int host_mask, const double c[8], void* x, const void*, const void*,
                       lbfgsx_trace* tr, lbfgsx_result* out) override
     {
         GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
+        VolumeObjective<Scalar> spaced(obj, slabs, rows, cols);  // binds with three extents when there are three
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
         LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
@@ -254,6 +255,7 @@ struct LbfgsImpl : lbfgsx_solver
                                    : (gr && gr->rowptr) ? static_cast<TermObjective<Scalar>&>(lined)
                                    : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
                                    : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
+                                   : slabs             ? static_cast<TermObjective<Scalar>&>(spaced)
                                                        : shaped;
         fill_term<Scalar>(f, p, host_mask, c, gr ? gr->counts : nullptr);
         run(f, n, x, tr, out);
@@ -358,11 +360,12 @@ struct LbfgsbImpl : lbfgsx_solver
             throw;
         }
     }
-    void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t rows, int64_t cols, const GraphSpec* gr,
+    void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t slabs, int64_t rows, int64_t cols, const GraphSpec* gr,
                       const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
                       lbfgsx_trace* tr, lbfgsx_result* out) override
     {
         GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
+        VolumeObjective<Scalar> spaced(obj, slabs, rows, cols);  // binds with three extents when there are three
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
         LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
@@ -385,6 +388,7 @@ struct LbfgsbImpl : lbfgsx_solver
                                    : (gr && gr->rowptr) ? static_cast<TermObjective<Scalar>&>(lined)
                                    : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
                                    : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
+                                   : slabs             ? static_cast<TermObjective<Scalar>&>(spaced)
                                                        : shaped;
         fill_term<Scalar>(f, p, host_mask, c, gr ? gr->counts : nullptr);
         run(f, n, x, lb, ub, tr, out);
@@ -966,6 +970,8 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
         const int K = lbfgsx_objective_K(obj);
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID)
             throw std::invalid_argument("a grid objective is minimised with its shape: lbfgsx_solver_minimize_grid");
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_VOLUME)
+            throw std::invalid_argument("a volume objective is minimised with its shape: lbfgsx_solver_minimize_volume");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRAPH)
             throw std::invalid_argument("a graph objective is minimised with its edges: lbfgsx_solver_minimize_graph");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_MESH)
@@ -997,7 +1003,7 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
         std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_obj: no HIP device available (this library has no CPU fallback)");
         return out->status;
     }
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, nullptr, p, host_mask, c, x, lb, ub, trace, out); });
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, 0, nullptr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 
 int lbfgsx_solver_minimize_grid(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
@@ -1027,7 +1033,39 @@ int lbfgsx_solver_minimize_grid(lbfgsx_solver* s, const lbfgsx_objective* obj, i
         std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_grid: no HIP device available (this library has no CPU fallback)");
         return out->status;
     }
-    return guarded(out, [&]() { s->minimize_obj(obj, int64_t(n), rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out); });
+    return guarded(out, [&]() { s->minimize_obj(obj, int64_t(n), 0, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out); });
+}
+
+int lbfgsx_solver_minimize_volume(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
+                                  const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
+                                  lbfgsx_trace* trace, lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    long long n = 0;
+    const int bad = guarded(out, [&]() {
+        if (!s || !obj)
+            throw std::invalid_argument("lbfgsx_solver_minimize_volume: invalid argument");
+        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_VOLUME)
+            throw std::invalid_argument("lbfgsx_solver_minimize_volume: the handle is not a volume objective (lbfgsx_objective_compile_volume)");
+        if (lbfgsx_objective_dtype(obj) != s->dtype)
+            throw std::invalid_argument("lbfgsx_solver_minimize_volume: the objective was compiled for the other dtype");
+        const std::string shape =
+            "slabs = " + std::to_string(slabs) + ", rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
+        if (slabs < 2 || rows < 2 || cols < 2)
+            throw std::invalid_argument("volume objective: " + shape +
+                                        ": a volume has at least 2 slabs, 2 rows and 2 columns (slabs >= 2, rows >= 2, cols >= 2)");
+        if (__builtin_mul_overflow((long long) rows, (long long) cols, &n) || __builtin_mul_overflow(n, (long long) slabs, &n))
+            throw std::invalid_argument("volume objective: " + shape + ": slabs*rows*cols overflows");
+    });
+    if (bad)
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_volume: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    return guarded(out, [&]() { s->minimize_obj(obj, int64_t(n), slabs, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 
 int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t E, const int32_t* ei,
@@ -1060,7 +1098,7 @@ int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, 
     }
     lbfgsx_solver::GraphSpec gr;
     gr.E = E, gr.ei = ei, gr.ej = ej, gr.on_device = edges_on_device, gr.counts = counts, gr.elems = nullptr;
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 
 int lbfgsx_solver_minimize_mesh(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t E, const int32_t* elems,
@@ -1094,7 +1132,7 @@ int lbfgsx_solver_minimize_mesh(lbfgsx_solver* s, const lbfgsx_objective* obj, i
     }
     lbfgsx_solver::GraphSpec gr;
     gr.E = E, gr.ei = gr.ej = nullptr, gr.on_device = elems_on_device, gr.counts = counts, gr.elems = elems;
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 
 int lbfgsx_solver_minimize_linear(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, int64_t nnz,
@@ -1132,7 +1170,7 @@ int lbfgsx_solver_minimize_linear(lbfgsx_solver* s, const lbfgsx_objective* obj,
     lbfgsx_solver::GraphSpec gr;
     gr.E = 0, gr.ei = gr.ej = nullptr, gr.on_device = matrix_on_device, gr.counts = counts, gr.elems = nullptr;
     gr.R = R, gr.nnz = nnz, gr.rowptr = rowptr, gr.col = col, gr.val = val, gr.lanes = lanes;
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 
 int lbfgsx_solver_minimize_linear_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, int64_t nnz,
@@ -1170,7 +1208,7 @@ int lbfgsx_solver_minimize_linear_graph(lbfgsx_solver* s, const lbfgsx_objective
     lbfgsx_solver::GraphSpec gr;
     gr.E = E, gr.ei = ei, gr.ej = ej, gr.on_device = matrix_on_device, gr.counts = counts, gr.elems = nullptr;
     gr.R = R, gr.nnz = nnz, gr.rowptr = rowptr, gr.col = col, gr.val = val, gr.lanes = lanes, gr.edges_dev = edges_on_device;
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 
 int lbfgsx_solver_minimize_dense(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, const void* A, int64_t lda,
@@ -1212,6 +1250,6 @@ int lbfgsx_solver_minimize_dense(lbfgsx_solver* s, const lbfgsx_objective* obj, 
     lbfgsx_solver::GraphSpec gr;
     gr.E = 0, gr.ei = gr.ej = nullptr, gr.on_device = a_on_device, gr.counts = counts, gr.elems = nullptr;
     gr.R = R, gr.A = A, gr.lda = lda, gr.lanes = lanes;
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
 }
 }

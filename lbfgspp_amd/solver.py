@@ -7,7 +7,7 @@ Names, argument meaning and error behaviour follow yixuan/LBFGSpp:
 Exceptions: std::invalid_argument -> ValueError, std::logic_error -> ArithmeticError,
 std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device objective
 (`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`), the caller's own term compiled into the same kernels (`TermObjective(body)`,
-`ChainObjective(body)` for terms that overlap, `GridObjective(body, shape)` for 2x2-cell terms on a grid, or
+`ChainObjective(body)` for terms that overlap, `GridObjective(body, shape)` for 2x2-cell terms on a grid, `VolumeObjective(body, shape)` for 2x2x2-cell terms on a 3-D array, or
 `GraphObjective(edge_body, edges)` for edge terms over an index list,
 `MeshObjective(elem_body, elements, dim)` for K-node elements with vector unknowns, or
 `LinearObjective(row_body, (rowptr, col, val), n)` for a linear model over a sparse matrix, or
@@ -272,6 +272,55 @@ class GridObjective(TermObjective):
     def _check_n(self, n):
         if self.shape[0] * self.shape[1] != n:
             raise ValueError("GridObjective: shape = (%d, %d) does not multiply to n = %d" % (self.shape + (n,)))
+
+
+class VolumeObjective(TermObjective):
+    """An objective on a 3-D array: x is a slab-major slabs x rows x cols array (flattened, n = slabs*rows*cols, every extent
+    >= 2; node (s, r, c) has flat index (s*rows + r)*cols + c) and f(x) = sum over the (slabs-1)(rows-1)(cols-1) cells of
+    phi(x[8]; s, r, c) with x[4*ds + 2*dr + dc] = x[s+ds, r+dr, c+dc] -- volumetric denoising, 3-D phase-field and Allen-Cahn
+    energies, tomographic volumes under bounds, obstacle problems in 3-D (include/lbfgsx.h, "volume objectives").  The body is
+    the text of ONE CELL: it sees T, const T x[8], T g[8] (the cell's eight partial derivatives, to fill), int64_t i (the flat
+    index of x[0]), int64_t slab, row, col, slabs, rows, cols, p0..p3 and c[8], may read p0 at the cell's eight corners
+    (p0[i + dc + dr*cols + ds*rows*cols]), and returns the cell's value.  grad[s,r,c] is g[7] of cell (s-1,r-1,c-1) + g[6] of
+    (s-1,r-1,c) + g[5] of (s-1,r,c-1) + g[4] of (s-1,r,c) + g[3] of (s,r-1,c-1) + g[2] of (s,r-1,c) + g[1] of (s,r,c-1) + g[0] of
+    (s,r,c), those that exist, in this order.
+
+        dirichlet = VolumeObjective("const T a = x[1] - x[0]; const T b = x[2] - x[0]; const T e = x[4] - x[0];"
+                                    "for (int k = 0; k < 8; k++) g[k] = T(0);"
+                                    "g[0] = (T(0) - a - b) - e; g[1] = a; g[2] = b; g[4] = e;"
+                                    "return T(0.5) * ((a * a + b * b) + e * e);", shape=(slabs, rows, cols))
+
+    A per-node term is written inside the body as for a GridObjective: node (slab, row, col) goes to the cell that starts
+    there, and the last layer of cells in each direction picks up the nodes no cell starts at -- the cell adds the node term of
+    its corner (ds, dr, dc) iff (ds == 0 or slab + 2 == slabs) and (dr == 0 or row + 2 == rows) and (dc == 0 or
+    col + 2 == cols), with the matching addition to g[4*ds + 2*dr + dc]; every node is then counted once.
+
+    data, scalars, set_data, set_scalars, source, compile and info as for a TermObjective (scratch_by_kernel names the four
+    kernels by their counterparts); usable wherever a GridObjective is, refused where one is.  minimize raises ValueError
+    when slabs*rows*cols != len(x)."""
+    _NAME = "VolumeObjective"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_volume", "lbfgsx_objective_source_volume"
+
+    def __init__(self, body, shape, data=(), scalars=()):
+        try:
+            slabs, rows, cols = (int(v) for v in shape)
+        except (TypeError, ValueError):
+            raise ValueError("VolumeObjective: shape must be (slabs, rows, cols)") from None
+        if slabs < 2 or rows < 2 or cols < 2:
+            raise ValueError("VolumeObjective: shape = (%d, %d, %d): a volume has at least 2 slabs, 2 rows and 2 columns"
+                             % (slabs, rows, cols))
+        self.shape = (slabs, rows, cols)
+        self.body, self.K = str(body), 8
+        self._h = {}
+        self.set_data(*data)
+        self.set_scalars(*scalars)
+
+    def _form_args(self):
+        return ()
+
+    def _check_n(self, n):
+        if self.shape[0] * self.shape[1] * self.shape[2] != n:
+            raise ValueError("VolumeObjective: shape = (%d, %d, %d) does not multiply to n = %d" % (self.shape + (n,)))
 
 
 def _is_torch(x):
@@ -897,6 +946,8 @@ class _SolverBase:
             rc = self._sol.lbfgsx_solver_minimize_graph(self._h, h, n, f.E, f.ei.ctypes.data_as(C.POINTER(C.c_int32)),
                                                         f.ej.ctypes.data_as(C.POINTER(C.c_int32)), 0, tail[0], mask,
                                                         C.byref(counts), *tail[2:])
+        elif isinstance(f, VolumeObjective):
+            rc = self._sol.lbfgsx_solver_minimize_volume(self._h, h, f.shape[0], f.shape[1], f.shape[2], *tail)
         elif isinstance(f, GridObjective):
             rc = self._sol.lbfgsx_solver_minimize_grid(self._h, h, f.shape[0], f.shape[1], *tail)
         else:
@@ -919,7 +970,7 @@ class _SolverBase:
             return self._minimize_obj(f, n, x, lb, ub, trace)
         if not hasattr(f, "objective"):
             raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body), "
-                            "GridObjective(body, shape), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim), "
+                            "GridObjective(body, shape), VolumeObjective(body, shape), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim), "
                             "LinearObjective(row_body, matrix, n), GraphLinearObjective(row_body, matrix, edges, edge_body, n), "
                             "MultiLinearObjective(row_body, matrix, features, outputs), "
                             "DenseLinearObjective(row_body, matrix, outputs) or DeviceObjective(fn)")

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Registers, scratch and occupancy of the kernels on the two kernel frames -- own_frame.cuh: graph, mesh and linear-model
-(sparse, multi-output, dense); halo_frame.cuh: chain and grid -- in two trees, side by side
+(sparse, multi-output, dense); halo_frame.cuh: chain, grid and volume -- in two trees, side by side
 (profiles/own_frame_kernel_resources.tsv).  No GPU is needed: the generated sources are compiled for gfx950 here.
 
 Each tree (a built checkout: the parent commit's and this one) is asked, in a process of its own, for the generated
 translation unit -- source() -- of
     chain    ASYM2, ASYM3, CHAINED_ROSEN, SECOND_DIFF at their K                 (tests/chain_ref.py)
     grid     ASYM4, ALLENCAHN                                                  (tests/grid_ref.py)
+    volume   ASYM8, ALLENCAHN3                                                 (tests/volume_ref.py)
     graph    ASYM_EDGE with and without NODE                                   (tests/graph_ref.py)
     mesh     every (K, D) with the bodies tests/test_mesh_objective_cpu.py compiles (tests/mesh_ref.py)
     linear   LOGISTIC with and without RIDGE                                   (tests/linear_ref.py)
@@ -15,6 +16,8 @@ translation unit -- source() -- of
 at f64 and f32.  Each is compiled against its own tree's lbfgspp_amd/csrc with the library's flags,
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off --cuda-device-only -S -Rpass-analysis=kernel-resource-usage
 and the compiler's remarks give VGPRs, scratch bytes per lane and occupancy (waves per SIMD) per kernel.
+
+A case the parent tree does not have (a form it lacks) has no parent figures (-) and is checked for scratch only.
 
 The script fails when a kernel of this tree has scratch or a lower occupancy than the parent's.
 
@@ -57,6 +60,10 @@ def emit_sources(tree):
             out["chain/K%d/%s/%s" % (K, name, dname)] = A.ChainObjective(body, K=K).source(dtype)
         for name, body in (("asym4", GD.ASYM4), ("allencahn", GD.ALLENCAHN)):
             out["grid/%s/%s" % (name, dname)] = A.GridObjective(body, shape=(2, 2)).source(dtype)
+        if hasattr(A, "VolumeObjective"):
+            import volume_ref as VR
+            for name, body in (("asym8", VR.ASYM8), ("allencahn3", VR.ALLENCAHN3)):
+                out["volume/%s/%s" % (name, dname)] = A.VolumeObjective(body, shape=(2, 2, 2)).source(dtype)
         for name, node in (("asym+node", GR.NODE), ("asym", None)):
             out["graph/%s/%s" % (name, dname)] = A.GraphObjective(GR.ASYM_EDGE, edges=one_edge, node_body=node).source(dtype)
         for K in (2, 3, 4):
@@ -120,20 +127,29 @@ def main():
     trees = {"parent": os.path.abspath(args.parent), "head": ROOT}
     srcs = {k: json.loads(subprocess.run([sys.executable, os.path.abspath(__file__), "--emit-sources", t], cwd=t, check=True,
                                          stdout=subprocess.PIPE, text=True).stdout) for k, t in trees.items()}
-    assert sorted(srcs["parent"]) == sorted(srcs["head"])
+    assert set(srcs["parent"]) <= set(srcs["head"])
     cases = sorted(srcs["head"])
-    jobs = [(srcs[k][c], os.path.join(trees[k], "lbfgspp_amd", "csrc")) for c in cases for k in ("parent", "head")]
+    jobs = [(srcs[k][c], os.path.join(trees[k], "lbfgspp_amd", "csrc")) for c in cases for k in ("parent", "head") if c in srcs[k]]
     with ThreadPoolExecutor(max_workers=args.jobs) as ex:
-        res = list(ex.map(resources, jobs))
+        done = iter(list(ex.map(resources, jobs)))
+    res = {(c, k): next(done) for c in cases for k in ("parent", "head") if c in srcs[k]}
     bad = []
     with open(args.out, "w") as f:
-        f.write("# VGPRs, scratch bytes per lane and occupancy (waves per SIMD) of every chain, grid, graph, mesh and linear-model\n"
-                "# kernel, from the compiler's kernel-resource-usage remarks: the parent commit and this tree's kernels on\n"
-                "# own_frame.cuh and halo_frame.cuh, side by side\n"
+        f.write("# VGPRs, scratch bytes per lane and occupancy (waves per SIMD) of every chain, grid, volume, graph, mesh and\n"
+                "# linear-model kernel, from the compiler's kernel-resource-usage remarks: the parent commit and this tree's kernels\n"
+                "# on own_frame.cuh and halo_frame.cuh, side by side; - where the parent has no such form\n"
                 "# (scripts/measure_own_frame_resources.py; case = form/bodies/dtype)\n")
         f.write("case\tkernel\tvgpr_parent\tvgpr_head\tscratch_parent\tscratch_head\toccupancy_parent\toccupancy_head\tsame_source\n")
-        for i, c in enumerate(cases):
-            parent, head = res[2 * i], res[2 * i + 1]
+        for c in cases:
+            head = res[c, "head"]
+            if c not in srcs["parent"]:
+                for k in sorted(head):
+                    h = head[k]
+                    f.write("%s\t%s\t-\t%d\t-\t%d\t-\t%d\t-\n" % (c, k, h[0], h[1], h[2]))
+                    if h[1] != 0:
+                        bad.append("%s %s: scratch %d" % (c, k, h[1]))
+                continue
+            parent = res[c, "parent"]
             assert sorted(parent) == sorted(head), (c, sorted(parent), sorted(head))
             for k in sorted(head):
                 p, h = parent[k], head[k]
