@@ -106,6 +106,8 @@ class TermObjective
     std::int64_t m_rows = 0, m_cols = 0;  // a GridObjective's shape; 0: the handle is bound without one
     std::int64_t m_slabs = 0;             // a VolumeObjective's slabs, with the two above
     bool m_volume = false;
+    bool m_wraps = false;                 // a PeriodicGridObjective or PeriodicVolumeObjective: bound with the mask below
+    int m_periodic = 0;
     std::int64_t m_E = 0;                 // a GraphObjective's edges; 0: the handle is bound without any
     const std::int32_t *m_ei = nullptr, *m_ej = nullptr;
     bool m_edges_dev = false;
@@ -146,6 +148,8 @@ protected:
                        : (form == LBFGSX_FORM_LINEAR)  ? lbfgsx_objective_compile_linear(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_MESH)  ? lbfgsx_objective_compile_mesh(&m_h, dt, K, D, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRAPH) ? lbfgsx_objective_compile_graph(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
+                       : (form == LBFGSX_FORM_VOLUME_PERIODIC) ? lbfgsx_objective_compile_volume_periodic(&m_h, dt, body.c_str(), log.data(), log.size())
+                       : (form == LBFGSX_FORM_GRID_PERIODIC) ? lbfgsx_objective_compile_grid_periodic(&m_h, dt, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_VOLUME) ? lbfgsx_objective_compile_volume(&m_h, dt, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRID)  ? lbfgsx_objective_compile_grid(&m_h, dt, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_CHAIN) ? lbfgsx_objective_compile_chain(&m_h, dt, K, body.c_str(), log.data(), log.size())
@@ -167,6 +171,11 @@ protected:
         m_slabs = slabs;
         m_rows = rows;
         m_cols = cols;
+    }
+    void set_periodic(int mask)
+    {
+        m_wraps = true;
+        m_periodic = mask;
     }
     void set_elements(std::int64_t E, const std::int32_t* elems, bool on_device)
     {
@@ -270,6 +279,10 @@ public:
             detail::check(lbfgsx_objective_bind_mesh(c, m_h, m_E, m_elems, m_edges_dev ? 1 : 0, p, m_c, &id));
         else if (m_E || m_ei || m_ej)
             detail::check(lbfgsx_objective_bind_graph(c, m_h, m_E, m_ei, m_ej, m_edges_dev ? 1 : 0, p, m_c, &id));
+        else if (m_volume && m_wraps)
+            detail::check(lbfgsx_objective_bind_volume_periodic(c, m_h, m_slabs, m_rows, m_cols, m_periodic, p, m_c, &id));
+        else if (m_wraps)
+            detail::check(lbfgsx_objective_bind_grid_periodic(c, m_h, m_rows, m_cols, m_periodic, p, m_c, &id));
         else if (m_volume)
             detail::check(lbfgsx_objective_bind_volume(c, m_h, m_slabs, m_rows, m_cols, p, m_c, &id));
         else if (m_rows || m_cols)
@@ -339,6 +352,54 @@ public:
         : TermObjective<Scalar>(compiled)
     {
         this->set_shape3(slabs, rows, cols);
+    }
+};
+
+// A GridObjective with wrap-around cells (include/lbfgsx.h, "periodic grid and volume objectives"): periodic has bit 0 for the
+// column direction and bit 1 for the row direction; cell (r, c) exists iff (c < cols-1 or bit 0) and (r < rows-1 or bit 1) and
+// its corners are taken modulo the extents.  The body sees what a GridObjective's sees, and const int64_t j[4], the flat
+// indices of its four corners (j[0] == i; read p0[j[k]], not p0[i + 1]: that is wrong at a seam), and int periodic.
+//     PeriodicGridObjective<double> f(rows, cols, 3, "const T a = x[1] - x[0]; const T b = x[2] - x[0]; g[1] = a; g[2] = b;"
+//                                                    "g[3] = T(0); g[0] = -a - b; return T(0.5) * (a * a + b * b);");
+// Accepted and refused where a GridObjective is; a mask outside 0 .. 3 throws std::invalid_argument at minimize(), its value named.
+template <typename Scalar>
+class PeriodicGridObjective : public TermObjective<Scalar>
+{
+public:
+    PeriodicGridObjective(std::int64_t rows, std::int64_t cols, int periodic, const std::string& body)
+        : TermObjective<Scalar>(LBFGSX_FORM_GRID_PERIODIC, 4, body, "PeriodicGridObjective: ")
+    {
+        this->set_shape(rows, cols);
+        this->set_periodic(periodic);
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile_grid_periodic); it stays the caller's
+    PeriodicGridObjective(const lbfgsx_objective* compiled, std::int64_t rows, std::int64_t cols, int periodic)
+        : TermObjective<Scalar>(compiled)
+    {
+        this->set_shape(rows, cols);
+        this->set_periodic(periodic);
+    }
+};
+
+// A VolumeObjective with wrap-around cells: periodic has bit 0 for the column, bit 1 for the row and bit 2 for the slab
+// direction.  The body sees what a VolumeObjective's sees, and const int64_t j[8], the flat indices of its eight corners, and
+// int periodic.  Accepted and refused where a VolumeObjective is; a mask outside 0 .. 7 throws std::invalid_argument at minimize(), its value named.
+template <typename Scalar>
+class PeriodicVolumeObjective : public TermObjective<Scalar>
+{
+public:
+    PeriodicVolumeObjective(std::int64_t slabs, std::int64_t rows, std::int64_t cols, int periodic, const std::string& body)
+        : TermObjective<Scalar>(LBFGSX_FORM_VOLUME_PERIODIC, 8, body, "PeriodicVolumeObjective: ")
+    {
+        this->set_shape3(slabs, rows, cols);
+        this->set_periodic(periodic);
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile_volume_periodic); it stays the caller's
+    PeriodicVolumeObjective(const lbfgsx_objective* compiled, std::int64_t slabs, std::int64_t rows, std::int64_t cols, int periodic)
+        : TermObjective<Scalar>(compiled)
+    {
+        this->set_shape3(slabs, rows, cols);
+        this->set_periodic(periodic);
     }
 };
 
@@ -521,6 +582,8 @@ struct is_compiled_objective
     static constexpr bool value = std::is_same<F, TermObjective<Scalar> >::value || std::is_same<F, ChainObjective<Scalar> >::value ||
                                   std::is_same<F, GridObjective<Scalar> >::value || std::is_same<F, GraphObjective<Scalar> >::value ||
                                   std::is_same<F, VolumeObjective<Scalar> >::value ||
+                                  std::is_same<F, PeriodicGridObjective<Scalar> >::value ||
+                                  std::is_same<F, PeriodicVolumeObjective<Scalar> >::value ||
                                   std::is_same<F, MeshObjective<Scalar> >::value || std::is_same<F, LinearObjective<Scalar> >::value ||
                                   std::is_same<F, MultiLinearObjective<Scalar> >::value ||
                                   std::is_same<F, GraphLinearObjective<Scalar> >::value ||

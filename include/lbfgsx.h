@@ -216,7 +216,8 @@ int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4]);
  * with n < K is refused (any n >= K is accepted: n need not be a multiple of anything).  The compile log, the refusal of
  * asm and the line numbers are those of lbfgsx_objective_compile. */
 enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2, LBFGSX_FORM_GRAPH = 3, LBFGSX_FORM_MESH = 4, LBFGSX_FORM_LINEAR = 5,
-       LBFGSX_FORM_LINEAR_MULTI = 6, LBFGSX_FORM_DENSE = 7, LBFGSX_FORM_LINEAR_GRAPH = 8, LBFGSX_FORM_VOLUME = 9 };
+       LBFGSX_FORM_LINEAR_MULTI = 6, LBFGSX_FORM_DENSE = 7, LBFGSX_FORM_LINEAR_GRAPH = 8, LBFGSX_FORM_VOLUME = 9,
+       LBFGSX_FORM_GRID_PERIODIC = 10, LBFGSX_FORM_VOLUME_PERIODIC = 11 };
 int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len);
 long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char* out, size_t len);
 int lbfgsx_objective_form(const lbfgsx_objective* obj);
@@ -289,6 +290,44 @@ long long lbfgsx_objective_source_volume(int dtype, const char* body, char* out,
 int lbfgsx_objective_bind_volume(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
                                  const void* const p[4], const double cs[8], int* id);
 int lbfgsx_objective_shape3(const lbfgsx_ctx* c, int64_t* slabs, int64_t* rows, int64_t* cols);
+/* ---- periodic grid and volume objectives: wrap-around cells --------------------------------------------------------------
+ * The grid and the volume form with periodic boundaries in the directions of a mask `periodic`: bit 0 the column direction,
+ * bit 1 the row direction, bit 2 (a volume only) the slab direction -- Allen-Cahn, Cahn-Hilliard and phase-field energies on a
+ * torus, XY, rotor and Ginzburg-Landau lattices, micromagnetic boxes, channels and cylinders (periodic in one direction,
+ * walled in the other), circular-convolution image models.
+ *   Periodic grid.  x is a row-major rows x cols array, n = rows*cols, rows >= 2, cols >= 2.  Cell (r, c) has the corners
+ *     x[r, c], x[r, c(+)1], x[r(+)1, c], x[r(+)1, c(+)1] in the grid form's slot order, (+) modulo the extent, and exists iff
+ *     (c < cols-1 or bit 0) and (r < rows-1 or bit 1).  With the mask 0 this is exactly the grid form.
+ *     grad[r,c] = g[3] of cell (r(-)1, c(-)1) + g[2] of (r(-)1, c) + g[1] of (r, c(-)1) + g[0] of (r, c): the cells that exist, in
+ *     this fixed order, started from the first (no leading 0 +); on a periodic axis (-) wraps, on an open axis a negative index
+ *     means the cell does not exist.  Away from the seams this is the grid form's order; on a torus it is translation-invariant.
+ *   Periodic volume.  The same on the slab-major slabs x rows x cols array, eight corners in the volume form's slot order,
+ *     x[4*ds + 2*dr + dc] = x[s(+)ds, r(+)dr, c(+)dc], and the volume form's order of the eight cells of a node with wrapped
+ *     indices.
+ *   f = the order-independent (compensated) sum of the existing cells' values, each added once, by the owner of the cell's
+ *     origin.  One rounding per source operation, no contraction, no floating-point atomic.  In the trial kernels every corner
+ *     value is xp + step*d, never a read of the x the launch writes.
+ * `body` sees what the grid or the volume body sees, plus const int64_t j[4] (j[8] for a volume), the flat indices of its
+ * corners with j[0] == i, and int periodic.  It may read p0[j[k]]; the i + 1 and i + cols arithmetic of the open forms is
+ * wrong at a seam.  A per-node term goes to the cell that starts at the node; on an open axis the last layer of cells picks
+ * up the nodes no cell starts at, as described above, and on a periodic axis there is nothing to pick up:
+ *     if (!(periodic & 1) && col + 2 == cols) v += node(x[1], j[1]);
+ * lbfgsx_objective_compile_grid_periodic and _volume_periodic wrap the body for the four kernels of
+ * csrc/periodic_grid_kernels.cuh and csrc/periodic_volume_kernels.cuh (same arguments, grids and reductions as the open
+ * forms') and cache by (form, body, K, dtype): the shape and the mask are not part of the key.  The forms are
+ * LBFGSX_FORM_GRID_PERIODIC and LBFGSX_FORM_VOLUME_PERIODIC.  The bind calls refuse (LBFGSX_E_INVALID, the values named) a
+ * handle of another form, an extent < 2, a product that is not n or overflows, and a mask with bits outside the form's
+ * directions; every other bind call refuses these handles.  lbfgsx_objective_shape and lbfgsx_objective_shape3 read the
+ * bound shape back, lbfgsx_objective_periodic the bound mask. */
+int lbfgsx_objective_compile_grid_periodic(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len);
+long long lbfgsx_objective_source_grid_periodic(int dtype, const char* body, char* out, size_t len);
+int lbfgsx_objective_bind_grid_periodic(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                        const void* const p[4], const double cs[8], int* id);
+int lbfgsx_objective_compile_volume_periodic(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len);
+long long lbfgsx_objective_source_volume_periodic(int dtype, const char* body, char* out, size_t len);
+int lbfgsx_objective_bind_volume_periodic(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
+                                          int periodic, const void* const p[4], const double cs[8], int* id);
+int lbfgsx_objective_periodic(const lbfgsx_ctx* c, int* mask);
 /* ---- graph objectives: edge terms over an index list ---------------------------------------------------------------------
  * x has n coordinates, the NODES; the caller gives E edges as two int32 arrays ei[E], ej[E], and
  *     f(x) = sum over nodes v of psi(x[v]; v)  +  sum over edges e of phi(x[ei[e]], x[ej[e]]; e)

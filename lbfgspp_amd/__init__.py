@@ -6,8 +6,9 @@ solver.py        Python mirror of LBFGSSolver / LBFGSBSolver / LBFGSParam over t
 from ._lib import (F32, F64, LS_BACKTRACKING, LS_BRACKETING, LS_MORE_THUENTE, LS_NOCEDAL_WRIGHT,
                    NativeLibraryMissing, load)
 from .solver import (ChainObjective, DenseLinearObjective, DeviceObjective, GraphLinearObjective, GraphObjective, GridObjective, LinearObjective, MeshObjective, MultiLinearObjective, DiagQuadratic, ExtendedRosenbrock, LBFGSBParam, LBFGSBSolver, LBFGSParam,
-                     LBFGSSolver, TermObjective, TraceBuffer, VolumeObjective)
+                     LBFGSSolver, PeriodicGridObjective, PeriodicVolumeObjective, TermObjective, TraceBuffer, VolumeObjective)
 
 __all__ = ["F32", "F64", "LS_BACKTRACKING", "LS_BRACKETING", "LS_MORE_THUENTE", "LS_NOCEDAL_WRIGHT",
            "NativeLibraryMissing", "load", "ChainObjective", "DenseLinearObjective", "DeviceObjective", "GraphLinearObjective", "GraphObjective", "GridObjective", "LinearObjective", "MeshObjective", "MultiLinearObjective", "DiagQuadratic", "ExtendedRosenbrock", "LBFGSBParam",
-           "LBFGSParam", "LBFGSSolver", "LBFGSBSolver", "TermObjective", "TraceBuffer", "VolumeObjective"]
+           "LBFGSParam", "LBFGSSolver", "LBFGSBSolver", "PeriodicGridObjective", "PeriodicVolumeObjective", "TermObjective", "TraceBuffer",
+           "VolumeObjective"]

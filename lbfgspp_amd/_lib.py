@@ -215,6 +215,20 @@ def load():
     sig(core, "lbfgsx_objective_shape3", i32, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64))
     sig(sol, "lbfgsx_solver_minimize_volume", i32, vp, vp, i64, i64, i64, C.POINTER(vp * 4), i32, C.POINTER(dbl * 8), vp, vp, vp,
         C.POINTER(Trace), C.POINTER(Result))
+    # periodic grid and volume objectives: the open forms' calls with a mask after the shape
+    sig(core, "lbfgsx_objective_compile_grid_periodic", i32, C.POINTER(vp), i32, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_source_grid_periodic", C.c_longlong, i32, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_bind_grid_periodic", i32, vp, vp, i64, i64, i32, C.POINTER(vp * 4), C.POINTER(dbl * 8),
+        C.POINTER(i32))
+    sig(core, "lbfgsx_objective_compile_volume_periodic", i32, C.POINTER(vp), i32, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_source_volume_periodic", C.c_longlong, i32, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_bind_volume_periodic", i32, vp, vp, i64, i64, i64, i32, C.POINTER(vp * 4), C.POINTER(dbl * 8),
+        C.POINTER(i32))
+    sig(core, "lbfgsx_objective_periodic", i32, vp, C.POINTER(i32))
+    sig(sol, "lbfgsx_solver_minimize_grid_periodic", i32, vp, vp, i64, i64, i32, C.POINTER(vp * 4), i32, C.POINTER(dbl * 8), vp, vp,
+        vp, C.POINTER(Trace), C.POINTER(Result))
+    sig(sol, "lbfgsx_solver_minimize_volume_periodic", i32, vp, vp, i64, i64, i64, i32, C.POINTER(vp * 4), i32, C.POINTER(dbl * 8),
+        vp, vp, vp, C.POINTER(Trace), C.POINTER(Result))
     # graph objectives: two bodies; the edges travel with the binding
     i32p, u32p = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
     sig(core, "lbfgsx_objective_compile_graph", i32, C.POINTER(vp), i32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t)

@@ -269,6 +269,7 @@ struct lbfgsx_ctx
     int term_form = 0;  // the bound handle's form (LBFGSX_FORM_*): which argument struct its kernels take (launch_args.hpp)
     int64_t term_rows = 0, term_cols = 0;  // a grid objective's shape (lbfgsx_objective_bind_grid)
     int64_t term_slabs = 0;                // a volume objective's slabs, with the two above (lbfgsx_objective_bind_volume)
+    int term_periodic = 0;                 // a periodic grid or volume objective's mask: bit 0 cols, bit 1 rows, bit 2 slabs
     void* term_own[4] = {nullptr, nullptr, nullptr, nullptr};
     int64_t term_own_count[4] = {0, 0, 0, 0};  // elements term_own[k] holds (lbfgsx_objective_upload_count)
     // a graph objective's incidence list (lbfgsx_objective_bind_graph, graph_topology.hip): the context's own, built from

@@ -8,7 +8,7 @@
 // same kernel text, the same flags, the same sums.  The code object is loaded per device with hipModuleLoadData and the
 // kernels are launched with hipModuleLaunchKernel from the arguments launch_args.hpp works out for both forms.
 //
-// Ten forms of objective share all of this (include/lbfgsx.h): a TERM objective (terms that do not overlap: the struct with
+// Twelve forms of objective share all of this (include/lbfgsx.h): a TERM objective (terms that do not overlap: the struct with
 // pack / tail / finish above), a CHAIN objective (one term starting at every coordinate: a second generated wrapper that
 // includes chain_kernels.cuh and instantiates its four kernels, which take the arguments of the four above) and a GRID
 // objective (one term per 2x2 cell of a row-major grid: a third wrapper around grid_kernels.cuh, whose struct also carries
@@ -25,7 +25,9 @@
 // over an index list on its coordinates: three bodies), is a wrapper around linear_graph_kernels.cuh with both the matrix and
 // the incidence list; its row passes are the sixth form's.  A tenth, a VOLUME objective (one term per 2x2x2 cell of a
 // slab-major 3-D array), is the grid form with one more extent: a wrapper around volume_kernels.cuh whose struct carries the
-// three extents.  A handle carries its form; the four slots of the
+// three extents.  An eleventh and a twelfth, a PERIODIC GRID and a PERIODIC VOLUME objective, are those two with wrap-around cells
+// in the directions of a mask: wrappers around periodic_grid_kernels.cuh and periodic_volume_kernels.cuh whose structs carry
+// the extents and the mask, and whose body also sees the flat indices of its corners.  A handle carries its form; the four slots of the
 // loaded-kernel table and everything that launches them are the same.  What the forms differ in -- names, kernel names, struct
 // members, the bodies' signatures, the K and D accepted, the cache key -- is one row each of kForms below; the generator, the
 // validation and the refusals are written once and read it.
@@ -85,7 +87,7 @@ struct FormDesc
     "    const T* part;\n    const int32_t* long_col;\n    const uint32_t* long_chunk;\n"           \
     "    int64_t R, nnz;\n    int32_t L, C, nlong, pad_;\n"
 const BodyDesc kNoBody = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-const FormDesc kForms[10] = {
+const FormDesc kForms[12] = {
     {"term objective", "", "ObjTerm", "#include \"lbfgs_kernels.cuh\"\n#include \"lbfgsb_kernels.cuh\"\n",
      {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial", nullptr, nullptr, "k_trial_post"}, "", kNoBody,
      {"    // one term: x[0..K) in, g[0..K) out, the term's value returned\n", TERM_SIGNATURE, "objective_body", "body", nullptr,
@@ -199,7 +201,28 @@ const FormDesc kForms[10] = {
       "    // x[4*ds + 2*dr + dc] = x[slab+ds, row+dr, col+dc] in, its eight partial derivatives g out, its value returned\n",
       "T term(const T (&x)[8], T (&g)[8], int64_t i, int64_t slab, int64_t row, int64_t col) const", "objective_body", "body",
       nullptr, nullptr},
-     "", 8, 8, 1, 1, "a cell reads K = 8 coordinates", nullptr, false, false, "shape"}};
+     "", 8, 8, 1, 1, "a cell reads K = 8 coordinates", nullptr, false, false, "shape"},
+    {"periodic grid objective", "_grid_periodic", "ObjGridPeriodic", "#include \"periodic_grid_kernels.cuh\"\n",
+     {"k_pgrid_eval", "k_pgrid_trial", "k_pgrid_b_eval", "k_pgrid_b_dg_maxstep_trial"},
+     // launch_args.hpp: PeriodicGridArgs
+     "    int64_t rows, cols;\n    int periodic, pad_;\n", kNoBody,
+     {"    // the cell whose origin is node (row, col), flat index i = row*cols + col: x = {x[row,col], x[row,col+1], x[row+1,col],\n"
+      "    // x[row+1,col+1]} in, + modulo the extent; j: the flat indices of those four nodes, j[0] == i; periodic: bit 0 the\n"
+      "    // column direction, bit 1 the row direction; its four partial derivatives g out, its value returned\n",
+      "T term(const T (&x)[4], T (&g)[4], int64_t i, int64_t row, int64_t col, const int64_t (&j)[4]) const", "objective_body",
+      "body", nullptr, nullptr},
+     "", 4, 4, 1, 1, "a cell reads K = 4 coordinates", nullptr, false, false, "shape and mask"},
+    {"periodic volume objective", "_volume_periodic", "ObjVolumePeriodic", "#include \"periodic_volume_kernels.cuh\"\n",
+     {"k_pvolume_eval", "k_pvolume_trial", "k_pvolume_b_eval", "k_pvolume_b_dg_maxstep_trial"},
+     // launch_args.hpp: PeriodicVolumeArgs
+     "    int64_t slabs, rows, cols;\n    int periodic, pad_;\n", kNoBody,
+     {"    // the cell whose origin is node (slab, row, col), flat index i = (slab*rows + row)*cols + col:\n"
+      "    // x[4*ds + 2*dr + dc] = x[slab+ds, row+dr, col+dc] in, + modulo the extent; j: the flat indices of those eight nodes,\n"
+      "    // j[0] == i; periodic: bit 0 the column, bit 1 the row, bit 2 the slab direction; its eight partial derivatives g out,\n"
+      "    // its value returned\n",
+      "T term(const T (&x)[8], T (&g)[8], int64_t i, int64_t slab, int64_t row, int64_t col, const int64_t (&j)[8]) const",
+      "objective_body", "body", nullptr, nullptr},
+     "", 8, 8, 1, 1, "a cell reads K = 8 coordinates", nullptr, false, false, "shape and mask"}};
 #undef LINEAR_MEMBERS
 #undef TERM_SIGNATURE
 #undef POINT_SIGNATURE
@@ -701,6 +724,14 @@ long long lbfgsx_objective_source_volume(int dtype, const char* body, char* out,
 {
     return objective_source(LBFGSX_FORM_VOLUME, dtype, 8, body, out, len);
 }
+long long lbfgsx_objective_source_grid_periodic(int dtype, const char* body, char* out, size_t len)
+{
+    return objective_source(LBFGSX_FORM_GRID_PERIODIC, dtype, 4, body, out, len);
+}
+long long lbfgsx_objective_source_volume_periodic(int dtype, const char* body, char* out, size_t len)
+{
+    return objective_source(LBFGSX_FORM_VOLUME_PERIODIC, dtype, 8, body, out, len);
+}
 long long lbfgsx_objective_source_graph(int dtype, const char* node_body, const char* edge_body, char* out, size_t len)
 {
     return objective_source(LBFGSX_FORM_GRAPH, dtype, 2, edge_body, out, len, node_body);
@@ -743,6 +774,14 @@ int lbfgsx_objective_compile_grid(lbfgsx_objective** out, int dtype, const char*
 int lbfgsx_objective_compile_volume(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len)
 {
     return objective_compile(LBFGSX_FORM_VOLUME, out, dtype, 8, body, log, log_len);
+}
+int lbfgsx_objective_compile_grid_periodic(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_GRID_PERIODIC, out, dtype, 4, body, log, log_len);
+}
+int lbfgsx_objective_compile_volume_periodic(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_VOLUME_PERIODIC, out, dtype, 8, body, log, log_len);
 }
 int lbfgsx_objective_compile_graph(lbfgsx_objective** out, int dtype, const char* node_body, const char* edge_body, char* log,
                                    size_t log_len)
@@ -843,9 +882,9 @@ int lbfgsx_objective_upload(lbfgsx_ctx* c, int slot, const void* host, void** de
 namespace {
 
 // lbfgsx_objective_bind, lbfgsx_objective_bind_grid and lbfgsx_objective_bind_volume: rows = cols = 0 for a handle without a
-// shape, slabs = 0 for every form but a volume objective
+// shape, slabs = 0 for every form but a volume objective, periodic = 0 for every form but the two periodic ones
 int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
-                   const double cs[8], int* id, int64_t slabs = 0)
+                   const double cs[8], int* id, int64_t slabs = 0, int periodic = 0)
 {
     c->st_valid = false;
     c->spec_valid = false;
@@ -855,6 +894,7 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
         c->term_np = 0;
         c->term_form = LBFGSX_FORM_TERM;
         c->term_slabs = c->term_rows = c->term_cols = 0;
+        c->term_periodic = 0;
         if (c->graph_inc || c->lin.colptr || c->dense.w)
         {
             lbfgsx::DeviceGuard dev_guard_(c->device);
@@ -919,6 +959,7 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
     c->term_slabs = slabs;
     c->term_rows = rows;
     c->term_cols = cols;
+    c->term_periodic = periodic;
     c->term_np = 0;
     for (int j = 0; j < 4; j++)
     {
@@ -1016,7 +1057,7 @@ int lbfgsx_objective_bind_grid(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64
 
 int lbfgsx_objective_shape(const lbfgsx_ctx* c, int64_t* rows, int64_t* cols)
 {
-    if (!c || !c->term || c->term_form != LBFGSX_FORM_GRID)
+    if (!c || !c->term || (c->term_form != LBFGSX_FORM_GRID && c->term_form != LBFGSX_FORM_GRID_PERIODIC))
     {
         lbfgsx::set_error("lbfgsx_objective_shape: no grid objective is bound to this context");
         return LBFGSX_E_INVALID;
@@ -1054,7 +1095,7 @@ int lbfgsx_objective_bind_volume(lbfgsx_ctx* c, const lbfgsx_objective* obj, int
 
 int lbfgsx_objective_shape3(const lbfgsx_ctx* c, int64_t* slabs, int64_t* rows, int64_t* cols)
 {
-    if (!c || !c->term || c->term_form != LBFGSX_FORM_VOLUME)
+    if (!c || !c->term || (c->term_form != LBFGSX_FORM_VOLUME && c->term_form != LBFGSX_FORM_VOLUME_PERIODIC))
     {
         lbfgsx::set_error("lbfgsx_objective_shape3: no volume objective is bound to this context");
         return LBFGSX_E_INVALID;
@@ -1065,6 +1106,76 @@ int lbfgsx_objective_shape3(const lbfgsx_ctx* c, int64_t* slabs, int64_t* rows, 
         *rows = c->term_rows;
     if (cols)
         *cols = c->term_cols;
+    return LBFGSX_OK;
+}
+
+int lbfgsx_objective_bind_grid_periodic(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                        const void* const p[4], const double cs[8], int* id)
+{
+    if (!c || !obj)
+        return LBFGSX_E_INVALID;
+    if (!handle_is(obj, LBFGSX_FORM_GRID_PERIODIC))
+        return LBFGSX_E_INVALID;
+    const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
+    long long prod = 0;
+    if (rows < 2 || cols < 2)
+    {
+        lbfgsx::set_error("periodic grid objective: " + shape + ": a grid has at least 2 rows and 2 columns (rows >= 2, cols >= 2)");
+        return LBFGSX_E_INVALID;
+    }
+    if (__builtin_mul_overflow((long long) rows, (long long) cols, &prod) || prod != (long long) c->n)
+    {
+        lbfgsx::set_error("periodic grid objective: " + shape + " does not multiply to n = " + std::to_string(c->n));
+        return LBFGSX_E_INVALID;
+    }
+    if (periodic < 0 || periodic > 3)
+    {
+        lbfgsx::set_error("periodic grid objective: periodic = " + std::to_string(periodic) +
+                          ": the mask has bit 0 for the column direction and bit 1 for the row direction (0 .. 3)");
+        return LBFGSX_E_INVALID;
+    }
+    return objective_bind(c, obj, rows, cols, p, cs, id, 0, periodic);
+}
+
+int lbfgsx_objective_bind_volume_periodic(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
+                                          int periodic, const void* const p[4], const double cs[8], int* id)
+{
+    if (!c || !obj)
+        return LBFGSX_E_INVALID;
+    if (!handle_is(obj, LBFGSX_FORM_VOLUME_PERIODIC))
+        return LBFGSX_E_INVALID;
+    const std::string shape = "slabs = " + std::to_string(slabs) + ", rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
+    long long prod = 0;
+    if (slabs < 2 || rows < 2 || cols < 2)
+    {
+        lbfgsx::set_error("periodic volume objective: " + shape +
+                          ": a volume has at least 2 slabs, 2 rows and 2 columns (slabs >= 2, rows >= 2, cols >= 2)");
+        return LBFGSX_E_INVALID;
+    }
+    if (__builtin_mul_overflow((long long) rows, (long long) cols, &prod) || __builtin_mul_overflow(prod, (long long) slabs, &prod) ||
+        prod != (long long) c->n)
+    {
+        lbfgsx::set_error("periodic volume objective: " + shape + " does not multiply to n = " + std::to_string(c->n));
+        return LBFGSX_E_INVALID;
+    }
+    if (periodic < 0 || periodic > 7)
+    {
+        lbfgsx::set_error("periodic volume objective: periodic = " + std::to_string(periodic) +
+                          ": the mask has bit 0 for the column, bit 1 for the row and bit 2 for the slab direction (0 .. 7)");
+        return LBFGSX_E_INVALID;
+    }
+    return objective_bind(c, obj, rows, cols, p, cs, id, slabs, periodic);
+}
+
+int lbfgsx_objective_periodic(const lbfgsx_ctx* c, int* mask)
+{
+    if (!c || !c->term || (c->term_form != LBFGSX_FORM_GRID_PERIODIC && c->term_form != LBFGSX_FORM_VOLUME_PERIODIC))
+    {
+        lbfgsx::set_error("lbfgsx_objective_periodic: no periodic grid or volume objective is bound to this context");
+        return LBFGSX_E_INVALID;
+    }
+    if (mask)
+        *mask = c->term_periodic;
     return LBFGSX_OK;
 }
 

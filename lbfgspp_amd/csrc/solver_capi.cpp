@@ -55,10 +55,11 @@ struct lbfgsx_solver
         const void* A = nullptr;
         int64_t lda = 0;
     };
-    // rows, cols: the shape of a grid objective, with slabs of a volume objective, 0 for the other forms; gr: null for every form but a graph objective
+    // rows, cols: the shape of a grid objective, with slabs of a volume objective, 0 for the other forms; gr: null for every form but a graph objective;
+    // periodic: the mask of a periodic grid or volume objective, -1 for the other forms
     virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t slabs, int64_t rows, int64_t cols, const GraphSpec* gr,
                               const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
-                              lbfgsx_trace* tr, lbfgsx_result* out) = 0;
+                              lbfgsx_trace* tr, lbfgsx_result* out, int periodic = -1) = 0;
 };
 
 namespace {
@@ -229,10 +230,12 @@ struct LbfgsImpl : lbfgsx_solver
     }
     void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t slabs, int64_t rows, int64_t cols, const GraphSpec* gr,
                       const void* const p[4], int host_mask, const double c[8], void* x, const void*, const void*,
-                      lbfgsx_trace* tr, lbfgsx_result* out) override
+                      lbfgsx_trace* tr, lbfgsx_result* out, int periodic) override
     {
         GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
         VolumeObjective<Scalar> spaced(obj, slabs, rows, cols);  // binds with three extents when there are three
+        PeriodicGridObjective<Scalar> wrapped(obj, rows, cols, periodic);            // binds with the mask when there is one (>= 0)
+        PeriodicVolumeObjective<Scalar> wrapped3(obj, slabs, rows, cols, periodic);  // ... and three extents
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
         LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
@@ -255,6 +258,8 @@ struct LbfgsImpl : lbfgsx_solver
                                    : (gr && gr->rowptr) ? static_cast<TermObjective<Scalar>&>(lined)
                                    : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
                                    : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
+                                   : (periodic >= 0 && slabs) ? static_cast<TermObjective<Scalar>&>(wrapped3)
+                                   : (periodic >= 0)   ? static_cast<TermObjective<Scalar>&>(wrapped)
                                    : slabs             ? static_cast<TermObjective<Scalar>&>(spaced)
                                                        : shaped;
         fill_term<Scalar>(f, p, host_mask, c, gr ? gr->counts : nullptr);
@@ -362,10 +367,12 @@ struct LbfgsbImpl : lbfgsx_solver
     }
     void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t slabs, int64_t rows, int64_t cols, const GraphSpec* gr,
                       const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
-                      lbfgsx_trace* tr, lbfgsx_result* out) override
+                      lbfgsx_trace* tr, lbfgsx_result* out, int periodic) override
     {
         GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
         VolumeObjective<Scalar> spaced(obj, slabs, rows, cols);  // binds with three extents when there are three
+        PeriodicGridObjective<Scalar> wrapped(obj, rows, cols, periodic);            // binds with the mask when there is one (>= 0)
+        PeriodicVolumeObjective<Scalar> wrapped3(obj, slabs, rows, cols, periodic);  // ... and three extents
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
         LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
@@ -388,6 +395,8 @@ struct LbfgsbImpl : lbfgsx_solver
                                    : (gr && gr->rowptr) ? static_cast<TermObjective<Scalar>&>(lined)
                                    : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
                                    : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
+                                   : (periodic >= 0 && slabs) ? static_cast<TermObjective<Scalar>&>(wrapped3)
+                                   : (periodic >= 0)   ? static_cast<TermObjective<Scalar>&>(wrapped)
                                    : slabs             ? static_cast<TermObjective<Scalar>&>(spaced)
                                                        : shaped;
         fill_term<Scalar>(f, p, host_mask, c, gr ? gr->counts : nullptr);
@@ -972,6 +981,10 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
             throw std::invalid_argument("a grid objective is minimised with its shape: lbfgsx_solver_minimize_grid");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_VOLUME)
             throw std::invalid_argument("a volume objective is minimised with its shape: lbfgsx_solver_minimize_volume");
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID_PERIODIC)
+            throw std::invalid_argument("a periodic grid objective is minimised with its shape and mask: lbfgsx_solver_minimize_grid_periodic");
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_VOLUME_PERIODIC)
+            throw std::invalid_argument("a periodic volume objective is minimised with its shape and mask: lbfgsx_solver_minimize_volume_periodic");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRAPH)
             throw std::invalid_argument("a graph objective is minimised with its edges: lbfgsx_solver_minimize_graph");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_MESH)
@@ -1066,6 +1079,82 @@ int lbfgsx_solver_minimize_volume(lbfgsx_solver* s, const lbfgsx_objective* obj,
         return out->status;
     }
     return guarded(out, [&]() { s->minimize_obj(obj, int64_t(n), slabs, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out); });
+}
+
+int lbfgsx_solver_minimize_grid_periodic(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                         const void* const p[4], int host_mask, const double c[8], void* x, const void* lb,
+                                         const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    long long n = 0;
+    const int bad = guarded(out, [&]() {
+        if (!s || !obj)
+            throw std::invalid_argument("lbfgsx_solver_minimize_grid_periodic: invalid argument");
+        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_GRID_PERIODIC)
+            throw std::invalid_argument("lbfgsx_solver_minimize_grid_periodic: the handle is not a periodic grid objective "
+                                        "(lbfgsx_objective_compile_grid_periodic)");
+        if (lbfgsx_objective_dtype(obj) != s->dtype)
+            throw std::invalid_argument("lbfgsx_solver_minimize_grid_periodic: the objective was compiled for the other dtype");
+        const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
+        if (rows < 2 || cols < 2)
+            throw std::invalid_argument("periodic grid objective: " + shape +
+                                        ": a grid has at least 2 rows and 2 columns (rows >= 2, cols >= 2)");
+        if (__builtin_mul_overflow((long long) rows, (long long) cols, &n))
+            throw std::invalid_argument("periodic grid objective: " + shape + ": rows*cols overflows");
+        if (periodic < 0 || periodic > 3)
+            throw std::invalid_argument("periodic grid objective: periodic = " + std::to_string(periodic) +
+                                        ": the mask has bit 0 for the column direction and bit 1 for the row direction (0 .. 3)");
+    });
+    if (bad)
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg),
+                      "lbfgsx_solver_minimize_grid_periodic: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    return guarded(out,
+                   [&]() { s->minimize_obj(obj, int64_t(n), 0, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out, periodic); });
+}
+
+int lbfgsx_solver_minimize_volume_periodic(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
+                                           int periodic, const void* const p[4], int host_mask, const double c[8], void* x,
+                                           const void* lb, const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    long long n = 0;
+    const int bad = guarded(out, [&]() {
+        if (!s || !obj)
+            throw std::invalid_argument("lbfgsx_solver_minimize_volume_periodic: invalid argument");
+        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_VOLUME_PERIODIC)
+            throw std::invalid_argument("lbfgsx_solver_minimize_volume_periodic: the handle is not a periodic volume objective "
+                                        "(lbfgsx_objective_compile_volume_periodic)");
+        if (lbfgsx_objective_dtype(obj) != s->dtype)
+            throw std::invalid_argument("lbfgsx_solver_minimize_volume_periodic: the objective was compiled for the other dtype");
+        const std::string shape =
+            "slabs = " + std::to_string(slabs) + ", rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
+        if (slabs < 2 || rows < 2 || cols < 2)
+            throw std::invalid_argument("periodic volume objective: " + shape +
+                                        ": a volume has at least 2 slabs, 2 rows and 2 columns (slabs >= 2, rows >= 2, cols >= 2)");
+        if (__builtin_mul_overflow((long long) rows, (long long) cols, &n) || __builtin_mul_overflow(n, (long long) slabs, &n))
+            throw std::invalid_argument("periodic volume objective: " + shape + ": slabs*rows*cols overflows");
+        if (periodic < 0 || periodic > 7)
+            throw std::invalid_argument("periodic volume objective: periodic = " + std::to_string(periodic) +
+                                        ": the mask has bit 0 for the column, bit 1 for the row and bit 2 for the slab direction (0 .. 7)");
+    });
+    if (bad)
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg),
+                      "lbfgsx_solver_minimize_volume_periodic: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    return guarded(out, [&]() {
+        s->minimize_obj(obj, int64_t(n), slabs, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out, periodic);
+    });
 }
 
 int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t E, const int32_t* ei,

@@ -7,7 +7,8 @@ Names, argument meaning and error behaviour follow yixuan/LBFGSpp:
 Exceptions: std::invalid_argument -> ValueError, std::logic_error -> ArithmeticError,
 std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device objective
 (`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`), the caller's own term compiled into the same kernels (`TermObjective(body)`,
-`ChainObjective(body)` for terms that overlap, `GridObjective(body, shape)` for 2x2-cell terms on a grid, `VolumeObjective(body, shape)` for 2x2x2-cell terms on a 3-D array, or
+`ChainObjective(body)` for terms that overlap, `GridObjective(body, shape)` for 2x2-cell terms on a grid, `VolumeObjective(body, shape)` for 2x2x2-cell terms on a 3-D array,
+`PeriodicGridObjective(body, shape, periodic)` and `PeriodicVolumeObjective(body, shape, periodic)` for those two with wrap-around cells, or
 `GraphObjective(edge_body, edges)` for edge terms over an index list,
 `MeshObjective(elem_body, elements, dim)` for K-node elements with vector unknowns, or
 `LinearObjective(row_body, (rowptr, col, val), n)` for a linear model over a sparse matrix, or
@@ -321,6 +322,94 @@ class VolumeObjective(TermObjective):
     def _check_n(self, n):
         if self.shape[0] * self.shape[1] * self.shape[2] != n:
             raise ValueError("VolumeObjective: shape = (%d, %d, %d) does not multiply to n = %d" % (self.shape + (n,)))
+
+
+def _periodic_mask(name, periodic, axes):
+    """the mask of a periodic form from its tuple of flags, outermost axis first: bit 0 the column direction"""
+    try:
+        flags = tuple(periodic)
+    except TypeError:
+        flags = ()
+    if len(flags) != len(axes):
+        raise ValueError("%s: periodic must have one flag per axis, (%s)" % (name, ", ".join(axes)))
+    for v in flags:
+        if not isinstance(v, (bool, np.bool_)) and not (isinstance(v, (int, np.integer)) and v in (0, 1)):
+            raise ValueError("%s: periodic = %r: a flag is True or False" % (name, periodic))
+    return sum(1 << k for k, v in enumerate(reversed(flags)) if v)
+
+
+class PeriodicGridObjective(TermObjective):
+    """A GridObjective with wrap-around cells (include/lbfgsx.h, "periodic grid and volume objectives"): periodic = (rows,
+    cols) says which directions wrap.  Cell (r, c) has the corners x[r,c], x[r,c+1], x[r+1,c], x[r+1,c+1] with + modulo the
+    extent and exists iff (c < cols-1 or the columns wrap) and (r < rows-1 or the rows wrap); with periodic = (False, False)
+    this is a GridObjective.  The body sees what a GridObjective's sees, plus const int64_t j[4], the flat indices of its four
+    corners (j[0] == i), and int periodic (bit 0: columns, bit 1: rows).  It reads data as p0[j[k]]: p0[i + 1] and
+    p0[i + cols] are wrong at a seam.  grad[r,c] is g[3] of cell (r-1,c-1) + g[2] of (r-1,c) + g[1] of (r,c-1) + g[0] of
+    (r,c) with - modulo the extent on a periodic axis, those that exist, in this order.
+
+        torus = PeriodicGridObjective("const T a = x[1] - x[0]; const T b = x[2] - x[0];"
+                                      "g[0] = T(0) - a - b; g[1] = a; g[2] = b; g[3] = T(0);"
+                                      "return T(0.5) * (a * a + b * b);", shape=(rows, cols))
+
+    A per-node term goes to the cell that starts at the node; on an open axis the last layer of cells picks up the nodes no
+    cell starts at (if (!(periodic & 1) && col + 2 == cols) ...), on a periodic axis there is nothing to pick up.  Everything
+    else as for a GridObjective; usable wherever one is, refused where one is."""
+    _NAME = "PeriodicGridObjective"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_grid_periodic", "lbfgsx_objective_source_grid_periodic"
+
+    def __init__(self, body, shape, periodic=(True, True), data=(), scalars=()):
+        try:
+            rows, cols = (int(v) for v in shape)
+        except (TypeError, ValueError):
+            raise ValueError("PeriodicGridObjective: shape must be (rows, cols)") from None
+        if rows < 2 or cols < 2:
+            raise ValueError("PeriodicGridObjective: shape = (%d, %d): a grid has at least 2 rows and 2 columns" % (rows, cols))
+        self.shape = (rows, cols)
+        self.periodic = _periodic_mask(self._NAME, periodic, ("rows", "cols"))
+        self.body, self.K = str(body), 4
+        self._h = {}
+        self.set_data(*data)
+        self.set_scalars(*scalars)
+
+    def _form_args(self):
+        return ()
+
+    def _check_n(self, n):
+        if self.shape[0] * self.shape[1] != n:
+            raise ValueError("PeriodicGridObjective: shape = (%d, %d) does not multiply to n = %d" % (self.shape + (n,)))
+
+
+class PeriodicVolumeObjective(TermObjective):
+    """A VolumeObjective with wrap-around cells: periodic = (slabs, rows, cols) says which directions wrap.  Cell (s, r, c) has
+    the corners x[4*ds + 2*dr + dc] = x[s+ds, r+dr, c+dc] with + modulo the extent and exists iff, per axis, its origin is not
+    in the last layer or the axis wraps; with no axis periodic this is a VolumeObjective.  The body sees what a
+    VolumeObjective's sees, plus const int64_t j[8], the flat indices of its eight corners (j[0] == i), and int periodic (bit
+    0: columns, bit 1: rows, bit 2: slabs); it reads data as p0[j[k]].  The gradient's order is the VolumeObjective's, with
+    wrapped indices.  Everything else as for a VolumeObjective; usable wherever one is, refused where one is."""
+    _NAME = "PeriodicVolumeObjective"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_volume_periodic", "lbfgsx_objective_source_volume_periodic"
+
+    def __init__(self, body, shape, periodic=(True, True, True), data=(), scalars=()):
+        try:
+            slabs, rows, cols = (int(v) for v in shape)
+        except (TypeError, ValueError):
+            raise ValueError("PeriodicVolumeObjective: shape must be (slabs, rows, cols)") from None
+        if slabs < 2 or rows < 2 or cols < 2:
+            raise ValueError("PeriodicVolumeObjective: shape = (%d, %d, %d): a volume has at least 2 slabs, 2 rows and 2 columns"
+                             % (slabs, rows, cols))
+        self.shape = (slabs, rows, cols)
+        self.periodic = _periodic_mask(self._NAME, periodic, ("slabs", "rows", "cols"))
+        self.body, self.K = str(body), 8
+        self._h = {}
+        self.set_data(*data)
+        self.set_scalars(*scalars)
+
+    def _form_args(self):
+        return ()
+
+    def _check_n(self, n):
+        if self.shape[0] * self.shape[1] * self.shape[2] != n:
+            raise ValueError("PeriodicVolumeObjective: shape = (%d, %d, %d) does not multiply to n = %d" % (self.shape + (n,)))
 
 
 def _is_torch(x):
@@ -946,6 +1035,10 @@ class _SolverBase:
             rc = self._sol.lbfgsx_solver_minimize_graph(self._h, h, n, f.E, f.ei.ctypes.data_as(C.POINTER(C.c_int32)),
                                                         f.ej.ctypes.data_as(C.POINTER(C.c_int32)), 0, tail[0], mask,
                                                         C.byref(counts), *tail[2:])
+        elif isinstance(f, PeriodicVolumeObjective):
+            rc = self._sol.lbfgsx_solver_minimize_volume_periodic(self._h, h, f.shape[0], f.shape[1], f.shape[2], f.periodic, *tail)
+        elif isinstance(f, PeriodicGridObjective):
+            rc = self._sol.lbfgsx_solver_minimize_grid_periodic(self._h, h, f.shape[0], f.shape[1], f.periodic, *tail)
         elif isinstance(f, VolumeObjective):
             rc = self._sol.lbfgsx_solver_minimize_volume(self._h, h, f.shape[0], f.shape[1], f.shape[2], *tail)
         elif isinstance(f, GridObjective):
@@ -970,7 +1063,8 @@ class _SolverBase:
             return self._minimize_obj(f, n, x, lb, ub, trace)
         if not hasattr(f, "objective"):
             raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body), "
-                            "GridObjective(body, shape), VolumeObjective(body, shape), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim), "
+                            "GridObjective(body, shape), VolumeObjective(body, shape), PeriodicGridObjective(body, shape, periodic), "
+                            "PeriodicVolumeObjective(body, shape, periodic), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim), "
                             "LinearObjective(row_body, matrix, n), GraphLinearObjective(row_body, matrix, edges, edge_body, n), "
                             "MultiLinearObjective(row_body, matrix, features, outputs), "
                             "DenseLinearObjective(row_body, matrix, outputs) or DeviceObjective(fn)")

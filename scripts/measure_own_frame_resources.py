@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Registers, scratch and occupancy of the kernels on the two kernel frames -- own_frame.cuh: graph, mesh and linear-model
-(sparse, multi-output, dense); halo_frame.cuh: chain, grid and volume -- in two trees, side by side
+(sparse, multi-output, dense); halo_frame.cuh: chain, grid, volume and the two periodic forms -- in two trees, side by side
 (profiles/own_frame_kernel_resources.tsv).  No GPU is needed: the generated sources are compiled for gfx950 here.
 
 Each tree (a built checkout: the parent commit's and this one) is asked, in a process of its own, for the generated
@@ -8,6 +8,7 @@ translation unit -- source() -- of
     chain    ASYM2, ASYM3, CHAINED_ROSEN, SECOND_DIFF at their K                 (tests/chain_ref.py)
     grid     ASYM4, ALLENCAHN                                                  (tests/grid_ref.py)
     volume   ASYM8, ALLENCAHN3                                                 (tests/volume_ref.py)
+    pgrid    PASYM4, ALLENCAHN; pvolume  PASYM8, ALLENCAHN3                     (tests/periodic_ref.py)
     graph    ASYM_EDGE with and without NODE                                   (tests/graph_ref.py)
     mesh     every (K, D) with the bodies tests/test_mesh_objective_cpu.py compiles (tests/mesh_ref.py)
     linear   LOGISTIC with and without RIDGE                                   (tests/linear_ref.py)
@@ -64,6 +65,12 @@ def emit_sources(tree):
             import volume_ref as VR
             for name, body in (("asym8", VR.ASYM8), ("allencahn3", VR.ALLENCAHN3)):
                 out["volume/%s/%s" % (name, dname)] = A.VolumeObjective(body, shape=(2, 2, 2)).source(dtype)
+        if hasattr(A, "PeriodicGridObjective"):
+            import periodic_ref as PR
+            for name, body in (("pasym4", PR.PASYM4), ("allencahn", PR.ALLENCAHN)):
+                out["pgrid/%s/%s" % (name, dname)] = A.PeriodicGridObjective(body, shape=(2, 2)).source(dtype)
+            for name, body in (("pasym8", PR.PASYM8), ("allencahn3", PR.ALLENCAHN3)):
+                out["pvolume/%s/%s" % (name, dname)] = A.PeriodicVolumeObjective(body, shape=(2, 2, 2)).source(dtype)
         for name, node in (("asym+node", GR.NODE), ("asym", None)):
             out["graph/%s/%s" % (name, dname)] = A.GraphObjective(GR.ASYM_EDGE, edges=one_edge, node_body=node).source(dtype)
         for K in (2, 3, 4):
@@ -135,7 +142,7 @@ def main():
     res = {(c, k): next(done) for c in cases for k in ("parent", "head") if c in srcs[k]}
     bad = []
     with open(args.out, "w") as f:
-        f.write("# VGPRs, scratch bytes per lane and occupancy (waves per SIMD) of every chain, grid, volume, graph, mesh and\n"
+        f.write("# VGPRs, scratch bytes per lane and occupancy (waves per SIMD) of every chain, grid, volume, periodic, graph, mesh and\n"
                 "# linear-model kernel, from the compiler's kernel-resource-usage remarks: the parent commit and this tree's kernels\n"
                 "# on own_frame.cuh and halo_frame.cuh, side by side; - where the parent has no such form\n"
                 "# (scripts/measure_own_frame_resources.py; case = form/bodies/dtype)\n")
