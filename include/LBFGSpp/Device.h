@@ -108,6 +108,7 @@ class TermObjective
     bool m_volume = false;
     bool m_wraps = false;                 // a PeriodicGridObjective or PeriodicVolumeObjective: bound with the mask below
     int m_periodic = 0;
+    bool m_field = false;                 // a GridFieldObjective: shape and mask, D unknowns per node (the handle's D)
     std::int64_t m_E = 0;                 // a GraphObjective's edges; 0: the handle is bound without any
     const std::int32_t *m_ei = nullptr, *m_ej = nullptr;
     bool m_edges_dev = false;
@@ -148,6 +149,7 @@ protected:
                        : (form == LBFGSX_FORM_LINEAR)  ? lbfgsx_objective_compile_linear(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_MESH)  ? lbfgsx_objective_compile_mesh(&m_h, dt, K, D, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRAPH) ? lbfgsx_objective_compile_graph(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
+                       : (form == LBFGSX_FORM_GRID_FIELD) ? lbfgsx_objective_compile_grid_field(&m_h, dt, D, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_VOLUME_PERIODIC) ? lbfgsx_objective_compile_volume_periodic(&m_h, dt, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRID_PERIODIC) ? lbfgsx_objective_compile_grid_periodic(&m_h, dt, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_VOLUME) ? lbfgsx_objective_compile_volume(&m_h, dt, body.c_str(), log.data(), log.size())
@@ -177,6 +179,7 @@ protected:
         m_wraps = true;
         m_periodic = mask;
     }
+    void set_field() { m_field = true; }
     void set_elements(std::int64_t E, const std::int32_t* elems, bool on_device)
     {
         m_E = E;
@@ -279,6 +282,8 @@ public:
             detail::check(lbfgsx_objective_bind_mesh(c, m_h, m_E, m_elems, m_edges_dev ? 1 : 0, p, m_c, &id));
         else if (m_E || m_ei || m_ej)
             detail::check(lbfgsx_objective_bind_graph(c, m_h, m_E, m_ei, m_ej, m_edges_dev ? 1 : 0, p, m_c, &id));
+        else if (m_field)
+            detail::check(lbfgsx_objective_bind_grid_field(c, m_h, m_rows, m_cols, m_periodic, p, m_c, &id));
         else if (m_volume && m_wraps)
             detail::check(lbfgsx_objective_bind_volume_periodic(c, m_h, m_slabs, m_rows, m_cols, m_periodic, p, m_c, &id));
         else if (m_wraps)
@@ -378,6 +383,34 @@ public:
     {
         this->set_shape(rows, cols);
         this->set_periodic(periodic);
+    }
+};
+
+// A PeriodicGridObjective whose nodes carry D = 1, 2 or 3 unknowns (include/lbfgsx.h, "grid field objectives"): x is node-major,
+// x[(r*cols + c)*D + d], n = rows*cols*D; periodic is the PeriodicGridObjective's mask, 0 = open.  The body is the text of one
+// cell and sees T, constexpr int D, const T x[4*D] and T g[4*D] (x[k*D + d]: unknown d of corner k), int64_t i, row, col and
+// const int64_t j[4] (NODE indices, j[0] == i; the flat coordinate of x[k*D + d] is j[k]*D + d), rows, cols, periodic, p0..p3
+// and c[8].  At D = 1 the text of a PeriodicGridObjective compiles unchanged.
+// Accepted and refused where a PeriodicGridObjective is; D outside 1 .. 3 throws std::invalid_argument at construction, a mask
+// outside 0 .. 3 or a shape that does not multiply to n at minimize(), the values named.
+template <typename Scalar>
+class GridFieldObjective : public TermObjective<Scalar>
+{
+public:
+    GridFieldObjective(std::int64_t rows, std::int64_t cols, int D, int periodic, const std::string& body)
+        : TermObjective<Scalar>(LBFGSX_FORM_GRID_FIELD, 4, body, "GridFieldObjective: ", std::string(), D)
+    {
+        this->set_shape(rows, cols);
+        this->set_periodic(periodic);
+        this->set_field();
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile_grid_field); it stays the caller's
+    GridFieldObjective(const lbfgsx_objective* compiled, std::int64_t rows, std::int64_t cols, int periodic)
+        : TermObjective<Scalar>(compiled)
+    {
+        this->set_shape(rows, cols);
+        this->set_periodic(periodic);
+        this->set_field();
     }
 };
 
@@ -584,6 +617,7 @@ struct is_compiled_objective
                                   std::is_same<F, VolumeObjective<Scalar> >::value ||
                                   std::is_same<F, PeriodicGridObjective<Scalar> >::value ||
                                   std::is_same<F, PeriodicVolumeObjective<Scalar> >::value ||
+                                  std::is_same<F, GridFieldObjective<Scalar> >::value ||
                                   std::is_same<F, MeshObjective<Scalar> >::value || std::is_same<F, LinearObjective<Scalar> >::value ||
                                   std::is_same<F, MultiLinearObjective<Scalar> >::value ||
                                   std::is_same<F, GraphLinearObjective<Scalar> >::value ||

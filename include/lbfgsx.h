@@ -217,7 +217,7 @@ int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4]);
  * asm and the line numbers are those of lbfgsx_objective_compile. */
 enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2, LBFGSX_FORM_GRAPH = 3, LBFGSX_FORM_MESH = 4, LBFGSX_FORM_LINEAR = 5,
        LBFGSX_FORM_LINEAR_MULTI = 6, LBFGSX_FORM_DENSE = 7, LBFGSX_FORM_LINEAR_GRAPH = 8, LBFGSX_FORM_VOLUME = 9,
-       LBFGSX_FORM_GRID_PERIODIC = 10, LBFGSX_FORM_VOLUME_PERIODIC = 11 };
+       LBFGSX_FORM_GRID_PERIODIC = 10, LBFGSX_FORM_VOLUME_PERIODIC = 11, LBFGSX_FORM_GRID_FIELD = 12 };
 int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len);
 long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char* out, size_t len);
 int lbfgsx_objective_form(const lbfgsx_objective* obj);
@@ -328,6 +328,39 @@ long long lbfgsx_objective_source_volume_periodic(int dtype, const char* body, c
 int lbfgsx_objective_bind_volume_periodic(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
                                           int periodic, const void* const p[4], const double cs[8], int* id);
 int lbfgsx_objective_periodic(const lbfgsx_ctx* c, int* mask);
+/* ---- grid field objectives: D unknowns per node of a grid ---------------------------------------------------------------------
+ * The periodic grid form with nodes that carry D = 1, 2 or 3 unknowns: complex Ginzburg-Landau lattices (2), micromagnetic and
+ * Heisenberg films (3), optical flow and 2-D elasticity (2), colour and multi-channel image models with vectorial TV (3),
+ * multi-phase fields.
+ *   Layout.  x is node-major, as for a mesh objective: x[(r*cols + c)*D + d] is unknown d of node (r, c); n = rows*cols*D,
+ *     rows >= 2, cols >= 2.
+ *   Mask.  `periodic` is the periodic grid form's: bit 0 the column direction, bit 1 the row direction, 0 = open.  Cell
+ *     existence and the wrapped corners are exactly those of "periodic grid and volume objectives" above.
+ *   Body.  The text of one cell; the generated method is
+ *       T term(const T (&x)[4 * D], T (&g)[4 * D], int64_t i, int64_t row, int64_t col, const int64_t (&j)[4]) const
+ *     x and g are slot-major like the mesh form's: x[k*D + d] is unknown d of corner k, in the grid form's corner order.  i is
+ *     the NODE index of corner 0 and j[k] are the node indices of the corners, j[0] == i; the flat coordinate of unknown d of
+ *     corner k is j[k]*D + d (data per coordinate: p0[j[k]*D + d]; data per node: p0[j[k]]).  The body also sees constexpr int D,
+ *     rows, cols, periodic, p0..p3 and c[8].  At D = 1 this is the periodic grid form's signature: one text compiles in both.
+ *   Gradient.  For every d, grad[(r,c), d] = g[3*D+d] of cell (r(-)1, c(-)1) + g[2*D+d] of (r(-)1, c) + g[D+d] of (r, c(-)1) +
+ *     g[d] of (r, c): the cells that exist, in this fixed order, started from the first (no leading 0 +); (-) wraps on a
+ *     periodic axis.
+ *   f = the order-independent (compensated) sum of the existing cells' values, each added once, by the owner of the cell's
+ *     origin.  One rounding per source operation, no contraction, no floating-point atomic.  In the trial kernels every corner
+ *     value is xp + step*d, never a read of the x the launch writes.  No index outside [0, n) is loaded.
+ * lbfgsx_objective_compile_grid_field wraps the body for the four kernels of csrc/grid_field_kernels.cuh (same arguments, grids
+ * and reductions as the periodic grid form's; a thread owns W = 16/sizeof(T) nodes, D aligned 16-byte packs) and caches by
+ * (form, body, dtype, D): the shape and the mask are not part of the key.  The form is LBFGSX_FORM_GRID_FIELD.  D outside
+ * 1 .. 3 is refused ("D = # is not supported: a node has D = 1, 2 or 3 unknowns").  lbfgsx_objective_bind_grid_field refuses
+ * (LBFGSX_E_INVALID, the values named) a handle of another form, an extent < 2, rows*cols*D that is not n or overflows, and a
+ * mask with bits above 3; every other bind call refuses this handle, lbfgsx_objective_bind saying that it is bound with its
+ * shape, mask and D.  lbfgsx_objective_shape and lbfgsx_objective_periodic read the bound shape and mask back,
+ * lbfgsx_objective_D the handle's D; lbfgsx_objective_K is 4. */
+int lbfgsx_objective_compile_grid_field(lbfgsx_objective** out, int dtype, int D, const char* body, char* log, size_t log_len);
+long long lbfgsx_objective_source_grid_field(int dtype, int D, const char* body, char* out, size_t len);
+int lbfgsx_objective_bind_grid_field(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                     const void* const p[4], const double cs[8], int* id);
+int lbfgsx_objective_D(const lbfgsx_objective* obj);
 /* ---- graph objectives: edge terms over an index list ---------------------------------------------------------------------
  * x has n coordinates, the NODES; the caller gives E edges as two int32 arrays ei[E], ej[E], and
  *     f(x) = sum over nodes v of psi(x[v]; v)  +  sum over edges e of phi(x[ei[e]], x[ej[e]]; e)

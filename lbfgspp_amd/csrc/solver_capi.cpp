@@ -56,10 +56,11 @@ struct lbfgsx_solver
         int64_t lda = 0;
     };
     // rows, cols: the shape of a grid objective, with slabs of a volume objective, 0 for the other forms; gr: null for every form but a graph objective;
-    // periodic: the mask of a periodic grid or volume objective, -1 for the other forms
+    // periodic: the mask of a periodic grid or volume objective or of a grid field objective, -1 for the other forms; field: a grid
+    // field objective
     virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t slabs, int64_t rows, int64_t cols, const GraphSpec* gr,
                               const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
-                              lbfgsx_trace* tr, lbfgsx_result* out, int periodic = -1) = 0;
+                              lbfgsx_trace* tr, lbfgsx_result* out, int periodic = -1, bool field = false) = 0;
 };
 
 namespace {
@@ -230,12 +231,13 @@ struct LbfgsImpl : lbfgsx_solver
     }
     void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t slabs, int64_t rows, int64_t cols, const GraphSpec* gr,
                       const void* const p[4], int host_mask, const double c[8], void* x, const void*, const void*,
-                      lbfgsx_trace* tr, lbfgsx_result* out, int periodic) override
+                      lbfgsx_trace* tr, lbfgsx_result* out, int periodic, bool field) override
     {
         GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
         VolumeObjective<Scalar> spaced(obj, slabs, rows, cols);  // binds with three extents when there are three
         PeriodicGridObjective<Scalar> wrapped(obj, rows, cols, periodic);            // binds with the mask when there is one (>= 0)
         PeriodicVolumeObjective<Scalar> wrapped3(obj, slabs, rows, cols, periodic);  // ... and three extents
+        GridFieldObjective<Scalar> fielded(obj, rows, cols, periodic);               // ... and D unknowns per node
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
         LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
@@ -258,6 +260,7 @@ struct LbfgsImpl : lbfgsx_solver
                                    : (gr && gr->rowptr) ? static_cast<TermObjective<Scalar>&>(lined)
                                    : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
                                    : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
+                                   : field             ? static_cast<TermObjective<Scalar>&>(fielded)
                                    : (periodic >= 0 && slabs) ? static_cast<TermObjective<Scalar>&>(wrapped3)
                                    : (periodic >= 0)   ? static_cast<TermObjective<Scalar>&>(wrapped)
                                    : slabs             ? static_cast<TermObjective<Scalar>&>(spaced)
@@ -367,12 +370,13 @@ struct LbfgsbImpl : lbfgsx_solver
     }
     void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t slabs, int64_t rows, int64_t cols, const GraphSpec* gr,
                       const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
-                      lbfgsx_trace* tr, lbfgsx_result* out, int periodic) override
+                      lbfgsx_trace* tr, lbfgsx_result* out, int periodic, bool field) override
     {
         GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
         VolumeObjective<Scalar> spaced(obj, slabs, rows, cols);  // binds with three extents when there are three
         PeriodicGridObjective<Scalar> wrapped(obj, rows, cols, periodic);            // binds with the mask when there is one (>= 0)
         PeriodicVolumeObjective<Scalar> wrapped3(obj, slabs, rows, cols, periodic);  // ... and three extents
+        GridFieldObjective<Scalar> fielded(obj, rows, cols, periodic);               // ... and D unknowns per node
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
         LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
@@ -395,6 +399,7 @@ struct LbfgsbImpl : lbfgsx_solver
                                    : (gr && gr->rowptr) ? static_cast<TermObjective<Scalar>&>(lined)
                                    : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
                                    : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
+                                   : field             ? static_cast<TermObjective<Scalar>&>(fielded)
                                    : (periodic >= 0 && slabs) ? static_cast<TermObjective<Scalar>&>(wrapped3)
                                    : (periodic >= 0)   ? static_cast<TermObjective<Scalar>&>(wrapped)
                                    : slabs             ? static_cast<TermObjective<Scalar>&>(spaced)
@@ -985,6 +990,8 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
             throw std::invalid_argument("a periodic grid objective is minimised with its shape and mask: lbfgsx_solver_minimize_grid_periodic");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_VOLUME_PERIODIC)
             throw std::invalid_argument("a periodic volume objective is minimised with its shape and mask: lbfgsx_solver_minimize_volume_periodic");
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID_FIELD)
+            throw std::invalid_argument("a grid field objective is minimised with its shape and mask: lbfgsx_solver_minimize_grid_field");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRAPH)
             throw std::invalid_argument("a graph objective is minimised with its edges: lbfgsx_solver_minimize_graph");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_MESH)
@@ -1116,6 +1123,45 @@ int lbfgsx_solver_minimize_grid_periodic(lbfgsx_solver* s, const lbfgsx_objectiv
     }
     return guarded(out,
                    [&]() { s->minimize_obj(obj, int64_t(n), 0, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out, periodic); });
+}
+
+int lbfgsx_solver_minimize_grid_field(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                      const void* const p[4], int host_mask, const double c[8], void* x, const void* lb,
+                                      const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    long long n = 0;
+    const int bad = guarded(out, [&]() {
+        if (!s || !obj)
+            throw std::invalid_argument("lbfgsx_solver_minimize_grid_field: invalid argument");
+        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_GRID_FIELD)
+            throw std::invalid_argument("lbfgsx_solver_minimize_grid_field: the handle is not a grid field objective "
+                                        "(lbfgsx_objective_compile_grid_field)");
+        if (lbfgsx_objective_dtype(obj) != s->dtype)
+            throw std::invalid_argument("lbfgsx_solver_minimize_grid_field: the objective was compiled for the other dtype");
+        const int D = lbfgsx_objective_D(obj);
+        const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols) + ", D = " + std::to_string(D);
+        if (rows < 2 || cols < 2)
+            throw std::invalid_argument("grid field objective: " + shape +
+                                        ": a grid has at least 2 rows and 2 columns (rows >= 2, cols >= 2)");
+        if (__builtin_mul_overflow((long long) rows, (long long) cols, &n) || __builtin_mul_overflow(n, (long long) D, &n))
+            throw std::invalid_argument("grid field objective: " + shape + ": rows*cols*D overflows");
+        if (periodic < 0 || periodic > 3)
+            throw std::invalid_argument("grid field objective: periodic = " + std::to_string(periodic) +
+                                        ": the mask has bit 0 for the column direction and bit 1 for the row direction (0 .. 3)");
+    });
+    if (bad)
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg),
+                      "lbfgsx_solver_minimize_grid_field: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    return guarded(out, [&]() {
+        s->minimize_obj(obj, int64_t(n), 0, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out, periodic, true);
+    });
 }
 
 int lbfgsx_solver_minimize_volume_periodic(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,

@@ -8,7 +8,8 @@ Exceptions: std::invalid_argument -> ValueError, std::logic_error -> ArithmeticE
 std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device objective
 (`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`), the caller's own term compiled into the same kernels (`TermObjective(body)`,
 `ChainObjective(body)` for terms that overlap, `GridObjective(body, shape)` for 2x2-cell terms on a grid, `VolumeObjective(body, shape)` for 2x2x2-cell terms on a 3-D array,
-`PeriodicGridObjective(body, shape, periodic)` and `PeriodicVolumeObjective(body, shape, periodic)` for those two with wrap-around cells, or
+`PeriodicGridObjective(body, shape, periodic)` and `PeriodicVolumeObjective(body, shape, periodic)` for those two with wrap-around cells,
+`GridFieldObjective(body, shape, D, periodic)` for a grid whose nodes carry D unknowns, or
 `GraphObjective(edge_body, edges)` for edge terms over an index list,
 `MeshObjective(elem_body, elements, dim)` for K-node elements with vector unknowns, or
 `LinearObjective(row_body, (rowptr, col, val), n)` for a linear model over a sparse matrix, or
@@ -410,6 +411,48 @@ class PeriodicVolumeObjective(TermObjective):
     def _check_n(self, n):
         if self.shape[0] * self.shape[1] * self.shape[2] != n:
             raise ValueError("PeriodicVolumeObjective: shape = (%d, %d, %d) does not multiply to n = %d" % (self.shape + (n,)))
+
+
+class GridFieldObjective(TermObjective):
+    """A PeriodicGridObjective whose nodes carry D = 1, 2 or 3 unknowns (include/lbfgsx.h, "grid field objectives"): complex
+    Ginzburg-Landau lattices, Heisenberg films, optical flow and 2-D elasticity, multi-channel image models.  x is node-major,
+    x[(r*cols + c)*D + d], n = rows*cols*D; periodic = (rows, cols) says which directions wrap, (False, False) is the open
+    grid.  The body is the text of one cell and sees T, constexpr int D, const T x[4*D] and T g[4*D] (x[k*D + d]: unknown d of
+    corner k, the corners in a GridObjective's order), int64_t i, row, col, const int64_t j[4] (the NODE indices of the
+    corners, j[0] == i: the flat coordinate of x[k*D + d] is j[k]*D + d), rows, cols, int periodic, p0..p3 and c[8].  For every
+    d, grad[(r,c), d] is g[3*D+d] of cell (r-1,c-1) + g[2*D+d] of (r-1,c) + g[D+d] of (r,c-1) + g[d] of (r,c) with - modulo the
+    extent on a periodic axis, those that exist, in this order.  At D = 1 the text of a PeriodicGridObjective compiles unchanged.
+
+        gl = GridFieldObjective("T v = T(0); for (int d = 0; d < D; d++) { const T a = x[D + d] - x[d], b = x[2 * D + d] - x[d];"
+                                " g[d] = T(0) - a - b; g[D + d] = a; g[2 * D + d] = b; g[3 * D + d] = T(0);"
+                                " v += T(0.5) * (a * a + b * b); } return v;", shape=(rows, cols), D=2, periodic=(True, True))
+
+    Everything else as for a PeriodicGridObjective; usable wherever one is, refused where one is."""
+    _NAME = "GridFieldObjective"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_grid_field", "lbfgsx_objective_source_grid_field"
+
+    def __init__(self, body, shape, D, periodic=(False, False), data=(), scalars=()):
+        try:
+            rows, cols = (int(v) for v in shape)
+        except (TypeError, ValueError):
+            raise ValueError("GridFieldObjective: shape must be (rows, cols)") from None
+        if rows < 2 or cols < 2:
+            raise ValueError("GridFieldObjective: shape = (%d, %d): a grid has at least 2 rows and 2 columns" % (rows, cols))
+        if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or D not in (1, 2, 3):
+            raise ValueError("GridFieldObjective: D = %r is not supported: a node has D = 1, 2 or 3 unknowns" % (D,))
+        self.shape, self.D = (rows, cols), int(D)
+        self.periodic = _periodic_mask(self._NAME, periodic, ("rows", "cols"))
+        self.body, self.K = str(body), 4
+        self._h = {}
+        self.set_data(*data)
+        self.set_scalars(*scalars)
+
+    def _form_args(self):
+        return (self.D,)
+
+    def _check_n(self, n):
+        if self.shape[0] * self.shape[1] * self.D != n:
+            raise ValueError("GridFieldObjective: shape = (%d, %d), D = %d does not multiply to n = %d" % (self.shape + (self.D, n)))
 
 
 def _is_torch(x):
@@ -1035,6 +1078,8 @@ class _SolverBase:
             rc = self._sol.lbfgsx_solver_minimize_graph(self._h, h, n, f.E, f.ei.ctypes.data_as(C.POINTER(C.c_int32)),
                                                         f.ej.ctypes.data_as(C.POINTER(C.c_int32)), 0, tail[0], mask,
                                                         C.byref(counts), *tail[2:])
+        elif isinstance(f, GridFieldObjective):
+            rc = self._sol.lbfgsx_solver_minimize_grid_field(self._h, h, f.shape[0], f.shape[1], f.periodic, *tail)
         elif isinstance(f, PeriodicVolumeObjective):
             rc = self._sol.lbfgsx_solver_minimize_volume_periodic(self._h, h, f.shape[0], f.shape[1], f.shape[2], f.periodic, *tail)
         elif isinstance(f, PeriodicGridObjective):
@@ -1064,7 +1109,7 @@ class _SolverBase:
         if not hasattr(f, "objective"):
             raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body), "
                             "GridObjective(body, shape), VolumeObjective(body, shape), PeriodicGridObjective(body, shape, periodic), "
-                            "PeriodicVolumeObjective(body, shape, periodic), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim), "
+                            "PeriodicVolumeObjective(body, shape, periodic), GridFieldObjective(body, shape, D, periodic), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim), "
                             "LinearObjective(row_body, matrix, n), GraphLinearObjective(row_body, matrix, edges, edge_body, n), "
                             "MultiLinearObjective(row_body, matrix, features, outputs), "
                             "DenseLinearObjective(row_body, matrix, outputs) or DeviceObjective(fn)")

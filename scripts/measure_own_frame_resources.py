@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Registers, scratch and occupancy of the kernels on the two kernel frames -- own_frame.cuh: graph, mesh and linear-model
-(sparse, multi-output, dense); halo_frame.cuh: chain, grid, volume and the two periodic forms -- in two trees, side by side
+(sparse, multi-output, dense); halo_frame.cuh: chain, grid, volume, the two periodic forms and the grid field form -- in two trees, side by side
 (profiles/own_frame_kernel_resources.tsv).  No GPU is needed: the generated sources are compiled for gfx950 here.
 
 Each tree (a built checkout: the parent commit's and this one) is asked, in a process of its own, for the generated
@@ -9,6 +9,7 @@ translation unit -- source() -- of
     grid     ASYM4, ALLENCAHN                                                  (tests/grid_ref.py)
     volume   ASYM8, ALLENCAHN3                                                 (tests/volume_ref.py)
     pgrid    PASYM4, ALLENCAHN; pvolume  PASYM8, ALLENCAHN3                     (tests/periodic_ref.py)
+    gfield   FASYM, GL at D = 1, 2, 3                                          (tests/field_ref.py)
     graph    ASYM_EDGE with and without NODE                                   (tests/graph_ref.py)
     mesh     every (K, D) with the bodies tests/test_mesh_objective_cpu.py compiles (tests/mesh_ref.py)
     linear   LOGISTIC with and without RIDGE                                   (tests/linear_ref.py)
@@ -71,6 +72,11 @@ def emit_sources(tree):
                 out["pgrid/%s/%s" % (name, dname)] = A.PeriodicGridObjective(body, shape=(2, 2)).source(dtype)
             for name, body in (("pasym8", PR.PASYM8), ("allencahn3", PR.ALLENCAHN3)):
                 out["pvolume/%s/%s" % (name, dname)] = A.PeriodicVolumeObjective(body, shape=(2, 2, 2)).source(dtype)
+        if hasattr(A, "GridFieldObjective"):
+            import field_ref as FR
+            for D in (1, 2, 3):
+                for name, body in (("fasym", FR.FASYM), ("gl", FR.GL)):
+                    out["gfield/D%d/%s/%s" % (D, name, dname)] = A.GridFieldObjective(body, shape=(2, 2), D=D).source(dtype)
         for name, node in (("asym+node", GR.NODE), ("asym", None)):
             out["graph/%s/%s" % (name, dname)] = A.GraphObjective(GR.ASYM_EDGE, edges=one_edge, node_body=node).source(dtype)
         for K in (2, 3, 4):
