@@ -882,7 +882,7 @@ int lbfgsx_b_sub_check(lbfgsx_ctx* c, int64_t counts[4]);
 int lbfgsx_b_sub_sweep_begin(lbfgsx_ctx* c, int first, int64_t* nL, int64_t* nU, int64_t* nP, int64_t counts[4]);
 /* lbfgsx_b_wtv(LBFGSX_VS_LBOUND, LBFGSX_ST_L) and lbfgsx_b_wtv(LBFGSX_VS_UBOUND, LBFGSX_ST_U) -- the inner products of the two
  * apply_PtBQv statements of a BOXCQP sweep (SubspaceMin.h:236-241, BFGSMat.h:570-594) -- in one launch over the index list of
- * L u U.  LBFGSX_E_INVALID when there is no list or 2c > 24: call lbfgsx_b_wtv per set. */
+ * L u U.  LBFGSX_E_INVALID when there is no list or 2c is outside 1..80 (LBFGSX_SPLIT=0: 1..24): call lbfgsx_b_wtv per set. */
 int lbfgsx_b_wtv_lu(lbfgsx_ctx* c, double* out_l, int64_t* nnz_l, double* out_u, int64_t* nnz_u);
 /* the same, plus negc_dd[2 k], [2 k + 1] = the un-rounded (hi, lo) sum of column k of W_{L u U}'(-c) (c = vecc of
  * SubspaceMin.h on the rows of L u U); negc_dd[0] = NaN when this context cannot deliver it (LBFGSX_RHS_IDENTITY=0, no
@@ -977,6 +977,17 @@ int lbfgsx_b_lu_sweep(lbfgsx_ctx* c, const double* coef, double theta, int64_t s
 int lbfgsx_b_sub_op(lbfgsx_ctx* c, int op);
 /* copy the per-coordinate state byte (LBFGSX_ST_* bits) to the host: n bytes */
 int lbfgsx_b_download_state(lbfgsx_ctx* c, unsigned char* host);
+/* Inspection entries (tests/test_subspace_statements_gpu.py): copy one vector of the subspace minimisation -- n elements of
+ * the context's scalar type -- to or from the host.  Like any other entry of the bounded path they first put live compact
+ * vectors back at their rows.  LBFGSX_E_INVALID for an unknown selector, a null pointer or a context that is not bounded. */
+enum { LBFGSX_SV_CF = 0, LBFGSX_SV_Y = 1, LBFGSX_SV_YFB = 2, LBFGSX_SV_LAM = 3, LBFGSX_SV_MU = 4, LBFGSX_SV_RHS = 5 };
+int lbfgsx_b_sub_download(lbfgsx_ctx* c, int which, void* host);
+int lbfgsx_b_sub_upload(lbfgsx_ctx* c, int which, const void* host);
+/* the current index list of L u U (rows in arrival order): *count entries copied to rows[0..cap); *count = -1 and nothing
+ * copied when the context holds no valid list; LBFGSX_E_INVALID when cap is too small.  Changes nothing: the list, a pending
+ * lbfgsx_b_lu_sweep and live compact vectors stay as they are, so it may be called between lbfgsx_b_solve_sweep(first = 0)
+ * and lbfgsx_b_lu_sweep. */
+int lbfgsx_b_lu_list_download(lbfgsx_ctx* c, int* rows, int64_t cap, int64_t* count);
 /* drt.dot(g) (SubspaceMin.h:281,289) */
 int lbfgsx_b_dot_drt_g(lbfgsx_ctx* c, double* dg);
 /* drt = xcp - x [, drt.normalize()]  (LBFGSB.h:163-164,191) */

@@ -549,4 +549,72 @@ int lbfgsx_b_download_state(lbfgsx_ctx* c, unsigned char* host)
     return LBFGSX_OK;
 }
 
+// ---- inspection entries: the vectors of the subspace minimisation and the index list of L u U
+static void* sub_vector(lbfgsb_state* b, int which)
+{
+    switch (which)
+    {
+    case LBFGSX_SV_CF: return b->cF;
+    case LBFGSX_SV_Y: return b->y;
+    case LBFGSX_SV_YFB: return b->yfb;
+    case LBFGSX_SV_LAM: return b->lam;
+    case LBFGSX_SV_MU: return b->mu;
+    case LBFGSX_SV_RHS: return b->rhs;
+    default: return nullptr;
+    }
+}
+static int sub_copy(lbfgsx_ctx* c, int which, void* host, bool up)
+{
+    if (!c || !c->bstate || !host || !sub_vector(c->bstate, which))
+    {
+        set_error("lbfgsx_b_sub_download / _upload: needs a bounded context, a LBFGSX_SV_* selector and a host pointer");
+        return LBFGSX_E_INVALID;
+    }
+    lbfgsx::DeviceGuard dev_guard_(c->device);
+    int rc = need_bounded(c);  // live compact vectors are put back at their rows first
+    if (rc)
+        return rc;
+    void* dev = sub_vector(c->bstate, which);
+    const size_t bytes = size_t(c->n) * c->esz;
+    if (up)
+        LBFGSX_HIP(lbfgsx::copy_async(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
+    else
+        LBFGSX_HIP(lbfgsx::copy_async(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    LBFGSX_HIP(lbfgsx::stream_sync(c->stream));
+    return LBFGSX_OK;
+}
+
+int lbfgsx_b_sub_download(lbfgsx_ctx* c, int which, void* host) { return sub_copy(c, which, host, false); }
+
+int lbfgsx_b_sub_upload(lbfgsx_ctx* c, int which, const void* host) { return sub_copy(c, which, const_cast<void*>(host), true); }
+
+int lbfgsx_b_lu_list_download(lbfgsx_ctx* c, int* rows, int64_t cap, int64_t* count)
+{
+    if (!c || !c->bstate || !count)
+    {
+        set_error("lbfgsx_b_lu_list_download: needs a bounded context and a count pointer");
+        return LBFGSX_E_INVALID;
+    }
+    // reads only: the list's flags, the pending sweep and the compact vectors stay as they are
+    const lbfgsb_state* b = c->bstate;
+    if (!b->lu_valid)
+    {
+        *count = -1;
+        return LBFGSX_OK;
+    }
+    if (cap < int64_t(b->lu_n) || (b->lu_n > 0 && !rows))
+    {
+        set_error("lbfgsx_b_lu_list_download: the list holds more rows than `cap`");
+        return LBFGSX_E_INVALID;
+    }
+    lbfgsx::DeviceGuard dev_guard_(c->device);
+    if (b->lu_n > 0)
+    {
+        LBFGSX_HIP(lbfgsx::copy_async(rows, b->lu_ptr(), sizeof(int) * size_t(b->lu_n), hipMemcpyDeviceToHost, c->stream));
+        LBFGSX_HIP(lbfgsx::stream_sync(c->stream));
+    }
+    *count = b->lu_n;
+    return LBFGSX_OK;
+}
+
 }  // extern "C"

@@ -627,6 +627,9 @@ __global__ void __launch_bounds__(kBlock, occ_sweep_x(NCL, G, FIRST))
             // a P row's multipliers are zero (the sweep that made it P stored them); the first sweep sets them
             const unsigned char s2 = sweep_row_v<T>(bw, iw, st0, yi, T(0), T(0), FIRST != 0, FIRST != 0, cnt, li, ui, x.cfi);
             app = (s2 & (ST_L | ST_U)) != 0;
+            // the pass that starts the compact vectors: a row outside P keeps its rhs (k_cv_back writes every free position back)
+            if (FIRST && cv == 1 && app)
+                bw.rhs[iw] = b.rhs[i];
         }
         if (lu_cap && !(LBFGSX_X_DBG & 256))
         {

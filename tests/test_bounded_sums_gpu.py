@@ -23,7 +23,7 @@ What is asserted per case (check_case), c = pairs stored, T = the context's scal
   lbfgsx_b_wtv              masks 0, ST_FREE, ST_NEWACT (first call right after the finish: the index list) x
                             LBFGSX_VS_DRT / _LBOUND / _UBOUND, nnz exact
   lbfgsx_b_wtv_prologue, lbfgsx_b_gram_fused_ex with LBFGSX_GP_LINEAR: coef1 NULL (v = -g) and random (numpy restatement)
-LBFGSX_GP_RHS is not tested: rhs cannot be given a known value through the ABI (bounded_sums_ref).
+LBFGSX_GP_RHS: tests/test_subspace_statements_gpu.py (test_gp_rhs), which gives rhs a known value through lbfgsx_b_sub_upload.
 
 Kernel classes by c, from the dispatch code (csrc/lbfgsb_gram.hip gram_dd_core, lbfgsb_dots.hip wtv_t / cauchy_wtd_t,
 lbfgsb_x.hip LBFGSX_XCLASS and gram_kpb); default = split-row kernels (LBFGSX_SPLIT=1), 2c columns:
@@ -59,8 +59,9 @@ lbfgsb_x.hip LBFGSX_XCLASS and gram_kpb); default = split-row kernels (LBFGSX_SP
   Carried pieces (test_carried_pieces): lbfgsx_b_gram_pairs_dd = kx_rows<.., NA = 3>, lbfgsx_b_gram_list_dd = kx_gram over
   an index list (one block finishes a list of <= 8192 rows itself).
 
-Left out for want of an observable: everything that needs the L / U / P partition (lbfgsx_b_wtv_lu*, lbfgsx_b_solve_sweep*,
-lbfgsx_b_lu_sweep, lbfgsx_b_wcombine, lbfgsx_b_solve_wty) and LBFGSX_GP_RHS."""
+Everything that needs the L / U / P partition (lbfgsx_b_wtv_lu*, lbfgsx_b_solve_sweep*, lbfgsx_b_lu_sweep, lbfgsx_b_wcombine,
+lbfgsx_b_solve_wty) and LBFGSX_GP_RHS: tests/test_subspace_statements_gpu.py (the vectors of the subspace minimisation are
+observable through lbfgsx_b_sub_download / _sub_upload)."""
 import ctypes as C
 import math
 import time
