@@ -55,6 +55,7 @@ class LBFGSSolver
     int m_nfev = 0;
     int m_x_at_throw = LBFGSX_VEC_X;  // which device vector is "x" for a caller that catches an exception of minimize()
     int m_recursion = RECURSION_VECTOR;  // extension: see set_recursion()
+    double m_dir_scale = -1.0;           // extension: see set_direction_scale()
     std::function<void(int, Scalar, DeviceState<Scalar>&)> m_trace;
     std::function<void(int)> m_iter_hook;
     std::function<void(double*, int)> m_reducer;  // extension: see set_reducer()
@@ -127,7 +128,17 @@ class LBFGSSolver
                 m_reducer(&dgd, 1);
         }
         else
-            detail::check(lbfgsx_apply_Hv(c, LBFGSX_VEC_G, -1.0, &dgd));
+            detail::check(lbfgsx_apply_Hv(c, LBFGSX_VEC_G, m_dir_scale, &dgd));
+        // grad.dot(drt) from the search's first trial (lbfgsx.h: lbfgsx_last_in_trial_request): the product then ends one step
+        // early and the first trial runs that step in its own pass.  Asked for where the search is the device form of a policy
+        // that can start without dg (LineSearchMoreThuente; the other built-in policies and every user policy get dg before
+        // their search, as always), the objective is a built-in one, the recursion the vector form and no reducer is set.
+        constexpr bool policy_defers =
+            detail::takes_pending_dg<LineSearch<Scalar> >::value &&
+            detail::has_device_line_search<LineSearch<Scalar>, detail::Evaluator<Scalar, Foo, HostVec>, LBFGSParam<Scalar>, Scalar>::value;
+        const bool defer_dg = policy_defers && !gram && !m_reducer && !detail::is_compiled_objective<Scalar, Foo>::value &&
+                              ev.builtin_id() >= 0;
+        detail::check(lbfgsx_last_in_trial_request(c, defer_dg ? 1 : 0));
         Scalar dg = Scalar(dgd);
         Scalar step = Scalar(1) / m_gnorm;
         constexpr Scalar eps = std::numeric_limits<Scalar>::epsilon();
@@ -138,7 +149,7 @@ class LBFGSSolver
             detail::Range range_iteration("lbfgs:iteration");
             detail::check(lbfgsx_ls_begin(c));
             if (!gram)  // the first trial may run the post statements of :130-161 in its own pass (lbfgsx.h)
-                detail::check(lbfgsx_ls_post_in_trial(c, -1.0));
+                detail::check(lbfgsx_ls_post_in_trial(c, m_dir_scale));
             const Scalar step_max = m_param.max_step;
             ev.trial_written = false;
             try
@@ -185,7 +196,7 @@ class LBFGSSolver
             else  // K3, with the recursion of :165 speculated on top of it in the same launch (lbfgsx.h)
             {
                 detail::Range range_post("lbfgs:post+apply_Hv");
-                detail::check(lbfgsx_post_linesearch_spec(c, -1.0, &g2, &x2, &syd, &yyd));
+                detail::check(lbfgsx_post_linesearch_spec(c, m_dir_scale, &g2, &x2, &syd, &yyd));
             }
             m_gnorm = sqrt(Scalar(g2));
             if (m_gnorm <= m_param.epsilon || m_gnorm <= m_param.epsilon_rel * sqrt(Scalar(x2)))
@@ -213,7 +224,11 @@ class LBFGSSolver
                     m_reducer(&dgd, 1);
             }
             else
-                detail::check(lbfgsx_apply_Hv(c, LBFGSX_VEC_G, -1.0, &dgd));
+            {
+                int dg_pending = 0;
+                detail::check(lbfgsx_apply_Hv_pending(c, LBFGSX_VEC_G, m_dir_scale, &dgd, defer_dg ? &dg_pending : nullptr));
+                ev.dg_pending = dg_pending != 0;
+            }
             dg = Scalar(dgd);
             step = Scalar(1);
             if (m_iter_hook)
@@ -242,6 +257,9 @@ public:
     // (f64 problems): half the history traffic again, the pairs perturbed at the 6e-8 level.  Environment
     // LBFGSX_RECURSION=gram | gram-f32h selects either at construction.
     void set_recursion(int form) { m_recursion = form; }
+    // Extension, for tests of the line searches' entry check: the directions computed from now on are a * H * grad (vector
+    // recursion).  -1 is the method; +1 gives an ascent direction, which every policy refuses.
+    void set_direction_scale(double a) { m_dir_scale = a; }
     // Extension: ROW-SHARDED run of one problem over several GPUs.  Each rank owns a contiguous
     // block of rows in its own solver / context (DeviceState of the local length; lbfgsx_set_shard for the built-in
     // data) and passes a function that sums a small array of doubles over all ranks in place (an all-reduce; RCCL

@@ -839,6 +839,30 @@ public:
         if (on_eval) on_eval(m_nfev, fx);
         m_nfev++;
     }
+    // ---- grad.dot(drt) from the first trial (lbfgsx.h: lbfgsx_last_in_trial_request).  The solver sets dg_pending when the
+    // product that precedes a search returned no grad.d; a policy whose device form knows the protocol (its constant
+    // takes_pending_dg) clears it and calls first_trial instead of trial for its first step: dg_init = grad.dot(drt) at xp comes
+    // back with fx and dg.  When dg_init >= 0 -- the entry check the policy could not make earlier -- nothing has happened as
+    // far as the caller can tell: the evaluation is not counted, no trial point is reported written (the pass wrote the trial
+    // buffer only), fx and dg are not assigned.
+    bool dg_pending = false;
+    bool first_trial(Scalar step, Scalar& fx, Scalar& dg, Scalar& dg_init)
+    {
+        double r0 = 0, r1 = 0, r2 = 0;
+        if constexpr (is_builtin)
+            check(lbfgsx_trial_first(m_s.ctx(), m_f.id, double(step), &r0, &r1, &r2));
+        else  // the solver asks for the protocol with a built-in objective only (LBFGS.h)
+            throw std::logic_error("grad.dot(drt) is pending for an objective evaluated outside the fused kernels");
+        dg_init = Scalar(r2);
+        if (dg_init >= Scalar(0))
+            return false;
+        trial_written = true;
+        fx = Scalar(r0);
+        dg = Scalar(r1);
+        if (on_eval) on_eval(m_nfev, fx);
+        m_nfev++;
+        return true;
+    }
     // ---- compatibility path of detail::run_line_search (LBFGSpp/Interop.h): a line-search policy with the reference's
     // signature drives the search on host vectors.  fx = f(x, grad) at a host point, whatever kind of objective Foo is.
     template <typename Vec>

@@ -13,9 +13,18 @@
 #define LBFGSX_DROPIN_HOST_EVAL_H
 
 #include <cstdint>
+#include <type_traits>
+#include <utility>
 
 namespace LBFGSpp {
 namespace detail {
+
+// Does the evaluator know the "grad.dot(drt) comes back with the first trial" protocol (Device.h: dg_pending, first_trial)?
+// The device evaluator does; this one always has dg when a search starts.
+template <typename Ev, typename = void>
+struct has_dg_pending : std::false_type {};
+template <typename Ev>
+struct has_dg_pending<Ev, std::void_t<decltype(std::declval<Ev&>().dg_pending)> > : std::true_type {};
 
 template <typename Scalar, typename Foo, typename Vector>
 class HostEval

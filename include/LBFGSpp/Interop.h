@@ -69,6 +69,14 @@ struct has_device_line_search<Policy, Ev, Param, Scalar,
                                                                       std::declval<Scalar&>(), std::declval<Scalar&>()))> >
     : std::true_type {};
 
+// can Policy's device form start without dg and take it from its first trial (Device.h: dg_pending, first_trial)?  A policy
+// says so with a constant takes_pending_dg = true; one without it -- a user policy, or a built-in one whose first step
+// depends on dg -- always gets dg before its search
+template <typename Policy, typename = void>
+struct takes_pending_dg : std::false_type {};
+template <typename Policy>
+struct takes_pending_dg<Policy, std::enable_if_t<Policy::takes_pending_dg> > : std::true_type {};
+
 // the objective as the reference's policies see it: Scalar f(const Vector& x, Vector& grad)
 template <typename Scalar, typename Ev, typename HostVec>
 struct HostObjective

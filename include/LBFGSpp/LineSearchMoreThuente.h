@@ -146,6 +146,14 @@ public:
         template <typename SolverParam>
         void start(const SolverParam& param, Scalar step_max, Scalar step, Scalar fx, Scalar dg)
         {
+            start_step(param, step_max, step, fx);
+            start_dg(param, dg);
+        }
+        // start() in two parts, for a caller that learns dg = phi'(0) from the pass that evaluates its first trial: the entry
+        // checks on the step and everything that does not depend on dg, which is enough to know the first step ...
+        template <typename SolverParam>
+        void start_step(const SolverParam& param, Scalar step_max, Scalar step, Scalar fx)
+        {
             m_step_min = param.min_step;
             if (step <= Scalar(0))
                 throw std::invalid_argument("'step' must be positive");
@@ -153,25 +161,30 @@ public:
                 throw std::invalid_argument("'step' is smaller than 'param.min_step'");
             if (step > step_max)
                 throw std::invalid_argument("'step' exceeds 'step_max'");
-            if (dg >= Scalar(0))
-                throw std::logic_error("the moving direction does not decrease the objective function value");
             const Scalar inf = std::numeric_limits<Scalar>::infinity();
             m_step = step;
             m_step_max = step_max;
             m_f0 = fx;
-            m_armijo = param.ftol * dg;
-            m_curvature = -param.wolfe * dg;
-            m_lo = Sample{Scalar(0), Scalar(0), (Scalar(1) - param.ftol) * dg};  // in terms of psi
             m_hi = Sample{inf, inf, inf};
             m_psi_lo = Scalar(0);
             m_f_best = fx;  // phi, phi' at lo.t
-            m_g_best = dg;
             m_bracketed = false;
             m_guard_min = (m_step_min > Scalar(0));
             m_width = m_width_prev = inf;
             m_stalls = 0;
             m_it = 0;
             m_max_it = param.max_linesearch;
+        }
+        // ... and the check on dg with what is derived from it, before the first feed()
+        template <typename SolverParam>
+        void start_dg(const SolverParam& param, Scalar dg)
+        {
+            if (dg >= Scalar(0))
+                throw std::logic_error("the moving direction does not decrease the objective function value");
+            m_armijo = param.ftol * dg;
+            m_curvature = -param.wolfe * dg;
+            m_lo = Sample{Scalar(0), Scalar(0), (Scalar(1) - param.ftol) * dg};  // in terms of psi
+            m_g_best = dg;
         }
 
         // fx, dg: objective and directional derivative at step().  keep_lo is set when the point just evaluated
@@ -254,16 +267,40 @@ public:
         }
     };
 
+    // the device form below can start without dg: it takes it from its first trial when the evaluator says it is pending
+    static constexpr bool takes_pending_dg = true;
+
     template <typename Eval, typename SolverParam>
     static void LineSearch(Eval& ev, const SolverParam& param, const Scalar& step_max, Scalar& step, Scalar& fx,
                            Scalar& dg)
     {
         Machine mt;
-        mt.start(param, step_max, step, fx, dg);
+        bool have_first = false;
+        if constexpr (detail::has_dg_pending<Eval>::value)
+        {
+            if (ev.dg_pending)
+            {
+                // dg = grad.dot(drt) comes back with the first trial (Device.h: first_trial).  The search uses it for its
+                // entry check and for the two Wolfe tests only, never for the first step, so the check moves behind that pass:
+                // when it fails nothing has been counted or reported written, and the reference's exception leaves as before
+                ev.dg_pending = false;
+                mt.start_step(param, step_max, step, fx);
+                Scalar f1 = fx, g1 = dg, dg0 = dg;
+                have_first = ev.first_trial(mt.step(), f1, g1, dg0);
+                mt.start_dg(param, dg0);
+                fx = f1;
+                dg = g1;
+            }
+        }
+        if (!have_first)
+            mt.start(param, step_max, step, fx, dg);
         for (;;)
         {
             step = mt.step();
-            ev.trial(step, fx, dg);
+            if (have_first)
+                have_first = false;
+            else
+                ev.trial(step, fx, dg);
             bool keep_lo = false;
             const typename Machine::Action a = mt.feed(fx, dg, keep_lo);
             if (keep_lo)

@@ -155,6 +155,28 @@ int lbfgsx_ls_post_in_trial(lbfgsx_ctx* c, double a);
 /* instrumentation: {post-form trials issued, of which accepted, persistent launches that started from the gradient,
  * 1 if the form is enabled for this context} */
 int lbfgsx_post_in_trial_counts(const lbfgsx_ctx* c, int64_t out[4]);
+/* Last step of the recursion in the first trial.  After an accepted post-form first trial the product's persistent launch
+ * writes d, and the next search's first trial -- a post-form one again -- reads it straight back, along with the gradient the
+ * last step has just reduced against.  A driver that can do without grad.d until its first trial has come back says so once
+ * per context with lbfgsx_last_in_trial_request(c, 1).  The launch that lbfgsx_post_linesearch_spec starts from the gradient
+ * then ends with step 2c-1, and
+ *   lbfgsx_apply_Hv_pending  is lbfgsx_apply_Hv, except that with *pending = 1 it returns no grad.d (NaN): D holds the vector
+ *                            before the last update;
+ *   lbfgsx_trial_first       is lbfgsx_trial, except that a first post-form trial of a built-in objective forms
+ *                            d = q + (alpha_0 - beta) s_0 (BFGSMat.h:298-299) in its own pass, without storing it, and returns
+ *                            *dg_init = grad.d with fx and dg: 8.12n instead of 10.88n elements around that kernel boundary
+ *                            at n = 1e8.  *dg_init is NaN when no step was pending.
+ * The caller checks the sign of dg_init itself (the reference does so before its first trial; the trial has then written
+ * only the trial buffer).  Every other entry point that reads D or replaces a vector the step reads -- lbfgsx_download,
+ * lbfgsx_vec, lbfgsx_trial, the second trial of a search, lbfgsx_apply_Hv, ... -- first runs the step as the step launches have
+ * it (k_twoloop), which leaves D and grad.d as the full launch does: same bits either way.  Only the built-in objectives
+ * have the form; a bounded context never defers.  LBFGSX_LAST_IN_TRIAL=0 (read when the context is created) switches it off. */
+int lbfgsx_last_in_trial_request(lbfgsx_ctx* c, int on);
+int lbfgsx_apply_Hv_pending(lbfgsx_ctx* c, int v_which, double a, double* dg, int* pending);
+int lbfgsx_trial_first(lbfgsx_ctx* c, int objective, double step, double* fx, double* dg, double* dg_init);
+/* instrumentation: {launches that ended one step early, steps run by a first trial, steps run on their own ahead of another
+ * reader of D, 1 if the form is enabled for this context} */
+int lbfgsx_last_in_trial_counts(const lbfgsx_ctx* c, int64_t out[4]);
 /* ---- term objectives compiled at run time -------------------------------------------------------------------------
  * An objective that is a sum of terms over K consecutive coordinates (K = 1 or 2), evaluated INSIDE the fused kernels like
  * the two built-in ones.  `body` is HIP/C++ text for one term: statements that see

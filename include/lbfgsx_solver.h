@@ -75,6 +75,9 @@ int lbfgsx_solver_set_iteration_hook(lbfgsx_solver* s, void (*fn)(int, void*), v
  * (include/LBFGSpp/GramSpace.h), 2 = Gram-space form with an f32 history (f64 solvers only).  LBFGSX_E_INVALID for
  * L-BFGS-B solvers. */
 int lbfgsx_solver_set_recursion(lbfgsx_solver* s, int form);
+/* LBFGSSolver::set_direction_scale (extension, for tests of the line searches' entry check): the directions computed from
+ * now on are a * H * grad; -1 is the method, +1 gives an ascent direction.  LBFGSX_E_INVALID for L-BFGS-B solvers. */
+int lbfgsx_solver_set_direction_scale(lbfgsx_solver* s, double a);
 /* LBFGSSolver::set_reducer (extension, row-sharded runs): fn(values, count, user) must sum `values` over all ranks in
  * place (an all-reduce); NULL switches back.  L-BFGS solvers with the Gram-space recursion only. */
 int lbfgsx_solver_set_allreduce(lbfgsx_solver* s, void (*fn)(double*, int, void*), void* user);

@@ -124,6 +124,10 @@ def load():
     sig(core, "lbfgsx_spec_counts", i32, vp, C.POINTER(i64 * 3))
     sig(core, "lbfgsx_ls_post_in_trial", i32, vp, dbl)
     sig(core, "lbfgsx_post_in_trial_counts", i32, vp, C.POINTER(i64 * 4))
+    sig(core, "lbfgsx_last_in_trial_request", i32, vp, i32)
+    sig(core, "lbfgsx_apply_Hv_pending", i32, vp, i32, dbl, pd, C.POINTER(i32))
+    sig(core, "lbfgsx_trial_first", i32, vp, i32, dbl, pd, pd, pd)
+    sig(core, "lbfgsx_last_in_trial_counts", i32, vp, C.POINTER(i64 * 4))
     sig(core, "lbfgsx_counters", i32, C.POINTER(i64 * 3), i32)
     sig(core, "lbfgsx_counters_ex", i32, C.POINTER(i64 * 8), i32)
     sig(core, "lbfgsx_poll_counts", i32, vp, C.POINTER(i64 * 2))
@@ -140,6 +144,7 @@ def load():
     sig(sol, "lbfgsx_solver_prepare", i32, vp, i64)
     sig(sol, "lbfgsx_solver_ctx", vp, vp)
     sig(sol, "lbfgsx_solver_set_recursion", i32, vp, i32)
+    sig(sol, "lbfgsx_solver_set_direction_scale", i32, vp, dbl)
     sig(sol, "lbfgsx_solver_set_allreduce", i32, vp, ALLREDUCE, vp)
     sig(sol, "lbfgsx_solver_set_devices", i32, vp, C.POINTER(i32), i32)
     sig(core, "lbfgsx_comm_unique_id", i32, C.c_char_p)

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/lbfgsx.h"
+#include "last_step.hpp"
 #include "reduce.cuh"
 
 struct lbfgsx_ctx;
@@ -135,6 +136,7 @@ struct ScLayout
 // Live contexts / batches per device in this process.  The persistent two-loop kernel needs the whole GPU for itself
 // (every block resident, grid-wide meeting points); it is only used while its context is the single live one.
 void live_add(int device, int delta);   // lbfgsx.hip
+int last_settle(lbfgsx_ctx* c);         // lbfgsx.hip: runs a deferred last recursion step (ctx.hpp: last); call before reading d
 int live_count(int device);
 
 int bounded_alloc(lbfgsx_ctx* c);   // lbfgsb.hip (the state itself: lbfgsb_state.hpp)
@@ -255,6 +257,12 @@ struct lbfgsx_ctx
     double pt_r[4] = {0, 0, 0, 0};  // {g.g, x.x, s.y, y.y}
     int64_t pt_issued = 0, pt_accepted = 0;  // instrumentation (lbfgsx_post_in_trial_counts)
     int64_t from_g_launches = 0;   // persistent launches that started the recursion from the gradient
+    // Last step in the trial (k_trial_last, PersistArgs::defer_last): a persistent launch from the gradient ends one step
+    // early and the next search's first trial, a post-form one, runs that step in its own pass.  While last.pending is set the
+    // d buffer holds q before the last update, and every other reader of d runs the step first (lbfgsx::last_settle,
+    // lbfgsx.hip).  The rules: last_step.hpp.  The keep slot of the recursion's dot(0) is sl.dot(2m+1), which no product uses.
+    lbfgsx::LastStep last;
+    bool pt_builtin = false;       // the latest post-form trial ran a built-in objective's kernel (those have the last form)
 
     // a term objective compiled at run time and bound to this context (lbfgsx_objective_bind, jit_objective.hip): the id
     // LBFGSX_OBJ_BOUND then evaluates it inside the fused kernels.  term_p: the caller's device arrays (term_own: the
@@ -324,6 +332,7 @@ struct lbfgsx_ctx
     bool timing = false;
     bool timing_per_launch = true;  // false (lbfgsx_timing_enable(ctx, 2)): events around whole apply_Hv calls only
     std::vector<lbfgsx::EventPair> ev_twoloop, ev_hv;
+    std::vector<lbfgsx::EventPair> ev_last;  // passes that ran a deferred last step: their time belongs to that product
     void* gather_tmp = nullptr;
     int64_t gather_cap = 0;
 

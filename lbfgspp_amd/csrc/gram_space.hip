@@ -774,6 +774,12 @@ int lbfgsx_gs_post_linesearch(lbfgsx_ctx* c, double scal[7], double* sdots, doub
     }
     c->spec_valid = false;  // the spare column is rewritten
     lbfgsx::DeviceGuard dev_guard_(c->device);
+    {
+        // a deferred last step of the vector recursion (ctx.hpp: last) runs while the columns it reads are as it left them
+        const int rcl = lbfgsx::last_settle(c);
+        if (rcl)
+            return rcl;
+    }
     if (2 * c->m > kGsMaxCols)
     {
         set_error("lbfgsx_gs_post_linesearch: the Gram-space recursion supports m <= 24");
@@ -797,6 +803,7 @@ int lbfgsx_gs_direction(lbfgsx_ctx* c, const double* coef, double coef_g, double
         return LBFGSX_E_INVALID;
     }
     c->spec_valid = false;  // the direction buffer is rewritten
+    c->last.drop();         // and with it what a deferred last step of the vector recursion would have completed
     lbfgsx::DeviceGuard dev_guard_(c->device);
     if (2 * c->m > kGsMaxCols)
     {

@@ -141,16 +141,43 @@ struct TrialPost
     T* dot0;          // sc[] slot of the recursion's first dot
 };
 
-template <class T, class OBJ, bool POST>
+// Last form (k_trial_last): a post-form pass that also runs the recursion's last step.  The persistent launch stopped one
+// step early (PersistArgs::defer_last), so the d buffer holds q before the last update and the pass forms
+//     d = q + (alpha_0 - beta) * s_0          (BFGSMat.h:298-299, the expression and the raw scalars of k_twoloop<TL_ADD>)
+// in registers, where the step would have stored it and this pass read it back; grad.d, the dot of that step, is one more
+// sum (gp is the gradient the step reduces against).  d is not stored: an accepted trial never reads it again, and after a
+// rejected one the step has to run after all.  The post sums overwrite the recursion's dot(0), which that step needs: the last
+// block moves it to dot0_keep first.
+// Settling form (k_trial_settle, LAST without POST): the second trial of a search whose last-form first trial was rejected.
+// A plain trial that forms d the same way and stores it (dout is the d buffer itself: every element is read, then written,
+// by one thread) -- 6n elements where the step launch and a plain trial move 8n.  grad.d is known since the first trial.
+template <class T>
+struct TrialLast
+{
+    const T* snew;    // newest history column s_0
+    const T* num;     // sc[] slots of the coefficient: *num / *den - *num2 / *den
+    const T* num2;
+    const T* den;
+    T* dot0_keep;     // receives *num (= the recursion's dot(0)) before the post form rewrites that slot
+    T* dg_slot;       // sc[] slot of the recursion's last dot, grad.d
+    T* dout;          // settling form: where d goes
+};
+
+template <class T, class OBJ, bool POST, bool LAST = false>
 __device__ __forceinline__ void trial_pass(const T* __restrict__ xp, const T* __restrict__ d, T step, T* __restrict__ x,
                                            T* __restrict__ g, int64_t n, const OBJ& obj, const RedWs& ws,
-                                           T* __restrict__ out, int rev, const TrialPost<T>& tp)
+                                           T* __restrict__ out, int rev, const TrialPost<T>& tp,
+                                           const TrialLast<T>& tl = TrialLast<T>())
 {
     typedef typename AccOf<T>::type A;
     constexpr int W = Vec16<T>::W;
     constexpr int U = 4;
-    constexpr int NRED = POST ? 7 : 2;
+    constexpr bool SETTLE = LAST && !POST;
+    constexpr int NRED = POST ? (LAST ? 8 : 7) : 2;
     A acc[NRED];
+    T coef = T(0);
+    if (LAST)
+        coef = *tl.num / *tl.den - *tl.num2 / *tl.den;  // alpha_j - beta (BFGSMat.h:298-299), as k_twoloop<TL_ADD> has it
     const int64_t nv = n / W;
     // tiles of U x kBlock vectors; both loads of every vector are issued before the first use.  The tile order
     // alternates between launches (TwoLoopArgs::rev)
@@ -159,13 +186,15 @@ __device__ __forceinline__ void trial_pass(const T* __restrict__ xp, const T* __
     for (int64_t t0 = int64_t(blockIdx.x) * tile; t0 < nv; t0 += int64_t(gridDim.x) * tile)
     {
         const int64_t base = (rev ? top - t0 : t0) + threadIdx.x;
-        Pack<T> pxp[U], pd[U], pgp[POST ? U : 1];
+        Pack<T> pxp[U], pd[U], pgp[POST ? U : 1], psn[LAST ? U : 1];
 #pragma unroll
         for (int u = 0; u < U; u++)
             if (base + u * kBlock < nv)
             {
                 pxp[u] = ldv(xp, base + u * kBlock);
                 pd[u] = ldv(d, base + u * kBlock);
+                if (LAST)
+                    psn[LAST ? u : 0] = ldv(tl.snew, base + u * kBlock);
                 if (POST)
                     pgp[POST ? u : 0] = ldv(tp.gp, base + u * kBlock);
             }
@@ -176,6 +205,18 @@ __device__ __forceinline__ void trial_pass(const T* __restrict__ xp, const T* __
             if (vi < nv)
             {
                 Pack<T> px, pg;
+                if (LAST)
+                {
+#pragma unroll
+                    for (int k = 0; k < W; k++)
+                    {
+                        pd[u].e[k] = pd[u].e[k] + coef * psn[LAST ? u : 0].e[k];  // res += (alpha-beta)*s_j (:299)
+                        if (POST)
+                            acc[POST && LAST ? 7 : 0].add_prod(pgp[POST ? u : 0].e[k], pd[u].e[k]);
+                    }
+                    if (SETTLE)
+                        stv(tl.dout, vi, pd[u]);
+                }
 #pragma unroll
                 for (int k = 0; k < W; k++)
                     px.e[k] = pxp[u].e[k] + step * pd[u].e[k];
@@ -208,12 +249,20 @@ __device__ __forceinline__ void trial_pass(const T* __restrict__ xp, const T* __
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
     {
+        // the direction at a tail element (the last form forms it again wherever it is used; the settling form stores it behind
+        // its last use)
+        auto dir = [&](int64_t i) { return LAST ? d[i] + coef * tl.snew[i] : d[i]; };
         for (int64_t i = nv * W; i < n; i++)
-            x[i] = xp[i] + step * d[i];
+            x[i] = xp[i] + step * dir(i);
         for (int64_t i = nv * W; i < n; i++)
         {
+            const T di = dir(i);
             obj.tail(i, n, x, g, acc[0]);
-            acc[1].add_prod(g[i], d[i]);
+            acc[1].add_prod(g[i], di);
+            if (POST && LAST)
+                acc[POST && LAST ? 7 : 0].add_prod(tp.gp[i], di);
+            if (SETTLE)
+                tl.dout[i] = di;
         }
         if (POST)
             for (int64_t i = nv * W; i < n; i++)
@@ -239,6 +288,13 @@ __device__ __forceinline__ void trial_pass(const T* __restrict__ xp, const T* __
             out[3] = T(acc[POST ? 3 : 0].value());
             out[4] = sy;
             out[5] = yy;
+            if (LAST)
+            {
+                const T dgd = T(acc[LAST ? 7 : 0].value());
+                out[6] = dgd;
+                *tl.dg_slot = dgd;
+                *tl.dot0_keep = *tl.num;  // every block read it before it arrived at the reduction
+            }
             *tp.ys_slot = sy;
             *tp.theta_slot = yy / sy;
             *tp.dot0 = T(acc[POST ? 6 : 0].value());
@@ -260,6 +316,23 @@ __global__ void __launch_bounds__(kBlock) k_trial_post(const T* __restrict__ xp,
                                                        RedWs ws, T* __restrict__ out, int rev, TrialPost<T> tp)
 {
     trial_pass<T, OBJ, true>(xp, d, step, x, g, n, obj, ws, out, rev, tp);
+}
+// (4 waves per SIMD asked for: the grid is 4 blocks per CU, and one stream more than the post form put the f64 Rosenbrock
+// instance at 132 registers, i.e. 3 resident blocks per CU and a second round for the fourth)
+template <class T, class OBJ>
+__global__ void __launch_bounds__(kBlock, 4) k_trial_last(const T* __restrict__ xp, const T* __restrict__ q, T step,
+                                                       T* __restrict__ x, T* __restrict__ g, int64_t n, OBJ obj,
+                                                       RedWs ws, T* __restrict__ out, int rev, TrialPost<T> tp,
+                                                       TrialLast<T> tl)
+{
+    trial_pass<T, OBJ, true, true>(xp, q, step, x, g, n, obj, ws, out, rev, tp, tl);
+}
+template <class T, class OBJ>
+__global__ void __launch_bounds__(kBlock) k_trial_settle(const T* __restrict__ xp, const T* q, T step, T* __restrict__ x,
+                                                         T* __restrict__ g, int64_t n, OBJ obj, RedWs ws,
+                                                         T* __restrict__ out, int rev, TrialLast<T> tl)
+{
+    trial_pass<T, OBJ, false, true>(xp, q, step, x, g, n, obj, ws, out, rev, TrialPost<T>(), tl);
 }
 
 // generic-functor path: x = xp + step*d only (user kernel evaluates f,g), and g.d
@@ -647,6 +720,9 @@ struct PersistArgs
     int from_g;            // 1 (FUSE = false only): the recursion starts from the gradient.  The post form of k_trial has left
                            // the first dot s.(a*g) in sc[DOT0]; step 0 then only fills the resident slots with a*g (no streamed
                            // part, no dot, no meeting point) and step 1 forms a*g from g where it would load the stored q
+    int defer_last;        // 1 (ncorr >= 1 only): the launch ends with step 2c-1.  q is then the vector before the last update,
+                           // sc[DOT0 + 2c-1] its dot with the newest y: what the last form of k_trial (k_trial_last) or a
+                           // k_twoloop<TL_ADD> launch needs to run step 2c.  Everything "last" below goes by 2c - defer_last
 };
 
 constexpr int kSc1 = 16;  // cache-policy bit of the buffer instructions: agent scope (loads bypass L1, stores write through)
@@ -1147,7 +1223,8 @@ __global__ void __launch_bounds__(kHvThreads, 2)
         }
     }
     bool was_last = false;  // MEET: this block closed the previous meeting point (it holds the dot already)
-    for (int L = FUSE ? 1 : 0; L <= 2 * cn; L++)
+    const int lend = 2 * cn - pa.defer_last;  // the launch's last step
+    for (int L = FUSE ? 1 : 0; L <= lend; L++)
     {
         const T* u;
         const T* w;
@@ -1311,12 +1388,12 @@ __global__ void __launch_bounds__(kHvThreads, 2)
                 // (The word in 2 / 8 / 16 copies in different memory channels, block b polling copy b % copies -- in case 512
                 // pollers of one address were the cost: 1184 / 1175 / 1204 it/s against 1200 on cfg2, nothing:
                 // profiles/r5_meet_ab.txt.)
-                if (pa.pub_first && L < 2 * cn)
+                if (pa.pub_first && L < lend)
                     persist_publish<false>(gen + 4, want, double(dv));
                 __hip_atomic_store(sc + DOT0 + L, dv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (!pa.pub_first && L < 2 * cn)  // the last dot is only read by the host
+                if (!pa.pub_first && L < lend)  // the last dot is only read by the host (defer_last: by the pass that runs step 2c)
                     persist_publish(gen + 4, want, double(dv));
-                if (!FUSE && fromg && L == 2 * cn)
+                if (!FUSE && fromg && L == lend)
                 {
                     // the same closing signal for the launch that started from the gradient (the sums went out with the trial)
                     T* o = reinterpret_cast<T*>(s_sig[FUSE ? 0 : 2]);
@@ -1327,7 +1404,7 @@ __global__ void __launch_bounds__(kHvThreads, 2)
                     __hip_atomic_store(o + 5, T(1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     ws_signal(wsig);
                 }
-                if (FUSE && L == 2 * cn)
+                if (FUSE && L == lend)
                 {
                     // the launch's last meeting point: everything the host reads next is known -- grad . d here, the post
                     // statements' sums since step 0.  A polling host (poll_arm) goes on while the blocks store the
@@ -1348,7 +1425,7 @@ __global__ void __launch_bounds__(kHvThreads, 2)
                 __hip_atomic_store(gen, want, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
-        if (L < 2 * cn)  // the last dot is only read by the host
+        if (L < lend)  // the last dot is only read by the host
         {
             if (tid == 0)
             {

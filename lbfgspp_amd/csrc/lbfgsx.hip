@@ -149,6 +149,15 @@ void set_error(const std::string& msg) { g_err = msg; }
 template <class T>
 static inline T* P(void* p) { return static_cast<T*>(p); }
 
+// a deferred last recursion step (ctx.hpp: last) runs before an entry point reads d or replaces a vector it needs
+#define LBFGSX_SETTLE(c)                           \
+    do                                             \
+    {                                              \
+        const int rc_settle_ = lbfgsx::last_settle(c); \
+        if (rc_settle_)                            \
+            return rc_settle_;                     \
+    } while (0)
+
 // ---- small utility kernels -------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t splitmix64(uint64_t z)
 {
@@ -275,6 +284,60 @@ static int third_point(int p, int q)
     return 0;
 }
 
+// event pair around a pass that runs a deferred last step (timing only): its time belongs to the product (ctx.hpp: ev_last)
+static int last_time_begin(lbfgsx_ctx* c, EventPair& ev)
+{
+    if (!c->timing)
+        return LBFGSX_OK;
+    LBFGSX_HIP(hipEventCreate(&ev.a));
+    LBFGSX_HIP(hipEventCreate(&ev.b));
+    LBFGSX_HIP(hipEventRecord(ev.a, c->stream));
+    return LBFGSX_OK;
+}
+static int last_time_end(lbfgsx_ctx* c, EventPair& ev)
+{
+    if (!c->timing)
+        return LBFGSX_OK;
+    LBFGSX_HIP(hipEventRecord(ev.b, c->stream));
+    c->ev_last.push_back(ev);
+    return LBFGSX_OK;
+}
+
+// Step 2c of a product whose persistent launch ended one step early (ctx.hpp: last), as lbfgsx_apply_Hv's step launches have it:
+// d = q + (alpha_0 - beta) s_0 and grad.d into sc[dot(2c)].  After a last-form trial the recursion's dot(0) is in its keep slot.
+template <class T>
+static int last_settle_t(lbfgsx_ctx* c, const LastStep& ls)
+{
+    const ScLayout& sl = c->sl;
+    TwoLoopArgs args = {0, 0, 0, 0, 0, 0};
+    args.i_num = ls.taken ? sl.dot(2 * c->m + 1) : sl.dot(0);
+    args.i_num2 = sl.dot(2 * ls.cn - 1);
+    args.i_den = sl.ys(ls.col);
+    args.i_out = sl.dot(2 * ls.cn);
+    // the step's turn in the alternation of traversal directions, unless a last-form trial has counted it already
+    args.rev = ((ls.taken ? c->tl_step : c->tl_step++) & 1u) ? 1 : 0;
+    const int grid = std::min(c->grid_for(c->n, 4), kGridCapTwoloop);
+    EventPair ev;
+    int rc = last_time_begin(c, ev);
+    if (rc)
+        return rc;
+    LBFGSX_LAUNCH((k_twoloop<T, TL_ADD>), dim3(grid), dim3(kBlock), 0, c->stream, P<T>(c->d), static_cast<const T*>(nullptr),
+                  T(0), static_cast<const T*>(c->col(c->S, ls.col)), static_cast<const T*>(c->gb[ls.g]), c->n, P<T>(c->sc),
+                  args, c->ws);
+    LBFGSX_HIP(hipGetLastError());
+    return last_time_end(c, ev);
+}
+int last_settle(lbfgsx_ctx* c)
+{
+    if (!c->last.pending)
+        return LBFGSX_OK;
+    lbfgsx::DeviceGuard dev_guard_(c->device);
+    return c->last.settle([c](const LastStep& ls) {
+        DISPATCH_T(c, { return last_settle_t<T>(c, ls); });
+        return int(LBFGSX_E_INVALID);
+    });
+}
+
 }  // namespace lbfgsx
 
 using namespace lbfgsx;
@@ -365,6 +428,8 @@ static int create_fill(lbfgsx_ctx* c, int dtype, int64_t n, int m, int device, i
         c->fuse_post = atoi(e) != 0;
     if (const char* e = getenv("LBFGSX_POST_IN_TRIAL"))
         c->post_in_trial = atoi(e) != 0;
+    if (const char* e = getenv("LBFGSX_LAST_IN_TRIAL"))
+        c->last.enabled = atoi(e) != 0;
     {
         // the persistent two-loop needs every block resident at once: occupancy * CUs
         int occ = 0;
@@ -503,6 +568,11 @@ void lbfgsx_destroy(lbfgsx_ctx* c)
         (void) hipEventDestroy(e.a);
         (void) hipEventDestroy(e.b);
     }
+    for (auto& e : c->ev_last)
+    {
+        (void) hipEventDestroy(e.a);
+        (void) hipEventDestroy(e.b);
+    }
     if (c->own_stream)
         (void) hipStreamDestroy(c->stream);
     delete c;
@@ -527,12 +597,18 @@ int lbfgsx_sync(lbfgsx_ctx* c)
 }
 
 int64_t lbfgsx_n(const lbfgsx_ctx* c) { return c->n; }
-void* lbfgsx_vec(lbfgsx_ctx* c, int which) { return vec_ptr(c, which); }
+void* lbfgsx_vec(lbfgsx_ctx* c, int which)
+{
+    if (which == LBFGSX_VEC_D && lbfgsx::last_settle(c))
+        return nullptr;
+    return vec_ptr(c, which);
+}
 
 int lbfgsx_upload(lbfgsx_ctx* c, int which, const void* host)
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
+    LBFGSX_SETTLE(c);
     void* p = vec_ptr(c, which);
     if (!p || !host)
     {
@@ -547,6 +623,7 @@ int lbfgsx_upload(lbfgsx_ctx* c, int which, const void* host)
 int lbfgsx_download(lbfgsx_ctx* c, int which, void* host)
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
+    LBFGSX_SETTLE(c);
     void* p = vec_ptr(c, which);
     if (!p || !host)
     {
@@ -561,6 +638,7 @@ int lbfgsx_download(lbfgsx_ctx* c, int which, void* host)
 int lbfgsx_gather(lbfgsx_ctx* c, int which, int64_t stride, double* host)
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
+    LBFGSX_SETTLE(c);
     void* p = vec_ptr(c, which);
     if (!p || !host || stride < 1)
     {
@@ -619,6 +697,7 @@ int lbfgsx_fill(lbfgsx_ctx* c, int which, double value)
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
+    LBFGSX_SETTLE(c);
     void* p = vec_ptr(c, which);
     if (!p)
     {
@@ -641,6 +720,7 @@ int lbfgsx_bfgs_reset(lbfgsx_ctx* c)
     c->pending = false;
     c->spec_valid = false;
     c->pt_valid = c->pt_armed = c->ls_first_ok = false;
+    c->last.drop();
     c->ls_trials = 0;
     c->tl_step = 0;  // the traversal direction of every launch of a run is a function of the run alone
     for (int j = 0; j < c->m; j++)
@@ -711,6 +791,7 @@ int lbfgsx_bfgs_stage_correction_host(lbfgsx_ctx* c, const void* s, const void* 
     lbfgsx::DeviceGuard dev_guard_(c->device);
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
     c->pt_valid = false;    // the spare column receives another pair
+    LBFGSX_SETTLE(c);
     if (c->gs_f32h)
     {
         set_error("lbfgsx_bfgs_stage_correction_host: this context keeps its history in f32 for the Gram-space recursion (lbfgsx_gs_set_history_dtype)");
@@ -762,6 +843,7 @@ static int apply_Hv_t(lbfgsx_ctx* c, const T* v, T a, double* dg)
 {
     const int cn = c->ncorr, m = c->m;
     const int grid = std::min(c->grid_for(c->n, 4), kGridCapTwoloop);
+    c->last.drop();  // d is computed anew
     T* q = P<T>(c->d);
     T* sc = P<T>(c->sc);
     const T* gcur = P<T>(c->gb[c->cur]);
@@ -800,6 +882,7 @@ static int apply_Hv_t(lbfgsx_ctx* c, const T* v, T a, double* dg)
         pa.pub_first = 1;
         pa.ld = c->ld;
         pa.from_g = 0;
+        pa.defer_last = 0;
         // one generation number per meeting point: the word the blocks wait for (LBFGSX_MEET=last) or the tag of the
         // 16-byte words they exchange (the default)
         c->gen_count += unsigned(2 * cn + 1);
@@ -938,9 +1021,13 @@ static int apply_Hv_t(lbfgsx_ctx* c, const T* v, T a, double* dg)
 }
 extern "C" {
 
-int lbfgsx_apply_Hv(lbfgsx_ctx* c, int v_which, double a, double* dg)
+int lbfgsx_apply_Hv(lbfgsx_ctx* c, int v_which, double a, double* dg) { return lbfgsx_apply_Hv_pending(c, v_which, a, dg, nullptr); }
+
+int lbfgsx_apply_Hv_pending(lbfgsx_ctx* c, int v_which, double a, double* dg, int* pending)
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
+    if (pending)
+        *pending = 0;
     void* v = vec_ptr(c, v_which);
     if (!v || v == c->d)
     {
@@ -962,6 +1049,23 @@ int lbfgsx_apply_Hv(lbfgsx_ctx* c, int v_which, double a, double* dg)
         if (hit)
         {
             c->spec_used++;
+            if (c->last.pending)
+            {
+                // the launch ended one step early (ctx.hpp: last).  A caller that takes grad.d from its first trial is told
+                // so; for any other the step runs now and leaves grad.d where the full launch does
+                if (pending)
+                {
+                    c->last.owe();
+                    *pending = 1;
+                    if (dg) *dg = std::numeric_limits<double>::quiet_NaN();
+                    return LBFGSX_OK;
+                }
+                const int cn = c->last.cn;
+                LBFGSX_SETTLE(c);
+                if (dg)
+                    DISPATCH_T(c, { return fetch_scalars<T>(c, c->sl.dot(2 * cn), 1, dg); });
+                return LBFGSX_OK;
+            }
             if (dg) *dg = c->spec_dg;
             return LBFGSX_OK;
         }
@@ -1002,6 +1106,7 @@ int lbfgsx_eval(lbfgsx_ctx* c, int objective, double* fx, double* gnorm2, double
     lbfgsx::DeviceGuard dev_guard_(c->device);
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
     c->pt_valid = false;
+    LBFGSX_SETTLE(c);  // the gradient is rewritten
     double r[3];
     int rc = LBFGSX_E_INVALID;
     if (objective == LBFGSX_OBJ_EXT_ROSENBROCK && (c->n & 1))
@@ -1101,7 +1206,68 @@ static int trial_post_t(lbfgsx_ctx* c, OBJ obj, T step, double* out2)
     out2[0] = r[0];
     out2[1] = r[1];
     trial_post_done(c, r);
+    c->pt_builtin = true;
     return LBFGSX_OK;
+}
+// the last form (k_trial_last): the post form that also runs the deferred last step of the recursion (ctx.hpp: last) on the way;
+// out3 = {f, g.d, gp.d}
+template <class T, class OBJ>
+static int trial_last_t(lbfgsx_ctx* c, OBJ obj, T step, double* out3)
+{
+    const lbfgsx::LastStep& ls = c->last;
+    if (ls.col == c->spare)
+    {
+        set_error("lbfgsx_trial: the newest history column is the spare column");
+        return LBFGSX_E_LOGIC;
+    }
+    c->tl_step++;  // the step this pass carries (post_spec_t)
+    const lbfgsx::TrialLaunch<T> a = lbfgsx::trial_launch<T>(c, step, (sizeof(OBJ) >= 2 * sizeof(void*) ? 2 : 0) + 1);
+    const lbfgsx::TrialPost<T> tp = trial_post_args<T>(c);
+    T* sc = P<T>(c->sc);
+    const lbfgsx::TrialLast<T> tl = {static_cast<const T*>(c->col(c->S, ls.col)), sc + c->sl.dot(0), sc + c->sl.dot(2 * ls.cn - 1),
+                                     sc + c->sl.ys(ls.col),                      sc + c->sl.dot(2 * c->m + 1), sc + c->sl.dot(2 * ls.cn)};
+    EventPair ev;
+    int rc = last_time_begin(c, ev);
+    if (rc)
+        return rc;
+    LBFGSX_LAUNCH((k_trial_last<T, OBJ>), dim3(a.grid), dim3(kBlock), 0, c->stream, a.xp, a.d, a.step, a.x, a.g, a.n, obj,
+                       a.ws, a.out, a.rev, tp, tl);
+    LBFGSX_HIP(hipGetLastError());
+    if ((rc = last_time_end(c, ev)))
+        return rc;
+    c->last.fuse();
+    double r[7];
+    rc = fetch_scalars<T>(c, c->sl.out(0), 7, r);
+    if (rc)
+        return rc;
+    out3[0] = r[0];
+    out3[1] = r[1];
+    out3[2] = r[6];
+    trial_post_done(c, r);
+    c->pt_builtin = true;
+    return LBFGSX_OK;
+}
+// the settling form (k_trial_settle): the trial after a rejected last-form first trial runs the step on the way and stores d
+template <class T, class OBJ>
+static int trial_settle_t(lbfgsx_ctx* c, OBJ obj, T step, double* out2)
+{
+    const lbfgsx::LastStep& ls = c->last;
+    const lbfgsx::TrialLaunch<T> a = lbfgsx::trial_launch<T>(c, step, (sizeof(OBJ) >= 2 * sizeof(void*) ? 2 : 0) + 2);
+    T* sc = P<T>(c->sc);
+    // the recursion's dot(0) is in its keep slot since the first trial; grad.d is in its slot already
+    const lbfgsx::TrialLast<T> tl = {static_cast<const T*>(c->col(c->S, ls.col)), sc + c->sl.dot(2 * c->m + 1),
+                                     sc + c->sl.dot(2 * ls.cn - 1), sc + c->sl.ys(ls.col), nullptr, nullptr, P<T>(c->d)};
+    EventPair ev;
+    int rc = last_time_begin(c, ev);
+    if (rc)
+        return rc;
+    LBFGSX_LAUNCH((k_trial_settle<T, OBJ>), dim3(a.grid), dim3(kBlock), 0, c->stream, a.xp, a.d, a.step, a.x, a.g, a.n, obj,
+                       a.ws, a.out, a.rev, tl);
+    LBFGSX_HIP(hipGetLastError());
+    if ((rc = last_time_end(c, ev)))
+        return rc;
+    (void) c->last.settle([](const lbfgsx::LastStep&) { return 0; });  // d is d again
+    return fetch_scalars<T>(c, c->sl.out(0), 2, out2);
 }
 // the post form of the kernel compiled for the context's bound term objective
 template <class T>
@@ -1121,6 +1287,7 @@ static int trial_post_term_t(lbfgsx_ctx* c, T step, double* out2)
     out2[0] = r[0];
     out2[1] = r[1];
     trial_post_done(c, r);
+    c->pt_builtin = false;  // the compiled kernels have no last form
     return LBFGSX_OK;
 }
 template <class T>
@@ -1142,10 +1309,29 @@ extern "C" {
 
 int lbfgsx_trial(lbfgsx_ctx* c, int objective, double step, double* fx, double* dg)
 {
+    return lbfgsx_trial_first(c, objective, step, fx, dg, nullptr);
+}
+
+int lbfgsx_trial_first(lbfgsx_ctx* c, int objective, double step, double* fx, double* dg, double* dg_init)
+{
     lbfgsx::DeviceGuard dev_guard_(c->device);
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
-    double r[2];
+    double r[3];
     int rc = LBFGSX_E_INVALID;
+    const bool builtin = objective == LBFGSX_OBJ_DIAG_QUAD || objective == LBFGSX_OBJ_EXT_ROSENBROCK;
+    // a deferred last recursion step (ctx.hpp: last) rides in this pass when it is the post-form first trial of a built-in
+    // objective and the caller reads grad.d from it; before any other trial the step runs on its own
+    const bool last = c->last.fusable(c->pt_armed && c->ls_trials == 0, builtin, dg_init != nullptr, c->xp) && !c->st_valid;
+    const int last_cn = c->last.cn;
+    // the trial behind a rejected last-form first trial runs the step itself and stores d (k_trial_settle)
+    const bool settle_here = !last && c->last.pending && c->last.taken && builtin && !c->st_valid && c->xp == c->last.g;
+    if (!last && !settle_here)
+        LBFGSX_SETTLE(c);
+    // a caller that was told "pending" in place of grad.d gets it here; where the step ran on its own -- just now, or for a
+    // download in between -- it is where every product leaves it
+    const bool owed = c->last.pay() && dg_init && !last;
+    if (dg_init)
+        *dg_init = std::numeric_limits<double>::quiet_NaN();  // nothing owed: the caller has grad.d from lbfgsx_apply_Hv
     if (c->st_valid)  // evaluated ahead by the pass that worked out dg and step_max (lbfgsx_b_dg_maxstep_trial)?
     {
         c->st_valid = false;
@@ -1172,19 +1358,27 @@ int lbfgsx_trial(lbfgsx_ctx* c, int objective, double step, double* fx, double* 
     c->pt_valid = false;
     DISPATCH_T(c, {
         if (objective == LBFGSX_OBJ_DIAG_QUAD)
-            rc = post ? trial_post_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, T(step), r)
-                      : trial_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, T(step), r);
+            rc = last          ? trial_last_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, T(step), r)
+                 : settle_here ? trial_settle_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, T(step), r)
+                 : post        ? trial_post_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, T(step), r)
+                               : trial_t<T>(c, ObjQuad<T>{P<T>(c->a), P<T>(c->b)}, T(step), r);
         else if (objective == LBFGSX_OBJ_EXT_ROSENBROCK)
-            rc = post ? trial_post_t<T>(c, ObjRosen<T>{}, T(step), r) : trial_t<T>(c, ObjRosen<T>{}, T(step), r);
+            rc = last          ? trial_last_t<T>(c, ObjRosen<T>{}, T(step), r)
+                 : settle_here ? trial_settle_t<T>(c, ObjRosen<T>{}, T(step), r)
+                 : post        ? trial_post_t<T>(c, ObjRosen<T>{}, T(step), r)
+                               : trial_t<T>(c, ObjRosen<T>{}, T(step), r);
         else if (lbfgsx::term_bound(c, objective))
             rc = post ? trial_post_term_t<T>(c, T(step), r) : trial_term_t<T>(c, T(step), r);
         else
             set_error("lbfgsx_trial: unknown objective");
+        if (!rc && owed)
+            rc = fetch_scalars<T>(c, c->sl.dot(2 * last_cn), 1, dg_init);
     });
     if (rc)
         return rc;
     if (fx) *fx = r[0];
     if (dg) *dg = r[1];
+    if (last) *dg_init = r[2];
     return LBFGSX_OK;
 }
 
@@ -1193,6 +1387,7 @@ int lbfgsx_trial_point(lbfgsx_ctx* c, double step)
     lbfgsx::DeviceGuard dev_guard_(c->device);
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
     c->pt_valid = false;
+    LBFGSX_SETTLE(c);
     c->ls_trials++;
     const int grid = c->grid_for(c->n);
     DISPATCH_T(c, {
@@ -1206,6 +1401,7 @@ int lbfgsx_trial_point(lbfgsx_ctx* c, double step)
 int lbfgsx_trial_dg(lbfgsx_ctx* c, double* dg)
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
+    LBFGSX_SETTLE(c);
     const int grid = c->grid_for(c->n);
     DISPATCH_T(c, {
         LBFGSX_LAUNCH((k_dot<T>), dim3(grid), dim3(kBlock), 0, c->stream, P<T>(c->gb[c->trial]), P<T>(c->d),
@@ -1283,6 +1479,7 @@ static int post_spec_t(lbfgsx_ctx* c, T a, double* r4, bool from_g = false)
     std::unique_lock<std::mutex> lock(g_persist_mu[c->device], std::try_to_lock);
     if (!lock.owns_lock())
         return 1;
+    c->last.drop();  // d is computed anew
     // history as it will be once the pending pair is committed (lbfgsx_commit_correction): slot loc takes the spare column
     const int loc = c->ptr % m;
     const int cn = std::min(c->ncorr + 1, m);
@@ -1305,8 +1502,15 @@ static int post_spec_t(lbfgsx_ctx* c, T a, double* r4, bool from_g = false)
     pa.pub_first = 1;
     pa.ld = c->ld;
     pa.from_g = from_g ? 1 : 0;
+    // The launch may end one step early (ctx.hpp: last): it follows an accepted post-form first trial, so the next search's first
+    // trial is a post-form one too, which runs the step in its own pass.  The pass that runs the step advances the traversal
+    // parity by the step's one (tl_step), so every launch of a run keeps the direction it has without the deferral.
+    const bool defer = from_g && !c->bstate &&
+                       c->last.want(c->post_in_trial, c->pt_builtin, c->ls_first_ok, cn, c->shard_off != 0 || c->n_global != c->n,
+                                    !c->gs_f32h);
+    pa.defer_last = defer ? 1 : 0;
     c->gen_count += unsigned(2 * cn + 1);
-    c->tl_step += unsigned(2 * cn + 1);
+    c->tl_step += unsigned(2 * cn + 1 - pa.defer_last);
     T* sc = P<T>(c->sc);
     PostFuse<T> pf;
     pf.x = P<T>(c->xb[c->cur]);
@@ -1421,6 +1625,11 @@ static int post_spec_t(lbfgsx_ctx* c, T a, double* r4, bool from_g = false)
         c->spec_cur = c->cur;
         c->spec_a = double(a);
         c->spec_dg = dgv;
+        if (defer)
+        {
+            c->spec_dg = std::numeric_limits<double>::quiet_NaN();  // the launch's last dot is not grad.d
+            c->last.defer(cn, pa.pcol[0], c->cur);
+        }
     }
     else
     {
@@ -1507,6 +1716,26 @@ int lbfgsx_post_in_trial_counts(const lbfgsx_ctx* c, int64_t out[4])
     out[1] = c->pt_accepted;
     out[2] = c->from_g_launches;
     out[3] = c->post_in_trial ? 1 : 0;
+    return LBFGSX_OK;
+}
+
+int lbfgsx_last_in_trial_request(lbfgsx_ctx* c, int on)
+{
+    if (!c)
+        return LBFGSX_E_INVALID;
+    // a bounded context's direction comes from the subspace minimisation, never from a product's launch
+    c->last.requested = on != 0 && !c->bstate;
+    return LBFGSX_OK;
+}
+
+int lbfgsx_last_in_trial_counts(const lbfgsx_ctx* c, int64_t out[4])
+{
+    if (!c || !out)
+        return LBFGSX_E_INVALID;
+    out[0] = c->last.deferred;
+    out[1] = c->last.fused;
+    out[2] = c->last.settled;
+    out[3] = c->last.enabled ? 1 : 0;
     return LBFGSX_OK;
 }
 
@@ -1656,8 +1885,14 @@ int lbfgsx_timing_enable(lbfgsx_ctx* c, int on)
         (void) hipEventDestroy(e.a);
         (void) hipEventDestroy(e.b);
     }
+    for (auto& e : c->ev_last)
+    {
+        (void) hipEventDestroy(e.a);
+        (void) hipEventDestroy(e.b);
+    }
     c->ev_twoloop.clear();
     c->ev_hv.clear();
+    c->ev_last.clear();
     c->persist_steps_timed = 0;
     c->coarse_steps_timed = 0;
     c->fused_timed = 0;
@@ -1679,6 +1914,15 @@ int lbfgsx_timing_read(lbfgsx_ctx* c, double* twoloop_ms_total, int64_t* twoloop
         t1 += ms;
     }
     for (auto& e : c->ev_hv)
+    {
+        float ms = 0.f;
+        LBFGSX_HIP(hipEventElapsedTime(&ms, e.a, e.b));
+        t2 += ms;
+    }
+    // A product whose launch ended one step early (ctx.hpp: last) still counts its 2c+1 steps; the pass that ran the last one
+    // -- a last-form trial or a step launch -- adds its whole time to the products' total, and no call: the per-step time
+    // can only be overstated by it, never understated
+    for (auto& e : c->ev_last)
     {
         float ms = 0.f;
         LBFGSX_HIP(hipEventElapsedTime(&ms, e.a, e.b));

@@ -23,6 +23,7 @@ struct lbfgsx_solver
     virtual void set_hook(void (*fn)(int, void*), void* user) = 0;
     virtual int hessians(double*, double*) { return LBFGSX_E_INVALID; }
     virtual int set_recursion(int) { return LBFGSX_E_INVALID; }
+    virtual int set_direction_scale(double) { return LBFGSX_E_INVALID; }
     virtual int set_allreduce(void (*)(double*, int, void*), void*) { return LBFGSX_E_INVALID; }
     virtual int set_devices(const int*, int) { return LBFGSX_E_INVALID; }
     int dtype = LBFGSX_F64;
@@ -181,6 +182,11 @@ struct LbfgsImpl : lbfgsx_solver
             !(form == RECURSION_GRAM_SPACE_F32H && std::is_same<Scalar, double>::value))
             return LBFGSX_E_INVALID;
         solver->set_recursion(form);
+        return LBFGSX_OK;
+    }
+    int set_direction_scale(double a) override
+    {
+        solver->set_direction_scale(a);
         return LBFGSX_OK;
     }
     int set_allreduce(void (*fn)(double*, int, void*), void* user) override
@@ -933,6 +939,7 @@ int lbfgsx_solver_stats3(lbfgsx_solver* s, long long out[8])
 }
 
 int lbfgsx_solver_set_recursion(lbfgsx_solver* s, int form) { return s->set_recursion(form); }
+int lbfgsx_solver_set_direction_scale(lbfgsx_solver* s, double a) { return s->set_direction_scale(a); }
 int lbfgsx_solver_set_allreduce(lbfgsx_solver* s, void (*fn)(double*, int, void*), void* user)
 {
     return s->set_allreduce(fn, user);

@@ -932,6 +932,11 @@ class _SolverBase:
         recursion over [S, Y, g]: about half the HBM traffic, equal to the vector form only up to rounding)."""
         L.check(self._sol.lbfgsx_solver_set_recursion(self._h, int(form)), "set_recursion: unknown form, or not an L-BFGS solver")
 
+    def set_direction_scale(self, a):
+        """Extension, for tests of the line searches' entry check: the directions computed from now on are a * H * grad
+        (-1 is the method, +1 an ascent direction)."""
+        L.check(self._sol.lbfgsx_solver_set_direction_scale(self._h, float(a)), "set_direction_scale: not an L-BFGS solver")
+
     def set_reducer(self, fn):
         """Extension, row-sharded runs: fn(values) receives a float64 numpy view of a small array and must replace it by
         its sum over all ranks (an all-reduce).  None switches back.  Gram-space recursion only."""
