@@ -853,6 +853,12 @@ int lbfgsx_b_cauchy_scan(lbfgsx_ctx* ctx, int64_t first, int64_t count, int64_t 
                          double t_prev, const double* state_in, int64_t* exit_at, double* state_out);
 /* xcp and the free / newly-active sets from the crossing threshold (Cauchy.h:201-206,219-233,265-282) */
 int lbfgsx_b_cauchy_finish(lbfgsx_ctx* c, double t_cross, double tfinal, int crossed_all, int64_t* nact, int64_t* nfree);
+/* Inspection entry (tests/test_cauchy_statements_gpu.py): copy one vector of the Cauchy search to the host -- the break points
+ * or vecd (n elements of the context's scalar type), or the row numbers the last sort delivered (n int; only the first
+ * nsorted of them mean anything).  Reads only: no pending statement is run, no flag of the context changes.
+ * LBFGSX_E_INVALID for an unknown selector, a null pointer or a context that is not bounded. */
+enum { LBFGSX_CV_BRK = 0, LBFGSX_CV_DVEC = 1, LBFGSX_CV_VALS_OUT = 2 };
+int lbfgsx_b_cauchy_download(lbfgsx_ctx* c, int which, void* host);
 /* drt = xcp - x0 (SubspaceMin.h:130) */
 int lbfgsx_b_sub_begin(lbfgsx_ctx* c);
 /* raw masked W'v: out[0..c) = Y_j.v, out[c..2c) = S_j.v over coordinates whose state has `mask` bits

@@ -167,6 +167,7 @@ def load():
     sig(core, "lbfgsx_b_sub_download", i32, vp, i32, vp)
     sig(core, "lbfgsx_b_sub_upload", i32, vp, i32, vp)
     sig(core, "lbfgsx_b_lu_list_download", i32, vp, vp, i64, C.POINTER(i64))
+    sig(core, "lbfgsx_b_cauchy_download", i32, vp, i32, vp)
     sig(core, "lbfgsx_comm_info", i32, vp, C.POINTER(i32 * 4))
     sig(core, "lbfgsx_comm_calls", i64, vp, i32)
     sig(core, "lbfgsx_comm_hook_arg", vp, vp, i32)

@@ -230,6 +230,12 @@ struct lbfgsx_ctx
     // direction for "history + the pending pair"; lbfgsx_apply_Hv returns that result when the pair was committed
     bool fuse_post = true;         // LBFGSX_FUSE_POST=0: never speculate
     bool fast_persist_out = true;  // LBFGSX_PERSIST_POLL=0: the fused launch's scalars by copies + stream wait (round 5)
+    // Counts the calls that write a vector from outside the solver's own statements: lbfgsx_upload, lbfgsx_fill and
+    // lbfgsx_gen_rosen_x0, whichever vector they wrote.  What a pass computed ahead from x, g or the bounds (lbfgsb_state::pb_*)
+    // is only used while the count stands.  A write through the raw device pointer lbfgsx_vec returns (the torch plumbing) is
+    // NOT seen: whoever writes that way between lbfgsx_b_post_linesearch_build and the build that follows it must call
+    // lbfgsx_b_force_bounds or an upload first.
+    unsigned vec_writes = 0;
     // the line search's first trial, evaluated ahead by lbfgsx_b_dg_maxstep_trial (L-BFGS-B): what lbfgsx_trial returns when it
     // is asked for exactly this step of this objective between these buffers -- and forgets otherwise
     bool st_valid = false;

@@ -594,7 +594,7 @@ int lbfgsx_b_cauchy_build_partial(lbfgsx_ctx* c, double tau, int64_t* nfree, int
         const int newest = (c->ptr + c->m - 1) % c->m;
         // the pass of the post statements has done this one's work (lbfgsx_b_post_linesearch_build) -- if the solver is where
         // that pass assumed it would be: same iterate, same threshold and lists, and nothing for the clamp to move
-        const bool from_post = b->pb_valid && b->pb_cur == c->cur && b->pb_tau == tau && b->pb_sel_inline == sel_inline &&
+        const bool from_post = b->pb_valid && b->pb_cur == c->cur && b->pb_writes == c->vec_writes && b->pb_tau == tau && b->pb_sel_inline == sel_inline &&
                                b->pb_wc == wc && !sel_ahead && (!force || b->pb_r[5] == 0.0);
         b->pb_valid = false;
         if (from_post)
@@ -932,6 +932,23 @@ int lbfgsx_b_cauchy_finish(lbfgsx_ctx* c, double t_cross, double tfinal, int cro
     b->drt_ready = fuse;
     b->na_prev = int64_t(r[0]);
     b->na_n = (want_list && r[2] >= 0 && r[2] <= double(b->na_cap)) ? int64_t(r[2]) : -1;
+    return LBFGSX_OK;
+}
+
+// inspection entry: the break points, vecd or the sorted row numbers as they stand; nothing of the context changes
+int lbfgsx_b_cauchy_download(lbfgsx_ctx* c, int which, void* host)
+{
+    if (!c || !c->bstate || !host || which < LBFGSX_CV_BRK || which > LBFGSX_CV_VALS_OUT)
+    {
+        set_error("lbfgsx_b_cauchy_download: needs a bounded context, a LBFGSX_CV_* selector and a host pointer");
+        return LBFGSX_E_INVALID;
+    }
+    lbfgsx::DeviceGuard dev_guard_(c->device);
+    const lbfgsb_state* b = c->bstate;
+    const void* dev = which == LBFGSX_CV_BRK ? b->brk : which == LBFGSX_CV_DVEC ? b->dvec : static_cast<const void*>(b->vals_out);
+    const size_t bytes = size_t(c->n) * (which == LBFGSX_CV_VALS_OUT ? sizeof(int) : c->esz);
+    LBFGSX_HIP(lbfgsx::copy_async(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    LBFGSX_HIP(lbfgsx::stream_sync(c->stream));
     return LBFGSX_OK;
 }
 

@@ -310,6 +310,7 @@ int lbfgsx_b_post_linesearch_build(lbfgsx_ctx* c, double tau, double* projgnorm,
     });
     b->pb_valid = true;
     b->pb_cur = c->cur;
+    b->pb_writes = c->vec_writes;
     b->pb_tau = tau;
     b->pb_sel_inline = sel_inline;
     g_pb_runs++;

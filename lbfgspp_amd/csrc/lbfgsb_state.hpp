@@ -111,6 +111,7 @@ struct lbfgsb_state
     bool rhs_identity = true;             // LBFGSX_RHS_IDENTITY=0: a sweep gets W_P'(-rhs) from a pass over P (kx_rows<NA = 1>), as before
     bool pb_valid = false;                // pb_r holds what k_cauchy_build would deliver for the state described below
     int pb_cur = -1;                      // the iterate buffer the pass read
+    unsigned pb_writes = 0;               // ctx::vec_writes when the pass ran: an upload since then may have moved x, g or a bound
     double pb_tau = 0.0;
     bool pb_wc = false, pb_sel_inline = false;
     double pb_r[6] = {0, 0, 0, -1, -1, 0};  // d.d, #free, #ordered, #listed outside rows, #sort candidates | #rows the clamp moves

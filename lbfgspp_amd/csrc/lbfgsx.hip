@@ -607,6 +607,7 @@ void* lbfgsx_vec(lbfgsx_ctx* c, int which)
 int lbfgsx_upload(lbfgsx_ctx* c, int which, const void* host)
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
+    c->vec_writes++;
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
     LBFGSX_SETTLE(c);
     void* p = vec_ptr(c, which);
@@ -686,6 +687,7 @@ int lbfgsx_gen_diag_quad(lbfgsx_ctx* c, double kappa, uint64_t seed)
 int lbfgsx_gen_rosen_x0(lbfgsx_ctx* c, uint64_t seed)
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
+    c->vec_writes++;
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
     DISPATCH_T(c, { LBFGSX_LAUNCH(k_gen_rosen<T>, dim3(2048), dim3(256), 0, c->stream, P<T>(c->xb[c->cur]),
                                        c->n, seed, c->shard_off); });
@@ -696,6 +698,7 @@ int lbfgsx_gen_rosen_x0(lbfgsx_ctx* c, uint64_t seed)
 int lbfgsx_fill(lbfgsx_ctx* c, int which, double value)
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
+    c->vec_writes++;
     c->spec_valid = false;  // a buffer the stored speculative direction was computed from may change (lbfgsx_apply_Hv)
     LBFGSX_SETTLE(c);
     void* p = vec_ptr(c, which);
