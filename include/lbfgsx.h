@@ -99,8 +99,20 @@ int lbfgsx_bfgs_stage_correction_host(lbfgsx_ctx* c, const void* s, const void* 
  * BFGSMat.h:42-48.  Meant for small n only. */
 int lbfgsx_bfgs_download_history(lbfgsx_ctx* c, void* S_out, void* Y_out, int* ncorr, int* ptr, double* theta);
 /* BFGSMat::apply_Hv (BFGSMat.h:276-302): D = a * H * v where v is a named vector; also returns
- * dg = G . D fused into the last pass when v == LBFGSX_VEC_G (LBFGS.h:123 of the next iteration). */
+ * dg = v . D fused into the last pass: G . D when v == LBFGSX_VEC_G (LBFGS.h:123 of the next iteration).  For any other
+ * vector it is the dot with that vector, in the step launches and in the persistent launch alike. */
 int lbfgsx_apply_Hv(lbfgsx_ctx* c, int v_which, double a, double* dg);
+/* inspection entry: the dots of the recursion as the last product left them, out[k] = sc[dot(k)] widened to double, k < count
+ * (1 <= count <= 2m + 1).  With c pairs stored a product leaves 2c + 1 of them: out[i] = s_i . q of the first loop (i < c,
+ * columns newest -> oldest, BFGSMat.h:288), out[c + t] = y_i . q of the second loop (t < c, i = c-1-t, :298) and out[2c] = v . D.
+ * Every form stores them: the step launches, the persistent launch, the fused post form (out[0] by its step 0) and the launch
+ * from the gradient (out[0] by the post-form trial before it).  The call reads; it settles no step that is still owed and
+ * invalidates nothing.  A launch that ended one step early (lbfgsx_last_in_trial_request below) leaves out[2c] unset -- the
+ * slot keeps what an earlier product stored there -- until the step has run: a step launch (lbfgsx_download, lbfgsx_vec, a
+ * second trial, ...) stores it there, and so does a first trial that forms the step in its own pass (lbfgsx_trial_first),
+ * besides returning it in *dg_init.  Every post-form trial (lbfgsx_ls_post_in_trial) rewrites out[0]: it holds the first dot
+ * of the NEXT product from then on; out[1 .. 2c] stay the last product's until the next launch. */
+int lbfgsx_bfgs_download_dots(lbfgsx_ctx* c, double* out, int count);
 
 /* ---- L-BFGS driver statements ------------------------------------------------------------------------*/
 /* fx = f(x, grad); gnorm = grad.norm(); x.norm()   (LBFGS.h:91-92,100) with a built-in objective */

@@ -99,6 +99,7 @@ def load():
     sig(core, "lbfgsx_bfgs_theta", dbl, vp)
     sig(core, "lbfgsx_bfgs_add_correction_host", i32, vp, vp, vp)
     sig(core, "lbfgsx_bfgs_download_history", i32, vp, vp, vp, C.POINTER(i32), C.POINTER(i32), pd)
+    sig(core, "lbfgsx_bfgs_download_dots", i32, vp, pd, i32)
     sig(core, "lbfgsx_apply_Hv", i32, vp, i32, dbl, pd)
     sig(core, "lbfgsx_eval", i32, vp, i32, pd, pd, pd)
     sig(core, "lbfgsx_norms", i32, vp, pd, pd)

@@ -765,6 +765,28 @@ int lbfgsx_bfgs_download_history(lbfgsx_ctx* c, void* S_out, void* Y_out, int* n
     return LBFGSX_OK;
 }
 
+// inspection entry: the recursion's dots as the last product left them in sc[dot(0 .. count-1)]; nothing of the context changes
+// (a step still owed stays owed: dot(2c) is then the previous product's)
+int lbfgsx_bfgs_download_dots(lbfgsx_ctx* c, double* out, int count)
+{
+    if (!c || !out || count < 1 || count > 2 * c->m + 1)
+    {
+        set_error("lbfgsx_bfgs_download_dots: needs a context, a host pointer and 1 <= count <= 2m + 1");
+        return LBFGSX_E_INVALID;
+    }
+    lbfgsx::DeviceGuard dev_guard_(c->device);
+    std::vector<double> raw(size_t(count), 0.0);  // count elements of T, never more than count doubles
+    LBFGSX_HIP(lbfgsx::copy_async(raw.data(), static_cast<const char*>(c->sc) + size_t(c->sl.dot(0)) * c->esz, size_t(count) * c->esz,
+                                  hipMemcpyDeviceToHost, c->stream));
+    LBFGSX_HIP(lbfgsx::stream_sync(c->stream));
+    DISPATCH_T(c, {
+        const T* h = reinterpret_cast<const T*>(raw.data());
+        for (int i = 0; i < count; i++)
+            out[i] = double(h[i]);
+    });
+    return LBFGSX_OK;
+}
+
 int lbfgsx_commit_correction(lbfgsx_ctx* c)
 {
     lbfgsx::DeviceGuard dev_guard_(c->device);
@@ -849,7 +871,6 @@ static int apply_Hv_t(lbfgsx_ctx* c, const T* v, T a, double* dg)
     c->last.drop();  // d is computed anew
     T* q = P<T>(c->d);
     T* sc = P<T>(c->sc);
-    const T* gcur = P<T>(c->gb[c->cur]);
     const ScLayout& sl = c->sl;
     // physical columns newest -> oldest (BFGSMat.h:284-287)
     std::vector<int> pcol(size_t(cn > 0 ? cn : 1));  // any history length (the reference has no limit on m)
@@ -973,11 +994,12 @@ static int apply_Hv_t(lbfgsx_ctx* c, const T* v, T a, double* dg)
     auto Ycol = [&](int i) { return static_cast<const T*>(c->col(c->Y, pcol[i])); };
     int rc;
     TwoLoopArgs args = {0, 0, 0, 0, 0, 0};
+    // the last step reduces against v, as the persistent launch does (its `vin`): v . d, which is grad . d when v is the gradient
     if (cn == 0)
     {
         // res = a*v; res /= theta with theta == 1 is the identity (BFGSMat.h:283,293)
         args.i_out = sl.dot(0);
-        if ((rc = launch(TL_INIT, nullptr, gcur, args)))
+        if ((rc = launch(TL_INIT, nullptr, v, args)))
             return rc;
     }
     else
@@ -1006,7 +1028,7 @@ static int apply_Hv_t(lbfgsx_ctx* c, const T* v, T a, double* dg)
             args.i_num2 = sl.dot(L - 1);
             args.i_den = sl.ys(pcol[i]);
             args.i_out = sl.dot(L);
-            if ((rc = launch(TL_ADD, Scol(i), (t < cn - 1) ? Ycol(i - 1) : gcur, args)))
+            if ((rc = launch(TL_ADD, Scol(i), (t < cn - 1) ? Ycol(i - 1) : v, args)))
                 return rc;
         }
     }

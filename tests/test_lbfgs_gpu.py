@@ -69,8 +69,14 @@ def test_apply_Hv_matches_oracle(A, oracle, dtype, n, m, npairs):
     scale = np.abs(ref).max() + 1e-300
     eps = np.finfo(dt).eps
     assert np.abs(got - ref).max() <= 4 * eps * scale, "two-loop recursion deviates from the oracle"
-    # with order-independent reductions the results are expected to be bit-identical almost everywhere
-    assert np.mean(got == ref) > 0.99
+    # the oracle equals the exact reference on these inputs, every element (tests/test_twoloop_ref_cpu.py), and no exact dot
+    # lies near a rounding boundary: the product is held to the exact reference, every element
+    import twoloop_ref as T
+    Sr, Yr, ptr = T.ring_fill([(S[k], Y[k]) for k in range(npairs)], m)
+    exact = T.two_loop(Sr, Yr, ptr, m, v, -1.0, None, dt)
+    assert not exact.ambiguous
+    assert np.array_equal(got, exact.d) and np.array_equal(ref, exact.d)
+    assert dg.value == exact.dg
     # fused dg = v . d
     want = float(np.dot(v.astype(np.float64), got.astype(np.float64)))
     assert abs(dg.value - want) <= 1e-5 * abs(want) + 1e-30 if dtype == O.F32 else abs(dg.value - want) <= 1e-12 * abs(want) + 1e-300
@@ -464,7 +470,16 @@ def test_fused_post_launch_statement_level(A, oracle, dtype, n, m, npairs, accep
     c.close()
     ref = oracle.apply_Hv(dtype, m, hist_S, hist_Y, g, -1.0)
     scale = np.abs(ref).max() + 1e-300
-    assert np.abs(got - ref).max() <= 4 * np.finfo(dt).eps * scale and np.mean(got == ref) > 0.99
+    assert np.abs(got - ref).max() <= 4 * np.finfo(dt).eps * scale
+    # held to the exact reference, every element (see test_apply_Hv_matches_oracle).  Three of these inputs (n = 70002 rejected in
+    # f64, n = 300002 in both types) have an exact dot within the accumulators' worst-case bound of a rounding boundary: there the
+    # contract admits two results, and the product is held to the oracle's -- every element as well
+    import twoloop_ref as T
+    Sr, Yr, ptr = T.ring_fill([(hist_S[k], hist_Y[k]) for k in range(len(hist_S))], m)
+    exact = T.two_loop(Sr, Yr, ptr, m, g, -1.0, None, dt)
+    assert np.array_equal(got, ref)
+    if not exact.ambiguous:
+        assert np.array_equal(got, exact.d) and dg.value == exact.dg
     want = float(np.dot(g.astype(f64), got.astype(f64)))
     assert abs(dg.value - want) <= (1e-12 if dtype == O.F64 else 1e-5) * abs(want)
 
