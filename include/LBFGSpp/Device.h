@@ -109,6 +109,7 @@ class TermObjective
     bool m_wraps = false;                 // a PeriodicGridObjective or PeriodicVolumeObjective: bound with the mask below
     int m_periodic = 0;
     bool m_field = false;                 // a GridFieldObjective: shape and mask, D unknowns per node (the handle's D)
+    bool m_stencil = false;               // a StencilObjective: shape and mask, 3x3 patches
     std::int64_t m_E = 0;                 // a GraphObjective's edges; 0: the handle is bound without any
     const std::int32_t *m_ei = nullptr, *m_ej = nullptr;
     bool m_edges_dev = false;
@@ -149,6 +150,7 @@ protected:
                        : (form == LBFGSX_FORM_LINEAR)  ? lbfgsx_objective_compile_linear(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_MESH)  ? lbfgsx_objective_compile_mesh(&m_h, dt, K, D, node.c_str(), body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRAPH) ? lbfgsx_objective_compile_graph(&m_h, dt, node.c_str(), body.c_str(), log.data(), log.size())
+                       : (form == LBFGSX_FORM_GRID_STENCIL) ? lbfgsx_objective_compile_grid_stencil(&m_h, dt, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRID_FIELD) ? lbfgsx_objective_compile_grid_field(&m_h, dt, D, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_VOLUME_PERIODIC) ? lbfgsx_objective_compile_volume_periodic(&m_h, dt, body.c_str(), log.data(), log.size())
                        : (form == LBFGSX_FORM_GRID_PERIODIC) ? lbfgsx_objective_compile_grid_periodic(&m_h, dt, body.c_str(), log.data(), log.size())
@@ -180,6 +182,7 @@ protected:
         m_periodic = mask;
     }
     void set_field() { m_field = true; }
+    void set_stencil() { m_stencil = true; }
     void set_elements(std::int64_t E, const std::int32_t* elems, bool on_device)
     {
         m_E = E;
@@ -284,6 +287,8 @@ public:
             detail::check(lbfgsx_objective_bind_graph(c, m_h, m_E, m_ei, m_ej, m_edges_dev ? 1 : 0, p, m_c, &id));
         else if (m_field)
             detail::check(lbfgsx_objective_bind_grid_field(c, m_h, m_rows, m_cols, m_periodic, p, m_c, &id));
+        else if (m_stencil)
+            detail::check(lbfgsx_objective_bind_grid_stencil(c, m_h, m_rows, m_cols, m_periodic, p, m_c, &id));
         else if (m_volume && m_wraps)
             detail::check(lbfgsx_objective_bind_volume_periodic(c, m_h, m_slabs, m_rows, m_cols, m_periodic, p, m_c, &id));
         else if (m_wraps)
@@ -411,6 +416,37 @@ public:
         this->set_shape(rows, cols);
         this->set_periodic(periodic);
         this->set_field();
+    }
+};
+
+// An objective of 3x3-node terms on a row-major rows x cols grid, open or periodic per direction (include/lbfgsx.h, "grid
+// stencil objectives"): rows >= 3, cols >= 3, periodic is the PeriodicGridObjective's mask, 0 = open.  Patch (r, c) has the nodes
+// x[3*dr + dc] = x[r+dr, c+dc], dr, dc = 0, 1, 2, modulo the extents (its centre is x[4]), and exists iff (c < cols-2 or bit 0)
+// and (r < rows-2 or bit 1).  The body is the text of one patch and sees T, const T x[9], T g[9], int64_t i, row, col (those of
+// x[0]), const int64_t j[9] (the flat indices of the nine nodes, j[0] == i), rows, cols, periodic, p0..p3 and c[8].
+//     StencilObjective<double> f(rows, cols, 3, "const T l = (((x[1] + x[3]) + x[5]) + x[7]) - T(4) * x[4];"
+//         "for (int k = 0; k < 9; k++) g[k] = T(0); g[1] = l; g[3] = l; g[5] = l; g[7] = l; g[4] = T(-4) * l;"
+//         "return T(0.5) * (l * l);");                                                        // sum (Laplace u)^2 / 2 on a torus
+// Accepted and refused where a PeriodicGridObjective is; an extent < 3, a mask outside 0 .. 3 or a shape that does not multiply
+// to n throws std::invalid_argument at minimize(), the values named.
+template <typename Scalar>
+class StencilObjective : public TermObjective<Scalar>
+{
+public:
+    StencilObjective(std::int64_t rows, std::int64_t cols, int periodic, const std::string& body)
+        : TermObjective<Scalar>(LBFGSX_FORM_GRID_STENCIL, 9, body, "StencilObjective: ")
+    {
+        this->set_shape(rows, cols);
+        this->set_periodic(periodic);
+        this->set_stencil();
+    }
+    // a handle compiled elsewhere (lbfgsx_objective_compile_grid_stencil); it stays the caller's
+    StencilObjective(const lbfgsx_objective* compiled, std::int64_t rows, std::int64_t cols, int periodic)
+        : TermObjective<Scalar>(compiled)
+    {
+        this->set_shape(rows, cols);
+        this->set_periodic(periodic);
+        this->set_stencil();
     }
 };
 
@@ -618,6 +654,7 @@ struct is_compiled_objective
                                   std::is_same<F, PeriodicGridObjective<Scalar> >::value ||
                                   std::is_same<F, PeriodicVolumeObjective<Scalar> >::value ||
                                   std::is_same<F, GridFieldObjective<Scalar> >::value ||
+                                  std::is_same<F, StencilObjective<Scalar> >::value ||
                                   std::is_same<F, MeshObjective<Scalar> >::value || std::is_same<F, LinearObjective<Scalar> >::value ||
                                   std::is_same<F, MultiLinearObjective<Scalar> >::value ||
                                   std::is_same<F, GraphLinearObjective<Scalar> >::value ||

@@ -251,7 +251,8 @@ int lbfgsx_objective_bound(const lbfgsx_ctx* c, const void* p[4]);
  * asm and the line numbers are those of lbfgsx_objective_compile. */
 enum { LBFGSX_FORM_TERM = 0, LBFGSX_FORM_CHAIN = 1, LBFGSX_FORM_GRID = 2, LBFGSX_FORM_GRAPH = 3, LBFGSX_FORM_MESH = 4, LBFGSX_FORM_LINEAR = 5,
        LBFGSX_FORM_LINEAR_MULTI = 6, LBFGSX_FORM_DENSE = 7, LBFGSX_FORM_LINEAR_GRAPH = 8, LBFGSX_FORM_VOLUME = 9,
-       LBFGSX_FORM_GRID_PERIODIC = 10, LBFGSX_FORM_VOLUME_PERIODIC = 11, LBFGSX_FORM_GRID_FIELD = 12 };
+       LBFGSX_FORM_GRID_PERIODIC = 10, LBFGSX_FORM_VOLUME_PERIODIC = 11, LBFGSX_FORM_GRID_FIELD = 12,
+       LBFGSX_FORM_GRID_STENCIL = 13 };
 int lbfgsx_objective_compile_chain(lbfgsx_objective** out, int dtype, int K, const char* body, char* log, size_t log_len);
 long long lbfgsx_objective_source_chain(int dtype, int K, const char* body, char* out, size_t len);
 int lbfgsx_objective_form(const lbfgsx_objective* obj);
@@ -395,6 +396,45 @@ long long lbfgsx_objective_source_grid_field(int dtype, int D, const char* body,
 int lbfgsx_objective_bind_grid_field(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
                                      const void* const p[4], const double cs[8], int* id);
 int lbfgsx_objective_D(const lbfgsx_objective* obj);
+/* ---- grid stencil objectives: 3x3-node terms on a row-major grid ------------------------------------------------------------
+ * One term per 3x3 block of nodes, open or periodic per direction: energies that need a second difference at a node -- plate
+ * bending and thin-plate splines, sum (Laplace u)^2 and the Hessian-Frobenius norm with its u_xy term, Swift-Hohenberg and
+ * phase-field-crystal functionals, second-order TV and TGV-type image priors, 3x3 clique priors (Fields of Experts), Willmore
+ * and Helfrich energies in the Monge gauge, anything on a 9-point stencil.
+ *   Layout.  x is a row-major rows x cols array, n = rows*cols, rows >= 3 and cols >= 3, so that the three nodes of a patch
+ *     along an axis are distinct on a periodic axis too.
+ *   Mask.  `periodic` is the periodic grid form's: bit 0 the column direction, bit 1 the row direction, 0 = open.
+ *   Patch.  Patch (r, c) has the nodes x[3*dr + dc] = x[r(+)dr, c(+)dc], dr, dc in {0, 1, 2}, (+) modulo the extent; its centre
+ *     is slot 4.  It exists iff (c < cols-2 or bit 0) and (r < rows-2 or bit 1).
+ *   Body.  The text of one patch; the generated method is
+ *       T term(const T (&x)[9], T (&g)[9], int64_t i, int64_t row, int64_t col, const int64_t (&j)[9]) const
+ *     i, row and col are those of slot 0; j[k] are the flat indices of the nine nodes, j[0] == i.  The body also sees rows, cols,
+ *     periodic, p0..p3 and c[8].  It may read p0[j[k]]; a patch that does not exist is never evaluated and no index outside
+ *     [0, n) is loaded.
+ *   Gradient.  grad[r,c] = the sum of g[3*dr + dc] of patch (r(-)dr, c(-)dc) over dr = 2, 1, 0 (outer) and dc = 2, 1, 0 (inner):
+ *     g[8] of (r(-)2, c(-)2) + g[7] of (r(-)2, c(-)1) + g[6] of (r(-)2, c) + g[5] of (r(-)1, c(-)2) + .. + g[0] of (r, c) -- the
+ *     patches that exist, in this fixed order, started from the first (no leading 0 +).  (-) wraps on a periodic axis; on an
+ *     open axis a negative origin means the patch does not exist.  On a torus the order is translation-invariant.
+ *   f = the order-independent (compensated) sum of the existing patches' values, each added once, by the owner of the patch's
+ *     origin.  One rounding per source operation, no contraction, no floating-point atomic.  In the trial kernels every window
+ *     value is xp + step*d, never a read of the x the launch writes.
+ *   Per-node terms.  A per-node term is written inside the body.  The term of the node in slot (dr, dc) is added by a patch iff
+ *       (dr == 0 || (!(periodic & 2) && row + 3 == rows)) && (dc == 0 || (!(periodic & 1) && col + 3 == cols)):
+ *     node (row, col) goes to the patch that starts there; on an open axis the last layer of patches picks up the two layers
+ *     of nodes no patch starts at, and on a periodic axis there is nothing to pick up.  Every node is then counted exactly
+ *     once.  A term on the CENTRE of every patch (a double well on x[4], say) is another sum: over the patches, not the nodes.
+ * lbfgsx_objective_compile_grid_stencil wraps the body for the four kernels of csrc/grid_stencil_kernels.cuh (same arguments,
+ * grids, reductions, out[] layout and completion signal as the periodic grid form's; the packs one and two rows away from a
+ * thread's pack are re-read through the caches) and caches by (form, body, K, dtype) with K = 9 (lbfgsx_objective_K): the
+ * shape and the mask are not part of the key, and the same text as a periodic grid and as a grid stencil objective are two
+ * entries.  The form is LBFGSX_FORM_GRID_STENCIL.  lbfgsx_objective_bind_grid_stencil refuses (LBFGSX_E_INVALID, the values
+ * named) a handle of another form, an extent < 3, rows*cols that is not n or overflows, and a mask with bits above 3; every
+ * other bind call refuses this handle, lbfgsx_objective_bind saying that it is bound with its shape and mask.
+ * lbfgsx_objective_shape and lbfgsx_objective_periodic read the bound shape and mask back. */
+int lbfgsx_objective_compile_grid_stencil(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len);
+long long lbfgsx_objective_source_grid_stencil(int dtype, const char* body, char* out, size_t len);
+int lbfgsx_objective_bind_grid_stencil(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                       const void* const p[4], const double cs[8], int* id);
 /* ---- graph objectives: edge terms over an index list ---------------------------------------------------------------------
  * x has n coordinates, the NODES; the caller gives E edges as two int32 arrays ei[E], ej[E], and
  *     f(x) = sum over nodes v of psi(x[v]; v)  +  sum over edges e of phi(x[ei[e]], x[ej[e]]; e)

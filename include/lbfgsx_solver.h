@@ -162,6 +162,12 @@ int lbfgsx_solver_minimize_volume_periodic(lbfgsx_solver* s, const lbfgsx_object
 int lbfgsx_solver_minimize_grid_field(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
                                       const void* const p[4], int host_mask, const double c[8], void* x, const void* lb,
                                       const void* ub, lbfgsx_trace* trace, lbfgsx_result* out);
+/* lbfgsx_solver_minimize_grid_periodic for a grid stencil objective (include/lbfgsx.h, lbfgsx_objective_compile_grid_stencil): x
+ * is a row-major rows x cols array.  An extent < 3, a product that overflows, a mask above 3 and a handle of another form are
+ * refused with LBFGSX_E_INVALID; lbfgsx_solver_minimize_obj refuses this handle (it carries no shape). */
+int lbfgsx_solver_minimize_grid_stencil(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                        const void* const p[4], int host_mask, const double c[8], void* x, const void* lb,
+                                        const void* ub, lbfgsx_trace* trace, lbfgsx_result* out);
 /* lbfgsx_solver_minimize_obj for a graph objective (include/lbfgsx.h, lbfgsx_objective_compile_graph): x has n nodes, the E
  * edges are (ei[e], ej[e]), host arrays or device arrays (edges_on_device != 0).  counts[k] is the number of elements of
  * p[k] where host_mask says it is a host array (n or E; NULL: n for all).  A handle of another form is refused with

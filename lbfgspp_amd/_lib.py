@@ -247,6 +247,13 @@ def load():
     sig(core, "lbfgsx_objective_D", i32, vp)
     sig(sol, "lbfgsx_solver_minimize_grid_field", i32, vp, vp, i64, i64, i32, C.POINTER(vp * 4), i32, C.POINTER(dbl * 8), vp, vp,
         vp, C.POINTER(Trace), C.POINTER(Result))
+    # grid stencil objectives: the periodic grid form's calls with a body of nine nodes
+    sig(core, "lbfgsx_objective_compile_grid_stencil", i32, C.POINTER(vp), i32, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_source_grid_stencil", C.c_longlong, i32, C.c_char_p, C.c_char_p, C.c_size_t)
+    sig(core, "lbfgsx_objective_bind_grid_stencil", i32, vp, vp, i64, i64, i32, C.POINTER(vp * 4), C.POINTER(dbl * 8),
+        C.POINTER(i32))
+    sig(sol, "lbfgsx_solver_minimize_grid_stencil", i32, vp, vp, i64, i64, i32, C.POINTER(vp * 4), i32, C.POINTER(dbl * 8), vp, vp,
+        vp, C.POINTER(Trace), C.POINTER(Result))
     # graph objectives: two bodies; the edges travel with the binding
     i32p, u32p = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
     sig(core, "lbfgsx_objective_compile_graph", i32, C.POINTER(vp), i32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t)

@@ -8,7 +8,7 @@
 // same kernel text, the same flags, the same sums.  The code object is loaded per device with hipModuleLoadData and the
 // kernels are launched with hipModuleLaunchKernel from the arguments launch_args.hpp works out for both forms.
 //
-// Thirteen forms of objective share all of this (include/lbfgsx.h): a TERM objective (terms that do not overlap: the struct with
+// Fourteen forms of objective share all of this (include/lbfgsx.h): a TERM objective (terms that do not overlap: the struct with
 // pack / tail / finish above), a CHAIN objective (one term starting at every coordinate: a second generated wrapper that
 // includes chain_kernels.cuh and instantiates its four kernels, which take the arguments of the four above) and a GRID
 // objective (one term per 2x2 cell of a row-major grid: a third wrapper around grid_kernels.cuh, whose struct also carries
@@ -29,7 +29,9 @@
 // in the directions of a mask: wrappers around periodic_grid_kernels.cuh and periodic_volume_kernels.cuh whose structs carry
 // the extents and the mask, and whose body also sees the flat indices of its corners.  A thirteenth, a GRID FIELD objective, is
 // the periodic grid form with D unknowns per node: a wrapper around grid_field_kernels.cuh with the same members, D a constant
-// of the struct and part of the cache key.  A handle carries its form; the four slots of the
+// of the struct and part of the cache key.  A fourteenth, a GRID STENCIL objective (one term per 3x3 block of nodes of a row-major
+// grid, open or periodic per direction), is a wrapper around grid_stencil_kernels.cuh with the periodic grid form's members
+// and a body of nine nodes.  A handle carries its form; the four slots of the
 // loaded-kernel table and everything that launches them are the same.  What the forms differ in -- names, kernel names, struct
 // members, the bodies' signatures, the K and D accepted, the cache key -- is one row each of kForms below; the generator, the
 // validation and the refusals are written once and read it.
@@ -89,7 +91,7 @@ struct FormDesc
     "    const T* part;\n    const int32_t* long_col;\n    const uint32_t* long_chunk;\n"           \
     "    int64_t R, nnz;\n    int32_t L, C, nlong, pad_;\n"
 const BodyDesc kNoBody = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-const FormDesc kForms[13] = {
+const FormDesc kForms[14] = {
     {"term objective", "", "ObjTerm", "#include \"lbfgs_kernels.cuh\"\n#include \"lbfgsb_kernels.cuh\"\n",
      {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial", nullptr, nullptr, "k_trial_post"}, "", kNoBody,
      {"    // one term: x[0..K) in, g[0..K) out, the term's value returned\n", TERM_SIGNATURE, "objective_body", "body", nullptr,
@@ -236,7 +238,17 @@ const FormDesc kForms[13] = {
       "T term(const T (&x)[4 * D], T (&g)[4 * D], int64_t i, int64_t row, int64_t col, const int64_t (&j)[4]) const",
       "objective_body", "body", nullptr, nullptr},
      "", 4, 4, 1, 3, "a cell has K = 4 corners", "D = # is not supported: a node has D = 1, 2 or 3 unknowns", false, true,
-     "shape, mask and D"}};
+     "shape, mask and D"},
+    {"grid stencil objective", "_grid_stencil", "ObjGridStencil", "#include \"grid_stencil_kernels.cuh\"\n",
+     {"k_stencil_eval", "k_stencil_trial", "k_stencil_b_eval", "k_stencil_b_dg_maxstep_trial"},
+     // launch_args.hpp: StencilArgs
+     "    int64_t rows, cols;\n    int periodic, pad_;\n", kNoBody,
+     {"    // the patch whose origin is node (row, col), flat index i = row*cols + col: x[3*dr + dc] = x[row+dr, col+dc] in, dr, dc =\n"
+      "    // 0, 1, 2, + modulo the extent; j: the flat indices of those nine nodes, j[0] == i; periodic: bit 0 the column direction,\n"
+      "    // bit 1 the row direction; its nine partial derivatives g out, its value returned\n",
+      "T term(const T (&x)[9], T (&g)[9], int64_t i, int64_t row, int64_t col, const int64_t (&j)[9]) const", "objective_body",
+      "body", nullptr, nullptr},
+     "", 9, 9, 1, 1, "a patch reads K = 9 coordinates", nullptr, false, false, "shape and mask"}};
 #undef LINEAR_MEMBERS
 #undef TERM_SIGNATURE
 #undef POINT_SIGNATURE
@@ -750,6 +762,10 @@ long long lbfgsx_objective_source_grid_field(int dtype, int D, const char* body,
 {
     return objective_source(LBFGSX_FORM_GRID_FIELD, dtype, 4, body, out, len, nullptr, D);
 }
+long long lbfgsx_objective_source_grid_stencil(int dtype, const char* body, char* out, size_t len)
+{
+    return objective_source(LBFGSX_FORM_GRID_STENCIL, dtype, 9, body, out, len);
+}
 long long lbfgsx_objective_source_graph(int dtype, const char* node_body, const char* edge_body, char* out, size_t len)
 {
     return objective_source(LBFGSX_FORM_GRAPH, dtype, 2, edge_body, out, len, node_body);
@@ -804,6 +820,10 @@ int lbfgsx_objective_compile_volume_periodic(lbfgsx_objective** out, int dtype, 
 int lbfgsx_objective_compile_grid_field(lbfgsx_objective** out, int dtype, int D, const char* body, char* log, size_t log_len)
 {
     return objective_compile(LBFGSX_FORM_GRID_FIELD, out, dtype, 4, body, log, log_len, nullptr, D);
+}
+int lbfgsx_objective_compile_grid_stencil(lbfgsx_objective** out, int dtype, const char* body, char* log, size_t log_len)
+{
+    return objective_compile(LBFGSX_FORM_GRID_STENCIL, out, dtype, 9, body, log, log_len);
 }
 int lbfgsx_objective_compile_graph(lbfgsx_objective** out, int dtype, const char* node_body, const char* edge_body, char* log,
                                    size_t log_len)
@@ -1081,7 +1101,8 @@ int lbfgsx_objective_bind_grid(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64
 int lbfgsx_objective_shape(const lbfgsx_ctx* c, int64_t* rows, int64_t* cols)
 {
     if (!c || !c->term ||
-        (c->term_form != LBFGSX_FORM_GRID && c->term_form != LBFGSX_FORM_GRID_PERIODIC && c->term_form != LBFGSX_FORM_GRID_FIELD))
+        (c->term_form != LBFGSX_FORM_GRID && c->term_form != LBFGSX_FORM_GRID_PERIODIC && c->term_form != LBFGSX_FORM_GRID_FIELD &&
+         c->term_form != LBFGSX_FORM_GRID_STENCIL))
     {
         lbfgsx::set_error("lbfgsx_objective_shape: no grid objective is bound to this context");
         return LBFGSX_E_INVALID;
@@ -1221,11 +1242,40 @@ int lbfgsx_objective_bind_grid_field(lbfgsx_ctx* c, const lbfgsx_objective* obj,
     return objective_bind(c, obj, rows, cols, p, cs, id, 0, periodic);
 }
 
+int lbfgsx_objective_bind_grid_stencil(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                       const void* const p[4], const double cs[8], int* id)
+{
+    if (!c || !obj)
+        return LBFGSX_E_INVALID;
+    if (!handle_is(obj, LBFGSX_FORM_GRID_STENCIL))
+        return LBFGSX_E_INVALID;
+    const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
+    long long prod = 0;
+    if (rows < 3 || cols < 3)
+    {
+        lbfgsx::set_error("grid stencil objective: " + shape +
+                          ": a 3x3 patch needs at least 3 rows and 3 columns (rows >= 3, cols >= 3)");
+        return LBFGSX_E_INVALID;
+    }
+    if (__builtin_mul_overflow((long long) rows, (long long) cols, &prod) || prod != (long long) c->n)
+    {
+        lbfgsx::set_error("grid stencil objective: " + shape + " does not multiply to n = " + std::to_string(c->n));
+        return LBFGSX_E_INVALID;
+    }
+    if (periodic < 0 || periodic > 3)
+    {
+        lbfgsx::set_error("grid stencil objective: periodic = " + std::to_string(periodic) +
+                          ": the mask has bit 0 for the column direction and bit 1 for the row direction (0 .. 3)");
+        return LBFGSX_E_INVALID;
+    }
+    return objective_bind(c, obj, rows, cols, p, cs, id, 0, periodic);
+}
+
 int lbfgsx_objective_periodic(const lbfgsx_ctx* c, int* mask)
 {
     if (!c || !c->term ||
         (c->term_form != LBFGSX_FORM_GRID_PERIODIC && c->term_form != LBFGSX_FORM_VOLUME_PERIODIC &&
-         c->term_form != LBFGSX_FORM_GRID_FIELD))
+         c->term_form != LBFGSX_FORM_GRID_FIELD && c->term_form != LBFGSX_FORM_GRID_STENCIL))
     {
         lbfgsx::set_error("lbfgsx_objective_periodic: no periodic grid or volume objective is bound to this context");
         return LBFGSX_E_INVALID;

@@ -156,6 +156,15 @@ struct GridFieldArgs
     int64_t rows, cols;
     int32_t periodic, pad_;
 };
+// the by-value argument of a grid stencil objective's kernels: layout of the generated struct ObjGridStencil (the periodic
+// grid form's members)
+template <class T>
+struct StencilArgs
+{
+    TermArgs<T> t;
+    int64_t rows, cols;
+    int32_t periodic, pad_;
+};
 // the by-value argument of a graph objective's kernels: layout of the generated struct ObjGraph (TermArgs, then the
 // context's incidence list: uint32 off[n+1], 8-byte entries inc[2E] (graph_entry.hpp), and E)
 struct GraphEntry;
@@ -257,7 +266,7 @@ inline bool form_is_linear(int form) { return form == LBFGSX_FORM_LINEAR || form
 // the forms whose evaluation is a row pass over a CSR matrix and a column walk: those two and the graph-regularised one
 inline bool form_has_csr(int form) { return form_is_linear(form) || form == LBFGSX_FORM_LINEAR_GRAPH; }
 // the objective argument of the bound handle's kernels, by its form: &term for a term or chain objective, &grid for a grid
-// one, &volume for a volume one, &pgrid and &pvolume for the periodic two, &gfield for a grid field one, &graph for a graph one, &mesh for a mesh one, &linear for a linear-model one of either form, &dense for a dense one,
+// one, &volume for a volume one, &pgrid and &pvolume for the periodic two, &gfield for a grid field one, &stencil for a grid stencil one, &graph for a graph one, &mesh for a mesh one, &linear for a linear-model one of either form, &dense for a dense one,
 // &linear_graph for a graph-regularised linear-model one
 template <class T>
 struct BoundArgs
@@ -268,6 +277,7 @@ struct BoundArgs
     PeriodicGridArgs<T> pgrid;
     PeriodicVolumeArgs<T> pvolume;
     GridFieldArgs<T> gfield;
+    StencilArgs<T> stencil;
     GraphArgs<T> graph;
     MeshArgs<T> mesh;
     LinearArgs<T> linear;
@@ -281,6 +291,7 @@ struct BoundArgs
           pgrid{term, c->term_rows, c->term_cols, c->term_periodic, 0},
           pvolume{term, c->term_slabs, c->term_rows, c->term_cols, c->term_periodic, 0},
           gfield{term, c->term_rows, c->term_cols, c->term_periodic, 0},
+          stencil{term, c->term_rows, c->term_cols, c->term_periodic, 0},
           graph{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const GraphEntry*>(c->graph_inc), c->graph_E},
           mesh{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const uint32_t*>(c->graph_inc), c->graph_E,
                c->mesh_D ? c->n / c->mesh_D : 0},
@@ -293,6 +304,7 @@ struct BoundArgs
               : (c->term_form == LBFGSX_FORM_GRID_PERIODIC) ? static_cast<void*>(&pgrid)
               : (c->term_form == LBFGSX_FORM_VOLUME_PERIODIC) ? static_cast<void*>(&pvolume)
               : (c->term_form == LBFGSX_FORM_GRID_FIELD) ? static_cast<void*>(&gfield)
+              : (c->term_form == LBFGSX_FORM_GRID_STENCIL) ? static_cast<void*>(&stencil)
               : (c->term_form == LBFGSX_FORM_GRAPH) ? static_cast<void*>(&graph)
               : (c->term_form == LBFGSX_FORM_MESH)  ? static_cast<void*>(&mesh)
               : form_is_linear(c->term_form)        ? static_cast<void*>(&linear)

@@ -244,6 +244,7 @@ struct LbfgsImpl : lbfgsx_solver
         PeriodicGridObjective<Scalar> wrapped(obj, rows, cols, periodic);            // binds with the mask when there is one (>= 0)
         PeriodicVolumeObjective<Scalar> wrapped3(obj, slabs, rows, cols, periodic);  // ... and three extents
         GridFieldObjective<Scalar> fielded(obj, rows, cols, periodic);               // ... and D unknowns per node
+        StencilObjective<Scalar> patched(obj, rows, cols, periodic);                 // ... and 3x3 patches: by the handle's form
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
         LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
@@ -267,6 +268,7 @@ struct LbfgsImpl : lbfgsx_solver
                                    : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
                                    : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
                                    : field             ? static_cast<TermObjective<Scalar>&>(fielded)
+                                   : (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID_STENCIL) ? static_cast<TermObjective<Scalar>&>(patched)
                                    : (periodic >= 0 && slabs) ? static_cast<TermObjective<Scalar>&>(wrapped3)
                                    : (periodic >= 0)   ? static_cast<TermObjective<Scalar>&>(wrapped)
                                    : slabs             ? static_cast<TermObjective<Scalar>&>(spaced)
@@ -383,6 +385,7 @@ struct LbfgsbImpl : lbfgsx_solver
         PeriodicGridObjective<Scalar> wrapped(obj, rows, cols, periodic);            // binds with the mask when there is one (>= 0)
         PeriodicVolumeObjective<Scalar> wrapped3(obj, slabs, rows, cols, periodic);  // ... and three extents
         GridFieldObjective<Scalar> fielded(obj, rows, cols, periodic);               // ... and D unknowns per node
+        StencilObjective<Scalar> patched(obj, rows, cols, periodic);                 // ... and 3x3 patches: by the handle's form
         GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
         MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
         LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
@@ -406,6 +409,7 @@ struct LbfgsbImpl : lbfgsx_solver
                                    : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
                                    : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
                                    : field             ? static_cast<TermObjective<Scalar>&>(fielded)
+                                   : (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID_STENCIL) ? static_cast<TermObjective<Scalar>&>(patched)
                                    : (periodic >= 0 && slabs) ? static_cast<TermObjective<Scalar>&>(wrapped3)
                                    : (periodic >= 0)   ? static_cast<TermObjective<Scalar>&>(wrapped)
                                    : slabs             ? static_cast<TermObjective<Scalar>&>(spaced)
@@ -999,6 +1003,8 @@ int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, in
             throw std::invalid_argument("a periodic volume objective is minimised with its shape and mask: lbfgsx_solver_minimize_volume_periodic");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID_FIELD)
             throw std::invalid_argument("a grid field objective is minimised with its shape and mask: lbfgsx_solver_minimize_grid_field");
+        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID_STENCIL)
+            throw std::invalid_argument("a grid stencil objective is minimised with its shape and mask: lbfgsx_solver_minimize_grid_stencil");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRAPH)
             throw std::invalid_argument("a graph objective is minimised with its edges: lbfgsx_solver_minimize_graph");
         if (lbfgsx_objective_form(obj) == LBFGSX_FORM_MESH)
@@ -1169,6 +1175,43 @@ int lbfgsx_solver_minimize_grid_field(lbfgsx_solver* s, const lbfgsx_objective* 
     return guarded(out, [&]() {
         s->minimize_obj(obj, int64_t(n), 0, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out, periodic, true);
     });
+}
+
+int lbfgsx_solver_minimize_grid_stencil(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                        const void* const p[4], int host_mask, const double c[8], void* x, const void* lb,
+                                        const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    long long n = 0;
+    const int bad = guarded(out, [&]() {
+        if (!s || !obj)
+            throw std::invalid_argument("lbfgsx_solver_minimize_grid_stencil: invalid argument");
+        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_GRID_STENCIL)
+            throw std::invalid_argument("lbfgsx_solver_minimize_grid_stencil: the handle is not a grid stencil objective "
+                                        "(lbfgsx_objective_compile_grid_stencil)");
+        if (lbfgsx_objective_dtype(obj) != s->dtype)
+            throw std::invalid_argument("lbfgsx_solver_minimize_grid_stencil: the objective was compiled for the other dtype");
+        const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
+        if (rows < 3 || cols < 3)
+            throw std::invalid_argument("grid stencil objective: " + shape +
+                                        ": a 3x3 patch needs at least 3 rows and 3 columns (rows >= 3, cols >= 3)");
+        if (__builtin_mul_overflow((long long) rows, (long long) cols, &n))
+            throw std::invalid_argument("grid stencil objective: " + shape + ": rows*cols overflows");
+        if (periodic < 0 || periodic > 3)
+            throw std::invalid_argument("grid stencil objective: periodic = " + std::to_string(periodic) +
+                                        ": the mask has bit 0 for the column direction and bit 1 for the row direction (0 .. 3)");
+    });
+    if (bad)
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg),
+                      "lbfgsx_solver_minimize_grid_stencil: no HIP device available (this library has no CPU fallback)");
+        return out->status;
+    }
+    return guarded(out,
+                   [&]() { s->minimize_obj(obj, int64_t(n), 0, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out, periodic); });
 }
 
 int lbfgsx_solver_minimize_volume_periodic(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,

@@ -9,7 +9,8 @@ std::runtime_error -> RuntimeError (same messages).  `f` is a built-in device ob
 (`DiagQuadratic(a, b)`, `ExtendedRosenbrock()`), the caller's own term compiled into the same kernels (`TermObjective(body)`,
 `ChainObjective(body)` for terms that overlap, `GridObjective(body, shape)` for 2x2-cell terms on a grid, `VolumeObjective(body, shape)` for 2x2x2-cell terms on a 3-D array,
 `PeriodicGridObjective(body, shape, periodic)` and `PeriodicVolumeObjective(body, shape, periodic)` for those two with wrap-around cells,
-`GridFieldObjective(body, shape, D, periodic)` for a grid whose nodes carry D unknowns, or
+`GridFieldObjective(body, shape, D, periodic)` for a grid whose nodes carry D unknowns,
+`StencilObjective(body, shape, periodic)` for 3x3-node terms on a grid, or
 `GraphObjective(edge_body, edges)` for edge terms over an index list,
 `MeshObjective(elem_body, elements, dim)` for K-node elements with vector unknowns, or
 `LinearObjective(row_body, (rowptr, col, val), n)` for a linear model over a sparse matrix, or
@@ -453,6 +454,58 @@ class GridFieldObjective(TermObjective):
     def _check_n(self, n):
         if self.shape[0] * self.shape[1] * self.D != n:
             raise ValueError("GridFieldObjective: shape = (%d, %d), D = %d does not multiply to n = %d" % (self.shape + (self.D, n)))
+
+
+class StencilObjective(TermObjective):
+    """An objective of 3x3-node terms on a 2-D grid (include/lbfgsx.h, "grid stencil objectives"): energies that need a second
+    difference at a node -- plate bending and thin-plate splines, sum (Laplace u)^2, Swift-Hohenberg and phase-field-crystal
+    functionals, second-order TV priors, 3x3 clique priors, anything on a 9-point stencil.  x is a row-major rows x cols array
+    (flattened, n = rows*cols, rows >= 3, cols >= 3).  periodic is the mask of a PeriodicGridObjective as a number, bit 0 the
+    columns and bit 1 the rows (0 = the open grid, 3 = the torus), or its tuple of flags (rows, cols).  Patch (r, c) has the
+    nodes x[3*dr + dc] = x[r+dr, c+dc], dr, dc = 0, 1, 2, with + modulo the extent (its centre is x[4]) and exists iff
+    (c < cols-2 or the columns wrap) and (r < rows-2 or the rows wrap).  The body is the text of ONE PATCH: it sees T,
+    const T x[9], T g[9] (the patch's nine partial derivatives, to fill), int64_t i, row, col (those of x[0]), const int64_t
+    j[9] (the flat indices of the nine nodes, j[0] == i), rows, cols, int periodic, p0..p3 and c[8], reads data as p0[j[k]],
+    and returns the patch's value.  grad[r,c] is the sum of g[3*dr + dc] of patch (r-dr, c-dc) over dr = 2, 1, 0 (outer) and
+    dc = 2, 1, 0 (inner) with - modulo the extent on a periodic axis, those that exist, in this order.
+
+        plate = StencilObjective("const T l = (((x[1] + x[3]) + x[5]) + x[7]) - T(4) * x[4];"
+                                 "for (int k = 0; k < 9; k++) g[k] = T(0);"
+                                 "g[1] = l; g[3] = l; g[5] = l; g[7] = l; g[4] = T(-4) * l;"
+                                 "return T(0.5) * (l * l);", shape=(rows, cols), periodic=3)
+
+    A per-node term is written inside the body: the patch adds the term of its node (dr, dc) iff (dr == 0 or (the rows do not
+    wrap and row + 3 == rows)) and (dc == 0 or (the columns do not wrap and col + 3 == cols)); every node is then counted
+    once.  Everything else as for a PeriodicGridObjective; usable wherever one is, refused where one is."""
+    _NAME = "StencilObjective"
+    _COMPILE, _SOURCE = "lbfgsx_objective_compile_grid_stencil", "lbfgsx_objective_source_grid_stencil"
+
+    def __init__(self, body, shape, periodic=0, data=(), scalars=()):
+        try:
+            rows, cols = (int(v) for v in shape)
+        except (TypeError, ValueError):
+            raise ValueError("StencilObjective: shape must be (rows, cols)") from None
+        if rows < 3 or cols < 3:
+            raise ValueError("StencilObjective: shape = (%d, %d): a 3x3 patch needs at least 3 rows and 3 columns" % (rows, cols))
+        self.shape = (rows, cols)
+        if isinstance(periodic, (int, np.integer)) and not isinstance(periodic, (bool, np.bool_)):
+            if not 0 <= periodic <= 3:
+                raise ValueError("StencilObjective: periodic = %d: the mask has bit 0 for the column direction and bit 1 for the "
+                                 "row direction (0 .. 3)" % periodic)
+            self.periodic = int(periodic)
+        else:
+            self.periodic = _periodic_mask(self._NAME, periodic, ("rows", "cols"))
+        self.body, self.K = str(body), 9
+        self._h = {}
+        self.set_data(*data)
+        self.set_scalars(*scalars)
+
+    def _form_args(self):
+        return ()
+
+    def _check_n(self, n):
+        if self.shape[0] * self.shape[1] != n:
+            raise ValueError("StencilObjective: shape = (%d, %d) does not multiply to n = %d" % (self.shape + (n,)))
 
 
 def _is_torch(x):
@@ -1085,6 +1138,8 @@ class _SolverBase:
                                                         C.byref(counts), *tail[2:])
         elif isinstance(f, GridFieldObjective):
             rc = self._sol.lbfgsx_solver_minimize_grid_field(self._h, h, f.shape[0], f.shape[1], f.periodic, *tail)
+        elif isinstance(f, StencilObjective):
+            rc = self._sol.lbfgsx_solver_minimize_grid_stencil(self._h, h, f.shape[0], f.shape[1], f.periodic, *tail)
         elif isinstance(f, PeriodicVolumeObjective):
             rc = self._sol.lbfgsx_solver_minimize_volume_periodic(self._h, h, f.shape[0], f.shape[1], f.shape[2], f.periodic, *tail)
         elif isinstance(f, PeriodicGridObjective):
@@ -1114,7 +1169,7 @@ class _SolverBase:
         if not hasattr(f, "objective"):
             raise TypeError("f must be DiagQuadratic, ExtendedRosenbrock, TermObjective(body), ChainObjective(body), "
                             "GridObjective(body, shape), VolumeObjective(body, shape), PeriodicGridObjective(body, shape, periodic), "
-                            "PeriodicVolumeObjective(body, shape, periodic), GridFieldObjective(body, shape, D, periodic), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim), "
+                            "PeriodicVolumeObjective(body, shape, periodic), GridFieldObjective(body, shape, D, periodic), StencilObjective(body, shape, periodic), GraphObjective(edge_body, edges), MeshObjective(elem_body, elements, dim), "
                             "LinearObjective(row_body, matrix, n), GraphLinearObjective(row_body, matrix, edges, edge_body, n), "
                             "MultiLinearObjective(row_body, matrix, features, outputs), "
                             "DenseLinearObjective(row_body, matrix, outputs) or DeviceObjective(fn)")

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Registers, scratch and occupancy of the kernels on the two kernel frames -- own_frame.cuh: graph, mesh and linear-model
-(sparse, multi-output, dense); halo_frame.cuh: chain, grid, volume, the two periodic forms and the grid field form -- in two trees, side by side
+(sparse, multi-output, dense); halo_frame.cuh: chain, grid, volume, the two periodic forms, the grid field form and the grid stencil
+form -- in two trees, side by side
 (profiles/own_frame_kernel_resources.tsv).  No GPU is needed: the generated sources are compiled for gfx950 here.
 
 Each tree (a built checkout: the parent commit's and this one) is asked, in a process of its own, for the generated
@@ -10,6 +11,7 @@ translation unit -- source() -- of
     volume   ASYM8, ALLENCAHN3                                                 (tests/volume_ref.py)
     pgrid    PASYM4, ALLENCAHN; pvolume  PASYM8, ALLENCAHN3                     (tests/periodic_ref.py)
     gfield   FASYM, GL at D = 1, 2, 3                                          (tests/field_ref.py)
+    stencil  SASYM9, PLATE                                                     (tests/stencil_ref.py)
     graph    ASYM_EDGE with and without NODE                                   (tests/graph_ref.py)
     mesh     every (K, D) with the bodies tests/test_mesh_objective_cpu.py compiles (tests/mesh_ref.py)
     linear   LOGISTIC with and without RIDGE                                   (tests/linear_ref.py)
@@ -77,6 +79,10 @@ def emit_sources(tree):
             for D in (1, 2, 3):
                 for name, body in (("fasym", FR.FASYM), ("gl", FR.GL)):
                     out["gfield/D%d/%s/%s" % (D, name, dname)] = A.GridFieldObjective(body, shape=(2, 2), D=D).source(dtype)
+        if hasattr(A, "StencilObjective"):
+            import stencil_ref as SR
+            for name, body in (("sasym9", SR.SASYM9), ("plate", SR.PLATE)):
+                out["stencil/%s/%s" % (name, dname)] = A.StencilObjective(body, shape=(3, 3)).source(dtype)
         for name, node in (("asym+node", GR.NODE), ("asym", None)):
             out["graph/%s/%s" % (name, dname)] = A.GraphObjective(GR.ASYM_EDGE, edges=one_edge, node_body=node).source(dtype)
         for K in (2, 3, 4):
