@@ -103,14 +103,10 @@ class TermObjective
     const Scalar* m_p[4] = {nullptr, nullptr, nullptr, nullptr};
     const Scalar* m_host[4] = {nullptr, nullptr, nullptr, nullptr};
     double m_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    std::int64_t m_rows = 0, m_cols = 0;  // a GridObjective's shape; 0: the handle is bound without one
-    std::int64_t m_slabs = 0;             // a VolumeObjective's slabs, with the two above
-    bool m_volume = false;
-    bool m_wraps = false;                 // a PeriodicGridObjective or PeriodicVolumeObjective: bound with the mask below
-    int m_periodic = 0;
-    bool m_field = false;                 // a GridFieldObjective: shape and mask, D unknowns per node (the handle's D)
-    bool m_stencil = false;               // a StencilObjective: shape and mask, 3x3 patches
-    std::int64_t m_E = 0;                 // a GraphObjective's edges; 0: the handle is bound without any
+    int m_lattice = LBFGSX_FORM_TERM;     // the form a class on a regular array declares (set_lattice): which call binds it
+    std::int64_t m_slabs = 0, m_rows = 0, m_cols = 0;  // its extents (m_slabs: a form on three axes) ...
+    int m_periodic = 0;                                // ... and mask (a form that has one)
+    std::int64_t m_E = 0;                // a GraphObjective's edges; 0: the handle is bound without any
     const std::int32_t *m_ei = nullptr, *m_ej = nullptr;
     bool m_edges_dev = false;
     const std::int32_t* m_elems = nullptr;  // a MeshObjective's connectivity table of m_E rows; null: bound without one
@@ -164,25 +160,16 @@ protected:
             throw std::runtime_error(std::string(who) + log.data());
         m_own = true;
     }
-    void set_shape(std::int64_t rows, std::int64_t cols)
+    // form: the LBFGSX_FORM_* of the class (not of the handle: a handle of another form is refused by the form's bind call);
+    // slabs = 0 on two axes, periodic = 0 for a form without a mask
+    void set_lattice(int form, std::int64_t slabs, std::int64_t rows, std::int64_t cols, int periodic)
     {
-        m_rows = rows;
-        m_cols = cols;
-    }
-    void set_shape3(std::int64_t slabs, std::int64_t rows, std::int64_t cols)
-    {
-        m_volume = true;
+        m_lattice = form;
         m_slabs = slabs;
         m_rows = rows;
         m_cols = cols;
+        m_periodic = periodic;
     }
-    void set_periodic(int mask)
-    {
-        m_wraps = true;
-        m_periodic = mask;
-    }
-    void set_field() { m_field = true; }
-    void set_stencil() { m_stencil = true; }
     void set_elements(std::int64_t E, const std::int32_t* elems, bool on_device)
     {
         m_E = E;
@@ -285,20 +272,29 @@ public:
             detail::check(lbfgsx_objective_bind_mesh(c, m_h, m_E, m_elems, m_edges_dev ? 1 : 0, p, m_c, &id));
         else if (m_E || m_ei || m_ej)
             detail::check(lbfgsx_objective_bind_graph(c, m_h, m_E, m_ei, m_ej, m_edges_dev ? 1 : 0, p, m_c, &id));
-        else if (m_field)
-            detail::check(lbfgsx_objective_bind_grid_field(c, m_h, m_rows, m_cols, m_periodic, p, m_c, &id));
-        else if (m_stencil)
-            detail::check(lbfgsx_objective_bind_grid_stencil(c, m_h, m_rows, m_cols, m_periodic, p, m_c, &id));
-        else if (m_volume && m_wraps)
-            detail::check(lbfgsx_objective_bind_volume_periodic(c, m_h, m_slabs, m_rows, m_cols, m_periodic, p, m_c, &id));
-        else if (m_wraps)
-            detail::check(lbfgsx_objective_bind_grid_periodic(c, m_h, m_rows, m_cols, m_periodic, p, m_c, &id));
-        else if (m_volume)
-            detail::check(lbfgsx_objective_bind_volume(c, m_h, m_slabs, m_rows, m_cols, p, m_c, &id));
-        else if (m_rows || m_cols)
-            detail::check(lbfgsx_objective_bind_grid(c, m_h, m_rows, m_cols, p, m_c, &id));
         else
-            detail::check(lbfgsx_objective_bind(c, m_h, p, m_c, &id));
+            detail::check(bind_lattice(c, p));
+    }
+
+private:
+    // the bind call of the form the class declares; a GridObjective of 0 x 0 is bound as a class without a shape is
+    int bind_lattice(lbfgsx_ctx* c, const void* const p[4])
+    {
+        switch (m_lattice)
+        {
+        case LBFGSX_FORM_GRID_FIELD: return lbfgsx_objective_bind_grid_field(c, m_h, m_rows, m_cols, m_periodic, p, m_c, &id);
+        case LBFGSX_FORM_GRID_STENCIL: return lbfgsx_objective_bind_grid_stencil(c, m_h, m_rows, m_cols, m_periodic, p, m_c, &id);
+        case LBFGSX_FORM_VOLUME_PERIODIC:
+            return lbfgsx_objective_bind_volume_periodic(c, m_h, m_slabs, m_rows, m_cols, m_periodic, p, m_c, &id);
+        case LBFGSX_FORM_GRID_PERIODIC: return lbfgsx_objective_bind_grid_periodic(c, m_h, m_rows, m_cols, m_periodic, p, m_c, &id);
+        case LBFGSX_FORM_VOLUME: return lbfgsx_objective_bind_volume(c, m_h, m_slabs, m_rows, m_cols, p, m_c, &id);
+        case LBFGSX_FORM_GRID:
+            if (m_rows || m_cols)
+                return lbfgsx_objective_bind_grid(c, m_h, m_rows, m_cols, p, m_c, &id);
+            break;
+        default: break;
+        }
+        return lbfgsx_objective_bind(c, m_h, p, m_c, &id);
     }
 };
 
@@ -330,12 +326,12 @@ public:
     GridObjective(std::int64_t rows, std::int64_t cols, const std::string& body)
         : TermObjective<Scalar>(LBFGSX_FORM_GRID, 4, body, "GridObjective: ")
     {
-        this->set_shape(rows, cols);
+        this->set_lattice(LBFGSX_FORM_GRID, 0, rows, cols, 0);
     }
     // a handle compiled elsewhere (lbfgsx_objective_compile_grid); it stays the caller's
     GridObjective(const lbfgsx_objective* compiled, std::int64_t rows, std::int64_t cols) : TermObjective<Scalar>(compiled)
     {
-        this->set_shape(rows, cols);
+        this->set_lattice(LBFGSX_FORM_GRID, 0, rows, cols, 0);
     }
 };
 
@@ -355,13 +351,13 @@ public:
     VolumeObjective(std::int64_t slabs, std::int64_t rows, std::int64_t cols, const std::string& body)
         : TermObjective<Scalar>(LBFGSX_FORM_VOLUME, 8, body, "VolumeObjective: ")
     {
-        this->set_shape3(slabs, rows, cols);
+        this->set_lattice(LBFGSX_FORM_VOLUME, slabs, rows, cols, 0);
     }
     // a handle compiled elsewhere (lbfgsx_objective_compile_volume); it stays the caller's
     VolumeObjective(const lbfgsx_objective* compiled, std::int64_t slabs, std::int64_t rows, std::int64_t cols)
         : TermObjective<Scalar>(compiled)
     {
-        this->set_shape3(slabs, rows, cols);
+        this->set_lattice(LBFGSX_FORM_VOLUME, slabs, rows, cols, 0);
     }
 };
 
@@ -379,15 +375,13 @@ public:
     PeriodicGridObjective(std::int64_t rows, std::int64_t cols, int periodic, const std::string& body)
         : TermObjective<Scalar>(LBFGSX_FORM_GRID_PERIODIC, 4, body, "PeriodicGridObjective: ")
     {
-        this->set_shape(rows, cols);
-        this->set_periodic(periodic);
+        this->set_lattice(LBFGSX_FORM_GRID_PERIODIC, 0, rows, cols, periodic);
     }
     // a handle compiled elsewhere (lbfgsx_objective_compile_grid_periodic); it stays the caller's
     PeriodicGridObjective(const lbfgsx_objective* compiled, std::int64_t rows, std::int64_t cols, int periodic)
         : TermObjective<Scalar>(compiled)
     {
-        this->set_shape(rows, cols);
-        this->set_periodic(periodic);
+        this->set_lattice(LBFGSX_FORM_GRID_PERIODIC, 0, rows, cols, periodic);
     }
 };
 
@@ -405,17 +399,13 @@ public:
     GridFieldObjective(std::int64_t rows, std::int64_t cols, int D, int periodic, const std::string& body)
         : TermObjective<Scalar>(LBFGSX_FORM_GRID_FIELD, 4, body, "GridFieldObjective: ", std::string(), D)
     {
-        this->set_shape(rows, cols);
-        this->set_periodic(periodic);
-        this->set_field();
+        this->set_lattice(LBFGSX_FORM_GRID_FIELD, 0, rows, cols, periodic);
     }
     // a handle compiled elsewhere (lbfgsx_objective_compile_grid_field); it stays the caller's
     GridFieldObjective(const lbfgsx_objective* compiled, std::int64_t rows, std::int64_t cols, int periodic)
         : TermObjective<Scalar>(compiled)
     {
-        this->set_shape(rows, cols);
-        this->set_periodic(periodic);
-        this->set_field();
+        this->set_lattice(LBFGSX_FORM_GRID_FIELD, 0, rows, cols, periodic);
     }
 };
 
@@ -436,17 +426,13 @@ public:
     StencilObjective(std::int64_t rows, std::int64_t cols, int periodic, const std::string& body)
         : TermObjective<Scalar>(LBFGSX_FORM_GRID_STENCIL, 9, body, "StencilObjective: ")
     {
-        this->set_shape(rows, cols);
-        this->set_periodic(periodic);
-        this->set_stencil();
+        this->set_lattice(LBFGSX_FORM_GRID_STENCIL, 0, rows, cols, periodic);
     }
     // a handle compiled elsewhere (lbfgsx_objective_compile_grid_stencil); it stays the caller's
     StencilObjective(const lbfgsx_objective* compiled, std::int64_t rows, std::int64_t cols, int periodic)
         : TermObjective<Scalar>(compiled)
     {
-        this->set_shape(rows, cols);
-        this->set_periodic(periodic);
-        this->set_stencil();
+        this->set_lattice(LBFGSX_FORM_GRID_STENCIL, 0, rows, cols, periodic);
     }
 };
 
@@ -460,15 +446,13 @@ public:
     PeriodicVolumeObjective(std::int64_t slabs, std::int64_t rows, std::int64_t cols, int periodic, const std::string& body)
         : TermObjective<Scalar>(LBFGSX_FORM_VOLUME_PERIODIC, 8, body, "PeriodicVolumeObjective: ")
     {
-        this->set_shape3(slabs, rows, cols);
-        this->set_periodic(periodic);
+        this->set_lattice(LBFGSX_FORM_VOLUME_PERIODIC, slabs, rows, cols, periodic);
     }
     // a handle compiled elsewhere (lbfgsx_objective_compile_volume_periodic); it stays the caller's
     PeriodicVolumeObjective(const lbfgsx_objective* compiled, std::int64_t slabs, std::int64_t rows, std::int64_t cols, int periodic)
         : TermObjective<Scalar>(compiled)
     {
-        this->set_shape3(slabs, rows, cols);
-        this->set_periodic(periodic);
+        this->set_lattice(LBFGSX_FORM_VOLUME_PERIODIC, slabs, rows, cols, periodic);
     }
 };
 

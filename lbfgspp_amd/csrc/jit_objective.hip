@@ -8,33 +8,12 @@
 // same kernel text, the same flags, the same sums.  The code object is loaded per device with hipModuleLoadData and the
 // kernels are launched with hipModuleLaunchKernel from the arguments launch_args.hpp works out for both forms.
 //
-// Fourteen forms of objective share all of this (include/lbfgsx.h): a TERM objective (terms that do not overlap: the struct with
-// pack / tail / finish above), a CHAIN objective (one term starting at every coordinate: a second generated wrapper that
-// includes chain_kernels.cuh and instantiates its four kernels, which take the arguments of the four above) and a GRID
-// objective (one term per 2x2 cell of a row-major grid: a third wrapper around grid_kernels.cuh, whose struct also carries
-// the grid's shape), and a GRAPH objective (one term per edge of an index list and an optional one per node: a fourth
-// wrapper around graph_kernels.cuh, whose struct also carries the context's incidence list, graph_topology.hip).  A fifth,
-// a MESH objective (one term per element of K nodes with D unknowns each and an optional one per node), is a wrapper around
-// mesh_kernels.cuh with the list of mesh_topology.hip.  A sixth, a LINEAR-MODEL objective (one term per row of a sparse matrix
-// product and an optional one per coordinate), is a wrapper around linear_kernels.cuh with the matrix of linear_topology.hip;
-// it has two more kernels, the row passes, in slots 4 and 5; so has the seventh, a MULTI-OUTPUT LINEAR-MODEL objective (D
-// outputs per row, x an F x D matrix), a wrapper around linear_multi_kernels.cuh over the same matrix and the same argument
-// struct, bound by the same call.  An eighth, a DENSE LINEAR-MODEL objective (the multi-output form's bodies over a dense
-// row-major matrix), is a wrapper around linear_dense_kernels.cuh with the matrix of dense_topology.hip; besides the row
-// passes it has the partial pass in slot 7.  A ninth, a GRAPH-REGULARISED LINEAR-MODEL objective (the sixth form with an edge term
-// over an index list on its coordinates: three bodies), is a wrapper around linear_graph_kernels.cuh with both the matrix and
-// the incidence list; its row passes are the sixth form's.  A tenth, a VOLUME objective (one term per 2x2x2 cell of a
-// slab-major 3-D array), is the grid form with one more extent: a wrapper around volume_kernels.cuh whose struct carries the
-// three extents.  An eleventh and a twelfth, a PERIODIC GRID and a PERIODIC VOLUME objective, are those two with wrap-around cells
-// in the directions of a mask: wrappers around periodic_grid_kernels.cuh and periodic_volume_kernels.cuh whose structs carry
-// the extents and the mask, and whose body also sees the flat indices of its corners.  A thirteenth, a GRID FIELD objective, is
-// the periodic grid form with D unknowns per node: a wrapper around grid_field_kernels.cuh with the same members, D a constant
-// of the struct and part of the cache key.  A fourteenth, a GRID STENCIL objective (one term per 3x3 block of nodes of a row-major
-// grid, open or periodic per direction), is a wrapper around grid_stencil_kernels.cuh with the periodic grid form's members
-// and a body of nine nodes.  A handle carries its form; the four slots of the
-// loaded-kernel table and everything that launches them are the same.  What the forms differ in -- names, kernel names, struct
-// members, the bodies' signatures, the K and D accepted, the cache key -- is one row each of kForms below; the generator, the
-// validation and the refusals are written once and read it.
+// Fourteen forms of objective share all of this (include/lbfgsx.h, LBFGSX_FORM_*).  A handle carries its form; the slots of the
+// loaded-kernel table and everything that launches them are the same.  What the forms differ in is one row each of two tables:
+// kFormRows (form_table.hpp) has what the host says about a form -- its names, what it is bound with, the rules of a shape and
+// a mask -- and is shared with liblbfgsx_solver.so; kForms below has what the generator needs -- kernel names, struct members,
+// the bodies' signatures, the K and D accepted, the cache key.  The generator, the validation and the refusals are written once
+// and read them.
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
 
@@ -48,9 +27,12 @@
 #include <string>
 #include <vector>
 
+#include "form_table.hpp"
 #include "launch_args.hpp"
 
 namespace {
+
+using lbfgsx::kFormRows;
 
 // ---- the forms: everything that differs between them in the generated translation unit, in the refusals and in the cache key
 // one body of a form: the method generated around the caller's text
@@ -63,10 +45,9 @@ struct BodyDesc
     const char* absent;     // an optional body: the method's text when the caller gives none; null: the body is required
     const char* flag;       // an optional body: the struct's constant that says whether the caller gave one
 };
+// what the generator needs of a form; its names in messages and entry points are its row of kFormRows (form_table.hpp)
 struct FormDesc
 {
-    const char* name;                         // in messages
-    const char* suffix;                       // of lbfgsx_objective_compile, _source and _bind for this form
     const char* obj;                          // the generated struct
     const char* includes;                     // the kernel headers
     const char* kernels[lbfgsx::JIT_NSLOTS];  // by slot; null: the form has no kernel there
@@ -76,9 +57,7 @@ struct FormDesc
     int k_lo, k_hi, d_lo, d_hi;               // the K and D accepted
     const char *k_refusal, *d_refusal;        // '#' stands for the value refused; null: the entry point fixes the value
     bool key_second, key_d;                   // do the second body and D enter the cache key
-    const char* bound_with;                   // what lbfgsx_objective_bind says the form is bound with; null: it binds it
-    const char* bind_suffix;                  // of the call that binds it, where that is another form's; null: suffix
-    BodyDesc third;                           // a form of three bodies: the required one between the two (no signature: none)
+    BodyDesc third;                          // a form of three bodies: the required one between the two (no signature: none)
 };
 #define TERM_SIGNATURE "T term(const T (&x)[K], T (&g)[K], int64_t i) const"
 #define POINT_SIGNATURE(name) "T " name "(const T (&x)[1], T (&g)[1], int64_t i) const"
@@ -92,7 +71,7 @@ struct FormDesc
     "    int64_t R, nnz;\n    int32_t L, C, nlong, pad_;\n"
 const BodyDesc kNoBody = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 const FormDesc kForms[14] = {
-    {"term objective", "", "ObjTerm", "#include \"lbfgs_kernels.cuh\"\n#include \"lbfgsb_kernels.cuh\"\n",
+    {"ObjTerm", "#include \"lbfgs_kernels.cuh\"\n#include \"lbfgsb_kernels.cuh\"\n",
      {"k_eval", "k_trial", "k_b_eval", "k_b_dg_maxstep_trial", nullptr, nullptr, "k_trial_post"}, "", kNoBody,
      {"    // one term: x[0..K) in, g[0..K) out, the term's value returned\n", TERM_SIGNATURE, "objective_body", "body", nullptr,
       nullptr},
@@ -124,30 +103,30 @@ const FormDesc kForms[14] = {
      1, 2, 1, 1,
      "K = # is not supported: a term reads K = 1 or K = 2 consecutive coordinates (a 16-byte pack of two doubles must hold whole "
      "terms)",
-     nullptr, false, false, nullptr},
-    {"chain objective", "_chain", "ObjChain", "#include \"chain_kernels.cuh\"\n",
+     nullptr, false, false},
+    {"ObjChain", "#include \"chain_kernels.cuh\"\n",
      {"k_chain_eval", "k_chain_trial", "k_chain_b_eval", "k_chain_b_dg_maxstep_trial"}, "", kNoBody,
      {"    // the term that starts at coordinate i: x[0..K) in, its K partial derivatives g[0..K) out, its value returned\n",
       TERM_SIGNATURE, "objective_body", "body", nullptr, nullptr},
      "", 2, 3, 1, 1,
      "K = # is not supported: a chain term reads K = 2 or K = 3 consecutive coordinates (its halo of K - 1 values must lie inside "
      "the neighbouring 16-byte pack of two doubles)",
-     nullptr, false, false, nullptr},
-    {"grid objective", "_grid", "ObjGrid", "#include \"grid_kernels.cuh\"\n",
+     nullptr, false, false},
+    {"ObjGrid", "#include \"grid_kernels.cuh\"\n",
      {"k_grid_eval", "k_grid_trial", "k_grid_b_eval", "k_grid_b_dg_maxstep_trial"}, "    int64_t rows, cols;\n", kNoBody,
      {"    // the cell whose origin is node (row, col), flat index i = row*cols + col: x = {x[row,col], x[row,col+1], x[row+1,col],\n"
       "    // x[row+1,col+1]} in, its four partial derivatives g out, its value returned\n",
       "T term(const T (&x)[4], T (&g)[4], int64_t i, int64_t row, int64_t col) const", "objective_body", "body", nullptr, nullptr},
-     "", 4, 4, 1, 1, "a cell reads K = 4 coordinates", nullptr, false, false, "shape"},
-    {"graph objective", "_graph", "ObjGraph", "#include \"graph_kernels.cuh\"\n",
+     "", 4, 4, 1, 1, "a cell reads K = 4 coordinates", nullptr, false, false},
+    {"ObjGraph", "#include \"graph_kernels.cuh\"\n",
      {"k_graph_eval", "k_graph_trial", "k_graph_b_eval", "k_graph_b_dg_maxstep_trial"},
      "    const uint32_t* off;\n    const GraphEntry* inc;\n    int64_t E;\n",
      {"    // the term of node i: x[0] = x[i] in, its derivative g[0] out, its value returned\n", POINT_SIGNATURE("node"), "node_body",
       "node body", POINT_ABSENT, "kNode"},
      {"    // the term of edge e = (i, j): x = {x[i], x[j]} in, its two partial derivatives g out, its value returned\n",
       "T edge(const T (&x)[2], T (&g)[2], int64_t e, int64_t i, int64_t j) const", "edge_body", "edge body", nullptr, nullptr},
-     "", 2, 2, 1, 1, "an edge reads K = 2 coordinates", nullptr, true, false, "edges"},
-    {"mesh objective", "_mesh", "ObjMesh", "#include \"mesh_kernels.cuh\"\n",
+     "", 2, 2, 1, 1, "an edge reads K = 2 coordinates", nullptr, true, false},
+    {"ObjMesh", "#include \"mesh_kernels.cuh\"\n",
      {"k_mesh_eval", "k_mesh_trial", "k_mesh_b_eval", "k_mesh_b_dg_maxstep_trial"},
      "    const uint32_t* off;\n    const uint32_t* inc;\n    int64_t E, N;\n",
      {"    // the term of node i: x[d] = x[i*D + d] in, its D partial derivatives g out, its value returned\n",
@@ -158,16 +137,16 @@ const FormDesc kForms[14] = {
       "T elem(const T (&x)[K * D], T (&g)[K * D], int64_t e, const int64_t (&v)[K]) const", "elem_body", "element body", nullptr,
       nullptr},
      "", 2, 4, 1, 3, "K = # is not supported: an element has K = 2, 3 or 4 nodes",
-     "D = # is not supported: a node has D = 1, 2 or 3 unknowns", true, true, "elements"},
-    {"linear-model objective", "_linear", "ObjLinear", "#include \"linear_kernels.cuh\"\n",
+     "D = # is not supported: a node has D = 1, 2 or 3 unknowns", true, true},
+    {"ObjLinear", "#include \"linear_kernels.cuh\"\n",
      {"k_lin_eval", "k_lin_trial", "k_lin_b_eval", "k_lin_b_dg_maxstep_trial", "k_lin_rows", "k_lin_rows_trial"},
      LINEAR_MEMBERS,
      {"    // the term of coordinate i: x[0] = x[i] in, its derivative g[0] out, its value returned\n", POINT_SIGNATURE("coord"),
       "coord_body", "coordinate body", POINT_ABSENT, "kCoord"},
      {"    // the term of row r: z = the row's product with x in, its derivative dz out, its value returned\n",
       "T row(const T z, T& dz, int64_t r) const", "row_body", "row body", nullptr, nullptr},
-     "", 1, 1, 1, 1, nullptr, nullptr, true, false, "matrix"},
-    {"multi-output linear-model objective", "_linear_multi", "ObjLinearMulti", "#include \"linear_multi_kernels.cuh\"\n",
+     "", 1, 1, 1, 1, nullptr, nullptr, true, false},
+    {"ObjLinearMulti", "#include \"linear_multi_kernels.cuh\"\n",
      {"k_linm_eval", "k_linm_trial", "k_linm_b_eval", "k_linm_b_dg_maxstep_trial", "k_linm_rows", "k_linm_rows_trial"},
      LINEAR_MEMBERS,
      {"    // the term of coordinate i = j*D + c: x[0] = x[i] in, its derivative g[0] out, its value returned\n", POINT_SIGNATURE("coord"),
@@ -175,8 +154,8 @@ const FormDesc kForms[14] = {
      {"    // the term of row r: z[c] = the row's product with column c of the F x D matrix x in, its D partial derivatives dz out,\n"
       "    // its value returned\n",
       "T row(const T (&z)[D], T (&dz)[D], int64_t r) const", "row_body", "row body", nullptr, nullptr},
-     "", 1, 1, 1, 16, nullptr, "D = # is not supported: a row has D = 1 .. 16 outputs", true, true, "matrix", "_linear"},
-    {"dense linear-model objective", "_dense", "ObjDense", "#include \"linear_dense_kernels.cuh\"\n",
+     "", 1, 1, 1, 16, nullptr, "D = # is not supported: a row has D = 1 .. 16 outputs", true, true},
+    {"ObjDense", "#include \"linear_dense_kernels.cuh\"\n",
      {"k_dense_eval", "k_dense_trial", "k_dense_b_eval", "k_dense_b_dg_maxstep_trial", "k_dense_rows", "k_dense_rows_trial", nullptr,
       "k_dense_partials"},
      // launch_args.hpp: DenseArgs
@@ -187,8 +166,8 @@ const FormDesc kForms[14] = {
      {"    // the term of row r: z[c] = row r of the dense matrix times column c of the F x D matrix x in, its D partial derivatives\n"
       "    // dz out, its value returned\n",
       "T row(const T (&z)[D], T (&dz)[D], int64_t r) const", "row_body", "row body", nullptr, nullptr},
-     "", 1, 1, 1, 16, nullptr, "D = # is not supported: a row has D = 1 .. 16 outputs", true, true, "matrix"},
-    {"graph-regularised linear-model objective", "_linear_graph", "ObjLinearGraph", "#include \"linear_graph_kernels.cuh\"\n",
+     "", 1, 1, 1, 16, nullptr, "D = # is not supported: a row has D = 1 .. 16 outputs", true, true},
+    {"ObjLinearGraph", "#include \"linear_graph_kernels.cuh\"\n",
      {"k_ling_eval", "k_ling_trial", "k_ling_b_eval", "k_ling_b_dg_maxstep_trial", "k_lin_rows", "k_lin_rows_trial"},
      // launch_args.hpp: LinearGraphArgs
      LINEAR_MEMBERS "    const uint32_t* off;\n    const GraphEntry* inc;\n    int64_t E;\n",
@@ -196,29 +175,29 @@ const FormDesc kForms[14] = {
       "coord_body", "coordinate body", POINT_ABSENT, "kCoord"},
      {"    // the term of row r: z = the row's product with x in, its derivative dz out, its value returned\n",
       "T row(const T z, T& dz, int64_t r) const", "row_body", "row body", nullptr, nullptr},
-     "", 1, 1, 1, 1, nullptr, nullptr, true, false, "matrix and edges", nullptr,
+     "", 1, 1, 1, 1, nullptr, nullptr, true, false,
      {"    // the term of edge e = (i, j): x = {x[i], x[j]} in, its two partial derivatives g out, its value returned\n",
       "T edge(const T (&x)[2], T (&g)[2], int64_t e, int64_t i, int64_t j) const", "edge_body", "edge body", nullptr, nullptr}},
-    {"volume objective", "_volume", "ObjVolume", "#include \"volume_kernels.cuh\"\n",
+    {"ObjVolume", "#include \"volume_kernels.cuh\"\n",
      {"k_volume_eval", "k_volume_trial", "k_volume_b_eval", "k_volume_b_dg_maxstep_trial"}, "    int64_t slabs, rows, cols;\n", kNoBody,
      {"    // the cell whose origin is node (slab, row, col), flat index i = (slab*rows + row)*cols + col:\n"
       "    // x[4*ds + 2*dr + dc] = x[slab+ds, row+dr, col+dc] in, its eight partial derivatives g out, its value returned\n",
       "T term(const T (&x)[8], T (&g)[8], int64_t i, int64_t slab, int64_t row, int64_t col) const", "objective_body", "body",
       nullptr, nullptr},
-     "", 8, 8, 1, 1, "a cell reads K = 8 coordinates", nullptr, false, false, "shape"},
-    {"periodic grid objective", "_grid_periodic", "ObjGridPeriodic", "#include \"periodic_grid_kernels.cuh\"\n",
+     "", 8, 8, 1, 1, "a cell reads K = 8 coordinates", nullptr, false, false},
+    {"ObjGridPeriodic", "#include \"periodic_grid_kernels.cuh\"\n",
      {"k_pgrid_eval", "k_pgrid_trial", "k_pgrid_b_eval", "k_pgrid_b_dg_maxstep_trial"},
-     // launch_args.hpp: PeriodicGridArgs
+     // launch_args.hpp: MaskedGridArgs
      "    int64_t rows, cols;\n    int periodic, pad_;\n", kNoBody,
      {"    // the cell whose origin is node (row, col), flat index i = row*cols + col: x = {x[row,col], x[row,col+1], x[row+1,col],\n"
       "    // x[row+1,col+1]} in, + modulo the extent; j: the flat indices of those four nodes, j[0] == i; periodic: bit 0 the\n"
       "    // column direction, bit 1 the row direction; its four partial derivatives g out, its value returned\n",
       "T term(const T (&x)[4], T (&g)[4], int64_t i, int64_t row, int64_t col, const int64_t (&j)[4]) const", "objective_body",
       "body", nullptr, nullptr},
-     "", 4, 4, 1, 1, "a cell reads K = 4 coordinates", nullptr, false, false, "shape and mask"},
-    {"periodic volume objective", "_volume_periodic", "ObjVolumePeriodic", "#include \"periodic_volume_kernels.cuh\"\n",
+     "", 4, 4, 1, 1, "a cell reads K = 4 coordinates", nullptr, false, false},
+    {"ObjVolumePeriodic", "#include \"periodic_volume_kernels.cuh\"\n",
      {"k_pvolume_eval", "k_pvolume_trial", "k_pvolume_b_eval", "k_pvolume_b_dg_maxstep_trial"},
-     // launch_args.hpp: PeriodicVolumeArgs
+     // launch_args.hpp: MaskedVolumeArgs
      "    int64_t slabs, rows, cols;\n    int periodic, pad_;\n", kNoBody,
      {"    // the cell whose origin is node (slab, row, col), flat index i = (slab*rows + row)*cols + col:\n"
       "    // x[4*ds + 2*dr + dc] = x[slab+ds, row+dr, col+dc] in, + modulo the extent; j: the flat indices of those eight nodes,\n"
@@ -226,10 +205,10 @@ const FormDesc kForms[14] = {
       "    // its value returned\n",
       "T term(const T (&x)[8], T (&g)[8], int64_t i, int64_t slab, int64_t row, int64_t col, const int64_t (&j)[8]) const",
       "objective_body", "body", nullptr, nullptr},
-     "", 8, 8, 1, 1, "a cell reads K = 8 coordinates", nullptr, false, false, "shape and mask"},
-    {"grid field objective", "_grid_field", "ObjGridField", "#include \"grid_field_kernels.cuh\"\n",
+     "", 8, 8, 1, 1, "a cell reads K = 8 coordinates", nullptr, false, false},
+    {"ObjGridField", "#include \"grid_field_kernels.cuh\"\n",
      {"k_gfield_eval", "k_gfield_trial", "k_gfield_b_eval", "k_gfield_b_dg_maxstep_trial"},
-     // launch_args.hpp: GridFieldArgs
+     // launch_args.hpp: MaskedGridArgs (D is a constant of the struct)
      "    int64_t rows, cols;\n    int periodic, pad_;\n", kNoBody,
      {"    // the cell whose origin is node (row, col), node index i = row*cols + col: x[k*D + d] = unknown d of corner k in, the\n"
       "    // corners {(row,col), (row,col+1), (row+1,col), (row+1,col+1)}, + modulo the extent; j: the node indices of those four\n"
@@ -237,18 +216,17 @@ const FormDesc kForms[14] = {
       "    // row direction; its 4*D partial derivatives g out, its value returned\n",
       "T term(const T (&x)[4 * D], T (&g)[4 * D], int64_t i, int64_t row, int64_t col, const int64_t (&j)[4]) const",
       "objective_body", "body", nullptr, nullptr},
-     "", 4, 4, 1, 3, "a cell has K = 4 corners", "D = # is not supported: a node has D = 1, 2 or 3 unknowns", false, true,
-     "shape, mask and D"},
-    {"grid stencil objective", "_grid_stencil", "ObjGridStencil", "#include \"grid_stencil_kernels.cuh\"\n",
+     "", 4, 4, 1, 3, "a cell has K = 4 corners", "D = # is not supported: a node has D = 1, 2 or 3 unknowns", false, true},
+    {"ObjGridStencil", "#include \"grid_stencil_kernels.cuh\"\n",
      {"k_stencil_eval", "k_stencil_trial", "k_stencil_b_eval", "k_stencil_b_dg_maxstep_trial"},
-     // launch_args.hpp: StencilArgs
+     // launch_args.hpp: MaskedGridArgs
      "    int64_t rows, cols;\n    int periodic, pad_;\n", kNoBody,
      {"    // the patch whose origin is node (row, col), flat index i = row*cols + col: x[3*dr + dc] = x[row+dr, col+dc] in, dr, dc =\n"
       "    // 0, 1, 2, + modulo the extent; j: the flat indices of those nine nodes, j[0] == i; periodic: bit 0 the column direction,\n"
       "    // bit 1 the row direction; its nine partial derivatives g out, its value returned\n",
       "T term(const T (&x)[9], T (&g)[9], int64_t i, int64_t row, int64_t col, const int64_t (&j)[9]) const", "objective_body",
       "body", nullptr, nullptr},
-     "", 9, 9, 1, 1, "a patch reads K = 9 coordinates", nullptr, false, false, "shape and mask"}};
+     "", 9, 9, 1, 1, "a patch reads K = 9 coordinates", nullptr, false, false}};
 #undef LINEAR_MEMBERS
 #undef TERM_SIGNATURE
 #undef POINT_SIGNATURE
@@ -358,7 +336,8 @@ std::string generate(int form, int dtype, int K, const char* body, const char* s
 {
     const FormDesc& f = kForms[form];
     std::string s;
-    s += std::string("// generated by lbfgsx_objective_compile") + f.suffix + ": one " + f.name + " for the fused kernels\n";
+    s += std::string("// generated by lbfgsx_objective_compile") + kFormRows[form].suffix + ": one " + kFormRows[form].name +
+         " for the fused kernels\n";
     s += f.includes;
     s += "namespace lbfgsx {\n";
     s += std::string("typedef ") + (dtype == LBFGSX_F64 ? "double" : "float") + " term_scalar_t;\n";
@@ -402,7 +381,7 @@ bool valid_request(int form, int dtype, int K, const char* body, const char* sec
                    const char* third = nullptr)
 {
     const FormDesc& f = kForms[form];
-    const std::string name = std::string(f.name) + ": ";
+    const std::string name = std::string(kFormRows[form].name) + ": ";
     const char* const no_asm = " contains 'asm': a term is plain C++ arithmetic, inline assembly is not accepted";
     if (dtype != LBFGSX_F64 && dtype != LBFGSX_F32)
         why = name + "unknown dtype";
@@ -632,7 +611,7 @@ int compile_code(int form, int dtype, int K, int D, const char* body, const char
     (void) r.destroy(&prog);
     if (!ok)
     {
-        log = std::string(kForms[form].name) + ": the compiled code object lacks a kernel or its descriptor";
+        log = std::string(kFormRows[form].name) + ": the compiled code object lacks a kernel or its descriptor";
         return LBFGSX_E_RUNTIME;
     }
     code->self.code = code.get();
@@ -716,7 +695,7 @@ int objective_compile(int form, lbfgsx_objective** out, int dtype, int K, const 
         const int rc = compile_code(form, dtype, K, D, body, node, third, code, text);
         if (rc)
         {
-            lbfgsx::set_error(std::string(kForms[form].name) + ": compilation failed\n" + text);
+            lbfgsx::set_error(std::string(kFormRows[form].name) + ": compilation failed\n" + text);
             put_log(log, log_len, text);
             return rc;
         }
@@ -1019,10 +998,10 @@ int objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int
 // is the handle one of `form`; the refusal names lbfgsx_objective_bind<suffix>, the call that asked
 bool handle_is(const lbfgsx_objective* obj, int form)
 {
-    const FormDesc& f = kForms[form];
+    const lbfgsx::FormRow& f = kFormRows[form];
     if (obj->code->form == form)
         return true;
-    lbfgsx::set_error(std::string("lbfgsx_objective_bind") + f.suffix + ": the handle is a " + kForms[obj->code->form].name +
+    lbfgsx::set_error(std::string("lbfgsx_objective_bind") + f.suffix + ": the handle is a " + kFormRows[obj->code->form].name +
                       ", not a " + f.name + " (lbfgsx_objective_compile" + f.suffix + ")");
     return false;
 }
@@ -1058,6 +1037,29 @@ int bind_end(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void* const p[4],
     return rc;
 }
 
+// the bind of a lattice form: the handle's form, then the rules of the form's row (form_table.hpp) -- the extents, the product
+// that is n (an overflow is a product that is not), the mask --, then the handle bound with them.  slabs = 0 on two axes,
+// periodic = 0 for a form without a mask
+int shaped_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, int form, int64_t slabs, int64_t rows, int64_t cols, int periodic,
+                const void* const p[4], const double cs[8], int* id)
+{
+    if (!c || !obj)
+        return LBFGSX_E_INVALID;
+    if (!handle_is(obj, form))
+        return LBFGSX_E_INVALID;
+    const int D = obj->code->D;
+    long long n = 0;
+    const lbfgsx::LatticeRule bad = lbfgsx::lattice_check(form, D, slabs, rows, cols, periodic, &n);
+    if (bad == lbfgsx::LATTICE_OVERFLOW || (bad != lbfgsx::LATTICE_EXTENT && n != (long long) c->n))
+        lbfgsx::set_error(std::string(kFormRows[form].name) + ": " + lbfgsx::lattice_shape(form, D, slabs, rows, cols) +
+                          " does not multiply to n = " + std::to_string(c->n));
+    else if (bad)
+        lbfgsx::set_error(lbfgsx::lattice_refusal(form, bad, D, slabs, rows, cols, periodic));
+    else
+        return objective_bind(c, obj, rows, cols, p, cs, id, slabs, periodic);
+    return LBFGSX_E_INVALID;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1066,43 +1068,50 @@ int lbfgsx_objective_bind(lbfgsx_ctx* c, const lbfgsx_objective* obj, const void
 {
     if (!c)
         return LBFGSX_E_INVALID;
-    if (obj && kForms[obj->code->form].bound_with)
+    if (obj && kFormRows[obj->code->form].bound_with)
     {
-        const FormDesc& f = kForms[obj->code->form];
-        lbfgsx::set_error(std::string("a ") + f.name + " is bound with its " + f.bound_with + ": lbfgsx_objective_bind" +
-                          (f.bind_suffix ? f.bind_suffix : f.suffix));
+        lbfgsx::set_error(lbfgsx::unshaped_refusal(obj->code->form, false));
         return LBFGSX_E_INVALID;
     }
     return objective_bind(c, obj, 0, 0, p, cs, id);
 }
 
+// ---- the six lattice forms: one bind (shaped_bind), by the form's row of kFormRows
 int lbfgsx_objective_bind_grid(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
                                const double cs[8], int* id)
 {
-    if (!c || !obj)
-        return LBFGSX_E_INVALID;
-    if (!handle_is(obj, LBFGSX_FORM_GRID))
-        return LBFGSX_E_INVALID;
-    const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
-    long long prod = 0;
-    if (rows < 2 || cols < 2)
-    {
-        lbfgsx::set_error("grid objective: " + shape + ": a grid has at least 2 rows and 2 columns (rows >= 2, cols >= 2)");
-        return LBFGSX_E_INVALID;
-    }
-    if (__builtin_mul_overflow((long long) rows, (long long) cols, &prod) || prod != (long long) c->n)
-    {
-        lbfgsx::set_error("grid objective: " + shape + " does not multiply to n = " + std::to_string(c->n));
-        return LBFGSX_E_INVALID;
-    }
-    return objective_bind(c, obj, rows, cols, p, cs, id);
+    return shaped_bind(c, obj, LBFGSX_FORM_GRID, 0, rows, cols, 0, p, cs, id);
+}
+int lbfgsx_objective_bind_volume(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
+                                 const void* const p[4], const double cs[8], int* id)
+{
+    return shaped_bind(c, obj, LBFGSX_FORM_VOLUME, slabs, rows, cols, 0, p, cs, id);
+}
+int lbfgsx_objective_bind_grid_periodic(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                        const void* const p[4], const double cs[8], int* id)
+{
+    return shaped_bind(c, obj, LBFGSX_FORM_GRID_PERIODIC, 0, rows, cols, periodic, p, cs, id);
+}
+int lbfgsx_objective_bind_volume_periodic(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
+                                          int periodic, const void* const p[4], const double cs[8], int* id)
+{
+    return shaped_bind(c, obj, LBFGSX_FORM_VOLUME_PERIODIC, slabs, rows, cols, periodic, p, cs, id);
+}
+int lbfgsx_objective_bind_grid_field(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                     const void* const p[4], const double cs[8], int* id)
+{
+    return shaped_bind(c, obj, LBFGSX_FORM_GRID_FIELD, 0, rows, cols, periodic, p, cs, id);
+}
+int lbfgsx_objective_bind_grid_stencil(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                       const void* const p[4], const double cs[8], int* id)
+{
+    return shaped_bind(c, obj, LBFGSX_FORM_GRID_STENCIL, 0, rows, cols, periodic, p, cs, id);
 }
 
+// what was bound, read back: the forms on two axes, those on three, those with a mask
 int lbfgsx_objective_shape(const lbfgsx_ctx* c, int64_t* rows, int64_t* cols)
 {
-    if (!c || !c->term ||
-        (c->term_form != LBFGSX_FORM_GRID && c->term_form != LBFGSX_FORM_GRID_PERIODIC && c->term_form != LBFGSX_FORM_GRID_FIELD &&
-         c->term_form != LBFGSX_FORM_GRID_STENCIL))
+    if (!c || !c->term || kFormRows[c->term_form].axes != 2)
     {
         lbfgsx::set_error("lbfgsx_objective_shape: no grid objective is bound to this context");
         return LBFGSX_E_INVALID;
@@ -1114,33 +1123,9 @@ int lbfgsx_objective_shape(const lbfgsx_ctx* c, int64_t* rows, int64_t* cols)
     return LBFGSX_OK;
 }
 
-int lbfgsx_objective_bind_volume(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
-                                 const void* const p[4], const double cs[8], int* id)
-{
-    if (!c || !obj)
-        return LBFGSX_E_INVALID;
-    if (!handle_is(obj, LBFGSX_FORM_VOLUME))
-        return LBFGSX_E_INVALID;
-    const std::string shape = "slabs = " + std::to_string(slabs) + ", rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
-    long long prod = 0;
-    if (slabs < 2 || rows < 2 || cols < 2)
-    {
-        lbfgsx::set_error("volume objective: " + shape +
-                          ": a volume has at least 2 slabs, 2 rows and 2 columns (slabs >= 2, rows >= 2, cols >= 2)");
-        return LBFGSX_E_INVALID;
-    }
-    if (__builtin_mul_overflow((long long) rows, (long long) cols, &prod) || __builtin_mul_overflow(prod, (long long) slabs, &prod) ||
-        prod != (long long) c->n)
-    {
-        lbfgsx::set_error("volume objective: " + shape + " does not multiply to n = " + std::to_string(c->n));
-        return LBFGSX_E_INVALID;
-    }
-    return objective_bind(c, obj, rows, cols, p, cs, id, slabs);
-}
-
 int lbfgsx_objective_shape3(const lbfgsx_ctx* c, int64_t* slabs, int64_t* rows, int64_t* cols)
 {
-    if (!c || !c->term || (c->term_form != LBFGSX_FORM_VOLUME && c->term_form != LBFGSX_FORM_VOLUME_PERIODIC))
+    if (!c || !c->term || kFormRows[c->term_form].axes != 3)
     {
         lbfgsx::set_error("lbfgsx_objective_shape3: no volume objective is bound to this context");
         return LBFGSX_E_INVALID;
@@ -1154,128 +1139,9 @@ int lbfgsx_objective_shape3(const lbfgsx_ctx* c, int64_t* slabs, int64_t* rows, 
     return LBFGSX_OK;
 }
 
-int lbfgsx_objective_bind_grid_periodic(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
-                                        const void* const p[4], const double cs[8], int* id)
-{
-    if (!c || !obj)
-        return LBFGSX_E_INVALID;
-    if (!handle_is(obj, LBFGSX_FORM_GRID_PERIODIC))
-        return LBFGSX_E_INVALID;
-    const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
-    long long prod = 0;
-    if (rows < 2 || cols < 2)
-    {
-        lbfgsx::set_error("periodic grid objective: " + shape + ": a grid has at least 2 rows and 2 columns (rows >= 2, cols >= 2)");
-        return LBFGSX_E_INVALID;
-    }
-    if (__builtin_mul_overflow((long long) rows, (long long) cols, &prod) || prod != (long long) c->n)
-    {
-        lbfgsx::set_error("periodic grid objective: " + shape + " does not multiply to n = " + std::to_string(c->n));
-        return LBFGSX_E_INVALID;
-    }
-    if (periodic < 0 || periodic > 3)
-    {
-        lbfgsx::set_error("periodic grid objective: periodic = " + std::to_string(periodic) +
-                          ": the mask has bit 0 for the column direction and bit 1 for the row direction (0 .. 3)");
-        return LBFGSX_E_INVALID;
-    }
-    return objective_bind(c, obj, rows, cols, p, cs, id, 0, periodic);
-}
-
-int lbfgsx_objective_bind_volume_periodic(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
-                                          int periodic, const void* const p[4], const double cs[8], int* id)
-{
-    if (!c || !obj)
-        return LBFGSX_E_INVALID;
-    if (!handle_is(obj, LBFGSX_FORM_VOLUME_PERIODIC))
-        return LBFGSX_E_INVALID;
-    const std::string shape = "slabs = " + std::to_string(slabs) + ", rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
-    long long prod = 0;
-    if (slabs < 2 || rows < 2 || cols < 2)
-    {
-        lbfgsx::set_error("periodic volume objective: " + shape +
-                          ": a volume has at least 2 slabs, 2 rows and 2 columns (slabs >= 2, rows >= 2, cols >= 2)");
-        return LBFGSX_E_INVALID;
-    }
-    if (__builtin_mul_overflow((long long) rows, (long long) cols, &prod) || __builtin_mul_overflow(prod, (long long) slabs, &prod) ||
-        prod != (long long) c->n)
-    {
-        lbfgsx::set_error("periodic volume objective: " + shape + " does not multiply to n = " + std::to_string(c->n));
-        return LBFGSX_E_INVALID;
-    }
-    if (periodic < 0 || periodic > 7)
-    {
-        lbfgsx::set_error("periodic volume objective: periodic = " + std::to_string(periodic) +
-                          ": the mask has bit 0 for the column, bit 1 for the row and bit 2 for the slab direction (0 .. 7)");
-        return LBFGSX_E_INVALID;
-    }
-    return objective_bind(c, obj, rows, cols, p, cs, id, slabs, periodic);
-}
-
-int lbfgsx_objective_bind_grid_field(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
-                                     const void* const p[4], const double cs[8], int* id)
-{
-    if (!c || !obj)
-        return LBFGSX_E_INVALID;
-    if (!handle_is(obj, LBFGSX_FORM_GRID_FIELD))
-        return LBFGSX_E_INVALID;
-    const int D = obj->code->D;
-    const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols) + ", D = " + std::to_string(D);
-    long long prod = 0;
-    if (rows < 2 || cols < 2)
-    {
-        lbfgsx::set_error("grid field objective: " + shape + ": a grid has at least 2 rows and 2 columns (rows >= 2, cols >= 2)");
-        return LBFGSX_E_INVALID;
-    }
-    if (__builtin_mul_overflow((long long) rows, (long long) cols, &prod) || __builtin_mul_overflow(prod, (long long) D, &prod) ||
-        prod != (long long) c->n)
-    {
-        lbfgsx::set_error("grid field objective: " + shape + " does not multiply to n = " + std::to_string(c->n));
-        return LBFGSX_E_INVALID;
-    }
-    if (periodic < 0 || periodic > 3)
-    {
-        lbfgsx::set_error("grid field objective: periodic = " + std::to_string(periodic) +
-                          ": the mask has bit 0 for the column direction and bit 1 for the row direction (0 .. 3)");
-        return LBFGSX_E_INVALID;
-    }
-    return objective_bind(c, obj, rows, cols, p, cs, id, 0, periodic);
-}
-
-int lbfgsx_objective_bind_grid_stencil(lbfgsx_ctx* c, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
-                                       const void* const p[4], const double cs[8], int* id)
-{
-    if (!c || !obj)
-        return LBFGSX_E_INVALID;
-    if (!handle_is(obj, LBFGSX_FORM_GRID_STENCIL))
-        return LBFGSX_E_INVALID;
-    const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
-    long long prod = 0;
-    if (rows < 3 || cols < 3)
-    {
-        lbfgsx::set_error("grid stencil objective: " + shape +
-                          ": a 3x3 patch needs at least 3 rows and 3 columns (rows >= 3, cols >= 3)");
-        return LBFGSX_E_INVALID;
-    }
-    if (__builtin_mul_overflow((long long) rows, (long long) cols, &prod) || prod != (long long) c->n)
-    {
-        lbfgsx::set_error("grid stencil objective: " + shape + " does not multiply to n = " + std::to_string(c->n));
-        return LBFGSX_E_INVALID;
-    }
-    if (periodic < 0 || periodic > 3)
-    {
-        lbfgsx::set_error("grid stencil objective: periodic = " + std::to_string(periodic) +
-                          ": the mask has bit 0 for the column direction and bit 1 for the row direction (0 .. 3)");
-        return LBFGSX_E_INVALID;
-    }
-    return objective_bind(c, obj, rows, cols, p, cs, id, 0, periodic);
-}
-
 int lbfgsx_objective_periodic(const lbfgsx_ctx* c, int* mask)
 {
-    if (!c || !c->term ||
-        (c->term_form != LBFGSX_FORM_GRID_PERIODIC && c->term_form != LBFGSX_FORM_VOLUME_PERIODIC &&
-         c->term_form != LBFGSX_FORM_GRID_FIELD && c->term_form != LBFGSX_FORM_GRID_STENCIL))
+    if (!c || !c->term || kFormRows[c->term_form].mask_hi < 0)
     {
         lbfgsx::set_error("lbfgsx_objective_periodic: no periodic grid or volume objective is bound to this context");
         return LBFGSX_E_INVALID;
@@ -1389,7 +1255,7 @@ int lbfgsx_objective_bind_linear(lbfgsx_ctx* c, const lbfgsx_objective* obj, int
     if (const int rc = bind_begin(c, obj, multi ? LBFGSX_FORM_LINEAR_MULTI : LBFGSX_FORM_LINEAR))
         return rc;
     const int D = multi ? obj->code->D : 1;
-    const std::string name = std::string(kForms[obj->code->form].name) + ": ";
+    const std::string name = std::string(kFormRows[obj->code->form].name) + ": ";
     const int64_t lim = 2147483647;
     std::string why;
     if (R < 1 || nnz < 1 || !rowptr || !col || !val)
@@ -1467,7 +1333,7 @@ int lbfgsx_objective_bind_linear_graph(lbfgsx_ctx* c, const lbfgsx_objective* ob
         why = "lanes = " + std::to_string(lanes) + ": the lanes that share a row are 0 (by the rule) or a power of two in 1..64";
     if (!why.empty())
     {
-        lbfgsx::set_error(std::string(kForms[LBFGSX_FORM_LINEAR_GRAPH].name) + ": " + why);
+        lbfgsx::set_error(std::string(kFormRows[LBFGSX_FORM_LINEAR_GRAPH].name) + ": " + why);
         return LBFGSX_E_INVALID;
     }
     {

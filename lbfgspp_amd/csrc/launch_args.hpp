@@ -3,6 +3,8 @@
 // (hipLaunchKernelGGL in lbfgsx.hip / lbfgsb_linesearch.hip) and the instantiations compiled at run time for a term objective
 // (hipModuleLaunchKernel, jit_objective.hip).  The members are the kernels' arguments in order, the objective left out.
 #pragma once
+#include <cstddef>
+
 #include "ctx.hpp"
 
 namespace lbfgsx {
@@ -117,54 +119,56 @@ inline TermArgs<T> term_args(const lbfgsx_ctx* c)
         a.c[j] = T(c->term_c[j]);
     return a;
 }
-// the by-value argument of a grid objective's kernels: layout of the generated struct ObjGrid (TermArgs, then the shape)
+// the by-value arguments of the lattice forms' kernels, one struct per layout the generator writes (jit_objective.hip,
+// kForms[..].members: TermArgs' members, then the int64_t extents, then for a form with a mask int periodic, pad_):
+//   GridArgs          ObjGrid
+//   VolumeArgs        ObjVolume
+//   MaskedGridArgs    ObjGridPeriodic, ObjGridField (D is a constant of the struct), ObjGridStencil
+//   MaskedVolumeArgs  ObjVolumePeriodic
 template <class T>
 struct GridArgs
 {
     TermArgs<T> t;
     int64_t rows, cols;
 };
-// the by-value argument of a volume objective's kernels: layout of the generated struct ObjVolume (TermArgs, then the shape)
 template <class T>
 struct VolumeArgs
 {
     TermArgs<T> t;
     int64_t slabs, rows, cols;
 };
-// the by-value arguments of a periodic grid and of a periodic volume objective's kernels: layouts of the generated structs
-// ObjGridPeriodic and ObjVolumePeriodic (the open form's, then the mask)
 template <class T>
-struct PeriodicGridArgs
+struct MaskedGridArgs
 {
     TermArgs<T> t;
     int64_t rows, cols;
     int32_t periodic, pad_;
 };
 template <class T>
-struct PeriodicVolumeArgs
+struct MaskedVolumeArgs
 {
     TermArgs<T> t;
     int64_t slabs, rows, cols;
     int32_t periodic, pad_;
 };
-// the by-value argument of a grid field objective's kernels: layout of the generated struct ObjGridField (the periodic grid
-// form's members; D is a constant of the struct)
+// a member that moved would corrupt a kernel's arguments without a word: the extents follow TermArgs directly, 8 bytes each,
+// the mask follows them, and nothing else is in the struct
 template <class T>
-struct GridFieldArgs
+constexpr bool lattice_layouts_hold()
 {
-    TermArgs<T> t;
-    int64_t rows, cols;
-    int32_t periodic, pad_;
-};
-// the by-value argument of a grid stencil objective's kernels: layout of the generated struct ObjGridStencil (the periodic
-// grid form's members)
-template <class T>
-struct StencilArgs
-{
-    TermArgs<T> t;
-    int64_t rows, cols;
-    int32_t periodic, pad_;
-};
+    constexpr size_t t = sizeof(TermArgs<T>);
+    return t == 4 * sizeof(const T*) + 8 * sizeof(T) && t % 8 == 0 && offsetof(GridArgs<T>, t) == 0 &&
+           offsetof(GridArgs<T>, rows) == t && offsetof(GridArgs<T>, cols) == t + 8 && sizeof(GridArgs<T>) == t + 16 &&
+           offsetof(VolumeArgs<T>, slabs) == t && offsetof(VolumeArgs<T>, rows) == t + 8 && offsetof(VolumeArgs<T>, cols) == t + 16 &&
+           sizeof(VolumeArgs<T>) == t + 24 && offsetof(MaskedGridArgs<T>, rows) == t && offsetof(MaskedGridArgs<T>, cols) == t + 8 &&
+           offsetof(MaskedGridArgs<T>, periodic) == t + 16 && offsetof(MaskedGridArgs<T>, pad_) == t + 20 &&
+           sizeof(MaskedGridArgs<T>) == t + 24 && offsetof(MaskedVolumeArgs<T>, slabs) == t &&
+           offsetof(MaskedVolumeArgs<T>, rows) == t + 8 && offsetof(MaskedVolumeArgs<T>, cols) == t + 16 &&
+           offsetof(MaskedVolumeArgs<T>, periodic) == t + 24 && offsetof(MaskedVolumeArgs<T>, pad_) == t + 28 &&
+           sizeof(MaskedVolumeArgs<T>) == t + 32;
+}
+static_assert(lattice_layouts_hold<double>() && lattice_layouts_hold<float>(),
+              "a lattice form's argument struct no longer has the layout of the struct generated for its kernels");
 // the by-value argument of a graph objective's kernels: layout of the generated struct ObjGraph (TermArgs, then the
 // context's incidence list: uint32 off[n+1], 8-byte entries inc[2E] (graph_entry.hpp), and E)
 struct GraphEntry;
@@ -265,19 +269,17 @@ struct LinearGraphArgs
 inline bool form_is_linear(int form) { return form == LBFGSX_FORM_LINEAR || form == LBFGSX_FORM_LINEAR_MULTI; }
 // the forms whose evaluation is a row pass over a CSR matrix and a column walk: those two and the graph-regularised one
 inline bool form_has_csr(int form) { return form_is_linear(form) || form == LBFGSX_FORM_LINEAR_GRAPH; }
-// the objective argument of the bound handle's kernels, by its form: &term for a term or chain objective, &grid for a grid
-// one, &volume for a volume one, &pgrid and &pvolume for the periodic two, &gfield for a grid field one, &stencil for a grid stencil one, &graph for a graph one, &mesh for a mesh one, &linear for a linear-model one of either form, &dense for a dense one,
-// &linear_graph for a graph-regularised linear-model one
+// the objective argument of the bound handle's kernels, by its form: &term for a term or chain objective, &grid, &volume,
+// &mgrid or &mvolume for a lattice one by its layout (above), &graph for a graph one, &mesh for a mesh one, &linear for a
+// linear-model one of either form, &dense for a dense one, &linear_graph for a graph-regularised linear-model one
 template <class T>
 struct BoundArgs
 {
     TermArgs<T> term;
     GridArgs<T> grid;
     VolumeArgs<T> volume;
-    PeriodicGridArgs<T> pgrid;
-    PeriodicVolumeArgs<T> pvolume;
-    GridFieldArgs<T> gfield;
-    StencilArgs<T> stencil;
+    MaskedGridArgs<T> mgrid;
+    MaskedVolumeArgs<T> mvolume;
     GraphArgs<T> graph;
     MeshArgs<T> mesh;
     LinearArgs<T> linear;
@@ -288,10 +290,8 @@ struct BoundArgs
         : term(term_args<T>(c)),
           grid{term, c->term_rows, c->term_cols},
           volume{term, c->term_slabs, c->term_rows, c->term_cols},
-          pgrid{term, c->term_rows, c->term_cols, c->term_periodic, 0},
-          pvolume{term, c->term_slabs, c->term_rows, c->term_cols, c->term_periodic, 0},
-          gfield{term, c->term_rows, c->term_cols, c->term_periodic, 0},
-          stencil{term, c->term_rows, c->term_cols, c->term_periodic, 0},
+          mgrid{term, c->term_rows, c->term_cols, c->term_periodic, 0},
+          mvolume{term, c->term_slabs, c->term_rows, c->term_cols, c->term_periodic, 0},
           graph{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const GraphEntry*>(c->graph_inc), c->graph_E},
           mesh{term, static_cast<const uint32_t*>(c->graph_off), static_cast<const uint32_t*>(c->graph_inc), c->graph_E,
                c->mesh_D ? c->n / c->mesh_D : 0},
@@ -299,18 +299,22 @@ struct BoundArgs
           dense(dense_args<T>(c, term)),
           linear_graph{linear, static_cast<const uint32_t*>(c->graph_off), static_cast<const GraphEntry*>(c->graph_inc), c->graph_E}
     {
-        ptr = (c->term_form == LBFGSX_FORM_GRID)    ? static_cast<void*>(&grid)
-              : (c->term_form == LBFGSX_FORM_VOLUME) ? static_cast<void*>(&volume)
-              : (c->term_form == LBFGSX_FORM_GRID_PERIODIC) ? static_cast<void*>(&pgrid)
-              : (c->term_form == LBFGSX_FORM_VOLUME_PERIODIC) ? static_cast<void*>(&pvolume)
-              : (c->term_form == LBFGSX_FORM_GRID_FIELD) ? static_cast<void*>(&gfield)
-              : (c->term_form == LBFGSX_FORM_GRID_STENCIL) ? static_cast<void*>(&stencil)
-              : (c->term_form == LBFGSX_FORM_GRAPH) ? static_cast<void*>(&graph)
-              : (c->term_form == LBFGSX_FORM_MESH)  ? static_cast<void*>(&mesh)
-              : form_is_linear(c->term_form)        ? static_cast<void*>(&linear)
-              : (c->term_form == LBFGSX_FORM_DENSE) ? static_cast<void*>(&dense)
-              : (c->term_form == LBFGSX_FORM_LINEAR_GRAPH) ? static_cast<void*>(&linear_graph)
-                                                    : static_cast<void*>(&term);
+        switch (c->term_form)
+        {
+        case LBFGSX_FORM_GRID: ptr = &grid; break;
+        case LBFGSX_FORM_VOLUME: ptr = &volume; break;
+        case LBFGSX_FORM_GRID_PERIODIC:
+        case LBFGSX_FORM_GRID_FIELD:
+        case LBFGSX_FORM_GRID_STENCIL: ptr = &mgrid; break;
+        case LBFGSX_FORM_VOLUME_PERIODIC: ptr = &mvolume; break;
+        case LBFGSX_FORM_GRAPH: ptr = &graph; break;
+        case LBFGSX_FORM_MESH: ptr = &mesh; break;
+        case LBFGSX_FORM_LINEAR:
+        case LBFGSX_FORM_LINEAR_MULTI: ptr = &linear; break;
+        case LBFGSX_FORM_DENSE: ptr = &dense; break;
+        case LBFGSX_FORM_LINEAR_GRAPH: ptr = &linear_graph; break;
+        default: ptr = &term;
+        }
     }
     BoundArgs(const BoundArgs&) = delete;
 };

@@ -12,6 +12,7 @@
 #include "../../include/LBFGSB.h"
 #include "../../include/LBFGSBatched.h"
 #include "../../include/lbfgsx_solver.h"
+#include "form_table.hpp"
 
 using namespace LBFGSpp;
 
@@ -35,16 +36,22 @@ struct lbfgsx_solver
                           const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) = 0;
     virtual void minimize_fn(int64_t n, lbfgsx_objective_fn fn, void* user, void* x, const void* lb, const void* ub,
                              lbfgsx_trace* tr, lbfgsx_result* out) = 0;
-    // the edges of a graph objective, and the element counts of its host data arrays (null: n each); elems: the
-    // connectivity table of a mesh objective (E rows) in place of ei and ej, null for a graph objective
-    struct GraphSpec
+    // what minimize_obj is asked for beside the handle: the form of the entry point that was called (LBFGSX_FORM_TERM: the one
+    // for a term or chain objective; LBFGSX_FORM_LINEAR: the one for either linear form) and that form's own arguments
+    struct ObjSpec
     {
-        int64_t E;
-        const int32_t *ei, *ej;
-        int on_device;
-        const int64_t* counts;
-        const int32_t* elems;
-        // a linear-model objective's CSR matrix in place of all of the above (rowptr null: not one): R rows, nnz entries
+        int form = LBFGSX_FORM_TERM;
+        // a lattice form's extents (slabs: three axes) and mask (a form that has one)
+        int64_t slabs = 0, rows = 0, cols = 0;
+        int periodic = 0;
+        // the edges of a graph objective, and the element counts of the host data arrays of a form with a list (null: n
+        // each); elems: the connectivity table of a mesh objective (E rows) in place of ei and ej
+        int64_t E = 0;
+        const int32_t *ei = nullptr, *ej = nullptr;
+        int on_device = 0;
+        const int64_t* counts = nullptr;
+        const int32_t* elems = nullptr;
+        // a linear-model objective's CSR matrix: R rows, nnz entries
         int64_t R = 0, nnz = 0;
         const int32_t *rowptr = nullptr, *col = nullptr;
         const void* val = nullptr;
@@ -52,16 +59,12 @@ struct lbfgsx_solver
         // a graph-regularised linear-model objective has both: the matrix above and the edges ei, ej, which are device arrays
         // when edges_dev says so (on_device then speaks of the matrix alone)
         int edges_dev = 0;
-        // a dense linear-model objective's matrix in place of all of the above (A null: not one): R rows, row stride lda
+        // a dense linear-model objective's matrix: R rows, row stride lda
         const void* A = nullptr;
         int64_t lda = 0;
     };
-    // rows, cols: the shape of a grid objective, with slabs of a volume objective, 0 for the other forms; gr: null for every form but a graph objective;
-    // periodic: the mask of a periodic grid or volume objective or of a grid field objective, -1 for the other forms; field: a grid
-    // field objective
-    virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t slabs, int64_t rows, int64_t cols, const GraphSpec* gr,
-                              const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
-                              lbfgsx_trace* tr, lbfgsx_result* out, int periodic = -1, bool field = false) = 0;
+    virtual void minimize_obj(const lbfgsx_objective* obj, int64_t n, const ObjSpec& spec, const void* const p[4], int host_mask,
+                              const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) = 0;
 };
 
 namespace {
@@ -155,6 +158,47 @@ void fill_term(TermObjective<Scalar>& f, const void* const p[4], int host_mask, 
         f.scalars(c, 8);
 }
 
+// the one objective object the spec asks for -- the class of the entry point's form around the handle, with the form's
+// arguments -- filled with its data and handed to run.  The class is chosen by the entry point that was called, never by the
+// handle: a handle of another form is refused by that class's bind call
+template <class Scalar, class Run>
+void with_objective(const lbfgsx_objective* obj, const lbfgsx_solver::ObjSpec& s, const void* const p[4], int host_mask,
+                    const double c[8], Run&& run)
+{
+    const auto go = [&](TermObjective<Scalar>& f) {
+        fill_term<Scalar>(f, p, host_mask, c, s.counts);
+        run(f);
+    };
+    const Scalar* val = static_cast<const Scalar*>(s.val);
+    switch (s.form)
+    {
+    case LBFGSX_FORM_GRID: { GridObjective<Scalar> f(obj, s.rows, s.cols); return go(f); }
+    case LBFGSX_FORM_VOLUME: { VolumeObjective<Scalar> f(obj, s.slabs, s.rows, s.cols); return go(f); }
+    case LBFGSX_FORM_GRID_PERIODIC: { PeriodicGridObjective<Scalar> f(obj, s.rows, s.cols, s.periodic); return go(f); }
+    case LBFGSX_FORM_VOLUME_PERIODIC: { PeriodicVolumeObjective<Scalar> f(obj, s.slabs, s.rows, s.cols, s.periodic); return go(f); }
+    case LBFGSX_FORM_GRID_FIELD: { GridFieldObjective<Scalar> f(obj, s.rows, s.cols, s.periodic); return go(f); }
+    case LBFGSX_FORM_GRID_STENCIL: { StencilObjective<Scalar> f(obj, s.rows, s.cols, s.periodic); return go(f); }
+    case LBFGSX_FORM_GRAPH: { GraphObjective<Scalar> f(obj); f.edges(s.E, s.ei, s.ej, s.on_device != 0); return go(f); }
+    case LBFGSX_FORM_MESH: { MeshObjective<Scalar> f(obj); f.elements(s.E, s.elems, s.on_device != 0); return go(f); }
+    case LBFGSX_FORM_LINEAR: {  // either linear form: lbfgsx_objective_bind_linear takes both
+        LinearObjective<Scalar> f(obj);
+        f.matrix(s.R, s.nnz, s.rowptr, s.col, val, s.on_device != 0, s.lanes);
+        return go(f);
+    }
+    case LBFGSX_FORM_LINEAR_GRAPH: {
+        GraphLinearObjective<Scalar> f(obj);
+        f.matrix(s.R, s.nnz, s.rowptr, s.col, val, s.on_device != 0, s.lanes).edges(s.E, s.ei, s.ej, s.edges_dev != 0);
+        return go(f);
+    }
+    case LBFGSX_FORM_DENSE: {
+        DenseLinearObjective<Scalar> f(obj);
+        f.matrix(s.R, static_cast<const Scalar*>(s.A), s.lda, s.on_device != 0, s.lanes);
+        return go(f);
+    }
+    default: { TermObjective<Scalar> f(obj); return go(f); }  // a term or chain objective: bound without arguments
+    }
+}
+
 template <class Scalar, template <class> class LS>
 struct LbfgsImpl : lbfgsx_solver
 {
@@ -235,46 +279,10 @@ struct LbfgsImpl : lbfgsx_solver
             throw;
         }
     }
-    void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t slabs, int64_t rows, int64_t cols, const GraphSpec* gr,
-                      const void* const p[4], int host_mask, const double c[8], void* x, const void*, const void*,
-                      lbfgsx_trace* tr, lbfgsx_result* out, int periodic, bool field) override
+    void minimize_obj(const lbfgsx_objective* obj, int64_t n, const ObjSpec& spec, const void* const p[4], int host_mask,
+                      const double c[8], void* x, const void*, const void*, lbfgsx_trace* tr, lbfgsx_result* out) override
     {
-        GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
-        VolumeObjective<Scalar> spaced(obj, slabs, rows, cols);  // binds with three extents when there are three
-        PeriodicGridObjective<Scalar> wrapped(obj, rows, cols, periodic);            // binds with the mask when there is one (>= 0)
-        PeriodicVolumeObjective<Scalar> wrapped3(obj, slabs, rows, cols, periodic);  // ... and three extents
-        GridFieldObjective<Scalar> fielded(obj, rows, cols, periodic);               // ... and D unknowns per node
-        StencilObjective<Scalar> patched(obj, rows, cols, periodic);                 // ... and 3x3 patches: by the handle's form
-        GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
-        MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
-        LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
-        DenseLinearObjective<Scalar> densed(obj);       // binds with the dense matrix when there is one
-        GraphLinearObjective<Scalar> coupled(obj);      // binds with the matrix and the edges when there are both
-        const bool both = gr && gr->rowptr && gr->ei;
-        if (gr && gr->A)
-            densed.matrix(gr->R, static_cast<const Scalar*>(gr->A), gr->lda, gr->on_device != 0, gr->lanes);
-        else if (both)
-            coupled.matrix(gr->R, gr->nnz, gr->rowptr, gr->col, static_cast<const Scalar*>(gr->val), gr->on_device != 0, gr->lanes)
-                .edges(gr->E, gr->ei, gr->ej, gr->edges_dev != 0);
-        else if (gr && gr->rowptr)
-            lined.matrix(gr->R, gr->nnz, gr->rowptr, gr->col, static_cast<const Scalar*>(gr->val), gr->on_device != 0, gr->lanes);
-        else if (gr && gr->elems)
-            meshed.elements(gr->E, gr->elems, gr->on_device != 0);
-        else if (gr)
-            graphed.edges(gr->E, gr->ei, gr->ej, gr->on_device != 0);
-        TermObjective<Scalar>& f = (gr && gr->A)       ? static_cast<TermObjective<Scalar>&>(densed)
-                                   : both              ? static_cast<TermObjective<Scalar>&>(coupled)
-                                   : (gr && gr->rowptr) ? static_cast<TermObjective<Scalar>&>(lined)
-                                   : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
-                                   : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
-                                   : field             ? static_cast<TermObjective<Scalar>&>(fielded)
-                                   : (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID_STENCIL) ? static_cast<TermObjective<Scalar>&>(patched)
-                                   : (periodic >= 0 && slabs) ? static_cast<TermObjective<Scalar>&>(wrapped3)
-                                   : (periodic >= 0)   ? static_cast<TermObjective<Scalar>&>(wrapped)
-                                   : slabs             ? static_cast<TermObjective<Scalar>&>(spaced)
-                                                       : shaped;
-        fill_term<Scalar>(f, p, host_mask, c, gr ? gr->counts : nullptr);
-        run(f, n, x, tr, out);
+        with_objective<Scalar>(obj, spec, p, host_mask, c, [&](TermObjective<Scalar>& f) { run(f, n, x, tr, out); });
     }
     template <class Foo>
     void run(Foo& f, int64_t n, void* x, lbfgsx_trace* tr, lbfgsx_result* out)
@@ -376,46 +384,10 @@ struct LbfgsbImpl : lbfgsx_solver
             throw;
         }
     }
-    void minimize_obj(const lbfgsx_objective* obj, int64_t n, int64_t slabs, int64_t rows, int64_t cols, const GraphSpec* gr,
-                      const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
-                      lbfgsx_trace* tr, lbfgsx_result* out, int periodic, bool field) override
+    void minimize_obj(const lbfgsx_objective* obj, int64_t n, const ObjSpec& spec, const void* const p[4], int host_mask,
+                      const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* tr, lbfgsx_result* out) override
     {
-        GridObjective<Scalar> shaped(obj, rows, cols);  // binds with the shape when there is one
-        VolumeObjective<Scalar> spaced(obj, slabs, rows, cols);  // binds with three extents when there are three
-        PeriodicGridObjective<Scalar> wrapped(obj, rows, cols, periodic);            // binds with the mask when there is one (>= 0)
-        PeriodicVolumeObjective<Scalar> wrapped3(obj, slabs, rows, cols, periodic);  // ... and three extents
-        GridFieldObjective<Scalar> fielded(obj, rows, cols, periodic);               // ... and D unknowns per node
-        StencilObjective<Scalar> patched(obj, rows, cols, periodic);                 // ... and 3x3 patches: by the handle's form
-        GraphObjective<Scalar> graphed(obj);            // binds with the edges when there are some
-        MeshObjective<Scalar> meshed(obj);              // binds with the elements when there are some
-        LinearObjective<Scalar> lined(obj);             // binds with the matrix when there is one
-        DenseLinearObjective<Scalar> densed(obj);       // binds with the dense matrix when there is one
-        GraphLinearObjective<Scalar> coupled(obj);      // binds with the matrix and the edges when there are both
-        const bool both = gr && gr->rowptr && gr->ei;
-        if (gr && gr->A)
-            densed.matrix(gr->R, static_cast<const Scalar*>(gr->A), gr->lda, gr->on_device != 0, gr->lanes);
-        else if (both)
-            coupled.matrix(gr->R, gr->nnz, gr->rowptr, gr->col, static_cast<const Scalar*>(gr->val), gr->on_device != 0, gr->lanes)
-                .edges(gr->E, gr->ei, gr->ej, gr->edges_dev != 0);
-        else if (gr && gr->rowptr)
-            lined.matrix(gr->R, gr->nnz, gr->rowptr, gr->col, static_cast<const Scalar*>(gr->val), gr->on_device != 0, gr->lanes);
-        else if (gr && gr->elems)
-            meshed.elements(gr->E, gr->elems, gr->on_device != 0);
-        else if (gr)
-            graphed.edges(gr->E, gr->ei, gr->ej, gr->on_device != 0);
-        TermObjective<Scalar>& f = (gr && gr->A)       ? static_cast<TermObjective<Scalar>&>(densed)
-                                   : both              ? static_cast<TermObjective<Scalar>&>(coupled)
-                                   : (gr && gr->rowptr) ? static_cast<TermObjective<Scalar>&>(lined)
-                                   : (gr && gr->elems) ? static_cast<TermObjective<Scalar>&>(meshed)
-                                   : gr                ? static_cast<TermObjective<Scalar>&>(graphed)
-                                   : field             ? static_cast<TermObjective<Scalar>&>(fielded)
-                                   : (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID_STENCIL) ? static_cast<TermObjective<Scalar>&>(patched)
-                                   : (periodic >= 0 && slabs) ? static_cast<TermObjective<Scalar>&>(wrapped3)
-                                   : (periodic >= 0)   ? static_cast<TermObjective<Scalar>&>(wrapped)
-                                   : slabs             ? static_cast<TermObjective<Scalar>&>(spaced)
-                                                       : shaped;
-        fill_term<Scalar>(f, p, host_mask, c, gr ? gr->counts : nullptr);
-        run(f, n, x, lb, ub, tr, out);
+        with_objective<Scalar>(obj, spec, p, host_mask, c, [&](TermObjective<Scalar>& f) { run(f, n, x, lb, ub, tr, out); });
     }
     template <class Foo>
     void run(Foo& f, int64_t n, void* x, const void* lb, const void* ub, lbfgsx_trace* tr, lbfgsx_result* out)
@@ -981,276 +953,124 @@ int lbfgsx_solver_minimize_fn(lbfgsx_solver* s, int64_t n, lbfgsx_objective_fn f
     });
 }
 
+}  // extern "C"
+
+namespace {
+
+typedef lbfgsx_solver::ObjSpec ObjSpec;
+
+// what every entry point for a compiled objective does around its own checks: the result cleared; what is wrong with the
+// request itself said first, with or without a device; then the refusal of a host without one; then the run
+template <class Checks, class Run>
+int objective_entry(const std::string& name, lbfgsx_result* out, Checks&& checks, Run&& run)
+{
+    std::memset(out, 0, sizeof(*out));
+    if (const int bad = guarded(out, checks))
+        return bad;
+    if (lbfgsx_device_count() <= 0)
+    {
+        out->status = LBFGSX_E_NOGPU;
+        std::snprintf(out->msg, sizeof(out->msg), "%s: no HIP device available (this library has no CPU fallback)", name.c_str());
+        return out->status;
+    }
+    return guarded(out, run);
+}
+
+// the entry point of a lattice form: the handle's form and dtype, then the rules of the form's row (form_table.hpp), which
+// also give n.  slabs = 0 on two axes, periodic = 0 for a form without a mask
+int minimize_lattice(int form, lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols, int periodic,
+                     const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
+                     lbfgsx_trace* trace, lbfgsx_result* out)
+{
+    const lbfgsx::FormRow& row = lbfgsx::kFormRows[form];
+    const std::string name = std::string("lbfgsx_solver_minimize") + row.suffix;
+    long long n = 0;
+    return objective_entry(
+        name, out,
+        [&]() {
+            if (!s || !obj)
+                throw std::invalid_argument(name + ": invalid argument");
+            if (lbfgsx_objective_form(obj) != form)
+                throw std::invalid_argument(name + ": the handle is not a " + row.name + " (lbfgsx_objective_compile" + row.suffix + ")");
+            if (lbfgsx_objective_dtype(obj) != s->dtype)
+                throw std::invalid_argument(name + ": the objective was compiled for the other dtype");
+            const int D = lbfgsx_objective_D(obj);
+            if (const lbfgsx::LatticeRule bad = lbfgsx::lattice_check(form, D, slabs, rows, cols, periodic, &n))
+                throw std::invalid_argument(lbfgsx::lattice_refusal(form, bad, D, slabs, rows, cols, periodic));
+        },
+        [&]() {
+            ObjSpec spec;
+            spec.form = form, spec.slabs = slabs, spec.rows = rows, spec.cols = cols, spec.periodic = periodic;
+            s->minimize_obj(obj, int64_t(n), spec, p, host_mask, c, x, lb, ub, trace, out);
+        });
+}
+
+}  // namespace
+
+extern "C" {
+
 int lbfgsx_solver_minimize_obj(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, const void* const p[4], int host_mask,
                                const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
                                lbfgsx_result* out)
 {
-    std::memset(out, 0, sizeof(*out));
-    // what is wrong with the request itself is said first, with or without a device
-    const int bad = guarded(out, [&]() {
-        if (!s || !obj || n <= 0)
-            throw std::invalid_argument("lbfgsx_solver_minimize_obj: invalid argument");
-        if (lbfgsx_objective_dtype(obj) != s->dtype)
-            throw std::invalid_argument("lbfgsx_solver_minimize_obj: the objective was compiled for the other dtype");
-        const int K = lbfgsx_objective_K(obj);
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID)
-            throw std::invalid_argument("a grid objective is minimised with its shape: lbfgsx_solver_minimize_grid");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_VOLUME)
-            throw std::invalid_argument("a volume objective is minimised with its shape: lbfgsx_solver_minimize_volume");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID_PERIODIC)
-            throw std::invalid_argument("a periodic grid objective is minimised with its shape and mask: lbfgsx_solver_minimize_grid_periodic");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_VOLUME_PERIODIC)
-            throw std::invalid_argument("a periodic volume objective is minimised with its shape and mask: lbfgsx_solver_minimize_volume_periodic");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID_FIELD)
-            throw std::invalid_argument("a grid field objective is minimised with its shape and mask: lbfgsx_solver_minimize_grid_field");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRID_STENCIL)
-            throw std::invalid_argument("a grid stencil objective is minimised with its shape and mask: lbfgsx_solver_minimize_grid_stencil");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_GRAPH)
-            throw std::invalid_argument("a graph objective is minimised with its edges: lbfgsx_solver_minimize_graph");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_MESH)
-            throw std::invalid_argument("a mesh objective is minimised with its elements: lbfgsx_solver_minimize_mesh");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_LINEAR)
-            throw std::invalid_argument("a linear-model objective is minimised with its matrix: lbfgsx_solver_minimize_linear");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_LINEAR_MULTI)
-            throw std::invalid_argument("a multi-output linear-model objective is minimised with its matrix: "
-                                        "lbfgsx_solver_minimize_linear");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_DENSE)
-            throw std::invalid_argument("a dense linear-model objective is minimised with its matrix: lbfgsx_solver_minimize_dense");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_LINEAR_GRAPH)
-            throw std::invalid_argument("a graph-regularised linear-model objective is minimised with its matrix and edges: "
-                                        "lbfgsx_solver_minimize_linear_graph");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_CHAIN)
-        {
-            if (n < K)
-                throw std::invalid_argument("chain objective: n = " + std::to_string(n) + " is less than K = " + std::to_string(K) +
-                                            ": there is no term");
-        }
-        else if (n % K != 0)
-            throw std::invalid_argument("term objective: n = " + std::to_string(n) + " is not a multiple of K = " + std::to_string(K));
-    });
-    if (bad)
-        return bad;
-    if (lbfgsx_device_count() <= 0)
-    {
-        out->status = LBFGSX_E_NOGPU;
-        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_obj: no HIP device available (this library has no CPU fallback)");
-        return out->status;
-    }
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, 0, nullptr, p, host_mask, c, x, lb, ub, trace, out); });
+    return objective_entry(
+        "lbfgsx_solver_minimize_obj", out,
+        [&]() {
+            if (!s || !obj || n <= 0)
+                throw std::invalid_argument("lbfgsx_solver_minimize_obj: invalid argument");
+            if (lbfgsx_objective_dtype(obj) != s->dtype)
+                throw std::invalid_argument("lbfgsx_solver_minimize_obj: the objective was compiled for the other dtype");
+            const int K = lbfgsx_objective_K(obj), form = lbfgsx_objective_form(obj);
+            if (lbfgsx::kFormRows[form].bound_with)
+                throw std::invalid_argument(lbfgsx::unshaped_refusal(form, true));
+            if (form == LBFGSX_FORM_CHAIN)
+            {
+                if (n < K)
+                    throw std::invalid_argument("chain objective: n = " + std::to_string(n) + " is less than K = " + std::to_string(K) +
+                                                ": there is no term");
+            }
+            else if (n % K != 0)
+                throw std::invalid_argument("term objective: n = " + std::to_string(n) + " is not a multiple of K = " + std::to_string(K));
+        },
+        [&]() { s->minimize_obj(obj, n, ObjSpec(), p, host_mask, c, x, lb, ub, trace, out); });
 }
 
+// ---- the six lattice forms: one entry (minimize_lattice), by the form's row of kFormRows
 int lbfgsx_solver_minimize_grid(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, const void* const p[4],
                                 int host_mask, const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
                                 lbfgsx_result* out)
 {
-    std::memset(out, 0, sizeof(*out));
-    long long n = 0;
-    const int bad = guarded(out, [&]() {
-        if (!s || !obj)
-            throw std::invalid_argument("lbfgsx_solver_minimize_grid: invalid argument");
-        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_GRID)
-            throw std::invalid_argument("lbfgsx_solver_minimize_grid: the handle is not a grid objective (lbfgsx_objective_compile_grid)");
-        if (lbfgsx_objective_dtype(obj) != s->dtype)
-            throw std::invalid_argument("lbfgsx_solver_minimize_grid: the objective was compiled for the other dtype");
-        const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
-        if (rows < 2 || cols < 2)
-            throw std::invalid_argument("grid objective: " + shape + ": a grid has at least 2 rows and 2 columns (rows >= 2, cols >= 2)");
-        if (__builtin_mul_overflow((long long) rows, (long long) cols, &n))
-            throw std::invalid_argument("grid objective: " + shape + ": rows*cols overflows");
-    });
-    if (bad)
-        return bad;
-    if (lbfgsx_device_count() <= 0)
-    {
-        out->status = LBFGSX_E_NOGPU;
-        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_grid: no HIP device available (this library has no CPU fallback)");
-        return out->status;
-    }
-    return guarded(out, [&]() { s->minimize_obj(obj, int64_t(n), 0, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out); });
+    return minimize_lattice(LBFGSX_FORM_GRID, s, obj, 0, rows, cols, 0, p, host_mask, c, x, lb, ub, trace, out);
 }
-
 int lbfgsx_solver_minimize_volume(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
                                   const void* const p[4], int host_mask, const double c[8], void* x, const void* lb, const void* ub,
                                   lbfgsx_trace* trace, lbfgsx_result* out)
 {
-    std::memset(out, 0, sizeof(*out));
-    long long n = 0;
-    const int bad = guarded(out, [&]() {
-        if (!s || !obj)
-            throw std::invalid_argument("lbfgsx_solver_minimize_volume: invalid argument");
-        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_VOLUME)
-            throw std::invalid_argument("lbfgsx_solver_minimize_volume: the handle is not a volume objective (lbfgsx_objective_compile_volume)");
-        if (lbfgsx_objective_dtype(obj) != s->dtype)
-            throw std::invalid_argument("lbfgsx_solver_minimize_volume: the objective was compiled for the other dtype");
-        const std::string shape =
-            "slabs = " + std::to_string(slabs) + ", rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
-        if (slabs < 2 || rows < 2 || cols < 2)
-            throw std::invalid_argument("volume objective: " + shape +
-                                        ": a volume has at least 2 slabs, 2 rows and 2 columns (slabs >= 2, rows >= 2, cols >= 2)");
-        if (__builtin_mul_overflow((long long) rows, (long long) cols, &n) || __builtin_mul_overflow(n, (long long) slabs, &n))
-            throw std::invalid_argument("volume objective: " + shape + ": slabs*rows*cols overflows");
-    });
-    if (bad)
-        return bad;
-    if (lbfgsx_device_count() <= 0)
-    {
-        out->status = LBFGSX_E_NOGPU;
-        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_volume: no HIP device available (this library has no CPU fallback)");
-        return out->status;
-    }
-    return guarded(out, [&]() { s->minimize_obj(obj, int64_t(n), slabs, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out); });
+    return minimize_lattice(LBFGSX_FORM_VOLUME, s, obj, slabs, rows, cols, 0, p, host_mask, c, x, lb, ub, trace, out);
 }
-
 int lbfgsx_solver_minimize_grid_periodic(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
                                          const void* const p[4], int host_mask, const double c[8], void* x, const void* lb,
                                          const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
 {
-    std::memset(out, 0, sizeof(*out));
-    long long n = 0;
-    const int bad = guarded(out, [&]() {
-        if (!s || !obj)
-            throw std::invalid_argument("lbfgsx_solver_minimize_grid_periodic: invalid argument");
-        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_GRID_PERIODIC)
-            throw std::invalid_argument("lbfgsx_solver_minimize_grid_periodic: the handle is not a periodic grid objective "
-                                        "(lbfgsx_objective_compile_grid_periodic)");
-        if (lbfgsx_objective_dtype(obj) != s->dtype)
-            throw std::invalid_argument("lbfgsx_solver_minimize_grid_periodic: the objective was compiled for the other dtype");
-        const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
-        if (rows < 2 || cols < 2)
-            throw std::invalid_argument("periodic grid objective: " + shape +
-                                        ": a grid has at least 2 rows and 2 columns (rows >= 2, cols >= 2)");
-        if (__builtin_mul_overflow((long long) rows, (long long) cols, &n))
-            throw std::invalid_argument("periodic grid objective: " + shape + ": rows*cols overflows");
-        if (periodic < 0 || periodic > 3)
-            throw std::invalid_argument("periodic grid objective: periodic = " + std::to_string(periodic) +
-                                        ": the mask has bit 0 for the column direction and bit 1 for the row direction (0 .. 3)");
-    });
-    if (bad)
-        return bad;
-    if (lbfgsx_device_count() <= 0)
-    {
-        out->status = LBFGSX_E_NOGPU;
-        std::snprintf(out->msg, sizeof(out->msg),
-                      "lbfgsx_solver_minimize_grid_periodic: no HIP device available (this library has no CPU fallback)");
-        return out->status;
-    }
-    return guarded(out,
-                   [&]() { s->minimize_obj(obj, int64_t(n), 0, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out, periodic); });
+    return minimize_lattice(LBFGSX_FORM_GRID_PERIODIC, s, obj, 0, rows, cols, periodic, p, host_mask, c, x, lb, ub, trace, out);
 }
-
-int lbfgsx_solver_minimize_grid_field(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
-                                      const void* const p[4], int host_mask, const double c[8], void* x, const void* lb,
-                                      const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
-{
-    std::memset(out, 0, sizeof(*out));
-    long long n = 0;
-    const int bad = guarded(out, [&]() {
-        if (!s || !obj)
-            throw std::invalid_argument("lbfgsx_solver_minimize_grid_field: invalid argument");
-        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_GRID_FIELD)
-            throw std::invalid_argument("lbfgsx_solver_minimize_grid_field: the handle is not a grid field objective "
-                                        "(lbfgsx_objective_compile_grid_field)");
-        if (lbfgsx_objective_dtype(obj) != s->dtype)
-            throw std::invalid_argument("lbfgsx_solver_minimize_grid_field: the objective was compiled for the other dtype");
-        const int D = lbfgsx_objective_D(obj);
-        const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols) + ", D = " + std::to_string(D);
-        if (rows < 2 || cols < 2)
-            throw std::invalid_argument("grid field objective: " + shape +
-                                        ": a grid has at least 2 rows and 2 columns (rows >= 2, cols >= 2)");
-        if (__builtin_mul_overflow((long long) rows, (long long) cols, &n) || __builtin_mul_overflow(n, (long long) D, &n))
-            throw std::invalid_argument("grid field objective: " + shape + ": rows*cols*D overflows");
-        if (periodic < 0 || periodic > 3)
-            throw std::invalid_argument("grid field objective: periodic = " + std::to_string(periodic) +
-                                        ": the mask has bit 0 for the column direction and bit 1 for the row direction (0 .. 3)");
-    });
-    if (bad)
-        return bad;
-    if (lbfgsx_device_count() <= 0)
-    {
-        out->status = LBFGSX_E_NOGPU;
-        std::snprintf(out->msg, sizeof(out->msg),
-                      "lbfgsx_solver_minimize_grid_field: no HIP device available (this library has no CPU fallback)");
-        return out->status;
-    }
-    return guarded(out, [&]() {
-        s->minimize_obj(obj, int64_t(n), 0, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out, periodic, true);
-    });
-}
-
-int lbfgsx_solver_minimize_grid_stencil(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
-                                        const void* const p[4], int host_mask, const double c[8], void* x, const void* lb,
-                                        const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
-{
-    std::memset(out, 0, sizeof(*out));
-    long long n = 0;
-    const int bad = guarded(out, [&]() {
-        if (!s || !obj)
-            throw std::invalid_argument("lbfgsx_solver_minimize_grid_stencil: invalid argument");
-        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_GRID_STENCIL)
-            throw std::invalid_argument("lbfgsx_solver_minimize_grid_stencil: the handle is not a grid stencil objective "
-                                        "(lbfgsx_objective_compile_grid_stencil)");
-        if (lbfgsx_objective_dtype(obj) != s->dtype)
-            throw std::invalid_argument("lbfgsx_solver_minimize_grid_stencil: the objective was compiled for the other dtype");
-        const std::string shape = "rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
-        if (rows < 3 || cols < 3)
-            throw std::invalid_argument("grid stencil objective: " + shape +
-                                        ": a 3x3 patch needs at least 3 rows and 3 columns (rows >= 3, cols >= 3)");
-        if (__builtin_mul_overflow((long long) rows, (long long) cols, &n))
-            throw std::invalid_argument("grid stencil objective: " + shape + ": rows*cols overflows");
-        if (periodic < 0 || periodic > 3)
-            throw std::invalid_argument("grid stencil objective: periodic = " + std::to_string(periodic) +
-                                        ": the mask has bit 0 for the column direction and bit 1 for the row direction (0 .. 3)");
-    });
-    if (bad)
-        return bad;
-    if (lbfgsx_device_count() <= 0)
-    {
-        out->status = LBFGSX_E_NOGPU;
-        std::snprintf(out->msg, sizeof(out->msg),
-                      "lbfgsx_solver_minimize_grid_stencil: no HIP device available (this library has no CPU fallback)");
-        return out->status;
-    }
-    return guarded(out,
-                   [&]() { s->minimize_obj(obj, int64_t(n), 0, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out, periodic); });
-}
-
 int lbfgsx_solver_minimize_volume_periodic(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t slabs, int64_t rows, int64_t cols,
                                            int periodic, const void* const p[4], int host_mask, const double c[8], void* x,
                                            const void* lb, const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
 {
-    std::memset(out, 0, sizeof(*out));
-    long long n = 0;
-    const int bad = guarded(out, [&]() {
-        if (!s || !obj)
-            throw std::invalid_argument("lbfgsx_solver_minimize_volume_periodic: invalid argument");
-        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_VOLUME_PERIODIC)
-            throw std::invalid_argument("lbfgsx_solver_minimize_volume_periodic: the handle is not a periodic volume objective "
-                                        "(lbfgsx_objective_compile_volume_periodic)");
-        if (lbfgsx_objective_dtype(obj) != s->dtype)
-            throw std::invalid_argument("lbfgsx_solver_minimize_volume_periodic: the objective was compiled for the other dtype");
-        const std::string shape =
-            "slabs = " + std::to_string(slabs) + ", rows = " + std::to_string(rows) + ", cols = " + std::to_string(cols);
-        if (slabs < 2 || rows < 2 || cols < 2)
-            throw std::invalid_argument("periodic volume objective: " + shape +
-                                        ": a volume has at least 2 slabs, 2 rows and 2 columns (slabs >= 2, rows >= 2, cols >= 2)");
-        if (__builtin_mul_overflow((long long) rows, (long long) cols, &n) || __builtin_mul_overflow(n, (long long) slabs, &n))
-            throw std::invalid_argument("periodic volume objective: " + shape + ": slabs*rows*cols overflows");
-        if (periodic < 0 || periodic > 7)
-            throw std::invalid_argument("periodic volume objective: periodic = " + std::to_string(periodic) +
-                                        ": the mask has bit 0 for the column, bit 1 for the row and bit 2 for the slab direction (0 .. 7)");
-    });
-    if (bad)
-        return bad;
-    if (lbfgsx_device_count() <= 0)
-    {
-        out->status = LBFGSX_E_NOGPU;
-        std::snprintf(out->msg, sizeof(out->msg),
-                      "lbfgsx_solver_minimize_volume_periodic: no HIP device available (this library has no CPU fallback)");
-        return out->status;
-    }
-    return guarded(out, [&]() {
-        s->minimize_obj(obj, int64_t(n), slabs, rows, cols, nullptr, p, host_mask, c, x, lb, ub, trace, out, periodic);
-    });
+    return minimize_lattice(LBFGSX_FORM_VOLUME_PERIODIC, s, obj, slabs, rows, cols, periodic, p, host_mask, c, x, lb, ub, trace, out);
+}
+int lbfgsx_solver_minimize_grid_field(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                      const void* const p[4], int host_mask, const double c[8], void* x, const void* lb,
+                                      const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
+{
+    return minimize_lattice(LBFGSX_FORM_GRID_FIELD, s, obj, 0, rows, cols, periodic, p, host_mask, c, x, lb, ub, trace, out);
+}
+int lbfgsx_solver_minimize_grid_stencil(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t rows, int64_t cols, int periodic,
+                                        const void* const p[4], int host_mask, const double c[8], void* x, const void* lb,
+                                        const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
+{
+    return minimize_lattice(LBFGSX_FORM_GRID_STENCIL, s, obj, 0, rows, cols, periodic, p, host_mask, c, x, lb, ub, trace, out);
 }
 
 int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t E, const int32_t* ei,
@@ -1258,32 +1078,27 @@ int lbfgsx_solver_minimize_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, 
                                  const int64_t counts[4], const double c[8], void* x, const void* lb, const void* ub,
                                  lbfgsx_trace* trace, lbfgsx_result* out)
 {
-    std::memset(out, 0, sizeof(*out));
-    const int bad = guarded(out, [&]() {
-        if (!s || !obj || n <= 0)
-            throw std::invalid_argument("lbfgsx_solver_minimize_graph: invalid argument");
-        if (lbfgsx_objective_form(obj) == LBFGSX_FORM_MESH)
-            throw std::invalid_argument("lbfgsx_solver_minimize_graph: the handle is a mesh objective: it is minimised with its "
-                                        "elements, lbfgsx_solver_minimize_mesh");
-        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_GRAPH)
-            throw std::invalid_argument("lbfgsx_solver_minimize_graph: the handle is not a graph objective (lbfgsx_objective_compile_graph)");
-        if (lbfgsx_objective_dtype(obj) != s->dtype)
-            throw std::invalid_argument("lbfgsx_solver_minimize_graph: the objective was compiled for the other dtype");
-        if (E < 1 || !ei || !ej)
-            throw std::invalid_argument("graph objective: E = " + std::to_string(E) +
-                                        ": a graph objective has at least one edge (E >= 1) and both index arrays");
-    });
-    if (bad)
-        return bad;
-    if (lbfgsx_device_count() <= 0)
-    {
-        out->status = LBFGSX_E_NOGPU;
-        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_graph: no HIP device available (this library has no CPU fallback)");
-        return out->status;
-    }
-    lbfgsx_solver::GraphSpec gr;
-    gr.E = E, gr.ei = ei, gr.ej = ej, gr.on_device = edges_on_device, gr.counts = counts, gr.elems = nullptr;
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+    return objective_entry(
+        "lbfgsx_solver_minimize_graph", out,
+        [&]() {
+            if (!s || !obj || n <= 0)
+                throw std::invalid_argument("lbfgsx_solver_minimize_graph: invalid argument");
+            if (lbfgsx_objective_form(obj) == LBFGSX_FORM_MESH)
+                throw std::invalid_argument("lbfgsx_solver_minimize_graph: the handle is a mesh objective: it is minimised with its "
+                                            "elements, lbfgsx_solver_minimize_mesh");
+            if (lbfgsx_objective_form(obj) != LBFGSX_FORM_GRAPH)
+                throw std::invalid_argument("lbfgsx_solver_minimize_graph: the handle is not a graph objective (lbfgsx_objective_compile_graph)");
+            if (lbfgsx_objective_dtype(obj) != s->dtype)
+                throw std::invalid_argument("lbfgsx_solver_minimize_graph: the objective was compiled for the other dtype");
+            if (E < 1 || !ei || !ej)
+                throw std::invalid_argument("graph objective: E = " + std::to_string(E) +
+                                            ": a graph objective has at least one edge (E >= 1) and both index arrays");
+        },
+        [&]() {
+            ObjSpec gr;
+            gr.form = LBFGSX_FORM_GRAPH, gr.E = E, gr.ei = ei, gr.ej = ej, gr.on_device = edges_on_device, gr.counts = counts;
+            s->minimize_obj(obj, n, gr, p, host_mask, c, x, lb, ub, trace, out);
+        });
 }
 
 int lbfgsx_solver_minimize_mesh(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t E, const int32_t* elems,
@@ -1291,33 +1106,28 @@ int lbfgsx_solver_minimize_mesh(lbfgsx_solver* s, const lbfgsx_objective* obj, i
                                 const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
                                 lbfgsx_result* out)
 {
-    std::memset(out, 0, sizeof(*out));
-    const int bad = guarded(out, [&]() {
-        if (!s || !obj || n <= 0)
-            throw std::invalid_argument("lbfgsx_solver_minimize_mesh: invalid argument");
-        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_MESH)
-            throw std::invalid_argument("lbfgsx_solver_minimize_mesh: the handle is not a mesh objective (lbfgsx_objective_compile_mesh)");
-        if (lbfgsx_objective_dtype(obj) != s->dtype)
-            throw std::invalid_argument("lbfgsx_solver_minimize_mesh: the objective was compiled for the other dtype");
-        if (E < 1 || !elems)
-            throw std::invalid_argument("mesh objective: E = " + std::to_string(E) +
-                                        ": a mesh objective has at least one element (E >= 1) and its connectivity table");
-        const int D = lbfgsx_objective_dim(obj);
-        if (n % D != 0)
-            throw std::invalid_argument("mesh objective: n = " + std::to_string(n) + " is not a multiple of D = " + std::to_string(D) +
-                                        ": x holds D unknowns per node");
-    });
-    if (bad)
-        return bad;
-    if (lbfgsx_device_count() <= 0)
-    {
-        out->status = LBFGSX_E_NOGPU;
-        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_mesh: no HIP device available (this library has no CPU fallback)");
-        return out->status;
-    }
-    lbfgsx_solver::GraphSpec gr;
-    gr.E = E, gr.ei = gr.ej = nullptr, gr.on_device = elems_on_device, gr.counts = counts, gr.elems = elems;
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+    return objective_entry(
+        "lbfgsx_solver_minimize_mesh", out,
+        [&]() {
+            if (!s || !obj || n <= 0)
+                throw std::invalid_argument("lbfgsx_solver_minimize_mesh: invalid argument");
+            if (lbfgsx_objective_form(obj) != LBFGSX_FORM_MESH)
+                throw std::invalid_argument("lbfgsx_solver_minimize_mesh: the handle is not a mesh objective (lbfgsx_objective_compile_mesh)");
+            if (lbfgsx_objective_dtype(obj) != s->dtype)
+                throw std::invalid_argument("lbfgsx_solver_minimize_mesh: the objective was compiled for the other dtype");
+            if (E < 1 || !elems)
+                throw std::invalid_argument("mesh objective: E = " + std::to_string(E) +
+                                            ": a mesh objective has at least one element (E >= 1) and its connectivity table");
+            const int D = lbfgsx_objective_dim(obj);
+            if (n % D != 0)
+                throw std::invalid_argument("mesh objective: n = " + std::to_string(n) + " is not a multiple of D = " + std::to_string(D) +
+                                            ": x holds D unknowns per node");
+        },
+        [&]() {
+            ObjSpec gr;
+            gr.form = LBFGSX_FORM_MESH, gr.E = E, gr.on_device = elems_on_device, gr.counts = counts, gr.elems = elems;
+            s->minimize_obj(obj, n, gr, p, host_mask, c, x, lb, ub, trace, out);
+        });
 }
 
 int lbfgsx_solver_minimize_linear(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, int64_t nnz,
@@ -1325,37 +1135,32 @@ int lbfgsx_solver_minimize_linear(lbfgsx_solver* s, const lbfgsx_objective* obj,
                                   const void* const p[4], int host_mask, const int64_t counts[4], const double c[8], void* x,
                                   const void* lb, const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
 {
-    std::memset(out, 0, sizeof(*out));
-    const int bad = guarded(out, [&]() {
-        if (!s || !obj || n <= 0)
-            throw std::invalid_argument("lbfgsx_solver_minimize_linear: invalid argument");
-        const bool multi = lbfgsx_objective_form(obj) == LBFGSX_FORM_LINEAR_MULTI;
-        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_LINEAR && !multi)
-            throw std::invalid_argument("lbfgsx_solver_minimize_linear: the handle is not a linear-model objective "
-                                        "(lbfgsx_objective_compile_linear)");
-        if (multi && n % lbfgsx_objective_dim(obj) != 0)
-            throw std::invalid_argument("multi-output linear-model objective: n = " + std::to_string(n) +
-                                        " is not a multiple of D = " + std::to_string(lbfgsx_objective_dim(obj)) +
-                                        ": x holds the D weights of each feature");
-        if (lbfgsx_objective_dtype(obj) != s->dtype)
-            throw std::invalid_argument("lbfgsx_solver_minimize_linear: the objective was compiled for the other dtype");
-        if (R < 1 || nnz < 1 || !rowptr || !col || !val)
-            throw std::invalid_argument("linear-model objective: R = " + std::to_string(R) + ", nnz = " + std::to_string(nnz) +
-                                        ": a linear-model objective has at least one row and one entry (R >= 1, nnz >= 1) and "
-                                        "its three CSR arrays");
-    });
-    if (bad)
-        return bad;
-    if (lbfgsx_device_count() <= 0)
-    {
-        out->status = LBFGSX_E_NOGPU;
-        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_linear: no HIP device available (this library has no CPU fallback)");
-        return out->status;
-    }
-    lbfgsx_solver::GraphSpec gr;
-    gr.E = 0, gr.ei = gr.ej = nullptr, gr.on_device = matrix_on_device, gr.counts = counts, gr.elems = nullptr;
-    gr.R = R, gr.nnz = nnz, gr.rowptr = rowptr, gr.col = col, gr.val = val, gr.lanes = lanes;
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+    return objective_entry(
+        "lbfgsx_solver_minimize_linear", out,
+        [&]() {
+            if (!s || !obj || n <= 0)
+                throw std::invalid_argument("lbfgsx_solver_minimize_linear: invalid argument");
+            const bool multi = lbfgsx_objective_form(obj) == LBFGSX_FORM_LINEAR_MULTI;
+            if (lbfgsx_objective_form(obj) != LBFGSX_FORM_LINEAR && !multi)
+                throw std::invalid_argument("lbfgsx_solver_minimize_linear: the handle is not a linear-model objective "
+                                            "(lbfgsx_objective_compile_linear)");
+            if (multi && n % lbfgsx_objective_dim(obj) != 0)
+                throw std::invalid_argument("multi-output linear-model objective: n = " + std::to_string(n) +
+                                            " is not a multiple of D = " + std::to_string(lbfgsx_objective_dim(obj)) +
+                                            ": x holds the D weights of each feature");
+            if (lbfgsx_objective_dtype(obj) != s->dtype)
+                throw std::invalid_argument("lbfgsx_solver_minimize_linear: the objective was compiled for the other dtype");
+            if (R < 1 || nnz < 1 || !rowptr || !col || !val)
+                throw std::invalid_argument("linear-model objective: R = " + std::to_string(R) + ", nnz = " + std::to_string(nnz) +
+                                            ": a linear-model objective has at least one row and one entry (R >= 1, nnz >= 1) and "
+                                            "its three CSR arrays");
+        },
+        [&]() {
+            ObjSpec gr;
+            gr.form = LBFGSX_FORM_LINEAR, gr.on_device = matrix_on_device, gr.counts = counts;
+            gr.R = R, gr.nnz = nnz, gr.rowptr = rowptr, gr.col = col, gr.val = val, gr.lanes = lanes;
+            s->minimize_obj(obj, n, gr, p, host_mask, c, x, lb, ub, trace, out);
+        });
 }
 
 int lbfgsx_solver_minimize_linear_graph(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, int64_t nnz,
@@ -1364,36 +1169,31 @@ int lbfgsx_solver_minimize_linear_graph(lbfgsx_solver* s, const lbfgsx_objective
                                         const void* const p[4], int host_mask, const int64_t counts[4], const double c[8],
                                         void* x, const void* lb, const void* ub, lbfgsx_trace* trace, lbfgsx_result* out)
 {
-    std::memset(out, 0, sizeof(*out));
-    const int bad = guarded(out, [&]() {
-        if (!s || !obj || n <= 0)
-            throw std::invalid_argument("lbfgsx_solver_minimize_linear_graph: invalid argument");
-        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_LINEAR_GRAPH)
-            throw std::invalid_argument("lbfgsx_solver_minimize_linear_graph: the handle is not a graph-regularised linear-model "
-                                        "objective (lbfgsx_objective_compile_linear_graph)");
-        if (lbfgsx_objective_dtype(obj) != s->dtype)
-            throw std::invalid_argument("lbfgsx_solver_minimize_linear_graph: the objective was compiled for the other dtype");
-        if (E < 1 || !ei || !ej)
-            throw std::invalid_argument("graph-regularised linear-model objective: E = " + std::to_string(E) +
-                                        ": a graph-regularised linear-model objective has at least one edge (E >= 1) and both "
-                                        "index arrays");
-        if (R < 1 || nnz < 1 || !rowptr || !col || !val)
-            throw std::invalid_argument("graph-regularised linear-model objective: R = " + std::to_string(R) + ", nnz = " +
-                                        std::to_string(nnz) + ": a linear-model objective has at least one row and one entry "
-                                        "(R >= 1, nnz >= 1) and its three CSR arrays");
-    });
-    if (bad)
-        return bad;
-    if (lbfgsx_device_count() <= 0)
-    {
-        out->status = LBFGSX_E_NOGPU;
-        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_linear_graph: no HIP device available (this library has no CPU fallback)");
-        return out->status;
-    }
-    lbfgsx_solver::GraphSpec gr;
-    gr.E = E, gr.ei = ei, gr.ej = ej, gr.on_device = matrix_on_device, gr.counts = counts, gr.elems = nullptr;
-    gr.R = R, gr.nnz = nnz, gr.rowptr = rowptr, gr.col = col, gr.val = val, gr.lanes = lanes, gr.edges_dev = edges_on_device;
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+    return objective_entry(
+        "lbfgsx_solver_minimize_linear_graph", out,
+        [&]() {
+            if (!s || !obj || n <= 0)
+                throw std::invalid_argument("lbfgsx_solver_minimize_linear_graph: invalid argument");
+            if (lbfgsx_objective_form(obj) != LBFGSX_FORM_LINEAR_GRAPH)
+                throw std::invalid_argument("lbfgsx_solver_minimize_linear_graph: the handle is not a graph-regularised linear-model "
+                                            "objective (lbfgsx_objective_compile_linear_graph)");
+            if (lbfgsx_objective_dtype(obj) != s->dtype)
+                throw std::invalid_argument("lbfgsx_solver_minimize_linear_graph: the objective was compiled for the other dtype");
+            if (E < 1 || !ei || !ej)
+                throw std::invalid_argument("graph-regularised linear-model objective: E = " + std::to_string(E) +
+                                            ": a graph-regularised linear-model objective has at least one edge (E >= 1) and both "
+                                            "index arrays");
+            if (R < 1 || nnz < 1 || !rowptr || !col || !val)
+                throw std::invalid_argument("graph-regularised linear-model objective: R = " + std::to_string(R) + ", nnz = " +
+                                            std::to_string(nnz) + ": a linear-model objective has at least one row and one entry "
+                                            "(R >= 1, nnz >= 1) and its three CSR arrays");
+        },
+        [&]() {
+            ObjSpec gr;
+            gr.form = LBFGSX_FORM_LINEAR_GRAPH, gr.E = E, gr.ei = ei, gr.ej = ej, gr.on_device = matrix_on_device, gr.counts = counts;
+            gr.R = R, gr.nnz = nnz, gr.rowptr = rowptr, gr.col = col, gr.val = val, gr.lanes = lanes, gr.edges_dev = edges_on_device;
+            s->minimize_obj(obj, n, gr, p, host_mask, c, x, lb, ub, trace, out);
+        });
 }
 
 int lbfgsx_solver_minimize_dense(lbfgsx_solver* s, const lbfgsx_objective* obj, int64_t n, int64_t R, const void* A, int64_t lda,
@@ -1401,40 +1201,35 @@ int lbfgsx_solver_minimize_dense(lbfgsx_solver* s, const lbfgsx_objective* obj, 
                                  const double c[8], void* x, const void* lb, const void* ub, lbfgsx_trace* trace,
                                  lbfgsx_result* out)
 {
-    std::memset(out, 0, sizeof(*out));
-    const int bad = guarded(out, [&]() {
-        if (!s || !obj || n <= 0)
-            throw std::invalid_argument("lbfgsx_solver_minimize_dense: invalid argument");
-        if (lbfgsx_objective_form(obj) != LBFGSX_FORM_DENSE)
-            throw std::invalid_argument("lbfgsx_solver_minimize_dense: the handle is not a dense linear-model objective "
-                                        "(lbfgsx_objective_compile_dense)");
-        const int D = lbfgsx_objective_dim(obj);
-        if (n % D != 0)
-            throw std::invalid_argument("dense linear-model objective: n = " + std::to_string(n) + " is not a multiple of D = " +
-                                        std::to_string(D) + ": x holds the D weights of each feature");
-        if (lbfgsx_objective_dtype(obj) != s->dtype)
-            throw std::invalid_argument("lbfgsx_solver_minimize_dense: the objective was compiled for the other dtype");
-        if (R < 1)
-            throw std::invalid_argument("dense linear-model objective: R = " + std::to_string(R) +
-                                        ": a dense linear-model objective has at least one row (R >= 1)");
-        if (!A)
-            throw std::invalid_argument("dense linear-model objective: A is null: a dense linear-model objective has its R x F "
-                                        "matrix (R = " + std::to_string(R) + ")");
-        if (lda < n / D)
-            throw std::invalid_argument("dense linear-model objective: lda = " + std::to_string(lda) + " is less than F = n / D = " +
-                                        std::to_string(n / D) + ": a row of the matrix holds its F values first");
-    });
-    if (bad)
-        return bad;
-    if (lbfgsx_device_count() <= 0)
-    {
-        out->status = LBFGSX_E_NOGPU;
-        std::snprintf(out->msg, sizeof(out->msg), "lbfgsx_solver_minimize_dense: no HIP device available (this library has no CPU fallback)");
-        return out->status;
-    }
-    lbfgsx_solver::GraphSpec gr;
-    gr.E = 0, gr.ei = gr.ej = nullptr, gr.on_device = a_on_device, gr.counts = counts, gr.elems = nullptr;
-    gr.R = R, gr.A = A, gr.lda = lda, gr.lanes = lanes;
-    return guarded(out, [&]() { s->minimize_obj(obj, n, 0, 0, 0, &gr, p, host_mask, c, x, lb, ub, trace, out); });
+    return objective_entry(
+        "lbfgsx_solver_minimize_dense", out,
+        [&]() {
+            if (!s || !obj || n <= 0)
+                throw std::invalid_argument("lbfgsx_solver_minimize_dense: invalid argument");
+            if (lbfgsx_objective_form(obj) != LBFGSX_FORM_DENSE)
+                throw std::invalid_argument("lbfgsx_solver_minimize_dense: the handle is not a dense linear-model objective "
+                                            "(lbfgsx_objective_compile_dense)");
+            const int D = lbfgsx_objective_dim(obj);
+            if (n % D != 0)
+                throw std::invalid_argument("dense linear-model objective: n = " + std::to_string(n) + " is not a multiple of D = " +
+                                            std::to_string(D) + ": x holds the D weights of each feature");
+            if (lbfgsx_objective_dtype(obj) != s->dtype)
+                throw std::invalid_argument("lbfgsx_solver_minimize_dense: the objective was compiled for the other dtype");
+            if (R < 1)
+                throw std::invalid_argument("dense linear-model objective: R = " + std::to_string(R) +
+                                            ": a dense linear-model objective has at least one row (R >= 1)");
+            if (!A)
+                throw std::invalid_argument("dense linear-model objective: A is null: a dense linear-model objective has its R x F "
+                                            "matrix (R = " + std::to_string(R) + ")");
+            if (lda < n / D)
+                throw std::invalid_argument("dense linear-model objective: lda = " + std::to_string(lda) + " is less than F = n / D = " +
+                                            std::to_string(n / D) + ": a row of the matrix holds its F values first");
+        },
+        [&]() {
+            ObjSpec gr;
+            gr.form = LBFGSX_FORM_DENSE, gr.on_device = a_on_device, gr.counts = counts;
+            gr.R = R, gr.A = A, gr.lda = lda, gr.lanes = lanes;
+            s->minimize_obj(obj, n, gr, p, host_mask, c, x, lb, ub, trace, out);
+        });
 }
 }

@@ -22,6 +22,7 @@ tensors that alias the library's device vectors.  All O(n) work of the solver ru
 pointers.  There is no CPU fallback: without the built extension or a GPU these calls raise.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -226,7 +227,62 @@ class ChainObjective(TermObjective):
             raise ValueError("ChainObjective: n = %d is less than K = %d: there is no term" % (n, self.K))
 
 
-class GridObjective(TermObjective):
+class _LatticeObjective(TermObjective):
+    """What the six forms on a regular array share: a shape of one extent per axis, each at least _MIN; for a form with a
+    mask (_MASKED) the axes that wrap; for the field form D unknowns per node; and the solver's entry point (_ENTRY), which
+    takes the shape and the mask.  A class states these as attributes and keeps its own signature."""
+    _AXES, _MIN, _EXTENT_RULE = ("rows", "cols"), 2, "a grid has at least 2 rows and 2 columns"
+    _MASKED = False       # periodic is taken, as a tuple of flags per axis
+    _MASK_NUMBER = False  # ... or as the mask itself
+    _HAS_D = False        # D is taken: it goes to the compiler and multiplies into n
+    _CELL, _ENTRY = 4, None
+
+    def _lattice_init(self, body, shape, data, scalars, periodic=None, D=None):
+        try:
+            shape = tuple(int(v) for v in shape)
+            if len(shape) != len(self._AXES):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError("%s: shape must be (%s)" % (self._NAME, ", ".join(self._AXES))) from None
+        if min(shape) < self._MIN:
+            raise ValueError("%s: shape = %s: %s" % (self._NAME, self._shape_text(shape), self._EXTENT_RULE))
+        self.shape = shape
+        if self._HAS_D:
+            if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or D not in (1, 2, 3):
+                raise ValueError("%s: D = %r is not supported: a node has D = 1, 2 or 3 unknowns" % (self._NAME, D))
+            self.D = int(D)
+        if self._MASKED:
+            if self._MASK_NUMBER and isinstance(periodic, (int, np.integer)) and not isinstance(periodic, (bool, np.bool_)):
+                if not 0 <= periodic <= 3:
+                    raise ValueError("%s: periodic = %d: the mask has bit 0 for the column direction and bit 1 for the "
+                                     "row direction (0 .. 3)" % (self._NAME, periodic))
+                self.periodic = int(periodic)
+            else:
+                self.periodic = _periodic_mask(self._NAME, periodic, self._AXES)
+        self.body, self.K = str(body), self._CELL
+        self._h = {}
+        self.set_data(*data)
+        self.set_scalars(*scalars)
+
+    @staticmethod
+    def _shape_text(shape):
+        return "(%s)" % ", ".join("%d" % v for v in shape)
+
+    def _form_args(self):
+        return (self.D,) if self._HAS_D else ()
+
+    def _check_n(self, n):
+        D = self.D if self._HAS_D else 1
+        if math.prod(self.shape) * D != n:
+            raise ValueError("%s: shape = %s%s does not multiply to n = %d"
+                             % (self._NAME, self._shape_text(self.shape), ", D = %d" % D if self._HAS_D else "", n))
+
+    def _entry_args(self):
+        """what the solver's entry point takes between the handle and the data"""
+        return self.shape + ((self.periodic,) if self._MASKED else ())
+
+
+class GridObjective(_LatticeObjective):
     """An objective on a 2-D grid: x is a row-major rows x cols array (flattened, n = rows*cols, rows >= 2, cols >= 2) and
     f(x) = sum over the (rows-1)(cols-1) cells of phi(x[r,c], x[r,c+1], x[r+1,c], x[r+1,c+1]; r, c) -- the MINPACK-2 energies
     (a cell covers both triangles of their discretisation), smoothness terms of image problems, membrane and Allen-Cahn
@@ -257,27 +313,13 @@ class GridObjective(TermObjective):
     kernels by their counterparts); usable wherever a ChainObjective is, refused where one is.  minimize raises ValueError
     when rows*cols != len(x)."""
     _NAME = "GridObjective"
-    _COMPILE, _SOURCE = "lbfgsx_objective_compile_grid", "lbfgsx_objective_source_grid"
+    _COMPILE, _SOURCE, _ENTRY = "lbfgsx_objective_compile_grid", "lbfgsx_objective_source_grid", "lbfgsx_solver_minimize_grid"
 
     def __init__(self, body, shape, data=(), scalars=()):
-        rows, cols = (int(v) for v in shape)
-        if rows < 2 or cols < 2:
-            raise ValueError("GridObjective: shape = (%d, %d): a grid has at least 2 rows and 2 columns" % (rows, cols))
-        self.shape = (rows, cols)
-        self.body, self.K = str(body), 4
-        self._h = {}
-        self.set_data(*data)
-        self.set_scalars(*scalars)
-
-    def _form_args(self):
-        return ()
-
-    def _check_n(self, n):
-        if self.shape[0] * self.shape[1] != n:
-            raise ValueError("GridObjective: shape = (%d, %d) does not multiply to n = %d" % (self.shape + (n,)))
+        self._lattice_init(body, shape, data, scalars)
 
 
-class VolumeObjective(TermObjective):
+class VolumeObjective(_LatticeObjective):
     """An objective on a 3-D array: x is a slab-major slabs x rows x cols array (flattened, n = slabs*rows*cols, every extent
     >= 2; node (s, r, c) has flat index (s*rows + r)*cols + c) and f(x) = sum over the (slabs-1)(rows-1)(cols-1) cells of
     phi(x[8]; s, r, c) with x[4*ds + 2*dr + dc] = x[s+ds, r+dr, c+dc] -- volumetric denoising, 3-D phase-field and Allen-Cahn
@@ -302,28 +344,11 @@ class VolumeObjective(TermObjective):
     kernels by their counterparts); usable wherever a GridObjective is, refused where one is.  minimize raises ValueError
     when slabs*rows*cols != len(x)."""
     _NAME = "VolumeObjective"
-    _COMPILE, _SOURCE = "lbfgsx_objective_compile_volume", "lbfgsx_objective_source_volume"
+    _COMPILE, _SOURCE, _ENTRY = "lbfgsx_objective_compile_volume", "lbfgsx_objective_source_volume", "lbfgsx_solver_minimize_volume"
+    _AXES, _EXTENT_RULE, _CELL = ("slabs", "rows", "cols"), "a volume has at least 2 slabs, 2 rows and 2 columns", 8
 
     def __init__(self, body, shape, data=(), scalars=()):
-        try:
-            slabs, rows, cols = (int(v) for v in shape)
-        except (TypeError, ValueError):
-            raise ValueError("VolumeObjective: shape must be (slabs, rows, cols)") from None
-        if slabs < 2 or rows < 2 or cols < 2:
-            raise ValueError("VolumeObjective: shape = (%d, %d, %d): a volume has at least 2 slabs, 2 rows and 2 columns"
-                             % (slabs, rows, cols))
-        self.shape = (slabs, rows, cols)
-        self.body, self.K = str(body), 8
-        self._h = {}
-        self.set_data(*data)
-        self.set_scalars(*scalars)
-
-    def _form_args(self):
-        return ()
-
-    def _check_n(self, n):
-        if self.shape[0] * self.shape[1] * self.shape[2] != n:
-            raise ValueError("VolumeObjective: shape = (%d, %d, %d) does not multiply to n = %d" % (self.shape + (n,)))
+        self._lattice_init(body, shape, data, scalars)
 
 
 def _periodic_mask(name, periodic, axes):
@@ -340,7 +365,7 @@ def _periodic_mask(name, periodic, axes):
     return sum(1 << k for k, v in enumerate(reversed(flags)) if v)
 
 
-class PeriodicGridObjective(TermObjective):
+class PeriodicGridObjective(_LatticeObjective):
     """A GridObjective with wrap-around cells (include/lbfgsx.h, "periodic grid and volume objectives"): periodic = (rows,
     cols) says which directions wrap.  Cell (r, c) has the corners x[r,c], x[r,c+1], x[r+1,c], x[r+1,c+1] with + modulo the
     extent and exists iff (c < cols-1 or the columns wrap) and (r < rows-1 or the rows wrap); with periodic = (False, False)
@@ -356,65 +381,31 @@ class PeriodicGridObjective(TermObjective):
     A per-node term goes to the cell that starts at the node; on an open axis the last layer of cells picks up the nodes no
     cell starts at (if (!(periodic & 1) && col + 2 == cols) ...), on a periodic axis there is nothing to pick up.  Everything
     else as for a GridObjective; usable wherever one is, refused where one is."""
-    _NAME = "PeriodicGridObjective"
+    _NAME, _MASKED = "PeriodicGridObjective", True
     _COMPILE, _SOURCE = "lbfgsx_objective_compile_grid_periodic", "lbfgsx_objective_source_grid_periodic"
+    _ENTRY = "lbfgsx_solver_minimize_grid_periodic"
 
     def __init__(self, body, shape, periodic=(True, True), data=(), scalars=()):
-        try:
-            rows, cols = (int(v) for v in shape)
-        except (TypeError, ValueError):
-            raise ValueError("PeriodicGridObjective: shape must be (rows, cols)") from None
-        if rows < 2 or cols < 2:
-            raise ValueError("PeriodicGridObjective: shape = (%d, %d): a grid has at least 2 rows and 2 columns" % (rows, cols))
-        self.shape = (rows, cols)
-        self.periodic = _periodic_mask(self._NAME, periodic, ("rows", "cols"))
-        self.body, self.K = str(body), 4
-        self._h = {}
-        self.set_data(*data)
-        self.set_scalars(*scalars)
-
-    def _form_args(self):
-        return ()
-
-    def _check_n(self, n):
-        if self.shape[0] * self.shape[1] != n:
-            raise ValueError("PeriodicGridObjective: shape = (%d, %d) does not multiply to n = %d" % (self.shape + (n,)))
+        self._lattice_init(body, shape, data, scalars, periodic)
 
 
-class PeriodicVolumeObjective(TermObjective):
+class PeriodicVolumeObjective(_LatticeObjective):
     """A VolumeObjective with wrap-around cells: periodic = (slabs, rows, cols) says which directions wrap.  Cell (s, r, c) has
     the corners x[4*ds + 2*dr + dc] = x[s+ds, r+dr, c+dc] with + modulo the extent and exists iff, per axis, its origin is not
     in the last layer or the axis wraps; with no axis periodic this is a VolumeObjective.  The body sees what a
     VolumeObjective's sees, plus const int64_t j[8], the flat indices of its eight corners (j[0] == i), and int periodic (bit
     0: columns, bit 1: rows, bit 2: slabs); it reads data as p0[j[k]].  The gradient's order is the VolumeObjective's, with
     wrapped indices.  Everything else as for a VolumeObjective; usable wherever one is, refused where one is."""
-    _NAME = "PeriodicVolumeObjective"
+    _NAME, _MASKED = "PeriodicVolumeObjective", True
     _COMPILE, _SOURCE = "lbfgsx_objective_compile_volume_periodic", "lbfgsx_objective_source_volume_periodic"
+    _ENTRY = "lbfgsx_solver_minimize_volume_periodic"
+    _AXES, _EXTENT_RULE, _CELL = VolumeObjective._AXES, VolumeObjective._EXTENT_RULE, 8
 
     def __init__(self, body, shape, periodic=(True, True, True), data=(), scalars=()):
-        try:
-            slabs, rows, cols = (int(v) for v in shape)
-        except (TypeError, ValueError):
-            raise ValueError("PeriodicVolumeObjective: shape must be (slabs, rows, cols)") from None
-        if slabs < 2 or rows < 2 or cols < 2:
-            raise ValueError("PeriodicVolumeObjective: shape = (%d, %d, %d): a volume has at least 2 slabs, 2 rows and 2 columns"
-                             % (slabs, rows, cols))
-        self.shape = (slabs, rows, cols)
-        self.periodic = _periodic_mask(self._NAME, periodic, ("slabs", "rows", "cols"))
-        self.body, self.K = str(body), 8
-        self._h = {}
-        self.set_data(*data)
-        self.set_scalars(*scalars)
-
-    def _form_args(self):
-        return ()
-
-    def _check_n(self, n):
-        if self.shape[0] * self.shape[1] * self.shape[2] != n:
-            raise ValueError("PeriodicVolumeObjective: shape = (%d, %d, %d) does not multiply to n = %d" % (self.shape + (n,)))
+        self._lattice_init(body, shape, data, scalars, periodic)
 
 
-class GridFieldObjective(TermObjective):
+class GridFieldObjective(_LatticeObjective):
     """A PeriodicGridObjective whose nodes carry D = 1, 2 or 3 unknowns (include/lbfgsx.h, "grid field objectives"): complex
     Ginzburg-Landau lattices, Heisenberg films, optical flow and 2-D elasticity, multi-channel image models.  x is node-major,
     x[(r*cols + c)*D + d], n = rows*cols*D; periodic = (rows, cols) says which directions wrap, (False, False) is the open
@@ -429,34 +420,15 @@ class GridFieldObjective(TermObjective):
                                 " v += T(0.5) * (a * a + b * b); } return v;", shape=(rows, cols), D=2, periodic=(True, True))
 
     Everything else as for a PeriodicGridObjective; usable wherever one is, refused where one is."""
-    _NAME = "GridFieldObjective"
+    _NAME, _MASKED, _HAS_D = "GridFieldObjective", True, True
     _COMPILE, _SOURCE = "lbfgsx_objective_compile_grid_field", "lbfgsx_objective_source_grid_field"
+    _ENTRY = "lbfgsx_solver_minimize_grid_field"
 
     def __init__(self, body, shape, D, periodic=(False, False), data=(), scalars=()):
-        try:
-            rows, cols = (int(v) for v in shape)
-        except (TypeError, ValueError):
-            raise ValueError("GridFieldObjective: shape must be (rows, cols)") from None
-        if rows < 2 or cols < 2:
-            raise ValueError("GridFieldObjective: shape = (%d, %d): a grid has at least 2 rows and 2 columns" % (rows, cols))
-        if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or D not in (1, 2, 3):
-            raise ValueError("GridFieldObjective: D = %r is not supported: a node has D = 1, 2 or 3 unknowns" % (D,))
-        self.shape, self.D = (rows, cols), int(D)
-        self.periodic = _periodic_mask(self._NAME, periodic, ("rows", "cols"))
-        self.body, self.K = str(body), 4
-        self._h = {}
-        self.set_data(*data)
-        self.set_scalars(*scalars)
-
-    def _form_args(self):
-        return (self.D,)
-
-    def _check_n(self, n):
-        if self.shape[0] * self.shape[1] * self.D != n:
-            raise ValueError("GridFieldObjective: shape = (%d, %d), D = %d does not multiply to n = %d" % (self.shape + (self.D, n)))
+        self._lattice_init(body, shape, data, scalars, periodic, D)
 
 
-class StencilObjective(TermObjective):
+class StencilObjective(_LatticeObjective):
     """An objective of 3x3-node terms on a 2-D grid (include/lbfgsx.h, "grid stencil objectives"): energies that need a second
     difference at a node -- plate bending and thin-plate splines, sum (Laplace u)^2, Swift-Hohenberg and phase-field-crystal
     functionals, second-order TV priors, 3x3 clique priors, anything on a 9-point stencil.  x is a row-major rows x cols array
@@ -477,35 +449,13 @@ class StencilObjective(TermObjective):
     A per-node term is written inside the body: the patch adds the term of its node (dr, dc) iff (dr == 0 or (the rows do not
     wrap and row + 3 == rows)) and (dc == 0 or (the columns do not wrap and col + 3 == cols)); every node is then counted
     once.  Everything else as for a PeriodicGridObjective; usable wherever one is, refused where one is."""
-    _NAME = "StencilObjective"
+    _NAME, _MASKED, _MASK_NUMBER = "StencilObjective", True, True
     _COMPILE, _SOURCE = "lbfgsx_objective_compile_grid_stencil", "lbfgsx_objective_source_grid_stencil"
+    _ENTRY = "lbfgsx_solver_minimize_grid_stencil"
+    _MIN, _EXTENT_RULE, _CELL = 3, "a 3x3 patch needs at least 3 rows and 3 columns", 9
 
     def __init__(self, body, shape, periodic=0, data=(), scalars=()):
-        try:
-            rows, cols = (int(v) for v in shape)
-        except (TypeError, ValueError):
-            raise ValueError("StencilObjective: shape must be (rows, cols)") from None
-        if rows < 3 or cols < 3:
-            raise ValueError("StencilObjective: shape = (%d, %d): a 3x3 patch needs at least 3 rows and 3 columns" % (rows, cols))
-        self.shape = (rows, cols)
-        if isinstance(periodic, (int, np.integer)) and not isinstance(periodic, (bool, np.bool_)):
-            if not 0 <= periodic <= 3:
-                raise ValueError("StencilObjective: periodic = %d: the mask has bit 0 for the column direction and bit 1 for the "
-                                 "row direction (0 .. 3)" % periodic)
-            self.periodic = int(periodic)
-        else:
-            self.periodic = _periodic_mask(self._NAME, periodic, ("rows", "cols"))
-        self.body, self.K = str(body), 9
-        self._h = {}
-        self.set_data(*data)
-        self.set_scalars(*scalars)
-
-    def _form_args(self):
-        return ()
-
-    def _check_n(self, n):
-        if self.shape[0] * self.shape[1] != n:
-            raise ValueError("StencilObjective: shape = (%d, %d) does not multiply to n = %d" % (self.shape + (n,)))
+        self._lattice_init(body, shape, data, scalars, periodic)
 
 
 def _is_torch(x):
@@ -1136,18 +1086,8 @@ class _SolverBase:
             rc = self._sol.lbfgsx_solver_minimize_graph(self._h, h, n, f.E, f.ei.ctypes.data_as(C.POINTER(C.c_int32)),
                                                         f.ej.ctypes.data_as(C.POINTER(C.c_int32)), 0, tail[0], mask,
                                                         C.byref(counts), *tail[2:])
-        elif isinstance(f, GridFieldObjective):
-            rc = self._sol.lbfgsx_solver_minimize_grid_field(self._h, h, f.shape[0], f.shape[1], f.periodic, *tail)
-        elif isinstance(f, StencilObjective):
-            rc = self._sol.lbfgsx_solver_minimize_grid_stencil(self._h, h, f.shape[0], f.shape[1], f.periodic, *tail)
-        elif isinstance(f, PeriodicVolumeObjective):
-            rc = self._sol.lbfgsx_solver_minimize_volume_periodic(self._h, h, f.shape[0], f.shape[1], f.shape[2], f.periodic, *tail)
-        elif isinstance(f, PeriodicGridObjective):
-            rc = self._sol.lbfgsx_solver_minimize_grid_periodic(self._h, h, f.shape[0], f.shape[1], f.periodic, *tail)
-        elif isinstance(f, VolumeObjective):
-            rc = self._sol.lbfgsx_solver_minimize_volume(self._h, h, f.shape[0], f.shape[1], f.shape[2], *tail)
-        elif isinstance(f, GridObjective):
-            rc = self._sol.lbfgsx_solver_minimize_grid(self._h, h, f.shape[0], f.shape[1], *tail)
+        elif isinstance(f, _LatticeObjective):
+            rc = getattr(self._sol, f._ENTRY)(self._h, h, *f._entry_args(), *tail)
         else:
             rc = self._sol.lbfgsx_solver_minimize_obj(self._h, h, n, *tail)
         del keep
